@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Benchmark of the CONE coarse-to-fine inference hot path on MI355X.
 
-    python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1         # the headline only
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full  # the headline + every extra listed below
+    python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR   # + the last timed step's outputs as DIR/*.npy
     python bench.py --gpus 8 --steps 3 --warmup 1         # starts its own 8 ranks (torch.distributed.run as a child process)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -13,10 +15,15 @@ NMS 0.5) with every feature already resident in HBM.
 
 Prints ONE JSON line (rank 0).  `value` (strong scaling): ONE such split per step whatever N -- at N > 1 it is sharded by
 window over the ranks (BASELINE configs[3]: cone_amd.parallel.predict_split_distributed_async, one RCCL all_gather of the
-per-window proposal rows ahead of the global NMS).  Extra objects on the same line:
+per-window proposal rows ahead of the global NMS).  `ms_per_step`: wall time of one timed step (W untimed warm-up steps,
+then exactly K = --steps timed ones).  A plain run sets up, warms up, times the K steps, writes the outputs of the last one
+when --dump-outputs is given (write_outputs below) and prints the line; besides the headline it carries only what is
+derived from the timed steps' own launch records:
   * `roofline`      -- the dominant kernel (the fp32-MFMA GEMM tile that accumulates the most time) priced from
                        hipEvent timings taken around each of its launches inside the timed region (cone_prof_*),
                        FLOPs = 2*M*N*K with the M actually processed;
+  * `kernels`, `window_model` -- per-kernel launch figures and the step's FLOP accounting from the same records.
+With --full the same line also carries every extra below, each measured in runs of its own after the headline:
   * `weak_scaling` (N > 1) -- every rank its own split of that size, the kept rows of all shards all-gathered (the N > 1
                        HEADLINE is BASELINE configs[3]: ONE split sharded by window, strong scaling -- see `value` below);
   * `dropin_forward`, `localizer` (N = 1) -- the reference's own Python API on the same kernels: its 640-window padded
@@ -32,7 +39,10 @@ per-window proposal rows ahead of the global NMS).  Extra objects on the same li
   * `prefilter_mad`, `latency_config1`, `config5` (N = 1) -- BASELINE configs[2], [0] and [4] on one GPU: the
                        MAD-scale pre-filter against the HBM roofline (1 and 64 queries), the single-query latency,
                        64 queries x one MAD-length video end to end;
-  * `cpu_baseline`  -- the CPU oracle (a torch-CPU port of the reference path) on a bounded sample.
+  * `cpu_baseline`  -- the CPU oracle (a torch-CPU port of the reference path) on a bounded sample;
+  * `ms_per_step_one_at_a_time`, `split_bf16x3`, `hip_graph` -- the headline split one step at a time, on the opt-in
+                       split-bf16 layer tails and as one hipGraph replay per step.
+(--no_extras / --no_cpu_baseline still trim a --full run.)
 """
 import argparse
 import json
@@ -680,6 +690,42 @@ def bench_config5_sharded(dist, world, timed_region, ctx_l=33_000, queries=64):
             "ranks_seen": dist.get_world_size(), "collectives_per_step": 2}
 
 
+DUMP_MAX_BYTES = 64_000_000
+
+
+def write_outputs(dirname, lists, info):
+    """--dump-outputs: what the caller of the timed path received from its last step, as float64 .npy files --
+    ``moments_fused`` / ``moments_proposal`` / ``moments_matching`` (nq, max rows, 5): each query's ``predicted_times`` rows
+    [st, ed, proposal, matching, fused] of the three submission lists, zero past ``moment_count`` (3, nq); ``top_windows``
+    (nq, top-k): the window indices stage A chose (-1: none).  At N > 1 the lists are rank 0's query shard.  Should the files
+    exceed DUMP_MAX_BYTES, a fixed (seed 0) sample of the queries is written instead, their indices in ``query_index``."""
+    nq = len(lists[0])
+    counts = np.array([[len(item["predicted_times"] or []) for item in lst] for lst in lists], dtype=np.float64)
+    width = max(1, int(counts.max())) if nq else 1
+    win = info.get("win_idx")
+    win = win.detach().cpu().numpy().astype(np.float64) if win is not None and win.shape[0] == nq else None
+    per_query = 8 * (3 * width * 5 + 3 + (win.shape[1] if win is not None else 0))
+    keep = np.arange(nq)
+    if nq * per_query > DUMP_MAX_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(nq, DUMP_MAX_BYTES // per_query - 1, replace=False))
+    out = {"moment_count": counts[:, keep]}
+    for name, lst in zip(("fused", "proposal", "matching"), lists):
+        m = np.zeros((len(keep), width, 5), dtype=np.float64)
+        for j, q in enumerate(keep.tolist()):
+            rows = lst[q]["predicted_times"]
+            if rows:
+                m[j, :len(rows)] = rows
+        out["moments_" + name] = m
+    if win is not None:
+        out["top_windows"] = win[keep]
+    if len(keep) < nq:
+        out["query_index"] = keep.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return sorted(out)
+
+
 def self_launch(n_gpus):
     """`python3 bench.py --gpus N` with N > 1 and no RANK in the environment: this process touches no GPU -- it starts
     `python -m torch.distributed.run --nproc-per-node N bench.py <same arguments>` as a CHILD process (never an exec),
@@ -749,16 +795,23 @@ def main():
     ap.add_argument("--elide_dead_work", action="store_true",
                     help="A/B: the headline step WITHOUT the saliency head and the intermediate decoder layer's heads "
                          "(CONE.forward computes them, cone/inference.py never reads them); the default headline computes "
-                         "both and reports the elided step beside it as ms_per_step_dead_work_elided")
+                         "both and, with --full, reports the elided step beside it as ms_per_step_dead_work_elided")
     ap.add_argument("--need_saliency", action="store_true", help="accepted for older command lines: now the default")
     ap.add_argument("--no_cpu_baseline", action="store_true")
     ap.add_argument("--no_extras", action="store_true",
-                    help="only the headline timed region (profiling runs): skip the full-forward region, the split_bf16 "
-                         "region and the configs[0]/[2]/[4] figures")
+                    help="with --full: skip the full-forward region, the split_bf16 region and the configs[0]/[2]/[4] "
+                         "figures (a run without --full times the headline region only)")
     ap.add_argument("--cpu_queries", type=int, default=400)
     ap.add_argument("--mad_ctx_l", type=int, default=6_200_000,
                     help="clips of the MAD-scale stress video of prefilter_mad_ctx_sharded (N > 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every extra of the module docstring too (CPU baseline, other configs, "
+                         "precisions and entries); off: the headline only")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float64; see write_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # plain `python3 bench.py --gpus N`: become the launcher (no GPU call has happened in this process)
@@ -887,6 +940,8 @@ def main():
     timed_region.steps = args.steps
     dt, rec, (out, dp) = timed_region(step)
     n_windows = dp["n_windows"]
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, out[0], dp)
 
     # ---- the headline object first: nothing below can take it down (every extra is guarded on its own)
     res = None
@@ -990,9 +1045,11 @@ def main():
         if v is not None:
             note(name, v)
 
+    # everything below the headline is an extra: only with --full (and not trimmed by --no_extras)
+    extras = args.full and not args.no_extras
     serial_ms = [dt / args.steps * 1e3]      # the dense step one at a time: what the one-at-a-time extras below compare with
     # ---- the same K steps one at a time (predict_split: the host half of a step runs before the next step is enqueued)
-    if not args.no_extras and max(1, args.steps_in_flight) > 1:
+    if extras and max(1, args.steps_in_flight) > 1:
         def serial():
             keep, args.steps_in_flight = args.steps_in_flight, 1
             try:
@@ -1005,7 +1062,7 @@ def main():
         guarded("one_at_a_time_error", serial)
 
     # ---- the eval pipeline's own default (cone_amd.inference): the outputs cone/inference.py never reads are not computed
-    if full and not args.no_extras:
+    if full and extras:
         def elided():
             opt.need_saliency = opt.need_aux = False
             try:
@@ -1016,7 +1073,7 @@ def main():
             note("value_dead_work_elided", round(fdp["n_windows"] * args.steps / fdt, 1))
         guarded("dead_work_elided_error", elided)
 
-    if world == 1 and not args.no_extras and not any(kv.startswith("split_bf16") for kv in args.set_option):
+    if world == 1 and extras and not any(kv.startswith("split_bf16") for kv in args.set_option):
         # OPT-IN path, reported beside the headline (which stays exact fp32): every layer tail on the bf16 matrix cores,
         # each fp32 product as six partial products of three-piece bf16 operands with fp32 accumulation (ffn_split.hip)
         def split_path():
@@ -1051,7 +1108,7 @@ def main():
                 model.set_option("split_bf16", 0)
         guarded("split_bf16x3", split_path)
 
-    if multi:
+    if multi and args.full:
         # the EASY curve beside the headline: every rank its own split of that size (seed = rank), the kept rows of all shards
         # all-gathered over RCCL -- per-GPU work fixed as N grows (weak scaling)
         def weak():
@@ -1080,13 +1137,13 @@ def main():
                     "ms_per_step": round(wdt / args.steps * 1e3, 2), "ranks_seen": dist.get_world_size(),
                     "collectives_per_step": 2}
         guarded("weak_scaling", weak)
-        if not args.no_extras:
+        if extras:
             # the other multi-GPU configs of BASELINE.json, as stated (collectives inside: every rank runs them)
             guarded("config5_sharded", lambda: bench_config5_sharded(dist, world, timed_region))
             guarded("prefilter_mad_ctx_sharded",
                     lambda: bench_prefilter_mad_ctx_sharded(dist, rank, world, timed_region, ctx_l=args.mad_ctx_l))
 
-    if world == 1 and not args.no_extras:
+    if world == 1 and extras:
         def dense_graph():
             # the headline workload with the step's launch sequence captured once and replayed as ONE hipGraph launch per step
             # (opt.hip_graph: the serving form for a split that is evaluated again at the same shapes); same stepping, same rows
@@ -1121,7 +1178,7 @@ def main():
         guarded("localizer", localizer)
         guarded("config5", bench_config5)
         guarded("prefilter_mad", bench_prefilter_mad)
-    if world == 1 and not args.no_cpu_baseline and args.cpu_queries > 0:
+    if world == 1 and args.full and not args.no_cpu_baseline and args.cpu_queries > 0:
         guarded("cpu_baseline", lambda: cpu_baseline(opt, sd, args.cpu_queries,
                                                      max(1, args.cpu_queries * args.videos // args.queries)))
     if res is not None and isinstance(res.get("roofline"), dict):

@@ -2365,6 +2365,45 @@ def test_criterion_forward_matches_reference_golden(golden_dir):
             assert abs(float(got[k]) - float(ref[k])) <= 1e-5 * max(1.0, abs(float(ref[k]))), (Nq, k)
 
 
+# ------------------------------------------------------------------------------------ bench.py, plain run
+def test_bench_plain_run_dumps_the_last_steps_outputs(tmp_path):
+    """`python3 bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: the headline line only (no extra), K timed steps,
+    and DIR/*.npy = the submission rows the timed path returned in its last step -- the same rows as predict_split on the
+    same seeded split in this process."""
+    import subprocess
+    import sys
+    from cone_amd import inference as inf
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--queries", "64", "--videos", "4", "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    res = json.loads(lines[0])
+    assert res["steps"] == 3 and res["warmup"] == 1 and res["ms_per_step"] > 0 and res["higher_is_better"] is True
+    assert res["unit"] == "windows/s" and res["dtype"] == "f32" and res["metric"].startswith("windows/sec")
+    nw = int(res["config"]["workload"].split(",")[-1].split()[0])
+    assert abs(res["value"] - nw / (res["ms_per_step"] * 1e-3)) < 0.01 * res["value"]
+    assert not {"cpu_baseline", "ms_per_step_one_at_a_time", "ms_per_step_dead_work_elided", "prefilter_mad",
+                "latency_config1", "hip_graph"} & set(res)
+    got = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(got) == {"moment_count", "moments_fused", "moments_proposal", "moments_matching", "top_windows"}
+    assert all(a.dtype == np.float64 for a in got.values())
+    # the same split in this process (bench.py's options at 64 queries: one query chunk)
+    opt = make_opt("ego4d", nms_thd=0.5, eval_split_name="test", topk_window=20, eval_bsz=32, window_batch=32768,
+                   pipeline_chunks=None, pipeline_tail=None, need_saliency=True, need_aux=True)
+    model, _, _ = get_model("ego4d", 0, need_saliency=True, need_aux=True)
+    ann, vf, qf = synth.make_dataset(opt, 64, 4, seed=0)
+    lists, info = inf.predict_split(model, inf.FeatureStore(opt, ann, vf, qf), opt)
+    assert np.array_equal(got["top_windows"], info["win_idx"].cpu().numpy())
+    for t, name in enumerate(("fused", "proposal", "matching")):
+        for q, item in enumerate(lists[t]):
+            k = len(item["predicted_times"])
+            assert got["moment_count"][t, q] == k
+            assert np.array_equal(got["moments_" + name][q, :k], np.array(item["predicted_times"]).reshape(k, 5)), (name, q)
+
+
 # ------------------------------------------------------------------------------------ bench.py launched with N > 1
 def test_bench_two_ranks_on_one_device():
     """N > 1 through the PLAIN entry the driver uses for one GPU -- `python3 bench.py --gpus 2 ...`, no RANK in the
@@ -2378,7 +2417,7 @@ def test_bench_two_ranks_on_one_device():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(CONE_BENCH_ONE_DEVICE="1", CONE_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--queries", "96", "--videos", "6", "--mad_ctx_l", "400000"]
+           "--warmup", "1", "--queries", "96", "--videos", "6", "--mad_ctx_l", "400000", "--full"]
     r = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -404,3 +404,32 @@ def test_store_views_are_cached_and_follow_replaced_arenas():
     assert sel.n_q.tolist() == [min(3, -(-store.ctx_l[v] // S) + 1) for v in store.q_vid.tolist()]
     assert sel.row_off[-1] == sel.n_rows and [sel.query_of_row(r) for r in range(sel.n_rows)] == \
         [q for q, n in enumerate(sel.n_q.tolist()) for _ in range(n)]
+
+
+def test_bench_write_outputs_layout_and_sample_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the three submission lists' rows as float64 arrays (zero past each query's count), the stage-A
+    window table beside them; above the byte cap a fixed, seeded sample of the queries (the same one every run)."""
+    import bench as B_
+    rows = lambda k, q: [[q, q + 1.0, 0.5, 0.25, 0.125 * j] for j in range(k)]
+    lists = tuple([{"query_idx": q, "predicted_times": rows((q + t) % 4, q)} for q in range(40)] for t in range(3))
+    info = {"win_idx": torch.arange(40 * 3, dtype=torch.int64).view(40, 3)}
+    names = B_.write_outputs(str(tmp_path / "a"), lists, info)
+    assert names == ["moment_count", "moments_fused", "moments_matching", "moments_proposal", "top_windows"]
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in names}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["moments_fused"].shape == (40, 3, 5) and got["moment_count"].shape == (3, 40)
+    for t, name in enumerate(("fused", "proposal", "matching")):
+        for q in range(40):
+            k = (q + t) % 4
+            assert got["moment_count"][t, q] == k
+            assert np.array_equal(got["moments_" + name][q, :k], np.array(rows(k, q)).reshape(k, 5))
+            assert not got["moments_" + name][q, k:].any()
+    assert np.array_equal(got["top_windows"], info["win_idx"].numpy())
+    per_query = 8 * (3 * 3 * 5 + 3 + 3)
+    monkeypatch.setattr(B_, "DUMP_MAX_BYTES", 10 * per_query)
+    d1, d2 = (B_.write_outputs(str(tmp_path / d), lists, info) for d in ("b", "c"))
+    assert d1 == d2 and "query_index" in d1
+    idx = np.load(tmp_path / "b" / "query_index.npy")
+    assert len(idx) < 10 and np.array_equal(idx, np.load(tmp_path / "c" / "query_index.npy"))
+    assert sum(os.path.getsize(tmp_path / "b" / f"{n}.npy") for n in d1) <= 10 * per_query + 128 * len(d1)
+    assert np.array_equal(np.load(tmp_path / "b" / "top_windows.npy"), info["win_idx"].numpy()[idx.astype(int)])

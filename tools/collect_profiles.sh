@@ -10,7 +10,7 @@ mkdir -p $out
 export TMPDIR=/tmp
 rm -rf $out/prof_$tag $out/pmc_fetch $out/pmc_write $out/pmc_mfma $out/pmc_fetch_pf $out/pmc_write_pf $out/pmc_mfma_pf
 # (1) per-kernel time of the whole default command (extras included: the pre-filter / config-5 / latency kernels)
-rocprofv3 --kernel-trace --stats -d $out/prof_$tag -o t -- python3 bench.py --steps 3 --warmup 1 --cpu_queries 0 \
+rocprofv3 --kernel-trace --stats -d $out/prof_$tag -o t -- python3 bench.py --steps 3 --warmup 1 --cpu_queries 0 --full \
     > $out/${tag}_prof_bench.json 2> $out/prof_$tag.log
 python3 tools/rocpd_summary.py $out/prof_$tag/t_results.db > $out/${tag}_bench_kernel_stats_all.csv 2>> $out/prof_$tag.log
 # (2) the timed region only: the last launches of the trace (3 steps), so that per-kernel averages are those of the step
@@ -81,7 +81,7 @@ python3 tools/prenorm_step.py > $out/${tag}_prenorm_step.txt 2>&1
 python3 tools/txtpos_step.py > $out/${tag}_txtpos_step.txt 2>&1
 # the bench line last: roofline.traffic is read from profiles/<tag>_pmc_*.json of THIS collection
 cp $out/${tag}_pmc_traffic.json $out/${tag}_pmc_counters.csv $out/${tag}_pmc_prefilter.json $out/${tag}_pmc_prefilter_counters.csv profiles/
-python3 bench.py > $out/${tag}_bench_line.json 2> $out/${tag}_bench.err
+python3 bench.py --full > $out/${tag}_bench_line.json 2> $out/${tag}_bench.err
 cat $out/${tag}_bench_line.json
 # gpurun copies back at most 64 MiB: the rocpd databases and raw counter tables stay on the box, their summaries travel
 mkdir -p $out/${tag}_profiles

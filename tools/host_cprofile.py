@@ -1,5 +1,5 @@
 import cProfile, pstats, sys, os, io, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from cone_amd import inference as inf, synth
 from cone_amd.config import make_opt

@@ -1,6 +1,6 @@
 """Per-tile fixed cost vs per-chunk cost of ffn_split_kernel<false>: time at several dim_feedforward."""
-import sys, torch
-sys.path.insert(0, "/root/repo")
+import os, sys, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from cone_amd import _lib
 M = 2021000
 dev = torch.device("cuda", 0)

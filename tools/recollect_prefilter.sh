@@ -11,7 +11,7 @@ rm -rf $out/lat
 rocprofv3 --kernel-trace -d $out/lat -o t -- python3 tools/latency_bench.py 1x1 > $out/lat.log 2>&1
 python3 tools/latency_trace.py $out/lat/t_results.db > $out/${tag}_latency_trace.txt 2>&1
 cp $out/${tag}_pmc_prefilter.json $out/${tag}_pmc_prefilter_counters.csv profiles/
-python3 bench.py > $out/${tag}_bench_line.json 2> $out/${tag}_bench.err
+python3 bench.py --full > $out/${tag}_bench_line.json 2> $out/${tag}_bench.err
 python3 -c "
 import json; r=json.load(open('$out/${tag}_bench_line.json'))
 print(r['value'], r['ms_per_step'], r['roofline']['frac'], r['roofline'].get('traffic_over_algorithmic'), r['roofline']['prefilter']['frac'], r['roofline']['prefilter'].get('traffic_over_algorithmic'), r['roofline']['prefilter_q64']['frac'])
