@@ -26,6 +26,7 @@ import io
 import json
 import logging
 import os
+import sys
 import time
 import warnings
 from collections import OrderedDict
@@ -35,7 +36,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .config import parse_test_options
+from .config import build_parser, parse_test_options
 from .model import build_model
 
 logger = logging.getLogger(__name__)
@@ -1054,7 +1055,7 @@ def evaluate_split(model, store: FeatureStore, opt, dp, ground_truth=None, epoch
     return (*out, strs)
 
 
-def eval_epoch(model, *args, epoch_i=None, criterion=None, tb_writer=None, ground_truth=None):
+def eval_epoch(model, *args, epoch_i=None, criterion=None, tb_writer=None, ground_truth=None, group=None, hooks=None):
     """cone/inference.py:227-499: writes the prediction files; on the splits the reference scores (Ego4D val,
     MAD val / test) also the metric tables + ``.txt`` file.  Returns the reference's tuple
     ``(results, mIoU, [window, fusion, proposal, matching score strings], latest_file_paths)`` -- ``(None, None,
@@ -1067,7 +1068,12 @@ def eval_epoch(model, *args, epoch_i=None, criterion=None, tb_writer=None, groun
       the training loop (cone/train.py:164-168), can switch imports: the two dataset objects are read once into a
       device-resident store (``FeatureStore.from_datasets``, cached on the intra-window dataset object).
     ``criterion`` / ``tb_writer`` are accepted and ignored: the reference only feeds them eval-loss meters, which
-    need the training criterion (out of scope here)."""
+    need the training criterion (out of scope here).
+
+    ``group`` (a torch.distributed process group; cone_amd extension): every rank of the group calls this with the same
+    (replicated) store and the split runs sharded over the ranks as ``parallel.shard_plan`` prescribes; rank 0 alone prints,
+    writes the files and scores them, and every rank returns rank 0's tuple.  ``hooks``: the per-rank compute of
+    ``cone_amd.parallel`` (default ``HipHooks(model)``)."""
     if isinstance(args[0], FeatureStore):
         store, opt, save_submission_filename = args[0], args[1], args[2]
         rest = args[3:]
@@ -1084,16 +1090,26 @@ def eval_epoch(model, *args, epoch_i=None, criterion=None, tb_writer=None, groun
         store.opt = opt
     if len(rest) > 0 and epoch_i is None:
         epoch_i = rest[0]
+    if group is not None:
+        return _eval_epoch_sharded(model, store, opt, save_submission_filename, epoch_i, ground_truth, group, hooks)
     logger.info("Generate submissions")
     (fusion, proposal, matching), info = predict_split(model, store, opt)
-    print("total model running time: ", info["model_seconds"])
+    if "ann" in info:           # --debug: only the first batch of queries went through the model
+        store = FeatureStore.subset(store, 0, len(info["ann"]))
+    return _write_and_score(model, store, opt, fusion, proposal, matching, info, info["model_seconds"],
+                            save_submission_filename, ground_truth, epoch_i)
+
+
+def _write_and_score(model, store, opt, fusion, proposal, matching, info, model_seconds, save_submission_filename,
+                     ground_truth, epoch_i):
+    """The tail of eval_epoch: the stdout line, the prediction files, and on a scored split the metric tables of the kept rows
+    ``info['rows'] / info['n']`` of the queries of ``store``."""
+    print("total model running time: ", model_seconds)
     paths = write_submissions(opt, fusion, proposal, matching, save_submission_filename)
     scored = opt.eval_split_name == "val" or (opt.dset_name == "mad" and opt.eval_split_name == "test")
     if not scored:
         print("end of inference on test split")
         return None, None, [], paths
-    if "ann" in info:           # --debug: only the first batch of queries went through the model
-        store = FeatureStore.subset(store, 0, len(info["ann"]))
     res, miou, res_p, miou_p, res_m, miou_m, strs = evaluate_split(model, store, opt, info, ground_truth, epoch_i)
     for s_ in strs:
         print(s_, flush=True)
@@ -1115,6 +1131,47 @@ def eval_epoch(model, *args, epoch_i=None, criterion=None, tb_writer=None, groun
     return out_res, (out_miou if opt.dset_name == "ego4d" else None), strs, latest
 
 
+def _eval_epoch_sharded(model, store, opt, save_submission_filename, epoch_i, ground_truth, group, hooks):
+    """eval_epoch over the ranks of ``group``.  Every rank runs its share of the split (``parallel.shard_plan``); the kept rows
+    of ALL queries end on every rank and rank 0 formats, writes and scores them exactly as one GPU does.  Rank 0's tuple -- or
+    the exception it raised -- goes to every rank in one ``broadcast_object_list``; a barrier precedes the return."""
+    import torch.distributed as dist
+    from . import parallel as par
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    if len(store.ann) == 0:     # (raised on every rank, before any collective)
+        raise ValueError("the evaluation split has no queries")
+    if rank == 0:
+        logger.info("Generate submissions")
+    t0 = time.time()
+    plan = par.shard_plan(store, world)
+    if plan == "plain":
+        (fusion, proposal, matching), info = predict_split(model, store, opt)
+        work = FeatureStore.subset(store, 0, len(info["ann"])) if "ann" in info else store
+    else:
+        # --debug (cone/inference.py:93-94): only the first batch of eval_bsz queries is evaluated, written and scored
+        cut = getattr(opt, "debug", False) and len(store.ann) > opt.eval_bsz
+        work = FeatureStore.subset(store, 0, opt.eval_bsz) if cut else store
+        lists, info = par.predict_split_distributed(model, work, opt, mode="window", prefilter=plan, group=group,
+                                                    hooks=hooks, format_shard=False)
+        fusion, proposal, matching = lists if rank == 0 else (None, None, None)
+    out, err = None, None
+    if rank == 0:
+        try:
+            out = _write_and_score(model, work, opt, fusion, proposal, matching, info, time.time() - t0,
+                                   save_submission_filename, ground_truth, epoch_i)
+        except Exception as e:      # noqa: BLE001  -- handed to every rank below, then raised
+            err = e
+    msg = [(out, None if err is None else f"{type(err).__name__}: {err}")]
+    dist.broadcast_object_list(msg, src=dist.get_global_rank(group, 0), group=group)
+    dist.barrier(group=group)
+    out, err_line = msg[0]
+    if err is not None:
+        raise err
+    if err_line is not None:
+        raise RuntimeError(f"rank 0 of the evaluation failed: {err_line}")
+    return out
+
+
 def setup_model(opt):
     """cone/inference.py:502-537 (inference part): build, load ``ckpt["model"]``."""
     model, criterion = build_model(opt)
@@ -1129,9 +1186,37 @@ def setup_model(opt):
 
 
 def start_inference(argv=None):
-    """cone/inference.py:540-607."""
+    """cone/inference.py:540-607.  ``--gpus N`` (cone_amd extension): a plain process with N > 1 starts N ranks of this
+    command through torch.distributed.run and returns their exit status as SystemExit (``cone_amd.launch``); a rank (RANK in
+    the environment) runs eval_epoch over the default process group."""
+    from . import launch
+    argv = sys.argv[1:] if argv is None else list(argv)
+    cli = build_parser().parse_args(argv)       # --gpus / --dist_backend: the command line's, never opt.json's
+    if cli.gpus < 1:
+        launch.fail(f"--gpus must be >= 1, got {cli.gpus}")
+    if not launch.launched_as_rank():
+        if cli.gpus > 1:        # become the launcher: nothing has touched the GPU or loaded libcone_hip.so yet
+            rc = launch.self_launch(cli.gpus, argv)
+            if rc != 0:
+                raise SystemExit(rc)
+            return None
+        return _start_inference(argv)
+    rank, world, local_rank = launch.rank_env()
+    if world != cli.gpus:
+        launch.fail(f"--gpus {cli.gpus} but the launcher started WORLD_SIZE={world} ranks")
+    if os.environ.get("CONE_DIST_LAUNCH_CHECK") == "1":
+        # test-only: rendezvous + preflight on CPU tensors over gloo with the message of one reference batch
+        launch.launch_check((cli.eval_bsz * cli.topk_window, cli.num_queries, 4))
+        return None
+    device = launch.rank_device(local_rank, cli.device)
+    torch.cuda.set_device(device)
+    return _start_inference(argv, rank=rank, device=device)
+
+
+def _start_inference(argv, rank=None, device=None):
+    """The CLI run itself: one process, or -- rank given -- one rank of a torch.distributed.run launch bound to ``device``."""
     logging.basicConfig(format="%(asctime)s.%(msecs)03d:%(levelname)s:%(name)s - %(message)s",
-                        datefmt="%Y-%m-%d %H:%M:%S", level=logging.INFO)
+                        datefmt="%Y-%m-%d %H:%M:%S", level=logging.INFO if not rank else logging.WARNING)
     opt = parse_test_options(argv)
     assert opt.eval_path is not None
     packed = getattr(opt, "packed_features", None)
@@ -1139,8 +1224,21 @@ def start_inference(argv=None):
     model, _, _, _ = setup_model(opt)
     ext = "jsonl" if opt.dset_name == "mad" else "json"
     fn = f"inference_{opt.dset_name}_{opt.eval_split_name}_{opt.eval_id}_preds.{ext}"
-    logger.info("Starting inference...")
-    return eval_epoch(model, store, opt, fn)
+    if rank is None:
+        logger.info("Starting inference...")
+        return eval_epoch(model, store, opt, fn)
+    # every rank has read its inputs (a missing file or a bad split has failed on every rank alike): now the collectives
+    import torch.distributed as dist
+    from . import launch
+    group = launch.init_group(opt.dist_backend, device)
+    try:
+        world = dist.get_world_size(group)
+        n_win = selection(store, opt).n_rows
+        launch.preflight((max(1, -(-n_win // world)), model.num_queries, 4), opt.dist_backend, device=device)
+        logger.info(f"Starting inference on {world} ranks ({opt.dist_backend})...")
+        return eval_epoch(model, store, opt, fn, group=group)
+    finally:
+        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -85,6 +85,36 @@ def prefilter_batched(ctx_arena, cls_norm, plan, max_v_l: int, k: int):
     return idx, fs, ws
 
 
+_ONE_VIDEO_PLANS = {}     # (ctx_l, nq, S, device) -> the prefilter_batched plan of one video and nq queries
+
+
+def prefilter_window_scores(ctx_rows, cls_norm, max_v_l: int):
+    """Window scores (nq, num_windows) of ONE video's adapted + normalised clip rows (ctx_l, dv) for all nq queries, through
+    ``prefilter_batched`` on the plan ``FeatureStore.prefilter_plan`` builds for a split of that one video (groups of up to 4
+    queries over the same rows): the bits of the split-level pre-filter for these rows, whatever nq is.  (``prefilter_scores``
+    switches kernel forms -- another summation order -- with the query count, CONE_PF_MQ_MIN.)"""
+    ctx_l, nq = int(ctx_rows.shape[0]), int(cls_norm.shape[0])
+    S = int(max_v_l / 2)
+    nw = num_windows(ctx_l, max_v_l)
+    key = (ctx_l, nq, S, str(ctx_rows.device))
+    plan = _ONE_VIDEO_PLANS.get(key)
+    if plan is None:
+        ng = -(-nq // 4)
+        q = torch.full((ng * 4,), -1, dtype=torch.int32)
+        q[:nq] = torch.arange(nq, dtype=torch.int32)
+        dev = ctx_rows.device
+        ar = torch.arange(nq, dtype=torch.int64)
+        plan = dict(g_row0=torch.zeros(ng, dtype=torch.int64, device=dev),
+                    g_ctx_l=torch.full((ng,), ctx_l, dtype=torch.int32, device=dev), g_q=q.view(ng, 4).to(dev),
+                    ng=ng, max_ctx_l=ctx_l, q_fs_off=(ar * ctx_l).to(dev), q_win_off=(ar * nw).to(dev),
+                    q_ctx_l=torch.full((nq,), ctx_l, dtype=torch.int32, device=dev), fs_total=nq * ctx_l, win_total=nq * nw)
+        if len(_ONE_VIDEO_PLANS) > 16:
+            _ONE_VIDEO_PLANS.clear()
+        _ONE_VIDEO_PLANS[key] = plan
+    _, _, ws = prefilter_batched(ctx_rows, cls_norm, plan, max_v_l, 1)
+    return ws.view(nq, nw)
+
+
 def topk_windows(win_scores: torch.Tensor, k: int):
     """First k of the stable descending sort of each row (cone/inference.py:297-299, H6)."""
     lib = _lib.load()

@@ -248,17 +248,25 @@ class HipHooks:
         return inf.prefilter(self.model, store, opt)
 
     def ctx_rows(self, store, f_lo: int, f_hi: int):
-        """Adapted + normalised clip rows [f_lo, f_hi) of the (single) video of ``store`` -- what the pre-filter scores
+        """Adapted + normalised clip rows [f_lo, f_hi) of the arena of ``store`` -- what the pre-filter scores
         (cone/inference.py:250-260) -- computed for that range only."""
         from . import ops
+        if f_hi <= f_lo:        # a rank that owns no window
+            return store.vid_raw.new_zeros((0, store.vid_raw.shape[1]))
         return self.model.adapter_norm(ops.l2_normalize(store.vid_raw[f_lo:f_hi], 1e-5))
 
     def cls_norm(self, store):
         from . import ops
         return store.cls_raw if store.cls_normalized else ops.l2_normalize(store.cls_raw, 1e-5)
 
-    window_scores_fn = None     # defaults of prefilter_ctx_sharded: the fused HIP window scores / stable top-k
-    topk_fn = None
+    @staticmethod
+    def window_scores_fn(ctx_local, cls_norm, max_v_l):
+        """The arithmetic of the single-GPU pre-filter (``inference.prefilter`` -> ``ops.prefilter_batched``) on the rank's
+        clip rows, for every query count: the merged rank list is the single-GPU list bit for bit, ties included."""
+        from . import ops
+        return ops.prefilter_window_scores(ctx_local, cls_norm, max_v_l)
+
+    topk_fn = None              # default of prefilter_ctx_sharded: the HIP stable top-k
 
     def project_video(self, store, row_range=None):
         from . import inference as inf
@@ -288,17 +296,32 @@ def _slice_table(wt, lo, hi, q_lo, tok_base):
     return sl
 
 
+def shard_plan(store, world: int) -> str:
+    """How ``inference.eval_epoch(..., group=...)`` runs a split over `world` ranks:
+      * ``"plain"``       -- world 1: ``inference.predict_split``, today's single-GPU path;
+      * ``"ctx"``         -- every query refers to ONE video (the MAD-scale case, BASELINE configs[4]): the pre-filter
+                             sharded along the video (``prefilter_one_video_ctx_sharded``), then the window-sharded model;
+      * ``"replicated"``  -- anything else: the window-sharded model, each rank running stage A only for the eval_bsz-aligned
+                             hull of its own queries (``_window_sharded``).
+    The ``prefilter=`` argument of ``predict_split_distributed`` for the last two."""
+    if world <= 1:
+        return "plain"
+    return "ctx" if len(np.unique(np.asarray(store.q_vid))) == 1 else "replicated"
+
+
 def prefilter_one_video_ctx_sharded(store, opt, hooks, group=None):
     """Stage A of a split that holds ONE long video (BASELINE configs 3 / 5), sharded along ctx_l: this rank adapts,
     normalises and scores only the clip rows its window range covers (``ctx_shard``: 1 / world of the video + a W - S
     halo), keeps a local stable top-k, and ONE all_gather of k (score, window) pairs per query yields the same
     (nq, topk) window table on every rank -- bit-identical to the single-GPU pre-filter, ties included."""
-    if len(store.ctx_l) != 1:
+    vids = np.unique(np.asarray(store.q_vid))
+    if len(vids) != 1:
         raise ValueError("the ctx-sharded pre-filter takes a split over ONE video; several videos shard by query / window")
     rank, world = dist.get_rank(group), dist.get_world_size(group)
-    ctx_l = int(store.ctx_l[0])
+    v = int(vids[0])
+    ctx_l, off = int(store.ctx_l[v]), int(store.vid_off[v])     # (off = 0 unless the store's arena holds other videos too)
     _, _, f_lo, f_hi = ctx_shard(ctx_l, opt.max_v_l, rank, world)
-    ctx_local = hooks.ctx_rows(store, f_lo, f_hi)
+    ctx_local = hooks.ctx_rows(store, off + f_lo, off + f_hi)
     idx, _ = prefilter_ctx_sharded(ctx_local, ctx_l, hooks.cls_norm(store), opt.max_v_l, opt.topk_window, group,
                                    window_scores_fn=getattr(hooks, "window_scores_fn", None),
                                    topk_fn=getattr(hooks, "topk_fn", None))
