@@ -157,6 +157,9 @@ _SIGNATURES = {
     "cone_test_dec_cross_slab_floats": (C.c_size_t, []),
     "cone_test_layernorm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
                                       C.c_void_p]),
+    # cone_test_gen_attn(Q, ldq, K, ldk, V, ldv, OUT, ldo, qoff, koff, B, nq, heads, head_dim, kcap, stream)
+    "cone_test_gen_attn": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                     C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -37,6 +37,21 @@ PRESETS = {
                 topk_window=30, eval_bsz=16),
 }
 
+# Model shapes the library runs (hidden_dim / nheads come from the checkpoint's opt.json, cone/config.py:107,116): 256 / 8,
+# every shipped configuration, on the fused kernels; any other shape of this set on the general-shape path.
+SUPPORTED_SHAPES = ("hidden_dim a multiple of 64 in [64, 512] with head_dim = hidden_dim / nheads in {16, 32, 64} "
+                    "(at most 32 heads)")
+
+
+def check_model_shape(hidden_dim, nheads) -> None:
+    """Raise ValueError unless (hidden_dim, nheads) is in SUPPORTED_SHAPES -- on the host, before any GPU work (the library's
+    cone_model_create checks the same)."""
+    d, h = int(hidden_dim), int(nheads)
+    ok = 64 <= d <= 512 and d % 64 == 0 and h >= 1 and d % h == 0 and d // h in (16, 32, 64)
+    if not ok:
+        raise ValueError(f"unsupported model shape hidden_dim={d} nheads={h}: supported are {SUPPORTED_SHAPES}")
+
+
 EVAL_DEFAULTS = dict(
     nms_thd=-1.0, max_before_nms=200, max_after_nms=5, no_sort_results=False,
     eval_split_name="val", eval_modality="both", save_all=False, debug=False,

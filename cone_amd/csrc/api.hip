@@ -82,6 +82,11 @@ struct cone_model {
                               // matching, as ONE launch each (rows_chain.h: the same arithmetic, bit-identical); 0 = separate launches
     int opt_ffn_fused = 2;    // 1: linear1 + ReLU + linear2 + residual + LayerNorm as one kernel (ffn.hip); 2: the attention
                               // output projection + residual + LayerNorm ahead of it in the same kernel as well; 0: GEMMs
+    // the general-shape path (general.hip: plain LayerNorm / GEMM / attention launches at any supported d / heads): every
+    // handle whose shape is not 256 / 8 (gen_native), or a 256 / 8 handle with option general_shape = 1 (A/B parity only)
+    int gen_native = 0;
+    int opt_general = 0;
+    bool general() const { return gen_native || opt_general; }
 };
 
 namespace cone {
@@ -103,11 +108,13 @@ static int64_t pos_table_rows(int max_v_l) { return (int64_t)max_v_l * (max_v_l 
 
 static int build_model(const cone_weights* w, cone_model** out) {
     CONE_REQUIRE(w && out, "model_create: null argument");
-    CONE_REQUIRE(w->hidden_dim == 256 && w->nheads == 8,
-                 "model_create: unsupported model shape hidden_dim=%d nheads=%d -- the attention / layer-tail kernels of this "
-                 "build are instantiated for hidden_dim 256 with 8 heads (head_dim 32: every shipped CONE configuration, "
-                 "cone/config.py:101-104); also required: dim_feedforward a multiple of 128, num_queries <= 16, feature dims "
-                 "multiples of 32 up to 1024, at most 256 tokens (clips + words) per window", w->hidden_dim, w->nheads);
+    const bool shipped = w->hidden_dim == 256 && w->nheads == 8;
+    CONE_REQUIRE(shipped || gen_shape_supported(w->hidden_dim, w->nheads),
+                 "model_create: unsupported model shape hidden_dim=%d nheads=%d -- supported: hidden_dim a multiple of 64 in "
+                 "[64, 512] with head_dim = hidden_dim / nheads in {16, 32, 64} (256 / 8, every shipped CONE configuration, runs "
+                 "the fused kernels; other shapes the general path); also required: dim_feedforward a multiple of 128, "
+                 "num_queries <= 16, feature dims multiples of 32 up to 1024, at most 256 tokens (clips + words) per window",
+                 w->hidden_dim, w->nheads);
     CONE_REQUIRE(w->dim_ff % 128 == 0 && w->dim_ff >= 128, "model_create: dim_feedforward=%d must be a multiple of 128", w->dim_ff);
     CONE_REQUIRE(w->enc_layers >= 1 && w->enc_layers <= CONE_MAX_LAYERS && w->dec_layers >= 1 &&
                      w->dec_layers <= CONE_MAX_LAYERS, "model_create: layer counts out of range");
@@ -118,10 +125,10 @@ static int build_model(const cone_weights* w, cone_model** out) {
                  "model_create: feature dims must be multiples of 32 and <= 1024 (t=%d v_appear=%d v_motion=%d)", w->t_dim,
                  w->v_dim, w->v_motion_dim);
     cone_model* m = new cone_model();
-    m->d = 256; m->heads = 8; m->ff = w->dim_ff; m->n_enc = w->enc_layers; m->n_dec = w->dec_layers;
+    m->d = w->hidden_dim; m->heads = w->nheads; m->gen_native = !shipped; m->ff = w->dim_ff; m->n_enc = w->enc_layers; m->n_dec = w->dec_layers;
     m->nq = w->num_queries; m->n_proj = w->n_input_proj; m->dt = w->t_dim; m->dv = w->v_dim; m->dvm = w->v_motion_dim;
     m->has_adapter = w->has_adapter;
-    const size_t d = 256, ff = m->ff;
+    const size_t d = m->d, ff = m->ff;
     ArenaBuilder ab;
     auto lin = [&](const cone_linear_w& s, size_t nout, size_t nin, Linear& dst) {
         ab.add(s.w, nout * nin, &dst.w);
@@ -187,8 +194,8 @@ static int build_model(const cone_weights* w, cone_model** out) {
             set_error("model_create: a required weight pointer is null");
             return CONE_E_INVALID;
         }
-    const size_t dec0_floats = (size_t)m->nq * (256 * 2 + 256 + 768 + 256) + 6 * 64 +
-                               (size_t)m->n_dec * (align_up((size_t)m->nq * 768, 64) + align_up((size_t)m->nq * 256, 64));
+    const size_t dec0_floats = (size_t)m->nq * (d * 2 + d + 3 * d + d) + 6 * 64 +
+                               (size_t)m->n_dec * (align_up((size_t)m->nq * 3 * d, 64) + align_up((size_t)m->nq * d, 64));
     const size_t stacked = (size_t)m->n_dec * (d * d + d) * 2 + 4 * 64 + (size_t)m->n_dec * d * d + dec0_floats;
     hipError_t e = hipMalloc((void**)&m->arena, (ab.total + stacked) * sizeof(float));
     if (e != hipSuccess) {
@@ -247,14 +254,14 @@ static int build_model(const cone_weights* w, cone_model** out) {
             m->dec_vT[i] = dst;
         }
     }
-    m->dec0_tgt1 = m->arena + cur; cur += align_up((size_t)m->nq * 256, 64);
-    m->dec0_dq = m->arena + cur; cur += align_up((size_t)m->nq * 256, 64);
-    m->dec0_scratch = m->arena + cur; cur += align_up((size_t)m->nq * (256 + 768 + 256), 64);
+    m->dec0_tgt1 = m->arena + cur; cur += align_up((size_t)m->nq * d, 64);
+    m->dec0_dq = m->arena + cur; cur += align_up((size_t)m->nq * d, 64);
+    m->dec0_scratch = m->arena + cur; cur += align_up((size_t)m->nq * (d + 3 * d + d), 64);
     for (int i = 0; i < m->n_dec; ++i) {
-        m->dec_sa_tab[i] = m->arena + cur; cur += align_up((size_t)m->nq * 768, 64);
-        m->dec_ca_tab[i] = m->arena + cur; cur += align_up((size_t)m->nq * 256, 64);
+        m->dec_sa_tab[i] = m->arena + cur; cur += align_up((size_t)m->nq * 3 * d, 64);
+        m->dec_ca_tab[i] = m->arena + cur; cur += align_up((size_t)m->nq * d, 64);
     }
-    if (d == 256 && ffn_split_supported(m->ff)) {   // split-bf16 images of every layer tail (13 MB at ff = 1024; opt-in path)
+    if (!m->gen_native && ffn_split_supported(m->ff)) {   // split-bf16 images of every layer tail (13 MB at ff = 1024; opt-in path)
         const size_t per = ffn_split_proj_image_bytes() + ffn_split_image_bytes(m->ff);
         const size_t qkv = rows256_split_image_bytes(768);
         e = hipMalloc((void**)&m->split_img, per * (size_t)(m->n_enc + m->n_dec) + qkv * (size_t)m->n_enc);
@@ -291,8 +298,9 @@ static int build_model(const cone_weights* w, cone_model** out) {
         delete m;
         return CONE_E_HIP;
     }
-    {   // the handle's own position tables, for the window lengths this checkpoint is built for (ABI 8: cone_weights.
-        // table_max_v_l; rows (256 + 512 per encoder layer) floats each: 21 MB at 90 clips, 167 MB at 255 with two layers)
+    if (!m->gen_native) {   // the handle's own position tables, for the window lengths this checkpoint is built for (ABI 8: cone_weights.
+        // table_max_v_l; rows (256 + 512 per encoder layer) floats each: 21 MB at 90 clips, 167 MB at 255 with two layers; the
+        // general path, which every other shape runs, reads no tables)
         const int tab_l = (w->table_max_v_l >= 1 && w->table_max_v_l <= CONE_TABLE_MAX_V_L) ? w->table_max_v_l : CONE_TABLE_MAX_V_L;
         const size_t rows = (size_t)pos_table_rows(tab_l);
         e = hipMalloc((void**)&m->tab_arena, rows * (256 + 512 * (size_t)m->n_enc) * sizeof(float));
@@ -341,19 +349,21 @@ static GemmArgs G(const cone_model* m, const float* A, int lda, const float* W, 
 // cone_model).  (2) The first layer on tgt = 0 (:66): its self-attention over the nq slots (q | k | v = the table rows), out_proj
 // + norm1, and its cross-attention queries -- no window enters, so the nq rows are constants too.  Computed with the kernels
 // and the row count (nq) a step uses for one window, hence the same bits as the per-window path (dec0_const = 0).
+// (A handle of another shape than 256 / 8 has the tables only: the general path runs its first decoder layer per window.)
 static int dec0_constants(cone_model* m, hipStream_t s) {
-    const int nq = m->nq;
-    float* TGT = m->dec0_scratch;                       // (nq, 256) zeros
+    const int nq = m->nq, d = m->d;
+    float* TGT = m->dec0_scratch;                       // (nq, d) zeros
     float* QKV = TGT + (size_t)nq * 256;                // (nq, 768)
     float* DATT = QKV + (size_t)nq * 768;               // (nq, 256)
-    CONE_CHECK_HIP(hipMemsetAsync(TGT, 0, (size_t)nq * 256 * sizeof(float), s));
+    CONE_CHECK_HIP(hipMemsetAsync(TGT, 0, (size_t)nq * d * sizeof(float), s));
     for (int l = 0; l < m->n_dec; ++l) {
         const DecLayer& dl = m->dec[l];
         // [qe W_q^T + b_q | qe W_k^T + b_k]  and  b_v rows (0 W_v^T + b_v)
-        RUN(launch_gemm(G(m, m->query_embed, 256, dl.sa.in_w, 256, dl.sa.in_b, m->dec_sa_tab[l], 768, nq, nullptr, 512, 256), s));
-        RUN(launch_gemm(G(m, TGT, 256, dl.sa.in_w + 512 * 256, 256, dl.sa.in_b + 512, m->dec_sa_tab[l] + 512, 768, nq, nullptr, 256, 256), s));
-        RUN(launch_gemm(G(m, m->query_embed, 256, dl.ca.in_w, 256, dl.ca.in_b, m->dec_ca_tab[l], 256, nq, nullptr, 256, 256), s));
+        RUN(launch_gemm(G(m, m->query_embed, d, dl.sa.in_w, d, dl.sa.in_b, m->dec_sa_tab[l], 3 * d, nq, nullptr, 2 * d, d), s));
+        RUN(launch_gemm(G(m, TGT, d, dl.sa.in_w + 2 * d * d, d, dl.sa.in_b + 2 * d, m->dec_sa_tab[l] + 2 * d, 3 * d, nq, nullptr, d, d), s));
+        RUN(launch_gemm(G(m, m->query_embed, d, dl.ca.in_w, d, dl.ca.in_b, m->dec_ca_tab[l], d, nq, nullptr, d, d), s));
     }
+    if (m->gen_native) return 0;
     const DecLayer& d0 = m->dec[0];
     GemmArgs g = G(m, TGT, 256, d0.sa.in_w, 256, nullptr, QKV, 768, nq, nullptr, 768, 256, EPI_RESIDUAL);
     g.R = m->dec_sa_tab[0]; g.ldr = 768; g.r_mod = nq;
@@ -372,6 +382,15 @@ static int dec0_constants(cone_model* m, hipStream_t s) {
 // encoder attention adds unconditionally instead of branching on the token kind
 static int build_pos_tables(const cone_model* m, int max_v_l, float* pos_rows, float* pos_qk, hipStream_t s) {
     const int64_t rows = pos_table_rows(max_v_l);
+    if (m->d != 256) {      // (the same rows d wide: sine rows, zero row, pos [W_q | W_k]^T per encoder layer)
+        const int d = m->d;
+        RUN(launch_gen_pos_rows(m->dim_t, max_v_l, d, pos_rows, s));
+        CONE_CHECK_HIP(hipMemsetAsync(pos_rows + (size_t)(rows - 1) * d, 0, d * sizeof(float), s));
+        for (int l = 0; l < m->n_enc; ++l)
+            RUN(launch_gemm(G(m, pos_rows, d, m->enc[l].sa.in_w, d, nullptr, pos_qk + (size_t)l * rows * 2 * d, 2 * d, (int)rows,
+                              nullptr, 2 * d, d), s));
+        return 0;
+    }
     RUN(launch_pos_rows(m->dim_t, max_v_l, pos_rows, s));
     CONE_CHECK_HIP(hipMemsetAsync(pos_rows + (size_t)(rows - 1) * 256, 0, 256 * sizeof(float), s));    // the zero row
     // pos W_q^T | pos W_k^T of every encoder layer, no bias (the bias travels with the clip / token rows): zero row -> zeros
@@ -385,17 +404,20 @@ static int build_pos_tables(const cone_model* m, int max_v_l, float* pos_rows, f
 // (post-norm, cone/transformer.py:237-239), resp. in_proj(norm1(x)) (--pre_norm, :250-252; tmp = n rows of scratch).
 static int layer0_rows(const cone_model* m, const float* rows, int n, const int* n_dev, float* qkv, float* tmp, hipStream_t s) {
     const float* a = rows;
+    const int d = m->d;
     if (m->pre_norm) {
-        RUN(launch_layernorm(rows, 256, m->enc[0].n1.g, m->enc[0].n1.b, tmp, 256, n, n_dev, 256, s));
+        RUN(launch_layernorm(rows, d, m->enc[0].n1.g, m->enc[0].n1.b, tmp, d, n, n_dev, d, s));
         a = tmp;
     }
-    return launch_gemm(G(m, a, 256, m->enc[0].sa.in_w, 256, m->enc[0].sa.in_b, qkv, 768, n, n_dev, 768, 256), s);
+    return launch_gemm(G(m, a, d, m->enc[0].sa.in_w, d, m->enc[0].sa.in_b, qkv, 3 * d, n, n_dev, 3 * d, d), s);
 }
 
 // input_{vid,txt}_proj: LN -> Linear -> ReLU (all but last) with the next LN fused into the GEMM epilogue.
+// (d != 256: the GEMM's LayerNorm epilogue is instantiated for N == 256 only -- a LayerNorm launch behind the GEMM instead,
+// through a third d-wide buffer)
 static size_t project_ws_bytes(const cone_model* m, int which, int64_t n) {
     const size_t din = which == 0 ? m->dvm : m->dt;
-    return align_up(n * din * 4, 256) + 2 * align_up(n * 256 * 4, 256);
+    return align_up(n * din * 4, 256) + (m->d == 256 ? 2 : 3) * align_up(n * m->d * 4, 256);
 }
 // src_row != null: row i of the projection reads row src_row[i] of x (the valid rows of a zero-padded batch, compacted by the
 // first LayerNorm's loads); n_dev != null: only the first *n_dev rows exist (device-side count, n bounds it)
@@ -405,10 +427,12 @@ static int project_tokens(const cone_model* m, int which, const float* x, int64_
     const int din = which == 0 ? m->dvm : m->dt;
     const LNorm* lns = which == 0 ? m->vproj_ln : m->tproj_ln;
     const Linear* lin = which == 0 ? m->vproj : m->tproj;
+    const int d = m->d;
     Carver c(ws, ws_bytes);
     float* t0 = c.take<float>((size_t)n * din);
-    float* ta = c.take<float>((size_t)n * 256);
-    float* tb = c.take<float>((size_t)n * 256);
+    float* ta = c.take<float>((size_t)n * d);
+    float* tb = c.take<float>((size_t)n * d);
+    float* tc = d == 256 ? nullptr : c.take<float>((size_t)n * d);
     if (!c.ok) { set_error("project: workspace too small (%zu < %zu)", ws_bytes, c.cur); return CONE_E_WORKSPACE; }
     RUN(launch_layernorm(x, din, lns[0].g, lns[0].b, t0, din, n, n_dev, din, s, src_row));
     const float* cur = t0;
@@ -416,11 +440,13 @@ static int project_tokens(const cone_model* m, int which, const float* x, int64_
     for (int i = 0; i < m->n_proj; ++i) {
         const bool last = i == m->n_proj - 1;
         float* dst = last ? out : (cur == ta ? tb : ta);
-        GemmArgs g = G(m, cur, K, lin[i].w, K, lin[i].b, dst, 256, (int)n, n_dev, 256, K, last ? 0 : EPI_RELU);
-        if (!last) { g.flags |= EPI_LN; g.ln_g = lns[i + 1].g; g.ln_b = lns[i + 1].b; }
+        GemmArgs g = G(m, cur, K, lin[i].w, K, lin[i].b, last || tc == nullptr ? dst : tc, d, (int)n, n_dev, d, K,
+                       last ? 0 : EPI_RELU);
+        if (!last && !tc) { g.flags |= EPI_LN; g.ln_g = lns[i + 1].g; g.ln_b = lns[i + 1].b; }
         RUN(launch_gemm(g, s));
+        if (!last && tc) RUN(launch_layernorm(tc, d, lns[i + 1].g, lns[i + 1].b, dst, d, n, n_dev, d, s));
         cur = dst;
-        K = 256;
+        K = d;
     }
     return 0;
 }
@@ -719,6 +745,153 @@ static int forward_packed_prenorm_fused(const cone_model* m, const float* vproj,
     return 0;
 }
 
+// ------------------------------------------------------------------------------ general-shape forward
+// Any supported (d, heads), post-norm and pre-norm (cone/transformer.py:233-260, 296-342), built from plain launches:
+// LayerNorm, row GEMMs with residual / ReLU epilogues, the attention core of general.hip (encoder self-attention over the
+// packed tokens, decoder self-attention over the slots, cross-attention to the window's memory: up to 256 keys), and the
+// d-wide pack / head / saliency kernels.  What it does not fuse: the LayerNorms (own launches, no GEMM epilogue), the layer
+// tails, the decoder's memory K / V projections (two GEMMs over all layers), the first decoder layer (run per window, from
+// tgt = 0, only the slot-position tables are per-checkpoint constants) -- and it reads no layer-0 caches or position tables:
+// q | k take x + pos as the GEMM's second A operand.
+struct GenBuffers {
+    int* off;
+    float *X, *X1, *T1, *POS, *QKV, *ATT, *H, *KD, *VD;
+    float *TGT, *TGT1, *TGT2, *DQK, *DATT, *DQ, *DH, *HS, *S1, *S2, *LG, *SP;
+};
+static void carve_gen(const cone_model* m, Carver& c, int B, int Lmax, GenBuffers& f) {
+    const size_t M = (size_t)B * Lmax, T = (size_t)B * m->nq, nd = m->n_dec, d = m->d;
+    f.off = c.take<int>(B + 1);
+    f.X = c.take<float>(M * d); f.X1 = c.take<float>(M * d); f.T1 = c.take<float>(M * d); f.POS = c.take<float>(M * d);
+    f.QKV = c.take<float>(M * 3 * d); f.ATT = c.take<float>(M * d); f.H = c.take<float>(M * m->ff);
+    f.KD = c.take<float>(M * d * nd); f.VD = c.take<float>(M * d * nd);
+    f.TGT = c.take<float>(T * d); f.TGT1 = c.take<float>(T * d); f.TGT2 = c.take<float>(T * d);
+    f.DQK = c.take<float>(T * 3 * d); f.DATT = c.take<float>(T * d); f.DQ = c.take<float>(T * d); f.DH = c.take<float>(T * m->ff);
+    f.HS = c.take<float>(nd * T * d); f.S1 = c.take<float>(nd * T * d); f.S2 = c.take<float>(nd * T * d);
+    f.LG = c.take<float>(nd * T * 2); f.SP = c.take<float>(nd * T * 2);
+}
+static size_t gen_ws_bytes(const cone_model* m, int B, int Lmax) {
+    Carver c(nullptr, ~(size_t)0);
+    GenBuffers f;
+    carve_gen(m, c, B, Lmax, f);
+    return c.cur;
+}
+
+static int forward_general(const cone_model* m, const float* vproj, const int* vrow0, const int* vlen, const float* tproj,
+                           const int* trow0, const int* qlen, int B, int Lv_max, int Lq_max, float* logits, float* spans,
+                           float* saliency, const cone_taps* taps, void* ws, size_t ws_bytes, hipStream_t s) {
+    const int d = m->d, hd = m->d / m->heads, nh = m->heads;
+    const int Lmax = Lv_max + Lq_max, Mmax = B * Lmax, T = B * m->nq, nd = m->n_dec, ff = m->ff, nq = m->nq;
+    const bool pre = m->pre_norm != 0;
+    Carver c(ws, ws_bytes);
+    GenBuffers f;
+    carve_gen(m, c, B, Lmax, f);
+    if (!c.ok) { set_error("forward: workspace too small (%zu < %zu)", ws_bytes, c.cur); return CONE_E_WORKSPACE; }
+    const int* Mdev = f.off + B;
+    RUN(launch_scan_lengths(vlen, qlen, B, f.off, s));
+    RUN(launch_gen_pack_pos(vproj, vrow0, vlen, tproj, trow0, qlen, f.off, m->dim_t, f.X, f.POS, d, B, Lmax, s, m->txt_pos_emb,
+                            m->txt_pos_ln.g, m->txt_pos_ln.b));
+    GemmArgs g;
+    auto residual = [&](const float* A, int K, const Linear& lin, const float* R, float* C, int M, const int* M_dev) {
+        GemmArgs r = G(m, A, K, lin.w, K, lin.b, C, d, M, M_dev, d, K, EPI_RESIDUAL);   // C = A W^T + b + R
+        r.R = R; r.ldr = d;
+        return launch_gemm(r, s);
+    };
+    for (int l = 0; l < m->n_enc; ++l) {
+        const EncLayer& e = m->enc[l];
+        const float* A = f.X;
+        if (pre) {                                                                                       // src2 = norm1(src)
+            RUN(launch_layernorm(f.X, d, e.n1.g, e.n1.b, f.X1, d, Mmax, Mdev, d, s));
+            A = f.X1;
+        }
+        g = G(m, A, d, e.sa.in_w, d, e.sa.in_b, f.QKV, 3 * d, Mmax, Mdev, 2 * d, d);                    // q | k = (a + pos) W^T
+        g.A2 = f.POS; g.lda2 = d;
+        RUN(launch_gemm(g, s));
+        RUN(launch_gemm(G(m, A, d, e.sa.in_w + 2 * d * d, d, e.sa.in_b + 2 * d, f.QKV + 2 * d, 3 * d, Mmax, Mdev, d, d), s));
+        RUN(launch_gen_attn(f.QKV, 3 * d, f.QKV + d, 3 * d, f.QKV + 2 * d, 3 * d, f.ATT, d, f.off, f.off, B, 0, nh, hd, Lmax, s));
+        if (pre) {
+            RUN(residual(f.ATT, d, e.sa.out, f.X, f.X, Mmax, Mdev));                                      // src += attn
+            RUN(launch_layernorm(f.X, d, e.n2.g, e.n2.b, f.X1, d, Mmax, Mdev, d, s));                     // src2 = norm2(src)
+            RUN(launch_gemm(G(m, f.X1, d, e.l1.w, d, e.l1.b, f.H, ff, Mmax, Mdev, ff, d, EPI_RELU), s));
+            RUN(residual(f.H, ff, e.l2, f.X, f.X, Mmax, Mdev));                                           // src += ffn(src2)
+        } else {
+            RUN(residual(f.ATT, d, e.sa.out, f.X, f.T1, Mmax, Mdev));
+            RUN(launch_layernorm(f.T1, d, e.n1.g, e.n1.b, f.X1, d, Mmax, Mdev, d, s));                    // norm1(src + attn)
+            RUN(launch_gemm(G(m, f.X1, d, e.l1.w, d, e.l1.b, f.H, ff, Mmax, Mdev, ff, d, EPI_RELU), s));
+            RUN(residual(f.H, ff, e.l2, f.X1, f.T1, Mmax, Mdev));
+            RUN(launch_layernorm(f.T1, d, e.n2.g, e.n2.b, f.X, d, Mmax, Mdev, d, s));                     // norm2(src + ffn)
+        }
+    }
+    const float* MEM = f.X;
+    if (pre) {                                                                                           // memory = encoder.norm(src)
+        RUN(launch_layernorm(f.X, d, m->enc_norm.g, m->enc_norm.b, f.X1, d, Mmax, Mdev, d, s));
+        MEM = f.X1;
+    }
+    // decoder keys / values of all layers: k = (memory + pos) W_k^T + b_k, v = memory W_v^T + b_v (cone/transformer.py:308-311)
+    g = G(m, MEM, d, m->dec_k.w, d, m->dec_k.b, f.KD, d * nd, Mmax, Mdev, d * nd, d);
+    g.A2 = f.POS; g.lda2 = d;
+    RUN(launch_gemm(g, s));
+    RUN(launch_gemm(G(m, MEM, d, m->dec_v.w, d, m->dec_v.b, f.VD, d * nd, Mmax, Mdev, d * nd, d), s));
+    CONE_CHECK_HIP(hipMemsetAsync(f.TGT, 0, (size_t)T * d * sizeof(float), s));                          // tgt = 0 (:66)
+    auto ln = [&](const float* x, const LNorm& n, float* out) { return launch_layernorm(x, d, n.g, n.b, out, d, T, nullptr, d, s); };
+    for (int l = 0; l < nd; ++l) {
+        const DecLayer& dl = m->dec[l];
+        // self-attention: q | k | v = a W^T + the slot-position table (q, k: (a + query_pos) W^T + b; v: a W_v^T + b_v)
+        const float* A = f.TGT;
+        if (pre) { RUN(ln(f.TGT, dl.n1, f.TGT1)); A = f.TGT1; }
+        g = G(m, A, d, dl.sa.in_w, d, nullptr, f.DQK, 3 * d, T, nullptr, 3 * d, d, EPI_RESIDUAL);
+        g.R = m->dec_sa_tab[l]; g.ldr = 3 * d; g.r_mod = nq;
+        RUN(launch_gemm(g, s));
+        RUN(launch_gen_attn(f.DQK, 3 * d, f.DQK + d, 3 * d, f.DQK + 2 * d, 3 * d, f.DATT, d, nullptr, nullptr, B, nq, nh, hd, nq, s));
+        if (pre) {
+            RUN(residual(f.DATT, d, dl.sa.out, f.TGT, f.TGT, T, nullptr));                                // tgt += sa
+            RUN(ln(f.TGT, dl.n2, f.TGT1)); A = f.TGT1;                                                    // tgt2 = norm2(tgt)
+        } else {
+            RUN(residual(f.DATT, d, dl.sa.out, f.TGT, f.TGT2, T, nullptr));
+            RUN(ln(f.TGT2, dl.n1, f.TGT)); A = f.TGT;                                                     // tgt = norm1(tgt + sa)
+        }
+        // cross-attention: query (a + query_pos) W_q^T + b_q = a W_q^T + the table; keys / values of this layer from KD / VD
+        g = G(m, A, d, dl.ca.in_w, d, nullptr, f.DQ, d, T, nullptr, d, d, EPI_RESIDUAL);
+        g.R = m->dec_ca_tab[l]; g.ldr = d; g.r_mod = nq;
+        RUN(launch_gemm(g, s));
+        RUN(launch_gen_attn(f.DQ, d, f.KD + (size_t)l * d, d * nd, f.VD + (size_t)l * d, d * nd, f.DATT, d, nullptr, f.off, B, nq, nh,
+                            hd, Lmax, s));
+        if (pre) {
+            RUN(residual(f.DATT, d, dl.ca.out, f.TGT, f.TGT, T, nullptr));                                // tgt += ca
+            RUN(ln(f.TGT, dl.n3, f.TGT1));                                                                // tgt2 = norm3(tgt)
+            RUN(launch_gemm(G(m, f.TGT1, d, dl.l1.w, d, dl.l1.b, f.DH, ff, T, nullptr, ff, d, EPI_RELU), s));
+            RUN(residual(f.DH, ff, dl.l2, f.TGT, f.TGT, T, nullptr));                                     // tgt += ffn(tgt2)
+        } else {
+            RUN(residual(f.DATT, d, dl.ca.out, f.TGT, f.TGT2, T, nullptr));
+            RUN(ln(f.TGT2, dl.n2, f.TGT1));                                                               // tgt = norm2(tgt + ca)
+            RUN(launch_gemm(G(m, f.TGT1, d, dl.l1.w, d, dl.l1.b, f.DH, ff, T, nullptr, ff, d, EPI_RELU), s));
+            RUN(residual(f.DH, ff, dl.l2, f.TGT1, f.TGT2, T, nullptr));
+            RUN(ln(f.TGT2, dl.n3, f.TGT));                                                                // tgt = norm3(tgt + ffn)
+        }
+        RUN(ln(f.TGT, m->dec_norm, f.HS + (size_t)l * T * d));                                            // decoder.norm (intermediate)
+    }
+    // heads (cone/model.py:112-117), every layer (aux_outputs), the last layer's rows out
+    const int HT = nd * T;
+    RUN(launch_gen_rowdot(f.HS, d, m->class_embed.w, m->class_embed.b, f.LG, 2, HT, 2, 0, d, s));
+    RUN(launch_gemm(G(m, f.HS, d, m->span[0].w, d, m->span[0].b, f.S1, d, HT, nullptr, d, d, EPI_RELU), s));
+    RUN(launch_gemm(G(m, f.S1, d, m->span[1].w, d, m->span[1].b, f.S2, d, HT, nullptr, d, d, EPI_RELU), s));
+    RUN(launch_gen_rowdot(f.S2, d, m->span[2].w, m->span[2].b, f.SP, 2, HT, 2, 1, d, s));
+    const size_t last = (size_t)(nd - 1) * T * 2;
+    CONE_CHECK_HIP(hipMemcpyAsync(logits, f.LG + last, (size_t)T * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    CONE_CHECK_HIP(hipMemcpyAsync(spans, f.SP + last, (size_t)T * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (taps) {
+        if (taps->hs)
+            CONE_CHECK_HIP(hipMemcpyAsync(taps->hs, f.HS, (size_t)nd * T * d * sizeof(float), hipMemcpyDeviceToDevice, s));
+        if (taps->aux_logits && nd > 1)
+            CONE_CHECK_HIP(hipMemcpyAsync(taps->aux_logits, f.LG, last * sizeof(float), hipMemcpyDeviceToDevice, s));
+        if (taps->aux_spans && nd > 1)
+            CONE_CHECK_HIP(hipMemcpyAsync(taps->aux_spans, f.SP, last * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
+    if (saliency || (taps && taps->memory))
+        RUN(launch_gen_saliency(MEM, f.off, vlen, qlen, m->saliency.w, m->saliency.b, saliency, Lv_max, taps ? taps->memory : nullptr,
+                                Lq_max, B, d, s));
+    return 0;
+}
+
 static int forward_packed(const cone_model* m, const float* vproj, const int* vrow0, const int* vlen,
                           const float* tproj, const int* trow0, const int* qlen, int B, int Lv_max, int Lq_max,
                           float* logits, float* spans, float* saliency, const cone_taps* taps, void* ws,
@@ -727,6 +900,14 @@ static int forward_packed(const cone_model* m, const float* vproj, const int* vr
     const int Lmax = Lv_max + Lq_max;
     CONE_REQUIRE(Lmax <= CONE_MAX_WINDOW_TOKENS, "forward: window length %d + %d exceeds %d tokens", Lv_max, Lq_max,
                  CONE_MAX_WINDOW_TOKENS);
+    if (m->general()) {     // (any window length up to the limit; no layer-0 caches or tables read)
+        CONE_REQUIRE((int64_t)B * Lmax < (1ll << 24), "forward: batch too large (B * L >= 2^24 tokens)");
+        if (m->txt_pos_emb)
+            CONE_REQUIRE(Lq_max <= m->txt_pos_rows, "forward: %d text tokens but txt_position_embed has %d rows (max_q_l)", Lq_max,
+                         m->txt_pos_rows);
+        return forward_general(m, vproj, vrow0, vlen, tproj, trow0, qlen, B, Lv_max, Lq_max, logits, spans, saliency, taps, ws,
+                               ws_bytes, s);
+    }
     // beyond 192 tokens only the default path exists (the 256-key forms of the encoder attention and of the folded cross-
     // attention): the A/B forms and the unfolded decoder stop at 192 keys
     CONE_REQUIRE(Lmax <= 192 || (m->opt_dec_fold >= 2 && dec_cross_mfma_supported(m->nq, Lmax, true) && !m->txt_pos_emb &&
@@ -1042,7 +1223,7 @@ extern "C" void cone_model_destroy(cone_model* m) {
 }
 
 extern "C" size_t cone_adapter_norm_workspace(const cone_model* m, int64_t n_rows) {
-    return align_up((size_t)n_rows * 256 * 4, 256) + align_up((size_t)n_rows * m->dv * 4, 256);
+    return align_up((size_t)n_rows * m->d * 4, 256) + align_up((size_t)n_rows * m->dv * 4, 256);
 }
 extern "C" int cone_adapter_norm(const cone_model* m, const float* x, int64_t n_rows, float* out, int renorm,
                                  void* ws, size_t ws_bytes, void* stream) {
@@ -1055,12 +1236,13 @@ extern "C" int cone_adapter_norm(const cone_model* m, const float* x, int64_t n_
         return 0;
     }
     Carver c(ws, ws_bytes);
-    float* h = c.take<float>((size_t)n_rows * 256);
+    const int d = m->d;       // the adapter's hidden width is hidden_dim (cone/model.py:80)
+    float* h = c.take<float>((size_t)n_rows * d);
     float* y = c.take<float>((size_t)n_rows * m->dv);
     if (!c.ok) { set_error("adapter_norm: workspace too small (%zu < %zu)", ws_bytes, c.cur); return CONE_E_WORKSPACE; }
-    RUN(launch_gemm(G(m, x, m->dv, m->adapter[0].w, m->dv, m->adapter[0].b, h, 256, (int)n_rows, nullptr, 256, m->dv, EPI_RELU), s));
-    GemmArgs g = G(m, h, 256, m->adapter[1].w, 256, m->adapter[1].b, renorm ? y : out, m->dv, (int)n_rows, nullptr, m->dv,
-                   256, EPI_RESIDUAL);
+    RUN(launch_gemm(G(m, x, m->dv, m->adapter[0].w, m->dv, m->adapter[0].b, h, d, (int)n_rows, nullptr, d, m->dv, EPI_RELU), s));
+    GemmArgs g = G(m, h, d, m->adapter[1].w, d, m->adapter[1].b, renorm ? y : out, m->dv, (int)n_rows, nullptr, m->dv,
+                   d, EPI_RESIDUAL);
     g.R = x; g.ldr = m->dv;
     RUN(launch_gemm(g, s));
     if (!renorm) return 0;                       // run_on_video/cone_localizator.py:135-138 keeps the raw sum
@@ -1084,6 +1266,7 @@ extern "C" int cone_project_tokens(const cone_model* m, int which, const float* 
 
 extern "C" size_t cone_forward_packed_workspace(const cone_model* m, int B, int Lv_max, int Lq_max,
                                                 const cone_layer0* l0) {
+    if (m->general()) return gen_ws_bytes(m, B, Lv_max + Lq_max);
     cone_layer0 eff;
     FwdPlan plan;
     resolve_l0(m, l0, Lv_max, Lv_max + Lq_max, &eff, &plan);
@@ -1111,11 +1294,16 @@ extern "C" int cone_pos_tables(const cone_model* m, int max_v_l, float* pos_rows
 // (rows of a GEMM are independent: an arena row and the same token as a compact row of the padded entry get the same bits)
 static int text_positions(const cone_model* m, const float* tproj, const int* tok_index, const int* src_row, int mod, int n,
                           const int* n_dev, float* txt_pos, float* txt_pos_qk, hipStream_t s) {
-    RUN(launch_txt_pos_rows(tproj, tok_index, src_row, mod, m->txt_pos_rows, m->txt_pos_emb, m->txt_pos_ln.g, m->txt_pos_ln.b, n,
-                            n_dev, txt_pos, s));
+    const int d = m->d;
+    if (d == 256)
+        RUN(launch_txt_pos_rows(tproj, tok_index, src_row, mod, m->txt_pos_rows, m->txt_pos_emb, m->txt_pos_ln.g, m->txt_pos_ln.b, n,
+                                n_dev, txt_pos, s));
+    else
+        RUN(launch_gen_txt_pos_rows(tproj, tok_index, src_row, mod, m->txt_pos_rows, m->txt_pos_emb, m->txt_pos_ln.g, m->txt_pos_ln.b,
+                                    n, n_dev, d, txt_pos, s));
     for (int l = 0; l < m->n_enc; ++l)
-        RUN(launch_gemm(G(m, txt_pos, 256, m->enc[l].sa.in_w, 256, nullptr, txt_pos_qk + (size_t)l * n * 512, 512, n, n_dev, 512,
-                          256), s));
+        RUN(launch_gemm(G(m, txt_pos, d, m->enc[l].sa.in_w, d, nullptr, txt_pos_qk + (size_t)l * n * 2 * d, 2 * d, n, n_dev, 2 * d,
+                          d), s));
     return 0;
 }
 extern "C" int cone_layer0_text_positions(const cone_model* m, const float* txt_proj_rows, const int32_t* tok_index,
@@ -1127,7 +1315,7 @@ extern "C" int cone_layer0_text_positions(const cone_model* m, const float* txt_
 }
 
 extern "C" size_t cone_layer0_project_workspace(const cone_model* m, int64_t n_rows) {
-    return m && m->pre_norm ? align_up((size_t)n_rows * 256 * 4, 256) : 0;
+    return m && m->pre_norm ? align_up((size_t)n_rows * m->d * 4, 256) : 0;
 }
 extern "C" int cone_layer0_project(const cone_model* m, const float* proj_rows, int64_t n_rows, float* qkv, void* ws,
                                    size_t ws_bytes, void* stream) {
@@ -1152,7 +1340,7 @@ static void carve_padded(const cone_model* m, Carver& c, int B, int Lv_pad, int 
     const size_t nv = (size_t)B * Lv_pad, nt = (size_t)B * Lq_pad;
     p.voff = c.take<int>(B + 1); p.toff = c.take<int>(B + 1);
     p.vidx = c.take<int>(nv); p.tidx = c.take<int>(nt);
-    p.vp = c.take<float>(nv * 256); p.tp = c.take<float>(nt * 256);
+    p.vp = c.take<float>(nv * m->d); p.tp = c.take<float>(nt * m->d);
     p.qv = p.qt = p.pt = p.ptqk = nullptr;
     if (caches) { p.qv = c.take<float>(nv * 768); p.qt = c.take<float>(nt * 768); }
     if (txt_tables) { p.pt = c.take<float>(nt * 256); p.ptqk = c.take<float>((size_t)m->n_enc * nt * 512); }   // --use_txt_pos
@@ -1164,6 +1352,10 @@ static void carve_padded(const cone_model* m, Carver& c, int B, int Lv_pad, int 
 // What the padded entry runs on: the handle's tables, first-layer row caches it builds itself, and for a --use_txt_pos model
 // the text position rows it builds itself (such a model off the table path: nothing of it -- the general path)
 static FwdPlan padded_plan(const cone_model* m, int Lv_pad, int Lmax, bool* caches, bool* txt_tables) {
+    if (m->general()) {         // the general path: the compact projected rows only
+        *caches = *txt_tables = false;
+        return FwdPlan{};
+    }
     cone_layer0 eff;
     const cone_layer0* l0 = effective_l0(m, nullptr, Lv_pad, &eff, true);
     *caches = l0 && m->opt_pos_tables && m->opt_l0_gather;
@@ -1178,7 +1370,7 @@ extern "C" size_t cone_forward_workspace(const cone_model* m, int B, int Lv_pad,
     Carver c(nullptr, ~(size_t)0);
     PaddedCarve p;
     carve_padded(m, c, B, Lv_pad, Lq_pad, caches, txt_tables, p);
-    return c.cur + fwd_ws_bytes(m, B, Lv_pad + Lq_pad, plan);
+    return c.cur + (m->general() ? gen_ws_bytes(m, B, Lv_pad + Lq_pad) : fwd_ws_bytes(m, B, Lv_pad + Lq_pad, plan));
 }
 extern "C" int cone_forward_windows(const cone_model* m, const float* vid, const int32_t* vid_len, const float* txt,
                                     const int32_t* txt_len, int B, int Lv_pad, int Lq_pad, float* logits,
@@ -1217,7 +1409,7 @@ extern "C" int cone_forward_windows(const cone_model* m, const float* vid, const
 
 extern "C" size_t cone_clip_matching_workspace(const cone_model* m, int B) {
     const size_t T = (size_t)B * m->nq;
-    return 2 * align_up(T * m->dv * 4, 256) + align_up(T * 256 * 4, 256) + 3 * align_up((size_t)B * 4, 256);
+    return 2 * align_up(T * m->dv * 4, 256) + align_up(T * m->d * 4, 256) + 3 * align_up((size_t)B * 4, 256);
 }
 extern "C" int cone_clip_matching_gathered(const cone_model* m, const float* cls, const int32_t* cls_row,
                                            const float* vid, const int32_t* vid_row0, const int32_t* vid_len,
@@ -1226,15 +1418,15 @@ extern "C" int cone_clip_matching_gathered(const cone_model* m, const float* cls
     CONE_REQUIRE(m && cls && vid && vid_row0 && vid_len && pad_len && spans && match, "clip_matching: null argument");
     if (B <= 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    const int T = B * m->nq, dv = m->dv;
+    const int T = B * m->nq, dv = m->dv, d = m->d;
     Carver c(ws, ws_bytes);
     float* pf = c.take<float>((size_t)T * dv);
     float* pa = c.take<float>((size_t)T * dv);
-    float* h = c.take<float>((size_t)T * 256);
+    float* h = c.take<float>((size_t)T * d);
     if (!c.ok) { set_error("clip_matching: workspace too small (%zu < %zu)", ws_bytes, c.cur); return CONE_E_WORKSPACE; }
     RUN(launch_proposal_mean(vid, vid_row0, vid_len, pad_len, spans, B, m->nq, dv, pf, s));
     const float* feat = pf;
-    if (m->has_adapter && dv == 256 && m->opt_chain && m->opt_gemm == GEMM_AUTO && rows_chain_supported(T) &&
+    if (m->has_adapter && dv == 256 && d == 256 && m->opt_chain && m->opt_gemm == GEMM_AUTO && rows_chain_supported(T) &&
         !(m->opt_spread && gemm_rows_spread_rows(T))) {
         ChainArgs ca{};     // few proposals: both adapter layers in one launch (rows_chain.h; the same arithmetic)
         ca.A = pf; ca.lda = dv; ca.M = T; ca.n_stages = 2;
@@ -1244,8 +1436,8 @@ extern "C" int cone_clip_matching_gathered(const cone_model* m, const float* cls
         RUN(launch_rows_chain(ca, s));
         feat = pa;
     } else if (m->has_adapter) {
-        RUN(launch_gemm(G(m, pf, dv, m->adapter[0].w, dv, m->adapter[0].b, h, 256, T, nullptr, 256, dv, EPI_RELU), s));
-        GemmArgs g = G(m, h, 256, m->adapter[1].w, 256, m->adapter[1].b, pa, dv, T, nullptr, dv, 256, EPI_RESIDUAL);
+        RUN(launch_gemm(G(m, pf, dv, m->adapter[0].w, dv, m->adapter[0].b, h, d, T, nullptr, d, dv, EPI_RELU), s));
+        GemmArgs g = G(m, h, d, m->adapter[1].w, d, m->adapter[1].b, pa, dv, T, nullptr, dv, d, EPI_RESIDUAL);
         g.R = pf; g.ldr = dv;
         RUN(launch_gemm(g, s));
         feat = pa;
@@ -1288,8 +1480,15 @@ extern "C" int cone_model_set_option(cone_model* m, const char* name, int value)
         m->opt_qkv_fused = value;
         return 0;
     }
+    if (!strcmp(name, "general_shape")) {
+        // 1: a 256 / 8 handle runs the general-shape path (A/B parity only); 0: the shipped path (a handle of any other shape
+        // has only the general path, whatever the value)
+        m->opt_general = value != 0;
+        return 0;
+    }
     if (!strcmp(name, "split_bf16")) {
-        CONE_REQUIRE(value == 0 || m->split_img, "set_option: split_bf16 needs hidden_dim 256 and dim_feedforward %% 32 == 0 (<= 2048)");
+        CONE_REQUIRE(value == 0 || m->split_img, "set_option: split_bf16 needs hidden_dim 256 with 8 heads and dim_feedforward %% 32 == 0 "
+                     "(<= 2048); this handle is hidden_dim %d with %d heads, dim_feedforward %d", m->d, m->heads, m->ff);
         m->opt_split_bf16 = value != 0;
         return 0;
     }
@@ -1389,4 +1588,9 @@ extern "C" size_t cone_test_dec_cross_slab_floats(void) { return dec_cross_mfma_
 extern "C" int cone_test_layernorm(const float* x, const float* g, const float* b, float* out, int64_t n_rows,
                                    int dim, void* stream) {
     return launch_layernorm(x, dim, g, b, out, dim, n_rows, nullptr, dim, (hipStream_t)stream);
+}
+extern "C" int cone_test_gen_attn(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* OUT, int ldo,
+                                  const int32_t* qoff, const int32_t* koff, int B, int nq, int heads, int head_dim, int kcap,
+                                  void* stream) {
+    return launch_gen_attn(Q, ldq, K, ldk, V, ldv, OUT, ldo, qoff, koff, B, nq, heads, head_dim, kcap, (hipStream_t)stream);
 }

@@ -288,4 +288,23 @@ int launch_proposal_mean(const float* vid, const int* vrow0, const int* vlen, co
 int launch_cosine_match(const float* pf, const float* cls, const int* cls_row, int B, int Nq, int dv, float* match,
                         hipStream_t s);
 
+// ---------------------------------------------------------------- general-shape path (general.hip)
+// hidden_dim d a multiple of 64 in [64, 512], head_dim = d / heads in {16, 32, 64}
+bool gen_shape_supported(int d, int heads);
+// Attention core, one workgroup per (window, head): query rows qoff[b] .. qoff[b + 1] (qoff == null: the nq slot rows b * nq ..),
+// key / value rows likewise from koff; kcap >= the longest key count (<= 256); OUT rows as the query rows, columns h * hd ..
+int launch_gen_attn(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* OUT, int ldo,
+                    const int* qoff, const int* koff, int B, int nq, int heads, int hd, int kcap, hipStream_t s);
+// d-wide forms of launch_pack_pos (X and POS only), launch_pos_rows, launch_txt_pos_rows, launch_rowdot, launch_saliency
+int launch_gen_pack_pos(const float* vproj, const int* vrow0, const int* vlen, const float* tproj, const int* trow0,
+                        const int* qlen, const int* off, const float* dim_t, float* X, float* POS, int d, int B, int Lmax,
+                        hipStream_t s, const float* tpe = nullptr, const float* tpg = nullptr, const float* tpb = nullptr);
+int launch_gen_pos_rows(const float* dim_t, int max_v_l, int d, float* out, hipStream_t s);
+int launch_gen_txt_pos_rows(const float* tproj, const int* tok_index, const int* src_row, int mod, int n_emb, const float* tpe,
+                            const float* tpg, const float* tpb, int n, const int* n_dev, int d, float* out, hipStream_t s);
+int launch_gen_rowdot(const float* X, int ldx, const float* W, const float* b, float* out, int ldo, int64_t n_rows, int nout,
+                      int act, int d, hipStream_t s);
+int launch_gen_saliency(const float* MEM, const int* off, const int* vlen, const int* qlen, const float* w, const float* bias,
+                        float* sal, int Lv_out, float* mem_tap, int Lq_out, int B, int d, hipStream_t s);
+
 }  // namespace cone

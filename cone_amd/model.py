@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .config import check_model_shape
 from .synth import state_dict_spec
 
 import os as _os
@@ -65,6 +66,7 @@ class CONE:
         self.aux_loss = getattr(args, "aux_loss", True)
         self.n_input_proj = args.n_input_proj
         self.hidden_dim = args.hidden_dim
+        check_model_shape(args.hidden_dim, getattr(args, "nheads", 8))      # an unsupported checkpoint fails here, not on the GPU
         self.device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
         self._handle = None
         self._sd = None

@@ -500,6 +500,13 @@ int cone_test_dec_cross(const float* DQ, const float* X, const float* pos_rows, 
 size_t cone_test_dec_cross_slab_floats(void);
 int cone_test_layernorm(const float* x, const float* g, const float* b, float* out, int64_t n_rows,
                         int dim, void* stream);
+/* Attention core of the general-shape path (any hidden_dim / nheads with head_dim in {16, 32, 64}): one workgroup per
+ * (window b, head).  Query rows qoff[b] .. qoff[b + 1] of Q (qoff == NULL: the nq rows b * nq ..), key / value rows koff[b] ..
+ * koff[b + 1] of K / V (koff == NULL: b * nq ..); head h reads / writes columns h * head_dim ..  OUT = softmax(q k^T /
+ * sqrt(head_dim)) v per query row, ahead of out_proj; a window without queries or keys writes nothing.  kcap >= the longest key
+ * count, <= 256 (CONE_MAX_WINDOW_TOKENS). */
+int cone_test_gen_attn(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* OUT, int ldo,
+                       const int32_t* qoff, const int32_t* koff, int B, int nq, int heads, int head_dim, int kcap, void* stream);
 
 #ifdef __cplusplus
 }
