@@ -18,7 +18,7 @@ from types import SimpleNamespace
 CLI_WINS = ("eval_path", "eval_split_name", "results_root", "num_workers", "nms_thd",
             "debug", "save_all", "max_before_nms", "max_after_nms", "max_pred_l",
             "min_pred_l", "eval_bsz", "data_ratio", "topk_window", "resume",
-            "resume_all", "no_sort_results", "packed_features", "split_bf16", "gpus", "dist_backend")
+            "resume_all", "no_sort_results", "packed_features", "split_bf16", "bf16", "gpus", "dist_backend")
 
 MODEL_DEFAULTS = dict(
     hidden_dim=256, nheads=8, dim_feedforward=1024, enc_layers=2, dec_layers=2,
@@ -95,6 +95,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="(cone_amd extension, opt-in) transformer layer tails on the bf16 matrix cores: every fp32 product as "
                         "six partial products of three-piece bf16 operands, fp32 accumulation -- fp32-MFMA accuracy "
                         "(measured against float64), ~1.3x the step rate; the default computes them on the fp32 MFMA")
+    p.add_argument("--bf16", action="store_true",
+                   help="(cone_amd extension, opt-in; excludes --split_bf16) the layer-tail GEMMs (attention output projection, "
+                        "linear1, linear2, q|k|v projections) with operands rounded once to bf16 and fp32 accumulation, one "
+                        "matrix-core product each; bias, ReLU, residual, LayerNorm, attention, heads and activations in memory "
+                        "stay fp32.  Stage A (pre-filter, window ranking) is unchanged, so the same windows are selected; only "
+                        "stage-B values differ, within the reference model's own bf16-autocast error")
     p.add_argument("--gpus", type=int, default=1,
                    help="(cone_amd extension) evaluate the split sharded over N GPUs of this node: a plain process starts "
                         "N ranks through torch.distributed.run; under torchrun it must equal WORLD_SIZE.  Rank 0 writes the files")

@@ -76,6 +76,13 @@ struct cone_model {
                               // the split_bf16 path (-0.3 ms), 2 = on the exact-fp32 path too (neutral), 0 = own launch
     int opt_split_bf16 = 0;   // OPT-IN: layer tails on the bf16 matrix cores (six partial products of three-piece operands,
                               // fp32 accumulation: fp32-MFMA accuracy); 0 = exact-fp32 MFMA (default)
+    // the single-piece images of the same weights (ffn_bf16.hip: the high piece only, one third of the bytes) and their switch
+    char* bf16_img = nullptr;
+    const void* enc_wo_img1[CONE_MAX_LAYERS] = {}; const void* enc_ffn_img1[CONE_MAX_LAYERS] = {};
+    const void* enc_qkv_img1[CONE_MAX_LAYERS] = {};
+    const void* dec_wo_img1[CONE_MAX_LAYERS] = {}; const void* dec_ffn_img1[CONE_MAX_LAYERS] = {};
+    int opt_bf16 = 0;         // OPT-IN: the same GEMMs with operands rounded ONCE to bf16, one MFMA per operand pair, fp32
+                              // accumulation (plain bf16 matrix arithmetic: NOT fp32-accurate); excludes split_bf16
     int opt_res_gather = 1;   // first encoder layer's residual rows gathered by the fused layer tail (no packed input copy)
     int opt_spread = 1;       // <= 16 row groups in a decoder tail: the spread form (four launches over single-wave workgroups)
     int opt_chain = 1;        // few rows: decoder.norm + class head + span MLP + span head, and the adapter pair of the proposal
@@ -284,16 +291,41 @@ static int build_model(const cone_weights* w, cone_model** out) {
             (enc ? m->enc_ffn_img : m->dec_ffn_img)[l] = ip + ffn_split_proj_image_bytes();
             ip += per;
         }
+        // the single-piece images of the same weights, in the same order (4.4 MB at ff = 1024; option bf16)
+        const size_t per1 = ffn_bf16_proj_image_bytes() + ffn_bf16_image_bytes(m->ff);
+        const size_t qkv1 = rows256_bf16_image_bytes(768);
+        if (e == hipSuccess && rc == 0)
+            e = hipMalloc((void**)&m->bf16_img, per1 * (size_t)(m->n_enc + m->n_dec) + qkv1 * (size_t)m->n_enc);
+        ip = m->bf16_img;
+        for (int l = 0; l < m->n_enc && e == hipSuccess && rc == 0; ++l) {
+            rc = launch_ffn_bf16_pack(m->enc[l].sa.in_w, nullptr, 768, ip, nullptr);
+            m->enc_qkv_img1[l] = ip;
+            ip += qkv1;
+        }
+        for (int i = 0; i < m->n_enc + m->n_dec && e == hipSuccess && rc == 0; ++i) {
+            const bool enc = i < m->n_enc;
+            const int l = enc ? i : i - m->n_enc;
+            const float* wo = enc ? m->enc[l].sa.out.w : m->dec[l].ca.out.w;
+            const Linear& l1 = enc ? m->enc[l].l1 : m->dec[l].l1;
+            const Linear& l2 = enc ? m->enc[l].l2 : m->dec[l].l2;
+            rc = launch_ffn_bf16_pack(wo, nullptr, 256, ip, nullptr);
+            if (rc == 0) rc = launch_ffn_bf16_pack(l1.w, l2.w, m->ff, ip + ffn_bf16_proj_image_bytes(), nullptr);
+            (enc ? m->enc_wo_img1 : m->dec_wo_img1)[l] = ip;
+            (enc ? m->enc_ffn_img1 : m->dec_ffn_img1)[l] = ip + ffn_bf16_proj_image_bytes();
+            ip += per1;
+        }
         if (e != hipSuccess || rc != 0 || hipDeviceSynchronize() != hipSuccess) {
             if (m->split_img) (void)hipFree(m->split_img);
+            if (m->bf16_img) (void)hipFree(m->bf16_img);
             (void)hipFree(m->arena);
             delete m;
-            if (rc == 0) set_error("model_create: building the split-bf16 weight images failed");
+            if (rc == 0) set_error("model_create: building the split-bf16 / bf16 weight images failed");
             return CONE_E_HIP;
         }
     }
     if (dec0_constants(m, nullptr) != 0 || hipDeviceSynchronize() != hipSuccess) {
         if (m->split_img) (void)hipFree(m->split_img);
+        if (m->bf16_img) (void)hipFree(m->bf16_img);
         (void)hipFree(m->arena);
         delete m;
         return CONE_E_HIP;
@@ -310,6 +342,7 @@ static int build_model(const cone_weights* w, cone_model** out) {
             if (e != hipSuccess) set_error("model_create: hipMalloc of the position tables failed: %s", hipGetErrorString(e));
             if (m->tab_arena) (void)hipFree(m->tab_arena);
             if (m->split_img) (void)hipFree(m->split_img);
+            if (m->bf16_img) (void)hipFree(m->bf16_img);
             (void)hipFree(m->arena);
             delete m;
             return CONE_E_HIP;
@@ -409,6 +442,8 @@ static int layer0_rows(const cone_model* m, const float* rows, int n, const int*
         RUN(launch_layernorm(rows, d, m->enc[0].n1.g, m->enc[0].n1.b, tmp, d, n, n_dev, d, s));
         a = tmp;
     }
+    if (m->opt_bf16 && m->bf16_img && !m->general())    // option bf16: the mode's row GEMM, cached rows or not
+        return launch_rows256_bf16(a, 256, m->enc_qkv_img1[0], m->enc[0].sa.in_b, qkv, 768, n, n_dev, 768, s);
     return launch_gemm(G(m, a, d, m->enc[0].sa.in_w, d, m->enc[0].sa.in_b, qkv, 3 * d, n, n_dev, 3 * d, d), s);
 }
 
@@ -650,7 +685,11 @@ static int forward_packed_prenorm(const cone_model* m, const float* vproj, const
 static int tail_prenorm(const cone_model* m, const FwdBuffers& f, const float* A, const float* Wo, const float* bo, const float* R,
                         const float* pg, const float* pb, const float* W1, const float* b1, const float* W2, const float* b2,
                         float* OUT, const float* n2g, const float* n2b, float* OUT2, int M, const int* M_dev, int ff, hipStream_t s,
-                        const int* r_idx = nullptr, const float* R2 = nullptr) {
+                        const int* r_idx = nullptr, const float* R2 = nullptr, const void* wo_img1 = nullptr,
+                        const void* ffn_img1 = nullptr) {
+    if (m->opt_bf16 && wo_img1 && ffn_img1)     // option bf16: the single-piece tail in its pre-norm form (ffn_bf16.hip)
+        return launch_proj_ffn_bf16_prenorm(A, 256, wo_img1, bo, R, 256, pg, pb, ffn_img1, b1, b2, OUT, 256, n2g, n2b, OUT2, 256, M,
+                                            M_dev, ff, s, r_idx, R2);
     if (m->opt_spread && f.SPR && ffn_spread_supported(M, ff))
         return launch_proj_ffn_spread(A, 256, Wo, bo, R, 256, pg, pb, W1, b1, W2, b2, n2g ? n2g : pg, n2b ? n2b : pb, OUT, 256, M, ff,
                                       f.SPR, s, M_dev, r_idx, R2, true, OUT2, 256);
@@ -690,13 +729,17 @@ static int forward_packed_prenorm_fused(const cone_model* m, const float* vproj,
         if (g0) {
             src.qkv_vid = l0->qkv_vid; src.qkv_txt = l0->qkv_txt; src.vrow0 = vrow0; src.trow0 = trow0;
         } else {
-            RUN(launch_gemm(G(m, Z, 256, e.sa.in_w, 256, e.sa.in_b, f.QKV, 768, Mmax, Mdev, 768, 256), s));   // q | k | v of src2
+            if (m->opt_bf16 && m->bf16_img)                                                                   // q | k | v of src2
+                RUN(launch_rows256_bf16(Z, 256, m->enc_qkv_img1[l], e.sa.in_b, f.QKV, 768, Mmax, Mdev, 768, s));
+            else
+                RUN(launch_gemm(G(m, Z, 256, e.sa.in_w, 256, e.sa.in_b, f.QKV, 768, Mmax, Mdev, 768, 256), s));
             src.Q = f.QKV; src.K = f.QKV + 256; src.V = f.QKV + 512; src.ldq = src.ldk = src.ldv = 768;
         }
         RUN(launch_enc_attn(g0 ? ATTN_GATHER : ATTN_POSADD, src, f.ATT, f.off, B, Lmax, s));
         const LNorm& nxt = l + 1 < m->n_enc ? m->enc[l + 1].n1 : m->enc_norm;
         RUN(tail_prenorm(m, f, f.ATT, e.sa.out.w, e.sa.out.b, g0 ? vproj : f.X, e.n2.g, e.n2.b, e.l1.w, e.l1.b, e.l2.w, e.l2.b, f.X,
-                         nxt.g, nxt.b, Z, Mmax, Mdev, ff, s, g0 ? f.RIDX : nullptr, g0 ? tproj : nullptr));
+                         nxt.g, nxt.b, Z, Mmax, Mdev, ff, s, g0 ? f.RIDX : nullptr, g0 ? tproj : nullptr, m->enc_wo_img1[l],
+                         m->enc_ffn_img1[l]));
     }
     const float* MEM = Z;                                                                            // encoder.norm(src)
     // --use_txt_pos: the keys memory + pos written once (text rows from the tokens' own position rows), x + pos form of the fold
@@ -721,7 +764,8 @@ static int forward_packed_prenorm_fused(const cone_model* m, const float* vproj,
         RUN(launch_dec_cross_mfma(f.DQ, xp ? f.XP : nullptr, MEM, xp ? nullptr : l0->pos_rows, vlen, f.off, dl.ca.in_w + 256 * 256,
                                   m->dec_vT[l], dl.ca.in_b + 512, f.DATT, B, m->nq, Lmax, nullptr, s, 3));
         RUN(tail_prenorm(m, f, f.DATT, dl.ca.out.w, dl.ca.out.b, f.TGT, dl.n3.g, dl.n3.b, dl.l1.w, dl.l1.b, dl.l2.w, dl.l2.b, f.TGT,
-                         m->dec_norm.g, m->dec_norm.b, f.HS + (size_t)l * T * 256, T, nullptr, ff, s));
+                         m->dec_norm.g, m->dec_norm.b, f.HS + (size_t)l * T * 256, T, nullptr, ff, s, nullptr, nullptr,
+                         m->dec_wo_img1[l], m->dec_ffn_img1[l]));
     }
     const int HT = nd * T;
     RUN(launch_rowdot(f.HS, 256, m->class_embed.w, m->class_embed.b, f.LG, 2, HT, 2, 0, s));
@@ -982,7 +1026,9 @@ static int forward_packed(const cone_model* m, const float* vproj, const int* vr
             // static table ((x + pos) W^T = x W^T + pos W^T): no x + pos matrix, no second A operand
             if (qkv_fused) {
                 // written by the previous layer's fused tail from the registers that held its output rows
-            } else if (m->opt_split_bf16 && m->split_img && l > 0)      // (l == 0: the kernel of cone_layer0_project, so that
+            } else if (m->opt_bf16 && m->bf16_img)      // (every layer, the first included: layer0_rows does the same)
+                RUN(launch_rows256_bf16(f.X, 256, m->enc_qkv_img1[l], e.sa.in_b, f.QKV, 768, Mmax, Mdev, 768, s));
+            else if (m->opt_split_bf16 && m->split_img && l > 0)      // (l == 0: the kernel of cone_layer0_project, so that
                                                                         // a window's bits do not depend on who projected it)
                 RUN(launch_rows256_split(f.X, 256, m->enc_qkv_img[l], e.sa.in_b, f.QKV, 768, Mmax, Mdev, 768, s));
             else
@@ -1003,7 +1049,15 @@ static int forward_packed(const cone_model* m, const float* vproj, const int* vr
             // everything behind the attention in ONE launch: norm2(x1 + ffn(x1)), x1 = norm1(x + attn Wo^T + bo); a
             // workgroup reads its 128 rows of x before it writes them, and nobody else touches them: in place
             const bool g0 = l == 0 && gather_res;
-            if (m->opt_split_bf16 && m->split_img) {
+            if (m->opt_bf16 && m->bf16_img) {
+                const bool next_qkv = m->opt_qkv_fused && l + 1 < m->n_enc && plan.tables && ffn_bf16_qkv_fits(ff, 768);
+                RUN(launch_proj_ffn_bf16(f.ATT, 256, m->enc_wo_img1[l], e.sa.out.b, g0 ? vproj : f.X, 256, e.n1.g, e.n1.b,
+                                         m->enc_ffn_img1[l], e.l1.b, e.l2.b, e.n2.g, e.n2.b, f.X, 256, Mmax, Mdev, ff, s,
+                                         g0 ? RIDX : nullptr, g0 ? tproj : nullptr,
+                                         next_qkv ? m->enc_qkv_img1[l + 1] : nullptr, next_qkv ? m->enc[l + 1].sa.in_b : nullptr,
+                                         next_qkv ? f.QKV : nullptr, 768, next_qkv ? 768 : 0));
+                qkv_fused = next_qkv;
+            } else if (m->opt_split_bf16 && m->split_img) {
                 // the next encoder layer's q | k | v projection rides in the same launch (its input rows are this kernel's
                 // output: no second pass over them); ATT and QKV are disjoint parts of the H region
                 const bool next_qkv = m->opt_qkv_fused && l + 1 < m->n_enc && plan.tables && ffn_split_qkv_fits(ff, 768);
@@ -1126,7 +1180,10 @@ static int forward_packed(const cone_model* m, const float* vproj, const int* vr
         else
             RUN(launch_small_attn(f.DQ, 256, f.KD + l * 256, 256 * nd, f.VD + l * 256, 256 * nd, f.DATT, 256, f.off, B,
                                   m->nq, Lmax, s));
-        if (m->opt_ffn_fused >= 2 && m->opt_split_bf16 && m->split_img) {
+        if (m->opt_ffn_fused >= 2 && m->opt_bf16 && m->bf16_img) {
+            RUN(launch_proj_ffn_bf16(f.DATT, 256, m->dec_wo_img1[l], dl.ca.out.b, f.TGT1, 256, dl.n2.g, dl.n2.b,
+                                     m->dec_ffn_img1[l], dl.l1.b, dl.l2.b, dl.n3.g, dl.n3.b, f.TGT, 256, T, nullptr, ff, s));
+        } else if (m->opt_ffn_fused >= 2 && m->opt_split_bf16 && m->split_img) {
             RUN(launch_proj_ffn_split(f.DATT, 256, m->dec_wo_img[l], dl.ca.out.b, f.TGT1, 256, dl.n2.g, dl.n2.b,
                                       m->dec_ffn_img[l], dl.l1.b, dl.l2.b, dl.n3.g, dl.n3.b, f.TGT, 256, T, nullptr, ff, s));
         } else if (m->opt_ffn_fused >= 2 && ffn_fused_supported(ff) && m->opt_spread && f.SPR && ffn_spread_supported(T, ff)) {
@@ -1218,6 +1275,7 @@ extern "C" void cone_model_destroy(cone_model* m) {
     if (!m) return;
     if (m->arena) (void)hipFree(m->arena);
     if (m->split_img) (void)hipFree(m->split_img);
+    if (m->bf16_img) (void)hipFree(m->bf16_img);
     if (m->tab_arena) (void)hipFree(m->tab_arena);
     delete m;
 }
@@ -1489,7 +1547,17 @@ extern "C" int cone_model_set_option(cone_model* m, const char* name, int value)
     if (!strcmp(name, "split_bf16")) {
         CONE_REQUIRE(value == 0 || m->split_img, "set_option: split_bf16 needs hidden_dim 256 with 8 heads and dim_feedforward %% 32 == 0 "
                      "(<= 2048); this handle is hidden_dim %d with %d heads, dim_feedforward %d", m->d, m->heads, m->ff);
+        CONE_REQUIRE(value == 0 || !m->opt_bf16, "set_option: split_bf16 = 1 while bf16 = 1: the two modes exclude each other "
+                     "(set bf16 = 0 first)");
         m->opt_split_bf16 = value != 0;
+        return 0;
+    }
+    if (!strcmp(name, "bf16")) {
+        CONE_REQUIRE(value == 0 || m->bf16_img, "set_option: bf16 needs hidden_dim 256 with 8 heads and dim_feedforward %% 32 == 0 "
+                     "(<= 2048); this handle is hidden_dim %d with %d heads, dim_feedforward %d", m->d, m->heads, m->ff);
+        CONE_REQUIRE(value == 0 || !m->opt_split_bf16, "set_option: bf16 = 1 while split_bf16 = 1: the two modes exclude each other "
+                     "(set split_bf16 = 0 first)");
+        m->opt_bf16 = value != 0;
         return 0;
     }
     if (!strcmp(name, "res_gather")) { m->opt_res_gather = value != 0; return 0; }
@@ -1537,6 +1605,13 @@ extern "C" size_t cone_test_ffn_split_image_bytes(int ff) { return ffn_split_sup
 extern "C" int cone_test_ffn_split(const float* X, const float* W1, const float* b1, const float* W2, const float* b2,
                                    const float* ln_g, const float* ln_b, float* OUT, int M, int ff, void* img, int pack,
                                    void* stream) {
+    if (pack & CONE_TEST_SINGLE_PIECE) {     // the single-piece form (ffn_bf16.hip)
+        if (pack & CONE_TEST_PACK) {
+            const int rc = launch_ffn_bf16_pack(W1, W2, ff, img, (hipStream_t)stream);
+            if (rc) return rc;
+        }
+        return launch_ffn_bf16(X, 256, img, b1, b2, ln_g, ln_b, OUT, 256, M, nullptr, ff, (hipStream_t)stream);
+    }
     if (pack) {
         const int rc = launch_ffn_split_pack(W1, W2, ff, img, (hipStream_t)stream);
         if (rc) return rc;
@@ -1546,6 +1621,13 @@ extern "C" int cone_test_ffn_split(const float* X, const float* W1, const float*
 extern "C" size_t cone_test_rows_split_image_bytes(int N) { return rows256_split_supported(N) ? rows256_split_image_bytes(N) : 0; }
 extern "C" int cone_test_rows_split(const float* X, const float* W, const float* bias, float* C, int M, int N, void* img,
                                     int pack, void* stream) {
+    if (pack & CONE_TEST_SINGLE_PIECE) {     // the single-piece form
+        if (pack & CONE_TEST_PACK) {
+            const int rc = launch_ffn_bf16_pack(W, nullptr, N, img, (hipStream_t)stream);
+            if (rc) return rc;
+        }
+        return launch_rows256_bf16(X, 256, img, bias, C, N, M, nullptr, N, (hipStream_t)stream);
+    }
     if (pack) {
         const int rc = launch_ffn_split_pack(W, nullptr, N, img, (hipStream_t)stream);
         if (rc) return rc;
@@ -1557,6 +1639,16 @@ extern "C" int cone_test_proj_ffn_split(const float* A, const float* Wo, const f
                                         const float* pb, const float* W1, const float* b1, const float* W2,
                                         const float* b2, const float* ln_g, const float* ln_b, float* OUT, int M, int ff,
                                         void* img, void* wo_img, int pack, void* stream) {
+    if (pack & CONE_TEST_SINGLE_PIECE) {     // the single-piece form
+        if (pack & CONE_TEST_PACK) {
+            int rc = launch_ffn_bf16_pack(W1, W2, ff, img, (hipStream_t)stream);
+            if (rc) return rc;
+            rc = launch_ffn_bf16_pack(Wo, nullptr, 256, wo_img, (hipStream_t)stream);
+            if (rc) return rc;
+        }
+        return launch_proj_ffn_bf16(A, 256, wo_img, bo, R, 256, pg, pb, img, b1, b2, ln_g, ln_b, OUT, 256, M, nullptr, ff,
+                                    (hipStream_t)stream);
+    }
     if (pack) {
         int rc = launch_ffn_split_pack(W1, W2, ff, img, (hipStream_t)stream);
         if (rc) return rc;

@@ -207,6 +207,34 @@ int launch_proj_ffn_split(const float* A, int lda, const void* Woimg, const floa
 // Qimg != null: the kernel also writes QKV (M, n_qkv) = OUT Wq^T + qb (the next layer's q | k | v projection; Qimg =
 // launch_ffn_split_pack(Wq, nullptr, n_qkv, ...)) from the registers that hold OUT
 
+// ---------------------------------------------------------------- the single-piece form (ffn_bf16.hip)
+// The same kernels with every GEMM operand rounded ONCE to bf16 and one MFMA per operand pair (fp32 accumulation; bias,
+// ReLU, residual -- the unrounded fp32 input -- and LayerNorm in fp32): plain bf16 matrix arithmetic, NOT fp32-accurate.
+// Images hold the high piece only (one third of the three-piece images), built by launch_ffn_bf16_pack.
+bool ffn_bf16_supported(int ff);
+size_t ffn_bf16_image_bytes(int ff);
+int launch_ffn_bf16_pack(const float* W1, const float* W2, int ff, void* img, hipStream_t s);
+int launch_ffn_bf16(const float* X, int ldx, const void* Wimg, const float* b1, const float* b2, const float* ln_g,
+                    const float* ln_b, float* OUT, int ldo, int M, const int* M_dev, int ff, hipStream_t s);
+bool rows256_bf16_supported(int N);
+size_t rows256_bf16_image_bytes(int N);
+int launch_rows256_bf16(const float* X, int ldx, const void* Wimg, const float* bias, float* C, int ldc, int M,
+                        const int* M_dev, int N, hipStream_t s);
+size_t ffn_bf16_proj_image_bytes();
+bool ffn_bf16_qkv_fits(int ff, int n_qkv);
+int launch_proj_ffn_bf16(const float* A, int lda, const void* Woimg, const float* bo, const float* R, int ldr,
+                         const float* pg, const float* pb, const void* Wimg, const float* b1, const float* b2,
+                         const float* ln_g, const float* ln_b, float* OUT, int ldo, int M, const int* M_dev, int ff,
+                         hipStream_t s, const int* r_idx = nullptr, const float* R2 = nullptr,
+                         const void* Qimg = nullptr, const float* qb = nullptr, float* QKV = nullptr, int ldq = 0,
+                         int n_qkv = 0);
+// the --pre_norm form (launch_proj_ffn_prenorm's computation): OUT = x1 + ffn(LayerNorm(x1; pg, pb)), x1 = R + A Wo^T + bo;
+// OUT2 (may be null) = LayerNorm(OUT; n2g, n2b)
+int launch_proj_ffn_bf16_prenorm(const float* A, int lda, const void* Woimg, const float* bo, const float* R, int ldr,
+                                 const float* pg, const float* pb, const void* Wimg, const float* b1, const float* b2,
+                                 float* OUT, int ldo, const float* n2g, const float* n2b, float* OUT2, int ldo2, int M,
+                                 const int* M_dev, int ff, hipStream_t s, const int* r_idx = nullptr, const float* R2 = nullptr);
+
 // ---------------------------------------------------------------- row kernels (rowops.hip)
 int launch_layernorm(const float* x, int ldx, const float* g, const float* b, float* out, int ldo,
                      int64_t n_rows, const int* n_rows_dev, int dim, hipStream_t s, const int* src_row = nullptr);

@@ -872,7 +872,10 @@ def _graph_key(model, opt):
     return (id(model), model._handle.value if getattr(model, "_handle", None) is not None else None, opt.topk_window,
             opt.eval_bsz, opt.max_v_l, opt.nms_thd, opt.max_before_nms, opt.max_after_nms, bool(opt.no_sort_results),
             bool(getattr(opt, "need_saliency", False)), bool(getattr(opt, "need_aux", False)),
-            int(getattr(opt, "window_batch", 32768)), float(opt.clip_length))
+            int(getattr(opt, "window_batch", 32768)), float(opt.clip_length),
+            # the handle's option switches (bf16, split_bf16, the A/B switches): flipping one after a capture must not
+            # replay the other setting's launches
+            tuple(sorted(getattr(model, "_options", {}).items())))
 
 
 @torch.no_grad()
@@ -1181,6 +1184,8 @@ def setup_model(opt):
     model.load_state_dict(ckpt["model"])
     if getattr(opt, "split_bf16", False):
         model.set_option("split_bf16", 1)
+    if getattr(opt, "bf16", False):         # (with --split_bf16 as well: the library refuses, naming both options)
+        model.set_option("bf16", 1)
     logger.info(f"Loaded model saved at epoch {ckpt.get('epoch')} from checkpoint: {opt.resume}")
     return model, criterion, None, None
 

@@ -297,6 +297,9 @@ class CONE:
     def set_option(self, name: str, value: int):
         """A/B switch of this model's handle (cone_model_set_option): parity tests and diagnostics only."""
         _lib.check(_lib.load().cone_model_set_option(self._h(), name.encode(), int(value)))
+        # what the handle now runs with: a captured hipGraph holds the launches of the options it was captured under
+        # (inference._graph_key)
+        self.__dict__.setdefault("_options", {})[name] = int(value)
         return self
 
     def layer0_rows(self, proj_rows, ws=None):

@@ -422,6 +422,18 @@ int64_t cone_prof_collect(double* out, int64_t max_rec);
  *   product as six partial products of three-piece bf16 operands (x = xh + xm + xl exactly), fp32 accumulation
  *   (ffn_split.hip).  Measured against float64: the same error as the exact-fp32 MFMA chain (1.5e-7 .. 2.4e-7 of
  *   sum |a b| vs 2.0e-7 .. 2.1e-7), at 1.65x its speed.  The default stays exact fp32.
+ * "bf16" (default 0, OPT-IN; excludes split_bf16: setting either to 1 while the other is 1 is an error): the GEMMs that
+ *   split_bf16 moves to the bf16 matrix cores -- attention output projection, linear1, linear2, the next layer's fused
+ *   q | k | v projection, the K = 256 row GEMMs, and here the first layer's q | k | v rows too (cone_layer0_project and the
+ *   uncached first layer alike) -- with every operand rounded ONCE to bf16 (round to nearest even) and ONE MFMA per operand
+ *   pair, fp32 accumulation (ffn_bf16.hip; weight images of one third the bytes).  Everything else -- bias, ReLU, the
+ *   residual (taken from the unrounded fp32 input), LayerNorm, attention, decoder cross-attention, input projections, heads,
+ *   matching, and all of stage A -- stays fp32 and activations stay fp32 in memory.  NOT fp32-accurate: errors are those
+ *   of bf16 operands (bounded by the reference model's own bf16-autocast error, tests/test_bf16_gpu.py).  Needs what
+ *   split_bf16 needs (hidden_dim 256, 8 heads, dim_feedforward % 32 == 0); 0 is always accepted.  --pre_norm handles run
+ *   the pre-norm form of the same kernels (fused table path).  Every tail takes the 128-row-tile kernel whatever the row
+ *   count (no spread form): for a handful of windows the default path can be the faster one.  With the diagnostic
+ *   switches ffn_fused < 2 or pos_tables 0 the tails run fp32 while the q | k | v row GEMMs stay bf16 (A/B use only).
  * "qkv_fused" (default 1): the next encoder layer's q | k | v projection is computed by the fused layer tail from the
  *   registers that hold its output rows: 1 = on the split_bf16 path (bit-identical to the separate launch), 2 = on the
  *   exact-fp32 path as well (measured neutral; another summation order than the GEMM launch), 0 = always its own launch.
@@ -454,6 +466,11 @@ int cone_test_ffn(const float* X, const float* W1, const float* b1, const float*
 int cone_test_proj_ffn(const float* A, const float* Wo, const float* bo, const float* R, const float* pg, const float* pb,
                        const float* W1, const float* b1, const float* W2, const float* b2, const float* ln_g,
                        const float* ln_b, float* OUT, int M, int ff, void* stream);
+/* pack, in the three entries below: CONE_TEST_PACK = build the weight image(s) first; | CONE_TEST_SINGLE_PIECE = the
+ * single-piece form of option "bf16" (operands rounded once, one MFMA per pair, ffn_bf16.hip), whose images fit the same
+ * scratch sizes. */
+#define CONE_TEST_PACK 1
+#define CONE_TEST_SINGLE_PIECE 2
 /* cone_test_ffn on the bf16 matrix cores (ffn_split.hip): every fp32 product as six partial products of three-piece bf16
  * operands with fp32 accumulation.  img = scratch of cone_test_ffn_split_image_bytes(ff) bytes for the split weight image
  * (pack != 0: built from W1 / W2 first; 0: reused from an earlier call). */
