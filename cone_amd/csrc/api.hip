@@ -67,20 +67,15 @@ struct cone_model {
     int opt_l0_gather = 1;    // first encoder layer's attention gathers q|k|v from the layer-0 caches itself
     int opt_pos_tables = 1;   // later layers / decoder keys take the position term from the static tables
     int opt_gemm = 0;         // GEMM tile family forced for every dense layer (GEMM_AUTO = by shape)
-    // derived (d = 256, ff % 32 == 0): the layer tails' weights split into bf16 pieces and laid out for ffn_split.hip
-    char* split_img = nullptr;                          // one allocation: per layer [Wo image | FFN image]
-    const void* enc_wo_img[CONE_MAX_LAYERS] = {}; const void* enc_ffn_img[CONE_MAX_LAYERS] = {};
-    const void* enc_qkv_img[CONE_MAX_LAYERS] = {};
-    const void* dec_wo_img[CONE_MAX_LAYERS] = {}; const void* dec_ffn_img[CONE_MAX_LAYERS] = {};
+    // derived: every layer tail's operands (launch_layer_tail) -- the fp32 pointers and (d = 256, ff % 32 == 0) the weight
+    // images of the two bf16 modes, each mode's in one allocation [encoder q | k | v images | per layer: Wo image, FFN image]:
+    // split_img the three-piece images of ffn_split.hip, bf16_img the single-piece ones of ffn_bf16.hip (one third of the bytes)
+    cone::TailWeights enc_tail[CONE_MAX_LAYERS] = {}, dec_tail[CONE_MAX_LAYERS] = {};
+    char* split_img = nullptr; char* bf16_img = nullptr;
     int opt_qkv_fused = 1;    // the next encoder layer's q | k | v projection inside the fused layer tail (same launch): 1 = on
                               // the split_bf16 path (-0.3 ms), 2 = on the exact-fp32 path too (neutral), 0 = own launch
     int opt_split_bf16 = 0;   // OPT-IN: layer tails on the bf16 matrix cores (six partial products of three-piece operands,
                               // fp32 accumulation: fp32-MFMA accuracy); 0 = exact-fp32 MFMA (default)
-    // the single-piece images of the same weights (ffn_bf16.hip: the high piece only, one third of the bytes) and their switch
-    char* bf16_img = nullptr;
-    const void* enc_wo_img1[CONE_MAX_LAYERS] = {}; const void* enc_ffn_img1[CONE_MAX_LAYERS] = {};
-    const void* enc_qkv_img1[CONE_MAX_LAYERS] = {};
-    const void* dec_wo_img1[CONE_MAX_LAYERS] = {}; const void* dec_ffn_img1[CONE_MAX_LAYERS] = {};
     int opt_bf16 = 0;         // OPT-IN: the same GEMMs with operands rounded ONCE to bf16, one MFMA per operand pair, fp32
                               // accumulation (plain bf16 matrix arithmetic: NOT fp32-accurate); excludes split_bf16
     int opt_res_gather = 1;   // first encoder layer's residual rows gathered by the fused layer tail (no packed input copy)
@@ -112,6 +107,44 @@ struct ArenaBuilder {
 static int dec0_constants(cone_model* m, hipStream_t s);
 static int build_pos_tables(const cone_model* m, int max_v_l, float* pos_rows, float* pos_qk, hipStream_t s);
 static int64_t pos_table_rows(int max_v_l) { return (int64_t)max_v_l * (max_v_l + 1) / 2 + 1; }
+
+static void free_model(cone_model* m) {
+    if (m->arena) (void)hipFree(m->arena);
+    if (m->split_img) (void)hipFree(m->split_img);
+    if (m->bf16_img) (void)hipFree(m->bf16_img);
+    if (m->tab_arena) (void)hipFree(m->tab_arena);
+    delete m;
+}
+
+// One numeric mode's weight images of every layer tail (13 MB split_bf16 / 4.4 MB bf16 at ff = 1024; opt-in paths), one
+// allocation: the encoder layers' q | k | v projections (768 x 256), then per layer (encoder, decoder) [Wo image | FFN image].
+struct TailImageMode {
+    size_t (*proj_bytes)(); size_t (*ffn_bytes)(int); size_t (*rows_bytes)(int);
+    int (*pack)(const float*, const float*, int, void*, hipStream_t);
+};
+static const TailImageMode TAIL_IMAGE_MODES[TAIL_IMG_MODES] = {
+    {ffn_split_proj_image_bytes, ffn_split_image_bytes, rows256_split_image_bytes, launch_ffn_split_pack},
+    {ffn_bf16_proj_image_bytes, ffn_bf16_image_bytes, rows256_bf16_image_bytes, launch_ffn_bf16_pack}};
+static int build_tail_images(cone_model* m, int mode, char** img) {
+    const TailImageMode& k = TAIL_IMAGE_MODES[mode];
+    const size_t per = k.proj_bytes() + k.ffn_bytes(m->ff), qkv = k.rows_bytes(768);
+    if (hipMalloc((void**)img, per * (size_t)(m->n_enc + m->n_dec) + qkv * (size_t)m->n_enc) != hipSuccess) {
+        set_error("model_create: building the split-bf16 / bf16 weight images failed");
+        return CONE_E_HIP;
+    }
+    char* ip = *img;
+    for (int l = 0; l < m->n_enc; ++l, ip += qkv) {
+        if (int rc = k.pack(m->enc_tail[l].Wq, nullptr, 768, ip, nullptr)) return rc;
+        m->enc_tail[l].img[mode].qkv = ip;
+    }
+    for (int i = 0; i < m->n_enc + m->n_dec; ++i, ip += per) {
+        TailWeights& t = i < m->n_enc ? m->enc_tail[i] : m->dec_tail[i - m->n_enc];
+        if (int rc = k.pack(t.Wo, nullptr, 256, ip, nullptr)) return rc;
+        if (int rc = k.pack(t.W1, t.W2, m->ff, ip + k.proj_bytes(), nullptr)) return rc;
+        t.img[mode].wo = ip; t.img[mode].ffn = ip + k.proj_bytes();
+    }
+    return 0;
+}
 
 static int build_model(const cone_weights* w, cone_model** out) {
     CONE_REQUIRE(w && out, "model_create: null argument");
@@ -183,7 +216,7 @@ static int build_model(const cone_weights* w, cone_model** out) {
     ab.add(w->pos_dim_t, d, &m->dim_t);
     if (w->txt_pos_embed) {     // --use_txt_pos
         if (w->txt_pos_rows < 1 || w->txt_pos_rows > 4096 || !w->txt_pos_ln.g || !w->txt_pos_ln.b) {
-            delete m;
+            free_model(m);
             set_error("model_create: txt_pos_embed needs txt_pos_rows in [1, 4096] (got %d) and its LayerNorm", w->txt_pos_rows);
             return CONE_E_INVALID;
         }
@@ -197,7 +230,7 @@ static int build_model(const cone_weights* w, cone_model** out) {
     }
     for (auto& it : ab.items)
         if (!it.src) {
-            delete m;
+            free_model(m);
             set_error("model_create: a required weight pointer is null");
             return CONE_E_INVALID;
         }
@@ -206,7 +239,7 @@ static int build_model(const cone_weights* w, cone_model** out) {
     const size_t stacked = (size_t)m->n_dec * (d * d + d) * 2 + 4 * 64 + (size_t)m->n_dec * d * d + dec0_floats;
     hipError_t e = hipMalloc((void**)&m->arena, (ab.total + stacked) * sizeof(float));
     if (e != hipSuccess) {
-        delete m;
+        free_model(m);
         set_error("model_create: hipMalloc of %zu bytes failed: %s", (ab.total + stacked) * sizeof(float),
                   hipGetErrorString(e));
         return CONE_E_HIP;
@@ -215,8 +248,7 @@ static int build_model(const cone_weights* w, cone_model** out) {
     for (auto& it : ab.items) {
         e = hipMemcpy(m->arena + cur, it.src, it.n * sizeof(float), hipMemcpyDefault);
         if (e != hipSuccess) {
-            (void)hipFree(m->arena);
-            delete m;
+            free_model(m);
             set_error("model_create: weight copy failed: %s", hipGetErrorString(e));
             return CONE_E_HIP;
         }
@@ -237,8 +269,7 @@ static int build_model(const cone_weights* w, cone_model** out) {
         e = hipMemcpy(vb + (size_t)i * d, ib + 2 * d, d * sizeof(float), hipMemcpyDeviceToDevice);
     }
     if (e != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-        (void)hipFree(m->arena);
-        delete m;
+        free_model(m);
         set_error("model_create: stacking decoder K/V weights failed");
         return CONE_E_HIP;
     }
@@ -253,8 +284,7 @@ static int build_model(const cone_weights* w, cone_model** out) {
                 for (size_t c = 0; c < d; ++c) ht[c * d + o] = h[o * d + c];
             if (e == hipSuccess) e = hipMemcpy(dst, ht.data(), d * d * sizeof(float), hipMemcpyHostToDevice);
             if (e != hipSuccess) {
-                (void)hipFree(m->arena);
-                delete m;
+                free_model(m);
                 set_error("model_create: transposing decoder V weights failed: %s", hipGetErrorString(e));
                 return CONE_E_HIP;
             }
@@ -268,66 +298,36 @@ static int build_model(const cone_weights* w, cone_model** out) {
         m->dec_sa_tab[i] = m->arena + cur; cur += align_up((size_t)m->nq * 3 * d, 64);
         m->dec_ca_tab[i] = m->arena + cur; cur += align_up((size_t)m->nq * d, 64);
     }
-    if (!m->gen_native && ffn_split_supported(m->ff)) {   // split-bf16 images of every layer tail (13 MB at ff = 1024; opt-in path)
-        const size_t per = ffn_split_proj_image_bytes() + ffn_split_image_bytes(m->ff);
-        const size_t qkv = rows256_split_image_bytes(768);
-        e = hipMalloc((void**)&m->split_img, per * (size_t)(m->n_enc + m->n_dec) + qkv * (size_t)m->n_enc);
-        char* ip = m->split_img;
-        int rc = 0;
-        for (int l = 0; l < m->n_enc && e == hipSuccess && rc == 0; ++l) {     // q | k | v projections (768 x 256)
-            rc = launch_ffn_split_pack(m->enc[l].sa.in_w, nullptr, 768, ip, nullptr);
-            m->enc_qkv_img[l] = ip;
-            ip += qkv;
+    auto tail = [](const Linear& o, const Linear& l1, const Linear& l2, const LNorm& in, const LNorm& outn) {
+        TailWeights t{};
+        t.Wo = o.w; t.bo = o.b; t.W1 = l1.w; t.b1 = l1.b; t.W2 = l2.w; t.b2 = l2.b;
+        t.in_g = in.g; t.in_b = in.b; t.out_g = outn.g; t.out_b = outn.b;
+        return t;
+    };
+    for (int l = 0; l < m->n_enc; ++l) {    // pre-norm: norm2 sits ahead of the block, the second output carries the next consumer's norm
+        const EncLayer& el = m->enc[l];
+        const LNorm& nxt = l + 1 < m->n_enc ? m->enc[l + 1].n1 : m->enc_norm;
+        m->enc_tail[l] = m->pre_norm ? tail(el.sa.out, el.l1, el.l2, el.n2, nxt) : tail(el.sa.out, el.l1, el.l2, el.n1, el.n2);
+        m->enc_tail[l].Wq = el.sa.in_w; m->enc_tail[l].qb = el.sa.in_b;
+    }
+    for (int l = 0; l < m->n_dec; ++l) {
+        const DecLayer& dl = m->dec[l];
+        m->dec_tail[l] = m->pre_norm ? tail(dl.ca.out, dl.l1, dl.l2, dl.n3, m->dec_norm) : tail(dl.ca.out, dl.l1, dl.l2, dl.n2, dl.n3);
+    }
+    if (!m->gen_native && ffn_split_supported(m->ff)) {
+        int rc = build_tail_images(m, TAIL_IMG_SPLIT, &m->split_img);
+        if (rc == 0) rc = build_tail_images(m, TAIL_IMG_BF16, &m->bf16_img);
+        if (rc == 0 && hipDeviceSynchronize() != hipSuccess) {
+            set_error("model_create: building the split-bf16 / bf16 weight images failed");
+            rc = CONE_E_HIP;
         }
-        for (int i = 0; i < m->n_enc + m->n_dec && e == hipSuccess && rc == 0; ++i) {
-            const bool enc = i < m->n_enc;
-            const int l = enc ? i : i - m->n_enc;
-            const float* wo = enc ? m->enc[l].sa.out.w : m->dec[l].ca.out.w;
-            const Linear& l1 = enc ? m->enc[l].l1 : m->dec[l].l1;
-            const Linear& l2 = enc ? m->enc[l].l2 : m->dec[l].l2;
-            rc = launch_ffn_split_pack(wo, nullptr, 256, ip, nullptr);
-            if (rc == 0) rc = launch_ffn_split_pack(l1.w, l2.w, m->ff, ip + ffn_split_proj_image_bytes(), nullptr);
-            (enc ? m->enc_wo_img : m->dec_wo_img)[l] = ip;
-            (enc ? m->enc_ffn_img : m->dec_ffn_img)[l] = ip + ffn_split_proj_image_bytes();
-            ip += per;
-        }
-        // the single-piece images of the same weights, in the same order (4.4 MB at ff = 1024; option bf16)
-        const size_t per1 = ffn_bf16_proj_image_bytes() + ffn_bf16_image_bytes(m->ff);
-        const size_t qkv1 = rows256_bf16_image_bytes(768);
-        if (e == hipSuccess && rc == 0)
-            e = hipMalloc((void**)&m->bf16_img, per1 * (size_t)(m->n_enc + m->n_dec) + qkv1 * (size_t)m->n_enc);
-        ip = m->bf16_img;
-        for (int l = 0; l < m->n_enc && e == hipSuccess && rc == 0; ++l) {
-            rc = launch_ffn_bf16_pack(m->enc[l].sa.in_w, nullptr, 768, ip, nullptr);
-            m->enc_qkv_img1[l] = ip;
-            ip += qkv1;
-        }
-        for (int i = 0; i < m->n_enc + m->n_dec && e == hipSuccess && rc == 0; ++i) {
-            const bool enc = i < m->n_enc;
-            const int l = enc ? i : i - m->n_enc;
-            const float* wo = enc ? m->enc[l].sa.out.w : m->dec[l].ca.out.w;
-            const Linear& l1 = enc ? m->enc[l].l1 : m->dec[l].l1;
-            const Linear& l2 = enc ? m->enc[l].l2 : m->dec[l].l2;
-            rc = launch_ffn_bf16_pack(wo, nullptr, 256, ip, nullptr);
-            if (rc == 0) rc = launch_ffn_bf16_pack(l1.w, l2.w, m->ff, ip + ffn_bf16_proj_image_bytes(), nullptr);
-            (enc ? m->enc_wo_img1 : m->dec_wo_img1)[l] = ip;
-            (enc ? m->enc_ffn_img1 : m->dec_ffn_img1)[l] = ip + ffn_bf16_proj_image_bytes();
-            ip += per1;
-        }
-        if (e != hipSuccess || rc != 0 || hipDeviceSynchronize() != hipSuccess) {
-            if (m->split_img) (void)hipFree(m->split_img);
-            if (m->bf16_img) (void)hipFree(m->bf16_img);
-            (void)hipFree(m->arena);
-            delete m;
-            if (rc == 0) set_error("model_create: building the split-bf16 / bf16 weight images failed");
+        if (rc != 0) {
+            free_model(m);
             return CONE_E_HIP;
         }
     }
     if (dec0_constants(m, nullptr) != 0 || hipDeviceSynchronize() != hipSuccess) {
-        if (m->split_img) (void)hipFree(m->split_img);
-        if (m->bf16_img) (void)hipFree(m->bf16_img);
-        (void)hipFree(m->arena);
-        delete m;
+        free_model(m);
         return CONE_E_HIP;
     }
     if (!m->gen_native) {   // the handle's own position tables, for the window lengths this checkpoint is built for (ABI 8: cone_weights.
@@ -340,11 +340,7 @@ static int build_model(const cone_weights* w, cone_model** out) {
         if (rc == 0) rc = build_pos_tables(m, tab_l, m->tab_arena, m->tab_arena + rows * 256, nullptr);
         if (rc != 0 || hipDeviceSynchronize() != hipSuccess) {
             if (e != hipSuccess) set_error("model_create: hipMalloc of the position tables failed: %s", hipGetErrorString(e));
-            if (m->tab_arena) (void)hipFree(m->tab_arena);
-            if (m->split_img) (void)hipFree(m->split_img);
-            if (m->bf16_img) (void)hipFree(m->bf16_img);
-            (void)hipFree(m->arena);
-            delete m;
+            free_model(m);
             return CONE_E_HIP;
         }
         m->tab_pos_rows = m->tab_arena; m->tab_pos_qk = m->tab_arena + rows * 256; m->tab_max_v_l = tab_l;
@@ -433,6 +429,23 @@ static int build_pos_tables(const cone_model* m, int max_v_l, float* pos_rows, f
     return 0;
 }
 
+// Encoder layer l's q | k | v = X in_proj^T + b (N = 768) in the handle's numeric mode -- the one place that picks its kernel:
+//   bf16       : the mode's row GEMM for every layer, the first included, and for the layer-0 row caches;
+//   split_bf16 : the mode's row GEMM only where split_ok (the post-norm layer loop) and only for l > 0: layer 0 keeps the
+//                kernel of cone_layer0_project, so that a window's bits do not depend on who projected it; never for the
+//                caches and never on the pre-norm path;
+//   otherwise  : the exact-fp32 GEMM (any hidden_dim: the general path's caches come through here too).
+static int encoder_qkv(const cone_model* m, int l, const float* X, float* QKV, int M, const int* M_dev, hipStream_t s,
+                       bool split_ok) {
+    const TailWeights& t = m->enc_tail[l];
+    const int d = m->d;
+    if (m->opt_bf16 && m->bf16_img && !m->general())
+        return launch_rows256_bf16(X, 256, t.img[TAIL_IMG_BF16].qkv, t.qb, QKV, 768, M, M_dev, 768, s);
+    if (split_ok && l > 0 && m->opt_split_bf16 && m->split_img)
+        return launch_rows256_split(X, 256, t.img[TAIL_IMG_SPLIT].qkv, t.qb, QKV, 768, M, M_dev, 768, s);
+    return launch_gemm(G(m, X, d, t.Wq, d, t.qb, QKV, 3 * d, M, M_dev, 3 * d, d), s);
+}
+
 // First encoder layer's in_proj hoisted out of the window loop: q | k | v = in_proj(x) once per projected clip / text token
 // (post-norm, cone/transformer.py:237-239), resp. in_proj(norm1(x)) (--pre_norm, :250-252; tmp = n rows of scratch).
 static int layer0_rows(const cone_model* m, const float* rows, int n, const int* n_dev, float* qkv, float* tmp, hipStream_t s) {
@@ -442,9 +455,7 @@ static int layer0_rows(const cone_model* m, const float* rows, int n, const int*
         RUN(launch_layernorm(rows, d, m->enc[0].n1.g, m->enc[0].n1.b, tmp, d, n, n_dev, d, s));
         a = tmp;
     }
-    if (m->opt_bf16 && m->bf16_img && !m->general())    // option bf16: the mode's row GEMM, cached rows or not
-        return launch_rows256_bf16(a, 256, m->enc_qkv_img1[0], m->enc[0].sa.in_b, qkv, 768, n, n_dev, 768, s);
-    return launch_gemm(G(m, a, d, m->enc[0].sa.in_w, d, m->enc[0].sa.in_b, qkv, 3 * d, n, n_dev, 3 * d, d), s);
+    return encoder_qkv(m, 0, a, qkv, n, n_dev, s, false);
 }
 
 // input_{vid,txt}_proj: LN -> Linear -> ReLU (all but last) with the next LN fused into the GEMM epilogue.
@@ -584,6 +595,42 @@ static size_t fwd_ws_bytes(const cone_model* m, int B, int Lmax, const FwdPlan& 
     return c.cur;
 }
 
+// The hs / aux_* taps: all layers' normalised slot rows and the intermediate layers' head outputs, from the workspace.
+static int copy_taps(const cone_taps* taps, const float* HS, const float* LG, const float* SP, int nd, int T, int d, hipStream_t s) {
+    if (!taps) return 0;
+    const size_t last = (size_t)(nd - 1) * T * 2;
+    if (taps->hs)
+        CONE_CHECK_HIP(hipMemcpyAsync(taps->hs, HS, (size_t)nd * T * d * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (taps->aux_logits && nd > 1)
+        CONE_CHECK_HIP(hipMemcpyAsync(taps->aux_logits, LG, last * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (taps->aux_spans && nd > 1)
+        CONE_CHECK_HIP(hipMemcpyAsync(taps->aux_spans, SP, last * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+// The plain epilogue of a forward (cone/model.py:112-117): class head, span MLP and span head of every layer's rows HS (nd * T, d)
+// into the workspace, the last layer's rows out, the taps, the saliency head of the memory rows.  gen: the d-wide row-dot /
+// saliency kernels of general.hip (the general path, also when it is forced at d = 256), else the 256-channel ones.
+struct HeadBufs { float *HS, *S1, *S2, *LG, *SP; const int* off; };
+static int heads_and_taps(const cone_model* m, const HeadBufs& f, const float* MEM, const int* vlen, const int* qlen, int B, int Lv_max,
+                          int Lq_max, float* logits, float* spans, float* saliency, const cone_taps* taps, bool gen, hipStream_t s) {
+    const int d = m->d, T = B * m->nq, nd = m->n_dec, HT = nd * T;
+    auto rowdot = [&](const float* X, const Linear& h, float* out, int act) {
+        return gen ? launch_gen_rowdot(X, d, h.w, h.b, out, 2, HT, 2, act, d, s) : launch_rowdot(X, d, h.w, h.b, out, 2, HT, 2, act, s);
+    };
+    RUN(rowdot(f.HS, m->class_embed, f.LG, 0));
+    RUN(launch_gemm(G(m, f.HS, d, m->span[0].w, d, m->span[0].b, f.S1, d, HT, nullptr, d, d, EPI_RELU), s));
+    RUN(launch_gemm(G(m, f.S1, d, m->span[1].w, d, m->span[1].b, f.S2, d, HT, nullptr, d, d, EPI_RELU), s));
+    RUN(rowdot(f.S2, m->span[2], f.SP, 1));
+    const size_t last = (size_t)(nd - 1) * T * 2;
+    CONE_CHECK_HIP(hipMemcpyAsync(logits, f.LG + last, (size_t)T * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    CONE_CHECK_HIP(hipMemcpyAsync(spans, f.SP + last, (size_t)T * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    RUN(copy_taps(taps, f.HS, f.LG, f.SP, nd, T, d, s));
+    float* mem_tap = taps ? taps->memory : nullptr;
+    if (!saliency && !mem_tap) return 0;
+    return gen ? launch_gen_saliency(MEM, f.off, vlen, qlen, m->saliency.w, m->saliency.b, saliency, Lv_max, mem_tap, Lq_max, B, d, s)
+               : launch_saliency(MEM, f.off, vlen, qlen, m->saliency.w, m->saliency.b, saliency, Lv_max, mem_tap, Lq_max, B, s);
+}
+
 // --pre_norm (cone/config.py:120 -> normalize_before, cone/transformer.py:19-36): every layer normalises its INPUT
 // (forward_pre, :248-260 / :319-342), the residual stream stays un-normalised, and the encoder ends with its own LayerNorm.
 // Off in every shipped configuration: built from the plain blocks (LayerNorm kernel, row GEMMs with residual epilogue, the
@@ -652,27 +699,84 @@ static int forward_packed_prenorm(const cone_model* m, const float* vproj, const
         RUN(launch_gemm(g, s));
         RUN(launch_layernorm(f.TGT, 256, m->dec_norm.g, m->dec_norm.b, f.HS + (size_t)l * T * 256, 256, T, nullptr, 256, s));
     }
-    // heads (cone/model.py:112-117), all layers into the workspace, the last layer's rows out
-    const int HT = nd * T;
-    RUN(launch_rowdot(f.HS, 256, m->class_embed.w, m->class_embed.b, f.LG, 2, HT, 2, 0, s));
-    RUN(launch_gemm(G(m, f.HS, 256, m->span[0].w, 256, m->span[0].b, f.S1, 256, HT, nullptr, 256, 256, EPI_RELU), s));
-    RUN(launch_gemm(G(m, f.S1, 256, m->span[1].w, 256, m->span[1].b, f.S2, 256, HT, nullptr, 256, 256, EPI_RELU), s));
-    RUN(launch_rowdot(f.S2, 256, m->span[2].w, m->span[2].b, f.SP, 2, HT, 2, 1, s));
-    const size_t last = (size_t)(nd - 1) * T * 2;
-    CONE_CHECK_HIP(hipMemcpyAsync(logits, f.LG + last, (size_t)T * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    CONE_CHECK_HIP(hipMemcpyAsync(spans, f.SP + last, (size_t)T * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (taps) {
-        if (taps->hs)
-            CONE_CHECK_HIP(hipMemcpyAsync(taps->hs, f.HS, (size_t)nd * T * 256 * sizeof(float), hipMemcpyDeviceToDevice, s));
-        if (taps->aux_logits && nd > 1)
-            CONE_CHECK_HIP(hipMemcpyAsync(taps->aux_logits, f.LG, last * sizeof(float), hipMemcpyDeviceToDevice, s));
-        if (taps->aux_spans && nd > 1)
-            CONE_CHECK_HIP(hipMemcpyAsync(taps->aux_spans, f.SP, last * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return heads_and_taps(m, HeadBufs{f.HS, f.S1, f.S2, f.LG, f.SP, f.off}, MEM, vlen, qlen, B, Lv_max, Lq_max, logits, spans, saliency,
+                          taps, false, s);
+}
+
+// ------------------------------------------------------------------------------ the layer tail
+// Everything of a transformer layer behind its attention, for encoder and decoder layers, post-norm and pre-norm: the one
+// place that reads the options (bf16, split_bf16, ffn_fused, ffn_spread, qkv_fused), the spread scratch f.SPR and the
+// *_supported / *_qkv_fits predicates, and picks a launcher.  The caller fills a TailArgs from enc_tail[l] / dec_tail[l] and
+// its buffers; t.next != null OFFERS the ride of the next encoder layer's q | k | v projection (QKV, n_qkv set), *rode says
+// whether it was taken (rode may be null where none is offered).  Every choice is by the host-known row bound t.M, never by *t.M_dev.  First matching row wins:
+//
+//   t.pre (the fused pre-norm path; plan_for admits it only with ffn_fused = 2 and an ff the fused kernels take;
+//   split_bf16 is not consulted; no ride)
+//     1  bf16                                                     launch_proj_ffn_bf16_prenorm
+//     2  ffn_spread, scratch, <= 64 row groups, ff % 256 == 0     launch_proj_ffn_spread (pre)
+//     3  ffn_spread, <= 768 row groups, ff the wide form takes    launch_proj_ffn_prenorm_wide (ffn_spread = 0 switches it off too)
+//     4  otherwise                                                launch_proj_ffn_prenorm (persistent 128-row kernel)
+//   post-norm with ffn_fused = 2, an ff the fused kernels take and no x + pos second output wanted (t.C2 == null)
+//     5  bf16                                                     launch_proj_ffn_bf16; rides if qkv_fused >= 1 and it fits the LDS
+//     6  split_bf16                                               launch_proj_ffn_split; rides likewise
+//     7  exact fp32, ride offered, qkv_fused = 2, fits the LDS    launch_proj_ffn_fused with the ride (persistent 128-row kernel)
+//     8  exact fp32, ffn_spread, scratch, <= 64 row groups, ...   launch_proj_ffn_spread
+//     9  exact fp32 otherwise                                     launch_proj_ffn_fused: wide form (<= 768 row groups), 64-row
+//                                                                 form, 128-row form + wide remainder -- chosen INSIDE it (ffn.hip)
+//   post-norm otherwise (ffn_fused = 1 / 0, an ff the fused kernels do not take, or t.C2: the encoder off the table path,
+//   whose next layer reads x + pos -- only the GEMM epilogue writes that)
+//    10  out-proj GEMM with residual + LayerNorm epilogue into t.X1, then
+//          ffn_fused >= 1, ff taken, no t.C2                      launch_ffn_fused (the block as one kernel)
+//          else                                                   GEMM + ReLU into t.H, GEMM + residual + LayerNorm (+ C2 = OUT + ADD)
+//   (The bf16 modes exist only with their images, and images only for an ff the fused kernels take: rows 5 / 6 need no
+//   check of their own.  A decoder layer offers no ride and has no M_dev; otherwise its ladder is the encoder's.)
+static int launch_layer_tail(const cone_model* m, const FwdBuffers& f, TailArgs t, hipStream_t s, bool* rode = nullptr) {
+    bool no_ride;
+    if (!rode) rode = &no_ride;
+    const TailWeights* next = t.next;
+    const int ff = t.ff;
+    const bool bf16 = m->opt_bf16 && m->bf16_img, split = m->opt_split_bf16 && m->split_img;
+    const bool spread = m->opt_spread && f.SPR && ffn_spread_supported(t.M, ff);
+    t.next = nullptr;
+    t.scratch = f.SPR;
+    *rode = false;
+    if (t.pre) {
+        if (bf16) return launch_proj_ffn_bf16_prenorm(t, s);
+        if (spread) return launch_proj_ffn_spread(t, s);
+        if (m->opt_spread && (t.M + 15) / 16 <= 768 && ffn_wide_supported(ff)) return launch_proj_ffn_prenorm_wide(t, s);
+        return launch_proj_ffn_prenorm(t, s);
     }
-    if (saliency || (taps && taps->memory))
-        RUN(launch_saliency(MEM, f.off, vlen, qlen, m->saliency.w, m->saliency.b, saliency, Lv_max,
-                            taps ? taps->memory : nullptr, Lq_max, B, s));
-    return 0;
+    const bool block_fused = !t.C2 && m->opt_ffn_fused && ffn_fused_supported(ff);
+    if (block_fused && m->opt_ffn_fused >= 2) {
+        if (bf16 || split) {
+            *rode = next && m->opt_qkv_fused && (bf16 ? ffn_bf16_qkv_fits(ff, t.n_qkv) : ffn_split_qkv_fits(ff, t.n_qkv));
+            if (*rode) t.next = next;
+            return bf16 ? launch_proj_ffn_bf16(t, s) : launch_proj_ffn_split(t, s);
+        }
+        // (the ride on the exact-fp32 kernel: measured neutral against the separate GEMM launch -- 44.3 vs 44.1 ms of kernel
+        // time per step -- so only on request: qkv_fused = 2)
+        *rode = next && m->opt_qkv_fused >= 2 && ffn_fused_qkv_fits(ff, t.n_qkv);
+        if (*rode) t.next = next;
+        else if (spread) return launch_proj_ffn_spread(t, s);
+        return launch_proj_ffn_fused(t, s);
+    }
+    const TailWeights& w = *t.w;
+    GemmArgs g = G(m, t.A, t.lda, w.Wo, 256, w.bo, t.X1, 256, t.M, t.M_dev, 256, 256, EPI_RESIDUAL | EPI_LN);
+    g.R = t.R; g.ldr = t.ldr; g.ln_g = w.in_g; g.ln_b = w.in_b;
+    RUN(launch_gemm(g, s));                                                             // LN_in(R + A Wo^T + bo)
+    if (block_fused)
+        return launch_ffn_fused(t.X1, 256, w.W1, w.b1, w.W2, w.b2, w.out_g, w.out_b, t.OUT, t.ldo, t.M, t.M_dev, ff, s);
+    RUN(launch_gemm(G(m, t.X1, 256, w.W1, 256, w.b1, t.H, ff, t.M, t.M_dev, ff, 256, EPI_RELU), s));
+    g = G(m, t.H, ff, w.W2, ff, w.b2, t.OUT, t.ldo, t.M, t.M_dev, 256, ff, EPI_RESIDUAL | EPI_LN);
+    g.R = t.X1; g.ldr = 256; g.ln_g = w.out_g; g.ln_b = w.out_b;
+    g.C2 = t.C2; g.ADD = t.ADD;
+    return launch_gemm(g, s);                                                           // LN_out(x1 + ffn(x1))
+}
+// a tail on 256-float rows: attention rows A, residual R, output OUT (may be R)
+static TailArgs tail_args(const TailWeights* w, const float* A, const float* R, float* OUT, int M, const int* M_dev, int ff) {
+    TailArgs t{};
+    t.A = A; t.lda = 256; t.R = R; t.ldr = 256; t.w = w; t.OUT = OUT; t.ldo = 256; t.M = M; t.M_dev = M_dev; t.ff = ff;
+    return t;
 }
 
 // --pre_norm on the table path (ABI 6): the same launches as the post-norm step -- position tables, ONE N = 768 GEMM per
@@ -680,26 +784,6 @@ static int forward_packed_prenorm(const cone_model* m, const float* vproj, const
 // block, the block, residual; the NEXT consumer's LayerNorm -- the next layer's norm1, the encoder's / decoder's final norm --
 // written as a second output), the folded decoder cross-attention.  What it does not have: the first layer's row caches (its
 // in_proj reads norm1(x)) and the first decoder layer's constants.
-// The pre-norm layer tail by row count, as the post-norm one: <= 1 024 rows the spread form, <= 12 288 the wide form, else the
-// persistent 128-row kernel -- the same bits in every form (option ffn_spread = 0: the persistent kernel only).
-static int tail_prenorm(const cone_model* m, const FwdBuffers& f, const float* A, const float* Wo, const float* bo, const float* R,
-                        const float* pg, const float* pb, const float* W1, const float* b1, const float* W2, const float* b2,
-                        float* OUT, const float* n2g, const float* n2b, float* OUT2, int M, const int* M_dev, int ff, hipStream_t s,
-                        const int* r_idx = nullptr, const float* R2 = nullptr, const void* wo_img1 = nullptr,
-                        const void* ffn_img1 = nullptr) {
-    if (m->opt_bf16 && wo_img1 && ffn_img1)     // option bf16: the single-piece tail in its pre-norm form (ffn_bf16.hip)
-        return launch_proj_ffn_bf16_prenorm(A, 256, wo_img1, bo, R, 256, pg, pb, ffn_img1, b1, b2, OUT, 256, n2g, n2b, OUT2, 256, M,
-                                            M_dev, ff, s, r_idx, R2);
-    if (m->opt_spread && f.SPR && ffn_spread_supported(M, ff))
-        return launch_proj_ffn_spread(A, 256, Wo, bo, R, 256, pg, pb, W1, b1, W2, b2, n2g ? n2g : pg, n2b ? n2b : pb, OUT, 256, M, ff,
-                                      f.SPR, s, M_dev, r_idx, R2, true, OUT2, 256);
-    if (m->opt_spread && (M + 15) / 16 <= 768 && ffn_wide_supported(ff))
-        return launch_proj_ffn_prenorm_wide(A, 256, Wo, bo, R, 256, pg, pb, W1, b1, W2, b2, OUT, 256, n2g, n2b, OUT2, 256, M, M_dev,
-                                            ff, s, r_idx, R2);
-    return launch_proj_ffn_prenorm(A, 256, Wo, bo, R, 256, pg, pb, W1, b1, W2, b2, OUT, 256, n2g, n2b, OUT2, 256, M, M_dev, ff, s,
-                                   r_idx, R2);
-}
-
 static int forward_packed_prenorm_fused(const cone_model* m, const float* vproj, const int* vrow0, const int* vlen,
                                         const float* tproj, const int* trow0, const int* qlen, int B, int Lv_max, int Lq_max,
                                         float* logits, float* spans, float* saliency, const cone_taps* taps, FwdBuffers& f,
@@ -720,7 +804,6 @@ static int forward_packed_prenorm_fused(const cone_model* m, const float* vproj,
         RUN(launch_layernorm(f.X, 256, m->enc[0].n1.g, m->enc[0].n1.b, Z, 256, Mmax, Mdev, 256, s)); // norm1 of layer 0
     }
     for (int l = 0; l < m->n_enc; ++l) {    // cone/transformer.py:248-260
-        const EncLayer& e = m->enc[l];
         const bool g0 = l == 0 && caches;
         AttnSrc src{};
         src.vlen = vlen; src.pos_zero_row = (int)pos_rows_n - 1;
@@ -729,17 +812,14 @@ static int forward_packed_prenorm_fused(const cone_model* m, const float* vproj,
         if (g0) {
             src.qkv_vid = l0->qkv_vid; src.qkv_txt = l0->qkv_txt; src.vrow0 = vrow0; src.trow0 = trow0;
         } else {
-            if (m->opt_bf16 && m->bf16_img)                                                                   // q | k | v of src2
-                RUN(launch_rows256_bf16(Z, 256, m->enc_qkv_img1[l], e.sa.in_b, f.QKV, 768, Mmax, Mdev, 768, s));
-            else
-                RUN(launch_gemm(G(m, Z, 256, e.sa.in_w, 256, e.sa.in_b, f.QKV, 768, Mmax, Mdev, 768, 256), s));
+            RUN(encoder_qkv(m, l, Z, f.QKV, Mmax, Mdev, s, false));                                          // q | k | v of src2
             src.Q = f.QKV; src.K = f.QKV + 256; src.V = f.QKV + 512; src.ldq = src.ldk = src.ldv = 768;
         }
         RUN(launch_enc_attn(g0 ? ATTN_GATHER : ATTN_POSADD, src, f.ATT, f.off, B, Lmax, s));
-        const LNorm& nxt = l + 1 < m->n_enc ? m->enc[l + 1].n1 : m->enc_norm;
-        RUN(tail_prenorm(m, f, f.ATT, e.sa.out.w, e.sa.out.b, g0 ? vproj : f.X, e.n2.g, e.n2.b, e.l1.w, e.l1.b, e.l2.w, e.l2.b, f.X,
-                         nxt.g, nxt.b, Z, Mmax, Mdev, ff, s, g0 ? f.RIDX : nullptr, g0 ? tproj : nullptr, m->enc_wo_img1[l],
-                         m->enc_ffn_img1[l]));
+        TailArgs t = tail_args(&m->enc_tail[l], f.ATT, g0 ? vproj : f.X, f.X, Mmax, Mdev, ff);
+        t.pre = true; t.OUT2 = Z; t.ldo2 = 256;                                                      // Z = the next consumer's norm of the stream
+        if (g0) { t.r_idx = f.RIDX; t.R2 = tproj; }
+        RUN(launch_layer_tail(m, f, t, s));
     }
     const float* MEM = Z;                                                                            // encoder.norm(src)
     // --use_txt_pos: the keys memory + pos written once (text rows from the tokens' own position rows), x + pos form of the fold
@@ -763,30 +843,12 @@ static int forward_packed_prenorm_fused(const cone_model* m, const float* vproj,
         RUN(launch_gemm(g, s));
         RUN(launch_dec_cross_mfma(f.DQ, xp ? f.XP : nullptr, MEM, xp ? nullptr : l0->pos_rows, vlen, f.off, dl.ca.in_w + 256 * 256,
                                   m->dec_vT[l], dl.ca.in_b + 512, f.DATT, B, m->nq, Lmax, nullptr, s, 3));
-        RUN(tail_prenorm(m, f, f.DATT, dl.ca.out.w, dl.ca.out.b, f.TGT, dl.n3.g, dl.n3.b, dl.l1.w, dl.l1.b, dl.l2.w, dl.l2.b, f.TGT,
-                         m->dec_norm.g, m->dec_norm.b, f.HS + (size_t)l * T * 256, T, nullptr, ff, s, nullptr, nullptr,
-                         m->dec_wo_img1[l], m->dec_ffn_img1[l]));
+        TailArgs t = tail_args(&m->dec_tail[l], f.DATT, f.TGT, f.TGT, T, nullptr, ff);
+        t.pre = true; t.OUT2 = f.HS + (size_t)l * T * 256; t.ldo2 = 256;                             // decoder.norm of this layer's rows
+        RUN(launch_layer_tail(m, f, t, s));
     }
-    const int HT = nd * T;
-    RUN(launch_rowdot(f.HS, 256, m->class_embed.w, m->class_embed.b, f.LG, 2, HT, 2, 0, s));
-    RUN(launch_gemm(G(m, f.HS, 256, m->span[0].w, 256, m->span[0].b, f.S1, 256, HT, nullptr, 256, 256, EPI_RELU), s));
-    RUN(launch_gemm(G(m, f.S1, 256, m->span[1].w, 256, m->span[1].b, f.S2, 256, HT, nullptr, 256, 256, EPI_RELU), s));
-    RUN(launch_rowdot(f.S2, 256, m->span[2].w, m->span[2].b, f.SP, 2, HT, 2, 1, s));
-    const size_t last = (size_t)(nd - 1) * T * 2;
-    CONE_CHECK_HIP(hipMemcpyAsync(logits, f.LG + last, (size_t)T * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    CONE_CHECK_HIP(hipMemcpyAsync(spans, f.SP + last, (size_t)T * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (taps) {
-        if (taps->hs)
-            CONE_CHECK_HIP(hipMemcpyAsync(taps->hs, f.HS, (size_t)nd * T * 256 * sizeof(float), hipMemcpyDeviceToDevice, s));
-        if (taps->aux_logits && nd > 1)
-            CONE_CHECK_HIP(hipMemcpyAsync(taps->aux_logits, f.LG, last * sizeof(float), hipMemcpyDeviceToDevice, s));
-        if (taps->aux_spans && nd > 1)
-            CONE_CHECK_HIP(hipMemcpyAsync(taps->aux_spans, f.SP, last * sizeof(float), hipMemcpyDeviceToDevice, s));
-    }
-    if (saliency || (taps && taps->memory))
-        RUN(launch_saliency(MEM, f.off, vlen, qlen, m->saliency.w, m->saliency.b, saliency, Lv_max,
-                            taps ? taps->memory : nullptr, Lq_max, B, s));
-    return 0;
+    return heads_and_taps(m, HeadBufs{f.HS, f.S1, f.S2, f.LG, f.SP, f.off}, MEM, vlen, qlen, B, Lv_max, Lq_max, logits, spans, saliency,
+                          taps, false, s);
 }
 
 // ------------------------------------------------------------------------------ general-shape forward
@@ -913,27 +975,8 @@ static int forward_general(const cone_model* m, const float* vproj, const int* v
         }
         RUN(ln(f.TGT, m->dec_norm, f.HS + (size_t)l * T * d));                                            // decoder.norm (intermediate)
     }
-    // heads (cone/model.py:112-117), every layer (aux_outputs), the last layer's rows out
-    const int HT = nd * T;
-    RUN(launch_gen_rowdot(f.HS, d, m->class_embed.w, m->class_embed.b, f.LG, 2, HT, 2, 0, d, s));
-    RUN(launch_gemm(G(m, f.HS, d, m->span[0].w, d, m->span[0].b, f.S1, d, HT, nullptr, d, d, EPI_RELU), s));
-    RUN(launch_gemm(G(m, f.S1, d, m->span[1].w, d, m->span[1].b, f.S2, d, HT, nullptr, d, d, EPI_RELU), s));
-    RUN(launch_gen_rowdot(f.S2, d, m->span[2].w, m->span[2].b, f.SP, 2, HT, 2, 1, d, s));
-    const size_t last = (size_t)(nd - 1) * T * 2;
-    CONE_CHECK_HIP(hipMemcpyAsync(logits, f.LG + last, (size_t)T * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    CONE_CHECK_HIP(hipMemcpyAsync(spans, f.SP + last, (size_t)T * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (taps) {
-        if (taps->hs)
-            CONE_CHECK_HIP(hipMemcpyAsync(taps->hs, f.HS, (size_t)nd * T * d * sizeof(float), hipMemcpyDeviceToDevice, s));
-        if (taps->aux_logits && nd > 1)
-            CONE_CHECK_HIP(hipMemcpyAsync(taps->aux_logits, f.LG, last * sizeof(float), hipMemcpyDeviceToDevice, s));
-        if (taps->aux_spans && nd > 1)
-            CONE_CHECK_HIP(hipMemcpyAsync(taps->aux_spans, f.SP, last * sizeof(float), hipMemcpyDeviceToDevice, s));
-    }
-    if (saliency || (taps && taps->memory))
-        RUN(launch_gen_saliency(MEM, f.off, vlen, qlen, m->saliency.w, m->saliency.b, saliency, Lv_max, taps ? taps->memory : nullptr,
-                                Lq_max, B, d, s));
-    return 0;
+    return heads_and_taps(m, HeadBufs{f.HS, f.S1, f.S2, f.LG, f.SP, f.off}, MEM, vlen, qlen, B, Lv_max, Lq_max, logits, spans, saliency,
+                          taps, true, s);
 }
 
 static int forward_packed(const cone_model* m, const float* vproj, const int* vrow0, const int* vlen,
@@ -944,23 +987,19 @@ static int forward_packed(const cone_model* m, const float* vproj, const int* vr
     const int Lmax = Lv_max + Lq_max;
     CONE_REQUIRE(Lmax <= CONE_MAX_WINDOW_TOKENS, "forward: window length %d + %d exceeds %d tokens", Lv_max, Lq_max,
                  CONE_MAX_WINDOW_TOKENS);
-    if (m->general()) {     // (any window length up to the limit; no layer-0 caches or tables read)
-        CONE_REQUIRE((int64_t)B * Lmax < (1ll << 24), "forward: batch too large (B * L >= 2^24 tokens)");
-        if (m->txt_pos_emb)
-            CONE_REQUIRE(Lq_max <= m->txt_pos_rows, "forward: %d text tokens but txt_position_embed has %d rows (max_q_l)", Lq_max,
-                         m->txt_pos_rows);
-        return forward_general(m, vproj, vrow0, vlen, tproj, trow0, qlen, B, Lv_max, Lq_max, logits, spans, saliency, taps, ws,
-                               ws_bytes, s);
-    }
     // beyond 192 tokens only the default path exists (the 256-key forms of the encoder attention and of the folded cross-
-    // attention): the A/B forms and the unfolded decoder stop at 192 keys
-    CONE_REQUIRE(Lmax <= 192 || (m->opt_dec_fold >= 2 && dec_cross_mfma_supported(m->nq, Lmax, true) && !m->txt_pos_emb &&
-                                 m->opt_pos_tables),
-                 "forward: windows of %d tokens (> 192) run only on the default table path with 3 / 5 / 8 decoder slots", Lmax);
+    // attention): the A/B forms and the unfolded decoder stop at 192 keys (the general path: any length up to the limit)
+    if (!m->general())
+        CONE_REQUIRE(Lmax <= 192 || (m->opt_dec_fold >= 2 && dec_cross_mfma_supported(m->nq, Lmax, true) && !m->txt_pos_emb &&
+                                     m->opt_pos_tables),
+                     "forward: windows of %d tokens (> 192) run only on the default table path with 3 / 5 / 8 decoder slots", Lmax);
     CONE_REQUIRE((int64_t)B * Lmax < (1ll << 24), "forward: batch too large (B * L >= 2^24 tokens)");
     if (m->txt_pos_emb)
         CONE_REQUIRE(Lq_max <= m->txt_pos_rows, "forward: %d text tokens but txt_position_embed has %d rows (max_q_l)", Lq_max,
                      m->txt_pos_rows);
+    if (m->general())       // (no layer-0 caches or tables read)
+        return forward_general(m, vproj, vrow0, vlen, tproj, trow0, qlen, B, Lv_max, Lq_max, logits, spans, saliency, taps, ws,
+                               ws_bytes, s);
     cone_layer0 eff;
     FwdPlan plan;
     l0 = resolve_l0(m, l0, Lv_max, Lmax, &eff, &plan);
@@ -1010,7 +1049,6 @@ static int forward_packed(const cone_model* m, const float* vproj, const int* vr
     bool qkv_fused = false;               // this layer's q | k | v rows were written by the previous layer's tail
     for (int l = 0; l < m->n_enc; ++l) {  // cone/transformer.py:233-246
         const EncLayer& e = m->enc[l];
-        GemmArgs g;
         AttnSrc src{};
         int mode = ATTN_PACKED;
         if (l == 0 && gather0) {
@@ -1024,15 +1062,8 @@ static int forward_packed(const cone_model* m, const float* vproj, const int* vr
         } else if (plan.tables) {
             // q | k | v = x W^T + b in ONE N = 768 GEMM on x; the attention adds pos W_qk^T of this layer from the
             // static table ((x + pos) W^T = x W^T + pos W^T): no x + pos matrix, no second A operand
-            if (qkv_fused) {
-                // written by the previous layer's fused tail from the registers that held its output rows
-            } else if (m->opt_bf16 && m->bf16_img)      // (every layer, the first included: layer0_rows does the same)
-                RUN(launch_rows256_bf16(f.X, 256, m->enc_qkv_img1[l], e.sa.in_b, f.QKV, 768, Mmax, Mdev, 768, s));
-            else if (m->opt_split_bf16 && m->split_img && l > 0)      // (l == 0: the kernel of cone_layer0_project, so that
-                                                                        // a window's bits do not depend on who projected it)
-                RUN(launch_rows256_split(f.X, 256, m->enc_qkv_img[l], e.sa.in_b, f.QKV, 768, Mmax, Mdev, 768, s));
-            else
-                RUN(launch_gemm(G(m, f.X, 256, e.sa.in_w, 256, e.sa.in_b, f.QKV, 768, Mmax, Mdev, 768, 256), s));
+            if (!qkv_fused)     // (else: written by the previous layer's tail from the registers that held its output rows)
+                RUN(encoder_qkv(m, l, f.X, f.QKV, Mmax, Mdev, s, true));
             mode = ATTN_POSADD;
             src.Q = f.QKV; src.K = f.QKV + 256; src.V = f.QKV + 512; src.ldq = src.ldk = src.ldv = 768;
             src.pos_qk = l0->pos_qk + (size_t)l * pos_rows_n * 512; src.vlen = vlen; src.pos_zero_row = (int)pos_rows_n - 1;
@@ -1044,62 +1075,17 @@ static int forward_packed(const cone_model* m, const float* vproj, const int* vr
             src.Q = QK; src.K = QK + 256; src.V = V; src.ldq = src.ldk = 512; src.ldv = 256;
         }
         RUN(launch_enc_attn(mode, src, f.ATT, f.off, B, Lmax, s));
-        const bool fuse_ffn = plan.tables && m->opt_ffn_fused && ffn_fused_supported(ff);
-        if (fuse_ffn && m->opt_ffn_fused >= 2) {
-            // everything behind the attention in ONE launch: norm2(x1 + ffn(x1)), x1 = norm1(x + attn Wo^T + bo); a
-            // workgroup reads its 128 rows of x before it writes them, and nobody else touches them: in place
-            const bool g0 = l == 0 && gather_res;
-            if (m->opt_bf16 && m->bf16_img) {
-                const bool next_qkv = m->opt_qkv_fused && l + 1 < m->n_enc && plan.tables && ffn_bf16_qkv_fits(ff, 768);
-                RUN(launch_proj_ffn_bf16(f.ATT, 256, m->enc_wo_img1[l], e.sa.out.b, g0 ? vproj : f.X, 256, e.n1.g, e.n1.b,
-                                         m->enc_ffn_img1[l], e.l1.b, e.l2.b, e.n2.g, e.n2.b, f.X, 256, Mmax, Mdev, ff, s,
-                                         g0 ? RIDX : nullptr, g0 ? tproj : nullptr,
-                                         next_qkv ? m->enc_qkv_img1[l + 1] : nullptr, next_qkv ? m->enc[l + 1].sa.in_b : nullptr,
-                                         next_qkv ? f.QKV : nullptr, 768, next_qkv ? 768 : 0));
-                qkv_fused = next_qkv;
-            } else if (m->opt_split_bf16 && m->split_img) {
-                // the next encoder layer's q | k | v projection rides in the same launch (its input rows are this kernel's
-                // output: no second pass over them); ATT and QKV are disjoint parts of the H region
-                const bool next_qkv = m->opt_qkv_fused && l + 1 < m->n_enc && plan.tables && ffn_split_qkv_fits(ff, 768);
-                RUN(launch_proj_ffn_split(f.ATT, 256, m->enc_wo_img[l], e.sa.out.b, g0 ? vproj : f.X, 256, e.n1.g, e.n1.b,
-                                          m->enc_ffn_img[l], e.l1.b, e.l2.b, e.n2.g, e.n2.b, f.X, 256, Mmax, Mdev, ff, s,
-                                          g0 ? RIDX : nullptr, g0 ? tproj : nullptr,
-                                          next_qkv ? m->enc_qkv_img[l + 1] : nullptr, next_qkv ? m->enc[l + 1].sa.in_b : nullptr,
-                                          next_qkv ? f.QKV : nullptr, 768, next_qkv ? 768 : 0));
-                qkv_fused = next_qkv;
-            } else {
-                // (exact-fp32 kernel: measured neutral against the separate GEMM launch -- 44.3 vs 44.1 ms of kernel time per
-                // step -- so only on request: qkv_fused = 2)
-                const bool next_qkv = m->opt_qkv_fused >= 2 && l + 1 < m->n_enc && plan.tables && ffn_fused_qkv_fits(ff, 768);
-                if (!next_qkv && m->opt_spread && f.SPR && ffn_spread_supported(Mmax, ff)) {
-                    // a few windows (<= 1 024 token rows): the spread form, as for the decoder tails of a small batch
-                    RUN(launch_proj_ffn_spread(f.ATT, 256, e.sa.out.w, e.sa.out.b, g0 ? vproj : f.X, 256, e.n1.g, e.n1.b, e.l1.w,
-                                               e.l1.b, e.l2.w, e.l2.b, e.n2.g, e.n2.b, f.X, 256, Mmax, ff, f.SPR, s, Mdev,
-                                               g0 ? RIDX : nullptr, g0 ? tproj : nullptr));
-                    qkv_fused = false;
-                    continue;
-                }
-                RUN(launch_proj_ffn_fused(f.ATT, 256, e.sa.out.w, e.sa.out.b, g0 ? vproj : f.X, 256, e.n1.g, e.n1.b, e.l1.w,
-                                          e.l1.b, e.l2.w, e.l2.b, e.n2.g, e.n2.b, f.X, 256, Mmax, Mdev, ff, s,
-                                          g0 ? RIDX : nullptr, g0 ? tproj : nullptr,
-                                          next_qkv ? m->enc[l + 1].sa.in_w : nullptr, next_qkv ? m->enc[l + 1].sa.in_b : nullptr,
-                                          next_qkv ? f.QKV : nullptr, 768, next_qkv ? 768 : 0));
-                qkv_fused = next_qkv;
-            }
-            continue;
-        }
-        g = G(m, f.ATT, 256, e.sa.out.w, 256, e.sa.out.b, f.X1, 256, Mmax, Mdev, 256, 256, EPI_RESIDUAL | EPI_LN);
-        g.R = f.X; g.ldr = 256; g.ln_g = e.n1.g; g.ln_b = e.n1.b;
-        RUN(launch_gemm(g, s));                                                             // norm1(x + attn)
-        if (fuse_ffn) {                                                                     // norm2(x + ffn), one kernel
-            RUN(launch_ffn_fused(f.X1, 256, e.l1.w, e.l1.b, e.l2.w, e.l2.b, e.n2.g, e.n2.b, f.X, 256, Mmax, Mdev, ff, s));
-        } else {
-            RUN(launch_gemm(G(m, f.X1, 256, e.l1.w, 256, e.l1.b, f.H, ff, Mmax, Mdev, ff, 256, EPI_RELU), s));
-            g = G(m, f.H, ff, e.l2.w, ff, e.l2.b, f.X, 256, Mmax, Mdev, 256, ff, EPI_RESIDUAL | EPI_LN);
-            g.R = f.X1; g.ldr = 256; g.ln_g = e.n2.g; g.ln_b = e.n2.b;
-            if (!plan.tables) { g.C2 = f.XP; g.ADD = f.POS; }   // x + pos for the next layer's q/k / the decoder's keys
-            RUN(launch_gemm(g, s));                                                         // norm2(x + ffn)
-        }
+        // everything behind the attention: norm2(x1 + ffn(x1)), x1 = norm1(x + attn Wo^T + bo) -- by default ONE launch, in place
+        // (a workgroup reads its 128 rows of x before it writes them, and nobody else touches them), in which the next layer's
+        // q | k | v projection may ride (its input rows are that kernel's output; ATT and QKV are disjoint parts of the H region)
+        const bool g0 = l == 0 && gather_res;
+        TailArgs t = tail_args(&m->enc_tail[l], f.ATT, g0 ? vproj : f.X, f.X, Mmax, Mdev, ff);
+        if (g0) { t.r_idx = RIDX; t.R2 = tproj; }
+        if (l + 1 < m->n_enc) t.next = &m->enc_tail[l + 1];
+        t.QKV = f.QKV; t.ldq = 768; t.n_qkv = 768;
+        t.X1 = f.X1; t.H = f.H;
+        if (!plan.tables) { t.C2 = f.XP; t.ADD = f.POS; }   // x + pos for the next layer's q/k / the decoder's keys
+        RUN(launch_layer_tail(m, f, t, s, &qkv_fused));
     }
     const float* MEM = f.X;
 
@@ -1180,33 +1166,9 @@ static int forward_packed(const cone_model* m, const float* vproj, const int* vr
         else
             RUN(launch_small_attn(f.DQ, 256, f.KD + l * 256, 256 * nd, f.VD + l * 256, 256 * nd, f.DATT, 256, f.off, B,
                                   m->nq, Lmax, s));
-        if (m->opt_ffn_fused >= 2 && m->opt_bf16 && m->bf16_img) {
-            RUN(launch_proj_ffn_bf16(f.DATT, 256, m->dec_wo_img1[l], dl.ca.out.b, f.TGT1, 256, dl.n2.g, dl.n2.b,
-                                     m->dec_ffn_img1[l], dl.l1.b, dl.l2.b, dl.n3.g, dl.n3.b, f.TGT, 256, T, nullptr, ff, s));
-        } else if (m->opt_ffn_fused >= 2 && m->opt_split_bf16 && m->split_img) {
-            RUN(launch_proj_ffn_split(f.DATT, 256, m->dec_wo_img[l], dl.ca.out.b, f.TGT1, 256, dl.n2.g, dl.n2.b,
-                                      m->dec_ffn_img[l], dl.l1.b, dl.l2.b, dl.n3.g, dl.n3.b, f.TGT, 256, T, nullptr, ff, s));
-        } else if (m->opt_ffn_fused >= 2 && ffn_fused_supported(ff) && m->opt_spread && f.SPR && ffn_spread_supported(T, ff)) {
-            // a handful of slot rows (a single query's 20 windows = 7 row groups): the group's output elements spread over
-            // single-wave workgroups in four launches instead of one CU walking the whole block -- the same bits
-            RUN(launch_proj_ffn_spread(f.DATT, 256, dl.ca.out.w, dl.ca.out.b, f.TGT1, 256, dl.n2.g, dl.n2.b, dl.l1.w, dl.l1.b,
-                                       dl.l2.w, dl.l2.b, dl.n3.g, dl.n3.b, f.TGT, 256, T, ff, f.SPR, s));
-        } else if (m->opt_ffn_fused >= 2 && ffn_fused_supported(ff)) {
-            RUN(launch_proj_ffn_fused(f.DATT, 256, dl.ca.out.w, dl.ca.out.b, f.TGT1, 256, dl.n2.g, dl.n2.b, dl.l1.w, dl.l1.b,
-                                      dl.l2.w, dl.l2.b, dl.n3.g, dl.n3.b, f.TGT, 256, T, nullptr, ff, s));
-        } else {
-            g = G(m, f.DATT, 256, dl.ca.out.w, 256, dl.ca.out.b, f.TGT2, 256, T, nullptr, 256, 256, EPI_RESIDUAL | EPI_LN);
-            g.R = f.TGT1; g.ldr = 256; g.ln_g = dl.n2.g; g.ln_b = dl.n2.b;
-            RUN(launch_gemm(g, s));
-            if (m->opt_ffn_fused && ffn_fused_supported(ff)) {
-                RUN(launch_ffn_fused(f.TGT2, 256, dl.l1.w, dl.l1.b, dl.l2.w, dl.l2.b, dl.n3.g, dl.n3.b, f.TGT, 256, T, nullptr, ff, s));
-            } else {
-                RUN(launch_gemm(G(m, f.TGT2, 256, dl.l1.w, 256, dl.l1.b, f.DH, ff, T, nullptr, ff, 256, EPI_RELU), s));
-                g = G(m, f.DH, ff, dl.l2.w, ff, dl.l2.b, f.TGT, 256, T, nullptr, 256, ff, EPI_RESIDUAL | EPI_LN);
-                g.R = f.TGT2; g.ldr = 256; g.ln_g = dl.n3.g; g.ln_b = dl.n3.b;
-                RUN(launch_gemm(g, s));
-            }
-        }
+        TailArgs t = tail_args(&m->dec_tail[l], f.DATT, f.TGT1, f.TGT, T, nullptr, ff);    // tgt = norm3(x1 + ffn(x1)), x1 = norm2(tgt1 + ca)
+        t.X1 = f.TGT2; t.H = f.DH;
+        RUN(launch_layer_tail(m, f, t, s));
         // decoder.norm + heads on an intermediate layer only feed aux_outputs / the hs tap (unused by inference,
         // cone/inference.py:54-59): computed on request only
         if (l == nd - 1 || want_aux) {
@@ -1244,14 +1206,7 @@ static int forward_packed(const cone_model* m, const float* vproj, const int* vr
         CONE_CHECK_HIP(hipMemcpyAsync(logits, f.LG + last, (size_t)T * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
         CONE_CHECK_HIP(hipMemcpyAsync(spans, f.SP + last, (size_t)T * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
-    if (taps) {
-        if (taps->hs)
-            CONE_CHECK_HIP(hipMemcpyAsync(taps->hs, f.HS, (size_t)nd * T * 256 * sizeof(float), hipMemcpyDeviceToDevice, s));
-        if (taps->aux_logits && nd > 1)
-            CONE_CHECK_HIP(hipMemcpyAsync(taps->aux_logits, f.LG, last * sizeof(float), hipMemcpyDeviceToDevice, s));
-        if (taps->aux_spans && nd > 1)
-            CONE_CHECK_HIP(hipMemcpyAsync(taps->aux_spans, f.SP, last * sizeof(float), hipMemcpyDeviceToDevice, s));
-    }
+    RUN(copy_taps(taps, f.HS, f.LG, f.SP, nd, T, 256, s));
     if ((saliency && !sal_done) || (taps && taps->memory))     // saliency == NULL: not wanted (cone/inference.py never reads it)
         RUN(launch_saliency(MEM, f.off, vlen, qlen, m->saliency.w, m->saliency.b, sal_done ? nullptr : saliency, Lv_max,
                             taps ? taps->memory : nullptr, Lq_max, B, s));
@@ -1587,19 +1542,29 @@ extern "C" int cone_test_ffn(const float* X, const float* W1, const float* b1, c
                              const float* ln_g, const float* ln_b, float* OUT, int M, int ff, void* stream) {
     return launch_ffn_fused(X, 256, W1, b1, W2, b2, ln_g, ln_b, OUT, 256, M, nullptr, ff, (hipStream_t)stream);
 }
+// the tail of the cone_test_* entries: raw operand pointers, 256-float rows, no device-side count
+static TailArgs test_tail(TailWeights* w, const float* A, const float* Wo, const float* bo, const float* R, const float* pg,
+                          const float* pb, const float* W1, const float* b1, const float* W2, const float* b2, const float* ln_g,
+                          const float* ln_b, float* OUT, int M, int ff) {
+    *w = TailWeights{};
+    w->Wo = Wo; w->bo = bo; w->W1 = W1; w->b1 = b1; w->W2 = W2; w->b2 = b2; w->in_g = pg; w->in_b = pb; w->out_g = ln_g; w->out_b = ln_b;
+    return tail_args(w, A, R, OUT, M, nullptr, ff);
+}
 extern "C" int cone_test_proj_ffn(const float* A, const float* Wo, const float* bo, const float* R, const float* pg,
                                   const float* pb, const float* W1, const float* b1, const float* W2, const float* b2,
                                   const float* ln_g, const float* ln_b, float* OUT, int M, int ff, void* stream) {
-    return launch_proj_ffn_fused(A, 256, Wo, bo, R, 256, pg, pb, W1, b1, W2, b2, ln_g, ln_b, OUT, 256, M, nullptr, ff,
-                                 (hipStream_t)stream);
+    TailWeights w;
+    return launch_proj_ffn_fused(test_tail(&w, A, Wo, bo, R, pg, pb, W1, b1, W2, b2, ln_g, ln_b, OUT, M, ff), (hipStream_t)stream);
 }
 extern "C" size_t cone_test_proj_ffn_spread_scratch_bytes(int ff) { return ffn_spread_scratch_floats(ff) * sizeof(float); }
 extern "C" int cone_test_proj_ffn_spread(const float* A, const float* Wo, const float* bo, const float* R, const float* pg,
                                          const float* pb, const float* W1, const float* b1, const float* W2, const float* b2,
                                          const float* ln_g, const float* ln_b, float* OUT, int M, int ff, void* scratch,
                                          void* stream) {
-    return launch_proj_ffn_spread(A, 256, Wo, bo, R, 256, pg, pb, W1, b1, W2, b2, ln_g, ln_b, OUT, 256, M, ff, (float*)scratch,
-                                  (hipStream_t)stream);
+    TailWeights w;
+    TailArgs t = test_tail(&w, A, Wo, bo, R, pg, pb, W1, b1, W2, b2, ln_g, ln_b, OUT, M, ff);
+    t.scratch = (float*)scratch;
+    return launch_proj_ffn_spread(t, (hipStream_t)stream);
 }
 extern "C" size_t cone_test_ffn_split_image_bytes(int ff) { return ffn_split_supported(ff) ? ffn_split_image_bytes(ff) : 0; }
 extern "C" int cone_test_ffn_split(const float* X, const float* W1, const float* b1, const float* W2, const float* b2,
@@ -1639,24 +1604,18 @@ extern "C" int cone_test_proj_ffn_split(const float* A, const float* Wo, const f
                                         const float* pb, const float* W1, const float* b1, const float* W2,
                                         const float* b2, const float* ln_g, const float* ln_b, float* OUT, int M, int ff,
                                         void* img, void* wo_img, int pack, void* stream) {
-    if (pack & CONE_TEST_SINGLE_PIECE) {     // the single-piece form
-        if (pack & CONE_TEST_PACK) {
-            int rc = launch_ffn_bf16_pack(W1, W2, ff, img, (hipStream_t)stream);
-            if (rc) return rc;
-            rc = launch_ffn_bf16_pack(Wo, nullptr, 256, wo_img, (hipStream_t)stream);
-            if (rc) return rc;
-        }
-        return launch_proj_ffn_bf16(A, 256, wo_img, bo, R, 256, pg, pb, img, b1, b2, ln_g, ln_b, OUT, 256, M, nullptr, ff,
-                                    (hipStream_t)stream);
-    }
-    if (pack) {
-        int rc = launch_ffn_split_pack(W1, W2, ff, img, (hipStream_t)stream);
+    const bool single = pack & CONE_TEST_SINGLE_PIECE;     // the single-piece form (ffn_bf16.hip)
+    const TailImageMode& k = TAIL_IMAGE_MODES[single ? TAIL_IMG_BF16 : TAIL_IMG_SPLIT];
+    if (single ? pack & CONE_TEST_PACK : pack) {
+        int rc = k.pack(W1, W2, ff, img, (hipStream_t)stream);
         if (rc) return rc;
-        rc = launch_ffn_split_pack(Wo, nullptr, 256, wo_img, (hipStream_t)stream);
+        rc = k.pack(Wo, nullptr, 256, wo_img, (hipStream_t)stream);
         if (rc) return rc;
     }
-    return launch_proj_ffn_split(A, 256, wo_img, bo, R, 256, pg, pb, img, b1, b2, ln_g, ln_b, OUT, 256, M, nullptr, ff,
-                                 (hipStream_t)stream);
+    TailWeights w;
+    const TailArgs t = test_tail(&w, A, Wo, bo, R, pg, pb, W1, b1, W2, b2, ln_g, ln_b, OUT, M, ff);
+    w.img[single ? TAIL_IMG_BF16 : TAIL_IMG_SPLIT] = TailImages{wo_img, img, nullptr};
+    return single ? launch_proj_ffn_bf16(t, (hipStream_t)stream) : launch_proj_ffn_split(t, (hipStream_t)stream);
 }
 extern "C" int cone_test_enc_attn(int mode, const float* QKV, const float* qkv_vid, const float* qkv_txt,
                                   const float* pos_qk, const int32_t* vrow0, const int32_t* vlen, const int32_t* trow0,

@@ -130,6 +130,39 @@ struct GemmArgs {
 enum { GEMM_AUTO = 0, GEMM_SQUARE = 1, GEMM_ROWS4 = 2, GEMM_ROWS8 = 3 };
 int launch_gemm(const GemmArgs& a, hipStream_t s);
 
+// ---------------------------------------------------------------- the layer tail's descriptor
+// A transformer layer behind its attention: x1 = LN_in(R + A Wo^T + bo), OUT = LN_out(x1 + W2 relu(W1 x1 + b1) + b2)
+// (post-norm), resp. x1 = R + A Wo^T + bo, OUT = x1 + FFN(LN_in(x1)), OUT2 = LN_out(OUT) (pre: --pre_norm).
+// TailWeights: one layer's operands, built once per model -- the fp32 pointers and, per numeric mode, the weight images.
+enum { TAIL_IMG_SPLIT = 0, TAIL_IMG_BF16 = 1, TAIL_IMG_MODES = 2 };   // split_bf16 (ffn_split.hip), bf16 (ffn_bf16.hip)
+struct TailImages { const void* wo; const void* ffn; const void* qkv; };   // of Wo, of W1 | W2, of Wq (encoder layers only)
+struct TailWeights {
+    const float *Wo, *bo;                 // attention output projection (256, 256)
+    const float *W1, *b1, *W2, *b2;       // linear1 (ff, 256), linear2 (256, ff)
+    const float *in_g, *in_b;             // the inner LayerNorm: behind the projection (post-norm) / ahead of the block (pre-norm)
+    const float *out_g, *out_b;           // the outer one: the layer's last (post-norm) / the NEXT consumer's, of OUT2 (pre-norm)
+    const float *Wq, *qb;                 // encoder layers: the layer's OWN q | k | v projection (768, 256) -- what the tail of
+                                          // the layer before it computes when the projection rides
+    TailImages img[TAIL_IMG_MODES];
+};
+// TailArgs: one launch.  Every launcher of a projecting tail takes it, checks what its form needs and fills its kernel's struct.
+struct TailArgs {
+    const float* A; int lda;              // attention rows (M, 256)
+    const float* R; int ldr;              // residual rows; r_idx != null: row i is gathered -- r_idx[i] >= 0: row r_idx[i] of R,
+    const int* r_idx; const float* R2;    //   else row ~r_idx[i] of R2 (launch_row_index)
+    const TailWeights* w;
+    float* OUT; int ldo;                  // may be R (in place: a workgroup reads its rows before it writes them)
+    float* OUT2; int ldo2;                // pre only (may be null)
+    int M; const int* M_dev; int ff;      // rows: the host bound (sizes the grid, picks the form) and the device-side count
+    bool pre;
+    const TailWeights* next;              // != null: the launch also writes QKV (M, n_qkv) = OUT next->Wq^T + next->qb (the next
+    float* QKV; int ldq; int n_qkv;       //   layer's q | k | v projection) from the registers that hold OUT
+    float* scratch;                       // the spread form's rows (ffn_spread_scratch_floats(ff) floats)
+    int m_off;                            // wide form: the rows are rows m_off .. m_off + M of a larger job whose count is *M_dev
+    float* X1; float* H;                  // the unfused forms' rows (api.hip, launch_layer_tail): LN_in's output (M, 256), hidden (M, ff)
+    float* C2; const float* ADD;          // != null: a second output C2 = OUT + ADD, which only the unfused GEMM epilogue writes
+};
+
 // ---------------------------------------------------------------- fused feed-forward block (ffn.hip)
 // OUT = LayerNorm(X + W2 relu(W1 X + b1) + b2): X, OUT (M, 256); W1 (ff, 256); W2 (256, ff).  OUT may alias nothing
 // the kernel reads (X is re-read as the residual from registers only, but other workgroups read other rows).
@@ -137,24 +170,12 @@ bool ffn_fused_supported(int ff);
 int launch_ffn_fused(const float* X, int ldx, const float* W1, const float* b1, const float* W2, const float* b2,
                      const float* ln_g, const float* ln_b, float* OUT, int ldo, int M, const int* M_dev, int ff,
                      hipStream_t s);
-// The same with the block input computed in the kernel too: X = LayerNorm_p(R + A Wo^T + bo) (attention output
-// projection + residual + norm), i.e. everything of a transformer layer behind its attention in one launch.
-int launch_proj_ffn_fused(const float* A, int lda, const float* Wo, const float* bo, const float* R, int ldr,
-                          const float* pg, const float* pb, const float* W1, const float* b1, const float* W2,
-                          const float* b2, const float* ln_g, const float* ln_b, float* OUT, int ldo, int M,
-                          const int* M_dev, int ff, hipStream_t s, const int* r_idx = nullptr, const float* R2 = nullptr,
-                          const float* Wq = nullptr, const float* qb = nullptr, float* QKV = nullptr, int ldq = 0,
-                          int n_qkv = 0);
-int launch_proj_ffn_prenorm(const float* A, int lda, const float* Wo, const float* bo, const float* R, int ldr, const float* pg,
-                            const float* pb, const float* W1, const float* b1, const float* W2, const float* b2, float* OUT,
-                            int ldo, const float* n2g, const float* n2b, float* OUT2, int ldo2, int M, const int* M_dev, int ff,
-                            hipStream_t s, const int* r_idx = nullptr, const float* R2 = nullptr);
-// pre-norm form of the layer tail: OUT = x1 + FFN(LayerNorm(x1; pg, pb)), x1 = R + A Wo^T + bo (un-normalised stream);
-// OUT2 (may be null) = LayerNorm(OUT; n2g, n2b)
-// Wq != null: the kernel also writes QKV (M, n_qkv) = OUT Wq^T + qb (the next layer's q | k | v projection) from the
-// registers that hold OUT
+// The same with the block input computed in the kernel too (the post-norm tail), i.e. everything of a transformer layer
+// behind its attention in one launch: the persistent 128-row kernel, its 64-row form, the wide form for a few row groups
+// and for the rows past the last full round -- chosen by the host-known row bound, the same bits in every form.
+int launch_proj_ffn_fused(const TailArgs& t, hipStream_t s);
+int launch_proj_ffn_prenorm(const TailArgs& t, hipStream_t s);     // the pre-norm tail, persistent 128-row kernel only
 bool ffn_fused_qkv_fits(int ff, int n_qkv);
-// r_idx != null: residual row i is gathered -- r_idx[i] >= 0: row r_idx[i] of R, else row ~r_idx[i] of R2 (launch_row_index)
 
 // ---------------------------------------------------------------- wide form for a few row groups (ffn_wide.hip)
 // The same two computations with ONE workgroup per 16 rows whose eight waves split the output elements (projection and
@@ -163,23 +184,13 @@ bool ffn_wide_supported(int ff);
 // the spread form of the projecting tail for <= 64 row groups (ffn_wide.hip): 4 launches over single-wave workgroups, same bits
 size_t ffn_spread_scratch_floats(int ff);
 bool ffn_spread_supported(int M, int ff);
-int launch_proj_ffn_spread(const float* A, int lda, const float* Wo, const float* bo, const float* R, int ldr, const float* pg,
-                           const float* pb, const float* W1, const float* b1, const float* W2, const float* b2,
-                           const float* ln_g, const float* ln_b, float* OUT, int ldo, int M, int ff, float* scratch,
-                           hipStream_t s, const int* M_dev = nullptr, const int* r_idx = nullptr, const float* R2 = nullptr,
-                           bool pre = false, float* OUT2 = nullptr, int ldo2 = 0);      // pre: the pre-norm tail (OUT = the stream, OUT2 = LN(OUT; ln_g, ln_b))
-int launch_proj_ffn_prenorm_wide(const float* A, int lda, const float* Wo, const float* bo, const float* R, int ldr, const float* pg,
-                                 const float* pb, const float* W1, const float* b1, const float* W2, const float* b2, float* OUT,
-                                 int ldo, const float* n2g, const float* n2b, float* OUT2, int ldo2, int M, const int* M_dev, int ff,
-                                 hipStream_t s, const int* r_idx = nullptr, const float* R2 = nullptr);
+int launch_proj_ffn_spread(const TailArgs& t, hipStream_t s);      // post-norm and pre-norm (t.pre)
+int launch_proj_ffn_prenorm_wide(const TailArgs& t, hipStream_t s);
+int launch_proj_ffn_wide(const TailArgs& t, hipStream_t s);
 // m_off: the rows are rows m_off .. m_off + M of a larger job whose device-side row count is *M_dev
 int launch_ffn_wide(const float* X, int ldx, const float* W1, const float* b1, const float* W2, const float* b2,
                     const float* ln_g, const float* ln_b, float* OUT, int ldo, int M, const int* M_dev, int ff, hipStream_t s,
                     int m_off = 0);
-int launch_proj_ffn_wide(const float* A, int lda, const float* Wo, const float* bo, const float* R, int ldr, const float* pg,
-                         const float* pb, const float* W1, const float* b1, const float* W2, const float* b2,
-                         const float* ln_g, const float* ln_b, float* OUT, int ldo, int M, const int* M_dev, int ff,
-                         hipStream_t s, const int* r_idx, const float* R2, int m_off = 0);
 
 // ---------------------------------------------------------------- the same on the bf16 matrix cores (ffn_split.hip)
 // fp32 products as six partial products of three-piece bf16 operands, fp32 accumulation: fp32-MFMA accuracy (measured),
@@ -195,22 +206,16 @@ bool rows256_split_supported(int N);
 size_t rows256_split_image_bytes(int N);
 int launch_rows256_split(const float* X, int ldx, const void* Wimg, const float* bias, float* C, int ldc, int M,
                          const int* M_dev, int N, hipStream_t s);
-// launch_proj_ffn_fused's computation: Woimg = launch_ffn_split_pack(Wo, nullptr, 256, ...) (ffn_split_proj_image_bytes())
+// launch_proj_ffn_fused's computation on img[TAIL_IMG_SPLIT]: wo = launch_ffn_split_pack(Wo, nullptr, 256, ...)
+// (ffn_split_proj_image_bytes()), ffn as above, the ride's qkv = launch_ffn_split_pack(Wq, nullptr, n_qkv, ...)
 size_t ffn_split_proj_image_bytes();
 bool ffn_split_qkv_fits(int ff, int n_qkv);
-int launch_proj_ffn_split(const float* A, int lda, const void* Woimg, const float* bo, const float* R, int ldr,
-                          const float* pg, const float* pb, const void* Wimg, const float* b1, const float* b2,
-                          const float* ln_g, const float* ln_b, float* OUT, int ldo, int M, const int* M_dev, int ff,
-                          hipStream_t s, const int* r_idx = nullptr, const float* R2 = nullptr,
-                          const void* Qimg = nullptr, const float* qb = nullptr, float* QKV = nullptr, int ldq = 0,
-                          int n_qkv = 0);
-// Qimg != null: the kernel also writes QKV (M, n_qkv) = OUT Wq^T + qb (the next layer's q | k | v projection; Qimg =
-// launch_ffn_split_pack(Wq, nullptr, n_qkv, ...)) from the registers that hold OUT
+int launch_proj_ffn_split(const TailArgs& t, hipStream_t s);
 
 // ---------------------------------------------------------------- the single-piece form (ffn_bf16.hip)
 // The same kernels with every GEMM operand rounded ONCE to bf16 and one MFMA per operand pair (fp32 accumulation; bias,
 // ReLU, residual -- the unrounded fp32 input -- and LayerNorm in fp32): plain bf16 matrix arithmetic, NOT fp32-accurate.
-// Images hold the high piece only (one third of the three-piece images), built by launch_ffn_bf16_pack.
+// Images (img[TAIL_IMG_BF16]) hold the high piece only (one third of the three-piece images), built by launch_ffn_bf16_pack.
 bool ffn_bf16_supported(int ff);
 size_t ffn_bf16_image_bytes(int ff);
 int launch_ffn_bf16_pack(const float* W1, const float* W2, int ff, void* img, hipStream_t s);
@@ -222,18 +227,8 @@ int launch_rows256_bf16(const float* X, int ldx, const void* Wimg, const float* 
                         const int* M_dev, int N, hipStream_t s);
 size_t ffn_bf16_proj_image_bytes();
 bool ffn_bf16_qkv_fits(int ff, int n_qkv);
-int launch_proj_ffn_bf16(const float* A, int lda, const void* Woimg, const float* bo, const float* R, int ldr,
-                         const float* pg, const float* pb, const void* Wimg, const float* b1, const float* b2,
-                         const float* ln_g, const float* ln_b, float* OUT, int ldo, int M, const int* M_dev, int ff,
-                         hipStream_t s, const int* r_idx = nullptr, const float* R2 = nullptr,
-                         const void* Qimg = nullptr, const float* qb = nullptr, float* QKV = nullptr, int ldq = 0,
-                         int n_qkv = 0);
-// the --pre_norm form (launch_proj_ffn_prenorm's computation): OUT = x1 + ffn(LayerNorm(x1; pg, pb)), x1 = R + A Wo^T + bo;
-// OUT2 (may be null) = LayerNorm(OUT; n2g, n2b)
-int launch_proj_ffn_bf16_prenorm(const float* A, int lda, const void* Woimg, const float* bo, const float* R, int ldr,
-                                 const float* pg, const float* pb, const void* Wimg, const float* b1, const float* b2,
-                                 float* OUT, int ldo, const float* n2g, const float* n2b, float* OUT2, int ldo2, int M,
-                                 const int* M_dev, int ff, hipStream_t s, const int* r_idx = nullptr, const float* R2 = nullptr);
+int launch_proj_ffn_bf16(const TailArgs& t, hipStream_t s);
+int launch_proj_ffn_bf16_prenorm(const TailArgs& t, hipStream_t s);    // the --pre_norm form
 
 // ---------------------------------------------------------------- row kernels (rowops.hip)
 int launch_layernorm(const float* x, int ldx, const float* g, const float* b, float* out, int ldo,

@@ -658,55 +658,57 @@ int launch_ffn_fused(const float* X, int ldx, const float* W1, const float* b1, 
                            s, m1);
 }
 
-int launch_proj_ffn_fused(const float* A, int lda, const float* Wo, const float* bo, const float* R, int ldr,
-                          const float* pg, const float* pb, const float* W1, const float* b1, const float* W2,
-                          const float* b2, const float* ln_g, const float* ln_b, float* OUT, int ldo, int M,
-                          const int* M_dev, int ff, hipStream_t s, const int* r_idx, const float* R2, const float* Wq,
-                          const float* qb, float* QKV, int ldq, int n_qkv) {
-    CONE_REQUIRE(!r_idx || R2, "fused layer tail: a gathered residual needs both source matrices");
-    CONE_REQUIRE(ffn_fused_supported(ff), "fused layer tail: dim_feedforward=%d unsupported", ff);
-    CONE_REQUIRE(A && Wo && bo && R && pg && pb && W1 && b1 && W2 && b2 && ln_g && ln_b && OUT, "fused layer tail: null argument");
-    CONE_REQUIRE(lda % 4 == 0 && ldr % 4 == 0 && ldo % 4 == 0, "fused layer tail: row strides must be multiples of 4");
+int launch_proj_ffn_fused(const TailArgs& t, hipStream_t s) {
+    const TailWeights& w = *t.w;
+    const float* Wq = t.next ? t.next->Wq : nullptr;
+    CONE_REQUIRE(!t.r_idx || t.R2, "fused layer tail: a gathered residual needs both source matrices");
+    CONE_REQUIRE(ffn_fused_supported(t.ff), "fused layer tail: dim_feedforward=%d unsupported", t.ff);
+    CONE_REQUIRE(t.A && w.Wo && w.bo && t.R && w.in_g && w.in_b && w.W1 && w.b1 && w.W2 && w.b2 && w.out_g && w.out_b && t.OUT,
+                 "fused layer tail: null argument");
+    CONE_REQUIRE(t.lda % 4 == 0 && t.ldr % 4 == 0 && t.ldo % 4 == 0, "fused layer tail: row strides must be multiples of 4");
+    const int M = t.M;
     if (M <= 0) return 0;
-    if (!Wq && (M + 15) / 16 <= FFN_WIDE_GROUPS && ffn_wide_supported(ff))     // a few row groups: the wide form (same bits)
-        return launch_proj_ffn_wide(A, lda, Wo, bo, R, ldr, pg, pb, W1, b1, W2, b2, ln_g, ln_b, OUT, ldo, M, M_dev, ff, s, r_idx, R2);
+    if (!Wq && (M + 15) / 16 <= FFN_WIDE_GROUPS && ffn_wide_supported(t.ff))     // a few row groups: the wide form (same bits)
+        return launch_proj_ffn_wide(t, s);
     FfnArgs a{};
-    a.A = A; a.lda = lda; a.Wo = Wo; a.bo = bo; a.R = R; a.ldr = ldr; a.pg = pg; a.pb = pb;
-    a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2; a.ln_g = ln_g; a.ln_b = ln_b;
-    a.OUT = OUT; a.ldo = ldo; a.M = M; a.M_dev = M_dev; a.ff = ff; a.r_idx = r_idx; a.R2 = R2;
+    a.A = t.A; a.lda = t.lda; a.Wo = w.Wo; a.bo = w.bo; a.R = t.R; a.ldr = t.ldr; a.pg = w.in_g; a.pb = w.in_b;
+    a.W1 = w.W1; a.b1 = w.b1; a.W2 = w.W2; a.b2 = w.b2; a.ln_g = w.out_g; a.ln_b = w.out_b;
+    a.OUT = t.OUT; a.ldo = t.ldo; a.M = M; a.M_dev = t.M_dev; a.ff = t.ff; a.r_idx = t.r_idx; a.R2 = t.R2;
     if (Wq) {
-        CONE_REQUIRE(qb && QKV && n_qkv >= 32 && n_qkv % 32 == 0 && ldq % 4 == 0, "fused layer tail: bad q|k|v arguments");
-        a.Wq = Wq; a.qb = qb; a.QKV = QKV; a.ldq = ldq; a.n_qkv = n_qkv;
+        CONE_REQUIRE(t.next->qb && t.QKV && t.n_qkv >= 32 && t.n_qkv % 32 == 0 && t.ldq % 4 == 0,
+                     "fused layer tail: bad q|k|v arguments");
+        a.Wq = Wq; a.qb = t.next->qb; a.QKV = t.QKV; a.ldq = t.ldq; a.n_qkv = t.n_qkv;
         return launch_ffn_t<true, true>(a, s);
     }
     int n_cu = 0;
     if (int rc = launch_ffn_nw<true, false, 8>(a, s, &n_cu)) return rc;
-    const int m1 = ffn_full_round_rows(M, n_cu, ff);
+    const int m1 = ffn_full_round_rows(M, n_cu, t.ff);
     if (m1 == M) return launch_ffn_t<true, false>(a, s);
     a.M = m1;
     if (int rc = launch_ffn_t<true, false>(a, s)) return rc;
-    return launch_proj_ffn_wide(A + (size_t)m1 * lda, lda, Wo, bo, r_idx ? R : R + (size_t)m1 * ldr, ldr, pg, pb, W1, b1, W2, b2,
-                                ln_g, ln_b, OUT + (size_t)m1 * ldo, ldo, M - m1, M_dev, ff, s, r_idx ? r_idx + m1 : nullptr, R2,
-                                m1);
+    TailArgs rem = t;           // the rows past the last full round: the wide form on offset pointers
+    rem.A += (size_t)m1 * t.lda; rem.OUT += (size_t)m1 * t.ldo; rem.M = M - m1; rem.m_off = m1;
+    if (t.r_idx) rem.r_idx += m1; else rem.R += (size_t)m1 * t.ldr;
+    return launch_proj_ffn_wide(rem, s);
 }
 
-// The pre-norm layer tail (--pre_norm): OUT = x1 + FFN(LN(x1; pg, pb)), x1 = R + A Wo^T + bo; OUT2 (may be null) =
-// LN(OUT; n2g, n2b).  The persistent 128-row kernel for every row count (the option is off in every shipped configuration:
+// The pre-norm layer tail (--pre_norm): OUT = x1 + FFN(LN(x1; in_g, in_b)), x1 = R + A Wo^T + bo; OUT2 (may be null) =
+// LN(OUT; out_g, out_b).  The persistent 128-row kernel for every row count (the option is off in every shipped configuration:
 // no wide / 64-row forms).  OUT may be R (in place).
-int launch_proj_ffn_prenorm(const float* A, int lda, const float* Wo, const float* bo, const float* R, int ldr, const float* pg,
-                            const float* pb, const float* W1, const float* b1, const float* W2, const float* b2, float* OUT,
-                            int ldo, const float* n2g, const float* n2b, float* OUT2, int ldo2, int M, const int* M_dev, int ff,
-                            hipStream_t s, const int* r_idx, const float* R2) {
-    CONE_REQUIRE(!r_idx || R2, "pre-norm layer tail: a gathered residual needs both source matrices");
-    CONE_REQUIRE(ffn_fused_supported(ff), "pre-norm layer tail: dim_feedforward=%d unsupported", ff);
-    CONE_REQUIRE(A && Wo && bo && R && pg && pb && W1 && b1 && W2 && b2 && OUT && (!OUT2 || (n2g && n2b)),
-                 "pre-norm layer tail: null argument");
-    CONE_REQUIRE(lda % 4 == 0 && ldr % 4 == 0 && ldo % 4 == 0 && ldo2 % 4 == 0, "pre-norm layer tail: row strides must be multiples of 4");
-    if (M <= 0) return 0;
+int launch_proj_ffn_prenorm(const TailArgs& t, hipStream_t s) {
+    const TailWeights& w = *t.w;
+    CONE_REQUIRE(!t.r_idx || t.R2, "pre-norm layer tail: a gathered residual needs both source matrices");
+    CONE_REQUIRE(ffn_fused_supported(t.ff), "pre-norm layer tail: dim_feedforward=%d unsupported", t.ff);
+    CONE_REQUIRE(t.A && w.Wo && w.bo && t.R && w.in_g && w.in_b && w.W1 && w.b1 && w.W2 && w.b2 && t.OUT &&
+                     (!t.OUT2 || (w.out_g && w.out_b)), "pre-norm layer tail: null argument");
+    CONE_REQUIRE(t.lda % 4 == 0 && t.ldr % 4 == 0 && t.ldo % 4 == 0 && t.ldo2 % 4 == 0,
+                 "pre-norm layer tail: row strides must be multiples of 4");
+    if (t.M <= 0) return 0;
     FfnArgs a{};
-    a.A = A; a.lda = lda; a.Wo = Wo; a.bo = bo; a.R = R; a.ldr = ldr; a.pg = pg; a.pb = pb;
-    a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2; a.ln_g = n2g ? n2g : pg; a.ln_b = n2b ? n2b : pb;
-    a.OUT = OUT; a.ldo = ldo; a.OUT2 = OUT2; a.ldo2 = ldo2; a.M = M; a.M_dev = M_dev; a.ff = ff; a.r_idx = r_idx; a.R2 = R2;
+    a.A = t.A; a.lda = t.lda; a.Wo = w.Wo; a.bo = w.bo; a.R = t.R; a.ldr = t.ldr; a.pg = w.in_g; a.pb = w.in_b;
+    a.W1 = w.W1; a.b1 = w.b1; a.W2 = w.W2; a.b2 = w.b2; a.ln_g = w.out_g ? w.out_g : w.in_g; a.ln_b = w.out_b ? w.out_b : w.in_b;
+    a.OUT = t.OUT; a.ldo = t.ldo; a.OUT2 = t.OUT2; a.ldo2 = t.ldo2; a.M = t.M; a.M_dev = t.M_dev; a.ff = t.ff;
+    a.r_idx = t.r_idx; a.R2 = t.R2;
     return launch_ffn_nw<true, false, 8, true>(a, s, nullptr);
 }
 

@@ -544,23 +544,26 @@ int launch_ffn_split(const float* X, int ldx, const void* Wimg, const float* b1,
     return launch_ffn_split_t<false, false>(a, s);
 }
 
-int launch_proj_ffn_split(const float* A, int lda, const void* Woimg, const float* bo, const float* R, int ldr,
-                          const float* pg, const float* pb, const void* Wimg, const float* b1, const float* b2,
-                          const float* ln_g, const float* ln_b, float* OUT, int ldo, int M, const int* M_dev, int ff,
-                          hipStream_t s, const int* r_idx, const float* R2, const void* Qimg, const float* qb, float* QKV,
-                          int ldq, int n_qkv) {
-    CONE_REQUIRE(ffn_split_supported(ff), "split-bf16 fused layer tail: dim_feedforward=%d unsupported", ff);
-    CONE_REQUIRE(A && Woimg && bo && R && pg && pb && Wimg && b1 && b2 && ln_g && ln_b && OUT, "split-bf16 fused layer tail: null argument");
-    CONE_REQUIRE(!r_idx || R2, "split-bf16 fused layer tail: a gathered residual needs both source matrices");
-    CONE_REQUIRE(lda % 4 == 0 && ldr % 4 == 0 && ldo % 4 == 0, "split-bf16 fused layer tail: row strides must be multiples of 4");
-    if (M <= 0) return 0;
+int launch_proj_ffn_split(const TailArgs& t, hipStream_t s) {
+    const TailWeights& w = *t.w;
+    const void* Woimg = w.img[TAIL_IMG_SPLIT].wo;
+    const void* Wimg = w.img[TAIL_IMG_SPLIT].ffn;
+    const void* Qimg = t.next ? t.next->img[TAIL_IMG_SPLIT].qkv : nullptr;
+    CONE_REQUIRE(ffn_split_supported(t.ff), "split-bf16 fused layer tail: dim_feedforward=%d unsupported", t.ff);
+    CONE_REQUIRE(t.A && Woimg && w.bo && t.R && w.in_g && w.in_b && Wimg && w.b1 && w.b2 && w.out_g && w.out_b && t.OUT,
+                 "split-bf16 fused layer tail: null argument");
+    CONE_REQUIRE(!t.r_idx || t.R2, "split-bf16 fused layer tail: a gathered residual needs both source matrices");
+    CONE_REQUIRE(t.lda % 4 == 0 && t.ldr % 4 == 0 && t.ldo % 4 == 0, "split-bf16 fused layer tail: row strides must be multiples of 4");
+    if (t.M <= 0) return 0;
     FfnSplitArgs a{};
-    a.A = A; a.lda = lda; a.Woimg = Woimg; a.bo = bo; a.R = R; a.ldr = ldr; a.pg = pg; a.pb = pb; a.r_idx = r_idx; a.R2 = R2;
-    a.Wimg = Wimg; a.b1 = b1; a.b2 = b2; a.ln_g = ln_g; a.ln_b = ln_b;
-    a.OUT = OUT; a.ldo = ldo; a.M = M; a.M_dev = M_dev; a.ff = ff;
+    a.A = t.A; a.lda = t.lda; a.Woimg = Woimg; a.bo = w.bo; a.R = t.R; a.ldr = t.ldr; a.pg = w.in_g; a.pb = w.in_b;
+    a.r_idx = t.r_idx; a.R2 = t.R2;
+    a.Wimg = Wimg; a.b1 = w.b1; a.b2 = w.b2; a.ln_g = w.out_g; a.ln_b = w.out_b;
+    a.OUT = t.OUT; a.ldo = t.ldo; a.M = t.M; a.M_dev = t.M_dev; a.ff = t.ff;
     if (Qimg) {
-        CONE_REQUIRE(qb && QKV && n_qkv >= 32 && n_qkv % 32 == 0 && ldq % 4 == 0, "split-bf16 fused layer tail: bad q|k|v arguments");
-        a.Qimg = Qimg; a.qb = qb; a.QKV = QKV; a.ldq = ldq; a.n_qkv = n_qkv;
+        CONE_REQUIRE(t.next->qb && t.QKV && t.n_qkv >= 32 && t.n_qkv % 32 == 0 && t.ldq % 4 == 0,
+                     "split-bf16 fused layer tail: bad q|k|v arguments");
+        a.Qimg = Qimg; a.qb = t.next->qb; a.QKV = t.QKV; a.ldq = t.ldq; a.n_qkv = t.n_qkv;
         return launch_ffn_split_t<true, true>(a, s);
     }
     return launch_ffn_split_t<true, false>(a, s);

@@ -547,28 +547,27 @@ int launch_ffn_wide(const float* X, int ldx, const float* W1, const float* b1, c
     return launch_wide_t<false>(a, s);
 }
 
-int launch_proj_ffn_wide(const float* A, int lda, const float* Wo, const float* bo, const float* R, int ldr, const float* pg,
-                         const float* pb, const float* W1, const float* b1, const float* W2, const float* b2,
-                         const float* ln_g, const float* ln_b, float* OUT, int ldo, int M, const int* M_dev, int ff,
-                         hipStream_t s, const int* r_idx, const float* R2, int m_off) {
+int launch_proj_ffn_wide(const TailArgs& t, hipStream_t s) {
+    const TailWeights& w = *t.w;
     FfnWideArgs a{};
-    a.m_off = m_off;
-    a.A = A; a.lda = lda; a.Wo = Wo; a.bo = bo; a.R = R; a.ldr = ldr; a.pg = pg; a.pb = pb; a.r_idx = r_idx; a.R2 = R2;
-    a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2; a.ln_g = ln_g; a.ln_b = ln_b;
-    a.OUT = OUT; a.ldo = ldo; a.M = M; a.M_dev = M_dev; a.ff = ff;
+    a.m_off = t.m_off;
+    a.A = t.A; a.lda = t.lda; a.Wo = w.Wo; a.bo = w.bo; a.R = t.R; a.ldr = t.ldr; a.pg = w.in_g; a.pb = w.in_b;
+    a.r_idx = t.r_idx; a.R2 = t.R2;
+    a.W1 = w.W1; a.b1 = w.b1; a.W2 = w.W2; a.b2 = w.b2; a.ln_g = w.out_g; a.ln_b = w.out_b;
+    a.OUT = t.OUT; a.ldo = t.ldo; a.M = t.M; a.M_dev = t.M_dev; a.ff = t.ff;
     return launch_wide_t<true>(a, s);
 }
 
 // The pre-norm tail (ffn.hip's PRE) in the wide form: OUT = x1 + FFN(LN_p(x1)), x1 = R + A Wo^T + bo; OUT2 (may be null) = LN(OUT).
-int launch_proj_ffn_prenorm_wide(const float* A, int lda, const float* Wo, const float* bo, const float* R, int ldr, const float* pg,
-                                 const float* pb, const float* W1, const float* b1, const float* W2, const float* b2, float* OUT,
-                                 int ldo, const float* n2g, const float* n2b, float* OUT2, int ldo2, int M, const int* M_dev, int ff,
-                                 hipStream_t s, const int* r_idx, const float* R2) {
-    CONE_REQUIRE(ffn_wide_supported(ff) && (!OUT2 || (n2g && n2b)) && (!r_idx || R2), "pre-norm wide tail: bad arguments");
+int launch_proj_ffn_prenorm_wide(const TailArgs& t, hipStream_t s) {
+    const TailWeights& w = *t.w;
+    CONE_REQUIRE(ffn_wide_supported(t.ff) && (!t.OUT2 || (w.out_g && w.out_b)) && (!t.r_idx || t.R2),
+                 "pre-norm wide tail: bad arguments");
     FfnWideArgs a{};
-    a.A = A; a.lda = lda; a.Wo = Wo; a.bo = bo; a.R = R; a.ldr = ldr; a.pg = pg; a.pb = pb; a.r_idx = r_idx; a.R2 = R2;
-    a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2; a.ln_g = n2g ? n2g : pg; a.ln_b = n2b ? n2b : pb;
-    a.OUT = OUT; a.ldo = ldo; a.OUT2 = OUT2; a.ldo2 = ldo2; a.M = M; a.M_dev = M_dev; a.ff = ff;
+    a.A = t.A; a.lda = t.lda; a.Wo = w.Wo; a.bo = w.bo; a.R = t.R; a.ldr = t.ldr; a.pg = w.in_g; a.pb = w.in_b;
+    a.r_idx = t.r_idx; a.R2 = t.R2;
+    a.W1 = w.W1; a.b1 = w.b1; a.W2 = w.W2; a.b2 = w.b2; a.ln_g = w.out_g ? w.out_g : w.in_g; a.ln_b = w.out_b ? w.out_b : w.in_b;
+    a.OUT = t.OUT; a.ldo = t.ldo; a.OUT2 = t.OUT2; a.ldo2 = t.ldo2; a.M = t.M; a.M_dev = t.M_dev; a.ff = t.ff;
     return launch_wide_t<true, true>(a, s);
 }
 
@@ -577,24 +576,24 @@ size_t ffn_spread_scratch_floats(int ff) { return (size_t)FS_MAX_GROUPS * (3 * 1
 bool ffn_spread_supported(int M, int ff) {
     return M > 0 && (M + 15) / 16 <= FS_MAX_GROUPS && ff >= 256 && ff % 256 == 0;
 }
-int launch_proj_ffn_spread(const float* A, int lda, const float* Wo, const float* bo, const float* R, int ldr, const float* pg,
-                           const float* pb, const float* W1, const float* b1, const float* W2, const float* b2,
-                           const float* ln_g, const float* ln_b, float* OUT, int ldo, int M, int ff, float* scratch,
-                           hipStream_t s, const int* M_dev, const int* r_idx, const float* R2, bool pre, float* OUT2, int ldo2) {
-    CONE_REQUIRE(ffn_spread_supported(M, ff) && scratch, "spread layer tail: unsupported size M=%d ff=%d", M, ff);
-    CONE_REQUIRE(!r_idx || R2, "spread layer tail: a gathered residual needs both source matrices");
-    CONE_REQUIRE(lda % 4 == 0 && ldr % 4 == 0 && ldo % 4 == 0, "spread layer tail: row strides must be multiples of 4");
+int launch_proj_ffn_spread(const TailArgs& t, hipStream_t s) {       // t.pre: the pre-norm tail (OUT = the stream, OUT2 = LN(OUT))
+    const TailWeights& w = *t.w;
+    CONE_REQUIRE(ffn_spread_supported(t.M, t.ff) && t.scratch, "spread layer tail: unsupported size M=%d ff=%d", t.M, t.ff);
+    CONE_REQUIRE(!t.r_idx || t.R2, "spread layer tail: a gathered residual needs both source matrices");
+    CONE_REQUIRE(t.lda % 4 == 0 && t.ldr % 4 == 0 && t.ldo % 4 == 0, "spread layer tail: row strides must be multiples of 4");
     FfnWideArgs a{};
-    a.A = A; a.lda = lda; a.Wo = Wo; a.bo = bo; a.R = R; a.ldr = ldr; a.pg = pg; a.pb = pb;
-    a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2; a.ln_g = ln_g; a.ln_b = ln_b;
-    a.OUT = OUT; a.ldo = ldo; a.M = M; a.ff = ff; a.M_dev = M_dev; a.r_idx = r_idx; a.R2 = R2; a.OUT2 = OUT2; a.ldo2 = ldo2;
-    const int groups = (M + 15) / 16, nc = ff >> 4;
+    a.A = t.A; a.lda = t.lda; a.Wo = w.Wo; a.bo = w.bo; a.R = t.R; a.ldr = t.ldr; a.pg = w.in_g; a.pb = w.in_b;
+    a.W1 = w.W1; a.b1 = w.b1; a.W2 = w.W2; a.b2 = w.b2;
+    a.ln_g = t.pre && !w.out_g ? w.in_g : w.out_g; a.ln_b = t.pre && !w.out_b ? w.in_b : w.out_b;
+    a.OUT = t.OUT; a.ldo = t.ldo; a.M = t.M; a.ff = t.ff; a.M_dev = t.M_dev; a.r_idx = t.r_idx; a.R2 = t.R2;
+    a.OUT2 = t.OUT2; a.ldo2 = t.ldo2;
+    const int groups = (t.M + 15) / 16, nc = t.ff >> 4;
     FfnSpreadBufs b;
-    b.XP = scratch; b.X1 = b.XP + (size_t)FS_MAX_GROUPS * 16 * 256; b.YG = b.X1 + (size_t)FS_MAX_GROUPS * 16 * 256;
+    b.XP = t.scratch; b.X1 = b.XP + (size_t)FS_MAX_GROUPS * 16 * 256; b.YG = b.X1 + (size_t)FS_MAX_GROUPS * 16 * 256;
     b.HG = b.YG + (size_t)FS_MAX_GROUPS * 16 * 256;
-    ProfScope ps(PK_FFN_PROJ_WIDE, M, ff, 256, M_dev, s, 0);
+    ProfScope ps(PK_FFN_PROJ_WIDE, t.M, t.ff, 256, t.M_dev, s, 0);
     hipLaunchKernelGGL(fs_proj_kernel, dim3(16, groups), dim3(64), 0, s, a, b);
-    if (pre) {
+    if (t.pre) {
         hipLaunchKernelGGL(fs_g1_kernel<true>, dim3(nc, groups), dim3(64), 0, s, a, b);
         hipLaunchKernelGGL(fs_g2_kernel<true>, dim3(16, groups), dim3(64), 0, s, a, b);
         hipLaunchKernelGGL(fs_ln_kernel<true>, dim3(groups), dim3(64), 0, s, a, b);
