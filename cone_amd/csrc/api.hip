@@ -510,15 +510,47 @@ struct FwdBuffers {
     float *X, *POS, *XP, *QKV, *ATT, *X1, *H, *KD, *VD;
     float *TGT, *TGT1, *TGT2, *DQK, *DV, *DATT, *DQ, *DH, *HS, *S1, *S2, *LG, *SP, *QKS, *SPR;
 };
-struct FwdPlan { bool tables, fold, dec_xp = false; };
-// What a call runs on: the caller's cone_layer0 with the handle's position tables filled in where it brings none (ABI 6: a
-// NULL cone_layer0, or one with the row caches only, still takes the table path), or nothing for --use_txt_pos (the general
-// path: the caches / tables assume a zero text position term) and for windows longer than the handle's tables cover.
-static const cone_layer0* effective_l0(const cone_model* m, const cone_layer0* l0, int Lv_max, cone_layer0* eff,
-                                       bool own_txt = false) {
-    // --use_txt_pos: the table path needs the tokens' own position rows (cone_layer0_text_positions) -- handed over in l0, or
-    // (own_txt: the padded entry) built by the caller itself; without them the general path
-    if (m->txt_pos_emb && !(own_txt || (l0 && l0->txt_pos && l0->txt_pos_qk))) return nullptr;
+// One call of the window model, as every internal forward function takes it (the extern "C" entries fill it after their
+// null checks): window b = rows vrow0[b] .. + vlen[b] of the projected clip rows, then rows trow0[b] .. + qlen[b] of the
+// projected token rows.
+struct FwdCall {
+    const float* vproj; const int* vrow0; const int* vlen;
+    const float* tproj; const int* trow0; const int* qlen;
+    int B, Lv_max, Lq_max;                      // windows; host bounds of the lengths
+    float *logits, *spans, *saliency;           // saliency == null: not wanted
+    const cone_taps* taps;                      // may be null
+};
+// Every path decision of a forward, made once (plan_forward) and read by the workspace carve, the workspace-size entries and
+// the forward bodies alike.
+enum { BODY_GENERAL, BODY_PRENORM_PLAIN, BODY_PACKED };     // forward_general / forward_packed_prenorm / forward_packed's own body
+enum { CROSS_SMALL = 0, CROSS_VALU = 1 };                   // a layer's cross-attention form; 2 .. 5: launch_dec_cross_mfma's form
+struct FwdPlan {
+    int body = BODY_GENERAL;
+    bool pre = false;           // --pre_norm on BODY_PACKED: the fused pre-norm tails, LayerNorms ahead of the decoder fronts
+    bool long_ok = false;       // windows beyond 192 tokens run (the default table path with 3 / 5 / 8 slots only)
+    bool tables = false;        // encoder position term from the static tables (one N = 768 GEMM per layer, no x + pos matrix)
+    bool fold = false;          // decoder memory K / V projections inside the cross-attention kernel
+    bool dec_xp = false;        // --use_txt_pos on the table path: the keys memory + pos written once behind the encoder
+    bool dec_tab = false;       // the cross-attention kernels add the position rows from the table themselves
+    bool have_l0 = false; cone_layer0 l0{};     // what the call runs on (effective_l0); the padded entry fills in what it builds:
+    bool mk_caches = false, mk_txt_pos = false; //   the first layer's row caches / the text position rows (own_rows)
+    bool caches = false;        // the first layer reads the row caches
+    bool gather0 = false;       // ... its attention gathers q | k | v from them itself (else a packing pass writes them out)
+    bool gather_res = false;    // ... and its tail gathers the residual rows through a row index: no packed copy of the input
+    bool own_ridx = false;      // the row index has its own buffer (pre-norm); else it lives in the X1 region, unused by then
+    int cross[CONE_MAX_LAYERS] = {};
+    bool sal_ride = false;      // the saliency head rides in the first cross-attention launch
+    bool dec0 = false;          // first decoder layer's front replicated from the per-checkpoint constants
+    bool slabs = false;         // ... and its cross-attention builds the folded-key operand once for all windows
+    bool want_aux = false; int h0 = 0;  // intermediate layers' heads asked for; first decoder layer whose heads are computed
+    bool heads_chain = false;   // decoder.norm + heads of a layer's rows as one launch (rows_chain.h)
+};
+// The caller's cone_layer0 with the handle's position tables filled in where it brings none (ABI 6: a NULL cone_layer0, or
+// one with the row caches only, still takes the table path), or nothing for --use_txt_pos without the tokens' own position
+// rows (cone_layer0_text_positions: handed over in l0, or -- own_rows, the padded entry -- built by the caller itself) and for
+// windows longer than the handle's tables cover.
+static const cone_layer0* effective_l0(const cone_model* m, const cone_layer0* l0, int Lv_max, cone_layer0* eff, bool own_rows) {
+    if (m->txt_pos_emb && !(own_rows || (l0 && l0->txt_pos && l0->txt_pos_qk))) return nullptr;
     *eff = l0 ? *l0 : cone_layer0{};
     if (!m->txt_pos_emb) eff->txt_pos = eff->txt_pos_qk = nullptr;
     if (!eff->qkv_vid || !eff->qkv_txt) eff->qkv_vid = eff->qkv_txt = nullptr;
@@ -528,47 +560,81 @@ static const cone_layer0* effective_l0(const cone_model* m, const cone_layer0* l
     }
     return eff;
 }
-// have_tables / caches: what effective_l0 resolved to (position tables available; first-layer row caches given)
-static FwdPlan plan_for(const cone_model* m, bool have_tables, bool caches, int Lmax) {
+// The one place that reads the forward-level inputs: the options dec_fold, pos_tables, l0_gather, res_gather, dec0_const,
+// rows_chain (and ffn_fused / ffn_spread / gemm where they gate a path), pre_norm, txt_pos_emb, general(), the *_supported
+// predicates, and what the caller handed over (cone_layer0, taps, saliency wanted).  own_rows: the padded entry, which
+// builds the row caches and the text position rows the plan asks for (mk_caches, mk_txt_pos) itself.  The workspace-size
+// entries call it with the sizes only.  In order:
+//
+//   body     general()                                            BODY_GENERAL: nothing below is read
+//            pre_norm without all of {tables, matrix-core fold,   BODY_PRENORM_PLAIN: plain LayerNorm / GEMM / attention launches,
+//              ffn_fused = 2, an ff the fused tails take}           no tables, no fold, no caches
+//            otherwise                                            BODY_PACKED (pre: with the fused pre-norm tails)
+//   l0       effective_l0; caches GIVEN = its row caches, resp. (own_rows) pos_tables and l0_gather both on
+//   tables   l0 there, pos_tables, and (no caches given or l0_gather); off again when the decoder is unfolded and the fold
+//            is switched off by option or nq = 5 (the fold off BY OPTION keeps meaning the whole general launch sequence)
+//   dec_xp   tables and --use_txt_pos; dec_tab = tables and not dec_xp
+//   fold     dec_fold >= 2: dec_cross_mfma_supported (its table form only with dec_tab); dec_fold = 1: dec_cross_supported
+//   --use_txt_pos with l0 there but tables off: the WHOLE general launch sequence -- l0 dropped (its row caches do not
+//            carry the text position term), everything above derived again without it
+//   gather_res  caches given, l0_gather, tables, ffn_fused = 2 with an ff it takes, res_gather
+//   gather0     post-norm: caches given and l0_gather; pre-norm: gather_res (its in_proj reads norm1(x): all or nothing)
+//   caches      post-norm: given; pre-norm: gather_res
+//   cross[l]    no fold: CROSS_SMALL; dec_fold = 1: CROSS_VALU; pre-norm: form 3; dec_fold = 2: form 5 for the first layer,
+//               3 behind it (by LAYER, never by the batch: a window's bits must not depend on the batch it rides in); else dec_fold
+//   sal_ride    post-norm, saliency wanted, dec_tab, fold, dec_fold in {2, 3, 5} (table form of the two-read kernel)
+//   dec0        post-norm and dec0_const; slabs: dec0 and more than one window
+//   want_aux    a tap asks for hs / aux_logits / aux_spans; h0 = 0 then, else the last layer (pre-norm: heads_and_taps
+//               computes every layer's whatever the taps)
+//   heads_chain post-norm, rows_chain, the automatic GEMM family, rows_chain_supported(B nq) and not the spread GEMM's rows
+static FwdPlan plan_forward(const cone_model* m, const FwdCall& c, const cone_layer0* l0, bool own_rows) {
     FwdPlan p;
-    p.tables = have_tables && m->opt_pos_tables && (!caches || m->opt_l0_gather);
-    // --use_txt_pos on the table path: the decoder's keys memory + pos are written once behind the encoder (clip rows from the
-    // table, text rows from the tokens' own position rows) and the cross-attention runs its x + pos form on them
-    p.dec_xp = p.tables && m->txt_pos_emb != nullptr;
-    p.fold = m->opt_dec_fold >= 2 ? dec_cross_mfma_supported(m->nq, Lmax, p.tables && !p.dec_xp)
-                                  : (m->opt_dec_fold == 1 && dec_cross_supported(m->nq, Lmax));
-    if (m->pre_norm) {  // the fused pre-norm path needs all of: tables, the fused layer tail, the matrix-core fold; else the
-                        // general pre-norm path (plain LayerNorm / GEMM / attention launches)
-        const bool fused = p.tables && p.fold && m->opt_dec_fold >= 2 && m->opt_ffn_fused >= 2 && ffn_fused_supported(m->ff);
-        p.tables = p.fold = fused;
-        if (!fused) p.dec_xp = false;
-        return p;
-    }
-    // the unfolded decoder projects its keys from memory + pos rows: on the table path that matrix is written once behind the
-    // encoder (launch_add_pos_rows) -- slot counts other than 5 keep the encoder's fast path.  The fold switched off BY OPTION
-    // (parity tests) keeps meaning the whole general path
-    if (!p.fold && !(m->opt_dec_fold && m->nq != 5)) p.tables = false;
-    if (!p.tables) p.dec_xp = false;
+    if (m->general()) return p;
+    const int Lmax = c.Lv_max + c.Lq_max, T = c.B * m->nq, fo = m->opt_dec_fold;
+    const bool pre = m->pre_norm != 0, txt = m->txt_pos_emb != nullptr;
+    const bool tail2 = m->opt_ffn_fused >= 2 && ffn_fused_supported(m->ff);
+    p.long_ok = fo >= 2 && dec_cross_mfma_supported(m->nq, Lmax, true) && !txt && m->opt_pos_tables;
+    const cone_layer0* e = effective_l0(m, l0, c.Lv_max, &p.l0, own_rows);
+    bool given = e && (own_rows ? m->opt_pos_tables && m->opt_l0_gather : e->qkv_vid != nullptr);
+    auto paths = [&](bool have_tables, bool caches) {
+        p.tables = have_tables && m->opt_pos_tables && (!caches || m->opt_l0_gather);
+        p.dec_xp = p.tables && txt;
+        p.fold = fo >= 2 ? dec_cross_mfma_supported(m->nq, Lmax, p.tables && !p.dec_xp) : (fo == 1 && dec_cross_supported(m->nq, Lmax));
+        if (pre) p.tables = p.fold = p.tables && p.fold && fo >= 2 && tail2;
+        // the unfolded decoder projects its keys from memory + pos rows: on the table path that matrix is written once behind
+        // the encoder (launch_add_pos_rows) -- slot counts other than 5 keep the encoder's fast path
+        else if (!p.fold && !(fo && m->nq != 5)) p.tables = false;
+        if (!p.tables) p.dec_xp = false;
+    };
+    paths(e != nullptr, given);
+    if (txt && e && !p.tables) { e = nullptr; given = false; paths(false, false); }
+    p.have_l0 = e != nullptr;
+    if (!e) p.l0 = cone_layer0{};
+    p.body = pre && !p.tables ? BODY_PRENORM_PLAIN : BODY_PACKED;
+    p.pre = pre; p.own_ridx = pre;
+    p.dec_tab = p.tables && !p.dec_xp;
+    p.mk_caches = own_rows && given; p.mk_txt_pos = own_rows && txt && p.tables;
+    p.gather_res = given && m->opt_l0_gather && p.tables && tail2 && m->opt_res_gather;
+    p.gather0 = pre ? p.gather_res : given && m->opt_l0_gather;
+    p.caches = pre ? p.gather_res : given;
+    for (int l = 0; l < m->n_dec; ++l)
+        p.cross[l] = !p.fold ? CROSS_SMALL : fo < 2 ? CROSS_VALU : pre ? 3 : fo == 2 ? (l == 0 ? 5 : 3) : fo;
+    p.sal_ride = !pre && c.saliency && p.dec_tab && p.fold && (fo == 2 || fo == 3 || fo == 5);
+    p.dec0 = !pre && m->opt_dec0_const;
+    p.slabs = p.dec0 && c.B != 1;
+    p.want_aux = c.taps && (c.taps->hs || c.taps->aux_logits || c.taps->aux_spans);
+    p.h0 = p.want_aux ? 0 : m->n_dec - 1;
+    p.heads_chain = !pre && m->opt_chain && m->opt_gemm == GEMM_AUTO && rows_chain_supported(T) &&
+                    !(m->opt_spread && gemm_rows_spread_rows(T));     // (few rows: the spread GEMM launches are faster)
     return p;
-}
-static FwdPlan plan_of(const cone_model* m, const cone_layer0* l0 /* effective_l0 */, int Lmax) {
-    return plan_for(m, l0 && l0->pos_rows && l0->pos_qk, l0 && l0->qkv_vid, Lmax);
-}
-// effective_l0 + plan_of; a --use_txt_pos model that cannot take the table path (an A/B switch, a window too long for the
-// x + pos form of the fold) drops to the WHOLE general path: its row caches do not carry the text position term
-static const cone_layer0* resolve_l0(const cone_model* m, const cone_layer0* l0, int Lv_max, int Lmax, cone_layer0* eff,
-                                     FwdPlan* plan) {
-    const cone_layer0* e = effective_l0(m, l0, Lv_max, eff);
-    *plan = plan_of(m, e, Lmax);
-    if (m->txt_pos_emb && e && !plan->tables) { e = nullptr; *plan = plan_of(m, nullptr, Lmax); }
-    return e;
 }
 static void carve_fwd(const cone_model* m, Carver& c, int B, int Lmax, const FwdPlan& p, FwdBuffers& f) {
     const size_t M = (size_t)B * Lmax, T = (size_t)B * m->nq, nd = m->n_dec;
     const size_t wide = m->ff > 1024 ? m->ff : 1024;
     f.off = c.take<int>(B + 1);
-    f.RIDX = m->pre_norm ? c.take<int>(M) : nullptr;    // (post-norm keeps the row index in the X1 region, unused on that path)
+    f.RIDX = p.own_ridx ? c.take<int>(M) : nullptr;
     f.X = c.take<float>(M * 256); f.X1 = c.take<float>(M * 256);
+    if (!f.RIDX) f.RIDX = reinterpret_cast<int*>(f.X1);     // (post-norm: the X1 region is unused while the row index lives)
     f.H = c.take<float>(M * wide);
     f.QKV = f.H; f.ATT = f.H + M * 768;            // aliases of the FFN hidden region (see above)
     f.POS = f.XP = f.KD = f.VD = nullptr;
@@ -588,12 +654,6 @@ static void carve_fwd(const cone_model* m, Carver& c, int B, int Lmax, const Fwd
     f.SPR = ffn_spread_supported((int)T, m->ff) || ffn_spread_supported((int)M, m->ff)                       // the spread tail's rows
                 ? c.take<float>(ffn_spread_scratch_floats(m->ff)) : nullptr;
 }
-static size_t fwd_ws_bytes(const cone_model* m, int B, int Lmax, const FwdPlan& p) {
-    Carver c(nullptr, ~(size_t)0);
-    FwdBuffers f;
-    carve_fwd(m, c, B, Lmax, p, f);
-    return c.cur;
-}
 
 // The hs / aux_* taps: all layers' normalised slot rows and the intermediate layers' head outputs, from the workspace.
 static int copy_taps(const cone_taps* taps, const float* HS, const float* LG, const float* SP, int nd, int T, int d, hipStream_t s) {
@@ -611,9 +671,9 @@ static int copy_taps(const cone_taps* taps, const float* HS, const float* LG, co
 // into the workspace, the last layer's rows out, the taps, the saliency head of the memory rows.  gen: the d-wide row-dot /
 // saliency kernels of general.hip (the general path, also when it is forced at d = 256), else the 256-channel ones.
 struct HeadBufs { float *HS, *S1, *S2, *LG, *SP; const int* off; };
-static int heads_and_taps(const cone_model* m, const HeadBufs& f, const float* MEM, const int* vlen, const int* qlen, int B, int Lv_max,
-                          int Lq_max, float* logits, float* spans, float* saliency, const cone_taps* taps, bool gen, hipStream_t s) {
-    const int d = m->d, T = B * m->nq, nd = m->n_dec, HT = nd * T;
+static int heads_and_taps(const cone_model* m, const FwdCall& c, const HeadBufs& f, const float* MEM, bool gen, hipStream_t s) {
+    const int d = m->d, B = c.B, T = B * m->nq, nd = m->n_dec, HT = nd * T;
+    const cone_taps* taps = c.taps;
     auto rowdot = [&](const float* X, const Linear& h, float* out, int act) {
         return gen ? launch_gen_rowdot(X, d, h.w, h.b, out, 2, HT, 2, act, d, s) : launch_rowdot(X, d, h.w, h.b, out, 2, HT, 2, act, s);
     };
@@ -622,27 +682,79 @@ static int heads_and_taps(const cone_model* m, const HeadBufs& f, const float* M
     RUN(launch_gemm(G(m, f.S1, d, m->span[1].w, d, m->span[1].b, f.S2, d, HT, nullptr, d, d, EPI_RELU), s));
     RUN(rowdot(f.S2, m->span[2], f.SP, 1));
     const size_t last = (size_t)(nd - 1) * T * 2;
-    CONE_CHECK_HIP(hipMemcpyAsync(logits, f.LG + last, (size_t)T * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    CONE_CHECK_HIP(hipMemcpyAsync(spans, f.SP + last, (size_t)T * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    CONE_CHECK_HIP(hipMemcpyAsync(c.logits, f.LG + last, (size_t)T * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    CONE_CHECK_HIP(hipMemcpyAsync(c.spans, f.SP + last, (size_t)T * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
     RUN(copy_taps(taps, f.HS, f.LG, f.SP, nd, T, d, s));
     float* mem_tap = taps ? taps->memory : nullptr;
-    if (!saliency && !mem_tap) return 0;
-    return gen ? launch_gen_saliency(MEM, f.off, vlen, qlen, m->saliency.w, m->saliency.b, saliency, Lv_max, mem_tap, Lq_max, B, d, s)
-               : launch_saliency(MEM, f.off, vlen, qlen, m->saliency.w, m->saliency.b, saliency, Lv_max, mem_tap, Lq_max, B, s);
+    if (!c.saliency && !mem_tap) return 0;
+    return gen ? launch_gen_saliency(MEM, f.off, c.vlen, c.qlen, m->saliency.w, m->saliency.b, c.saliency, c.Lv_max, mem_tap, c.Lq_max, B, d, s)
+               : launch_saliency(MEM, f.off, c.vlen, c.qlen, m->saliency.w, m->saliency.b, c.saliency, c.Lv_max, mem_tap, c.Lq_max, B, s);
+}
+
+// ---- stages the 256-wide bodies share (each issues exactly the launches written here, in this order)
+// A decoder layer ahead of its cross-attention (cone/transformer.py:296-311, pre: :319-331): the slots' q | k | v in ONE
+// N = 768 GEMM, the slot-position term from the layer's table as a row-periodic residual; their self-attention; out_proj +
+// residual (post-norm: + norm1 in the epilogue, into TGT1); the cross-attention queries, slot term from the table, into DQ.
+// pre: norm1 / norm2 as LayerNorm launches ahead of the two projections, the residual stream stays in TGT.
+static int dec_layer_front(const cone_model* m, const FwdBuffers& f, int l, int B, bool pre, hipStream_t s) {
+    const DecLayer& dl = m->dec[l];
+    const int T = B * m->nq;
+    if (pre) RUN(launch_layernorm(f.TGT, 256, dl.n1.g, dl.n1.b, f.TGT1, 256, T, nullptr, 256, s));          // tgt2 = norm1(tgt)
+    GemmArgs g = G(m, pre ? f.TGT1 : f.TGT, 256, dl.sa.in_w, 256, nullptr, f.DQK, 768, T, nullptr, 768, 256, EPI_RESIDUAL);
+    g.R = m->dec_sa_tab[l]; g.ldr = 768; g.r_mod = m->nq;
+    RUN(launch_gemm(g, s));
+    RUN(launch_small_attn(f.DQK, 768, f.DQK + 256, 768, f.DQK + 512, 768, f.DATT, 256, nullptr, B, m->nq, m->nq, s));
+    g = G(m, f.DATT, 256, dl.sa.out.w, 256, dl.sa.out.b, pre ? f.TGT : f.TGT1, 256, T, nullptr, 256, 256,
+          pre ? EPI_RESIDUAL : EPI_RESIDUAL | EPI_LN);
+    g.R = f.TGT; g.ldr = 256;
+    if (!pre) { g.ln_g = dl.n1.g; g.ln_b = dl.n1.b; }
+    RUN(launch_gemm(g, s));
+    if (pre) RUN(launch_layernorm(f.TGT, 256, dl.n2.g, dl.n2.b, f.TGT1, 256, T, nullptr, 256, s));          // tgt2 = norm2(tgt)
+    g = G(m, f.TGT1, 256, dl.ca.in_w, 256, nullptr, f.DQ, 256, T, nullptr, 256, 256, EPI_RESIDUAL);
+    g.R = m->dec_ca_tab[l]; g.ldr = 256; g.r_mod = m->nq;
+    return launch_gemm(g, s);
+}
+// Decoder layer l's cross-attention in the form the plan picked, queries DQ -> DATT.  The folded forms take their keys
+// memory + pos either from the table inside the kernel (dec_tab) or as the matrix XP; the unfolded one reads the layer's
+// columns of the stacked K / V rows.  In the first layer's matrix-core launch the saliency head may ride (every memory row
+// of the batch is in registers anyway), and the folded-key operand is built once when its queries are the replicated ones.
+static int dec_cross_attn(const cone_model* m, const FwdCall& c, const FwdPlan& p, const FwdBuffers& f, int l, const float* MEM,
+                          hipStream_t s) {
+    const DecLayer& dl = m->dec[l];
+    const int nd = m->n_dec, Lmax = c.Lv_max + c.Lq_max;
+    const float* XP = p.dec_tab ? nullptr : f.XP;
+    const float* pos = p.dec_tab ? p.l0.pos_rows : nullptr;
+    if (p.cross[l] == CROSS_SMALL)
+        return launch_small_attn(f.DQ, 256, f.KD + l * 256, 256 * nd, f.VD + l * 256, 256 * nd, f.DATT, 256, f.off, c.B, m->nq, Lmax, s);
+    if (p.cross[l] == CROSS_VALU)
+        return launch_dec_cross(f.DQ, XP, MEM, pos, c.vlen, f.off, dl.ca.in_w + 256 * 256, m->dec_vT[l], dl.ca.in_b + 512, f.DATT, c.B,
+                                m->nq, Lmax, s);
+    const bool ride = l == 0 && p.sal_ride;
+    if (ride) CONE_CHECK_HIP(hipMemsetAsync(c.saliency, 0, (size_t)c.B * c.Lv_max * sizeof(float), s));     // padded clips: 0
+    return launch_dec_cross_mfma(f.DQ, XP, MEM, pos, c.vlen, f.off, dl.ca.in_w + 256 * 256, m->dec_vT[l], dl.ca.in_b + 512, f.DATT,
+                                 c.B, m->nq, Lmax, l == 0 && p.slabs ? f.QKS : nullptr, s, p.cross[l], ride ? m->saliency.w : nullptr,
+                                 ride ? m->saliency.b : nullptr, ride ? c.saliency : nullptr, ride ? c.Lv_max : 0);
+}
+// Encoder layer l's attention source on the table path, less where q | k | v come from: the layer's pos W_qk^T rows (and,
+// --use_txt_pos, the tokens' own), which the kernel adds to q | k in its staging loads ((x + pos) W^T = x W^T + pos W^T)
+static AttnSrc table_attn_src(const FwdCall& c, const cone_layer0& l0, int l) {
+    const size_t rows = (size_t)pos_table_rows(l0.max_v_l);
+    AttnSrc src{};
+    src.vlen = c.vlen; src.pos_zero_row = (int)rows - 1;
+    src.pos_qk = l0.pos_qk + (size_t)l * rows * 512;
+    if (l0.txt_pos_qk) { src.txt_pos_qk = l0.txt_pos_qk + (size_t)l * l0.n_txt * 512; src.trow0 = c.trow0; }
+    return src;
 }
 
 // --pre_norm (cone/config.py:120 -> normalize_before, cone/transformer.py:19-36): every layer normalises its INPUT
 // (forward_pre, :248-260 / :319-342), the residual stream stays un-normalised, and the encoder ends with its own LayerNorm.
 // Off in every shipped configuration: built from the plain blocks (LayerNorm kernel, row GEMMs with residual epilogue, the
 // packed encoder attention, the small decoder attentions) -- no fused tails, no caches.
-static int forward_packed_prenorm(const cone_model* m, const float* vproj, const int* vrow0, const int* vlen,
-                                  const float* tproj, const int* trow0, const int* qlen, int B, int Lv_max, int Lq_max,
-                                  float* logits, float* spans, float* saliency, const cone_taps* taps, FwdBuffers& f,
-                                  hipStream_t s) {
-    const int Lmax = Lv_max + Lq_max, Mmax = B * Lmax, T = B * m->nq, nd = m->n_dec, ff = m->ff;
+static int forward_packed_prenorm(const cone_model* m, const FwdCall& c, const FwdPlan& p, FwdBuffers& f, hipStream_t s) {
+    const int B = c.B, Lmax = c.Lv_max + c.Lq_max, Mmax = B * Lmax, T = B * m->nq, nd = m->n_dec, ff = m->ff;
     const int* Mdev = f.off + B;
-    RUN(launch_scan_lengths(vlen, qlen, B, f.off, s));
-    RUN(launch_pack_pos(vproj, vrow0, vlen, tproj, trow0, qlen, f.off, m->dim_t, f.X, f.POS, f.XP, B, Lmax, s,
+    RUN(launch_scan_lengths(c.vlen, c.qlen, B, f.off, s));
+    RUN(launch_pack_pos(c.vproj, c.vrow0, c.vlen, c.tproj, c.trow0, c.qlen, f.off, m->dim_t, f.X, f.POS, f.XP, B, Lmax, s,
                         m->txt_pos_emb, m->txt_pos_ln.g, m->txt_pos_ln.b));
     GemmArgs g;
     for (int l = 0; l < m->n_enc; ++l) {
@@ -675,20 +787,8 @@ static int forward_packed_prenorm(const cone_model* m, const float* vproj, const
     CONE_CHECK_HIP(hipMemsetAsync(f.TGT, 0, (size_t)T * 256 * sizeof(float), s));                       // tgt = 0 (:66)
     for (int l = 0; l < nd; ++l) {
         const DecLayer& dl = m->dec[l];
-        RUN(launch_layernorm(f.TGT, 256, dl.n1.g, dl.n1.b, f.TGT1, 256, T, nullptr, 256, s));           // tgt2 = norm1(tgt)
-        g = G(m, f.TGT1, 256, dl.sa.in_w, 256, nullptr, f.DQK, 768, T, nullptr, 768, 256, EPI_RESIDUAL); // q | k | v, slot term from the table
-        g.R = m->dec_sa_tab[l]; g.ldr = 768; g.r_mod = m->nq;
-        RUN(launch_gemm(g, s));
-        RUN(launch_small_attn(f.DQK, 768, f.DQK + 256, 768, f.DQK + 512, 768, f.DATT, 256, nullptr, B, m->nq, m->nq, s));
-        g = G(m, f.DATT, 256, dl.sa.out.w, 256, dl.sa.out.b, f.TGT, 256, T, nullptr, 256, 256, EPI_RESIDUAL);
-        g.R = f.TGT; g.ldr = 256;
-        RUN(launch_gemm(g, s));
-        RUN(launch_layernorm(f.TGT, 256, dl.n2.g, dl.n2.b, f.TGT1, 256, T, nullptr, 256, s));           // tgt2 = norm2(tgt)
-        g = G(m, f.TGT1, 256, dl.ca.in_w, 256, nullptr, f.DQ, 256, T, nullptr, 256, 256, EPI_RESIDUAL);
-        g.R = m->dec_ca_tab[l]; g.ldr = 256; g.r_mod = m->nq;
-        RUN(launch_gemm(g, s));
-        RUN(launch_small_attn(f.DQ, 256, f.KD + l * 256, 256 * nd, f.VD + l * 256, 256 * nd, f.DATT, 256, f.off, B, m->nq,
-                              Lmax, s));
+        RUN(dec_layer_front(m, f, l, B, true, s));
+        RUN(dec_cross_attn(m, c, p, f, l, MEM, s));                                                     // (CROSS_SMALL: no fold here)
         g = G(m, f.DATT, 256, dl.ca.out.w, 256, dl.ca.out.b, f.TGT, 256, T, nullptr, 256, 256, EPI_RESIDUAL);
         g.R = f.TGT; g.ldr = 256;
         RUN(launch_gemm(g, s));
@@ -699,8 +799,7 @@ static int forward_packed_prenorm(const cone_model* m, const float* vproj, const
         RUN(launch_gemm(g, s));
         RUN(launch_layernorm(f.TGT, 256, m->dec_norm.g, m->dec_norm.b, f.HS + (size_t)l * T * 256, 256, T, nullptr, 256, s));
     }
-    return heads_and_taps(m, HeadBufs{f.HS, f.S1, f.S2, f.LG, f.SP, f.off}, MEM, vlen, qlen, B, Lv_max, Lq_max, logits, spans, saliency,
-                          taps, false, s);
+    return heads_and_taps(m, c, HeadBufs{f.HS, f.S1, f.S2, f.LG, f.SP, f.off}, MEM, false, s);
 }
 
 // ------------------------------------------------------------------------------ the layer tail
@@ -710,7 +809,7 @@ static int forward_packed_prenorm(const cone_model* m, const float* vproj, const
 // its buffers; t.next != null OFFERS the ride of the next encoder layer's q | k | v projection (QKV, n_qkv set), *rode says
 // whether it was taken (rode may be null where none is offered).  Every choice is by the host-known row bound t.M, never by *t.M_dev.  First matching row wins:
 //
-//   t.pre (the fused pre-norm path; plan_for admits it only with ffn_fused = 2 and an ff the fused kernels take;
+//   t.pre (the fused pre-norm path; plan_forward admits it only with ffn_fused = 2 and an ff the fused kernels take;
 //   split_bf16 is not consulted; no ride)
 //     1  bf16                                                     launch_proj_ffn_bf16_prenorm
 //     2  ffn_spread, scratch, <= 64 row groups, ff % 256 == 0     launch_proj_ffn_spread (pre)
@@ -779,78 +878,6 @@ static TailArgs tail_args(const TailWeights* w, const float* A, const float* R, 
     return t;
 }
 
-// --pre_norm on the table path (ABI 6): the same launches as the post-norm step -- position tables, ONE N = 768 GEMM per
-// encoder layer, the fused layer tail in its pre-norm form (attention out_proj + residual, norm ahead of the feed-forward
-// block, the block, residual; the NEXT consumer's LayerNorm -- the next layer's norm1, the encoder's / decoder's final norm --
-// written as a second output), the folded decoder cross-attention.  What it does not have: the first layer's row caches (its
-// in_proj reads norm1(x)) and the first decoder layer's constants.
-static int forward_packed_prenorm_fused(const cone_model* m, const float* vproj, const int* vrow0, const int* vlen,
-                                        const float* tproj, const int* trow0, const int* qlen, int B, int Lv_max, int Lq_max,
-                                        float* logits, float* spans, float* saliency, const cone_taps* taps, FwdBuffers& f,
-                                        hipStream_t s, const cone_layer0* l0) {
-    const int Lmax = Lv_max + Lq_max, Mmax = B * Lmax, T = B * m->nq, nd = m->n_dec, ff = m->ff;
-    const int* Mdev = f.off + B;
-    const size_t pos_rows_n = (size_t)cone_pos_table_rows(l0->max_v_l);
-    RUN(launch_scan_lengths(vlen, qlen, B, f.off, s));
-    // with the row caches (q | k | v = in_proj(norm1(row)) once per clip / token: layer0_rows) the first layer is a pure gather:
-    // its attention reads the caches, its tail gathers the residual rows through a row index -- as on the post-norm path
-    const bool caches = l0->qkv_vid && m->opt_l0_gather && m->opt_res_gather;
-    float* Z = f.X1;                                                                                 // the normalised rows
-    if (caches) {
-        RUN(launch_row_index(vrow0, vlen, trow0, qlen, f.off, f.RIDX, B, Lmax, s));
-    } else {
-        RUN(launch_pack_l0(vproj, vrow0, vlen, tproj, trow0, qlen, f.off, m->dim_t, nullptr, nullptr, nullptr, f.X, nullptr,
-                           nullptr, nullptr, B, Lmax, s));                                           // the residual stream
-        RUN(launch_layernorm(f.X, 256, m->enc[0].n1.g, m->enc[0].n1.b, Z, 256, Mmax, Mdev, 256, s)); // norm1 of layer 0
-    }
-    for (int l = 0; l < m->n_enc; ++l) {    // cone/transformer.py:248-260
-        const bool g0 = l == 0 && caches;
-        AttnSrc src{};
-        src.vlen = vlen; src.pos_zero_row = (int)pos_rows_n - 1;
-        src.pos_qk = l0->pos_qk + (size_t)l * pos_rows_n * 512;
-        if (l0->txt_pos_qk) { src.txt_pos_qk = l0->txt_pos_qk + (size_t)l * l0->n_txt * 512; src.trow0 = trow0; }   // --use_txt_pos
-        if (g0) {
-            src.qkv_vid = l0->qkv_vid; src.qkv_txt = l0->qkv_txt; src.vrow0 = vrow0; src.trow0 = trow0;
-        } else {
-            RUN(encoder_qkv(m, l, Z, f.QKV, Mmax, Mdev, s, false));                                          // q | k | v of src2
-            src.Q = f.QKV; src.K = f.QKV + 256; src.V = f.QKV + 512; src.ldq = src.ldk = src.ldv = 768;
-        }
-        RUN(launch_enc_attn(g0 ? ATTN_GATHER : ATTN_POSADD, src, f.ATT, f.off, B, Lmax, s));
-        TailArgs t = tail_args(&m->enc_tail[l], f.ATT, g0 ? vproj : f.X, f.X, Mmax, Mdev, ff);
-        t.pre = true; t.OUT2 = Z; t.ldo2 = 256;                                                      // Z = the next consumer's norm of the stream
-        if (g0) { t.r_idx = f.RIDX; t.R2 = tproj; }
-        RUN(launch_layer_tail(m, f, t, s));
-    }
-    const float* MEM = Z;                                                                            // encoder.norm(src)
-    // --use_txt_pos: the keys memory + pos written once (text rows from the tokens' own position rows), x + pos form of the fold
-    const bool xp = l0->txt_pos != nullptr;
-    if (xp) RUN(launch_add_pos_rows(MEM, f.off, vlen, l0->pos_rows, f.XP, B, Lmax, s, l0->txt_pos, trow0));
-    CONE_CHECK_HIP(hipMemsetAsync(f.TGT, 0, (size_t)T * 256 * sizeof(float), s));                    // tgt = 0 (:66)
-    GemmArgs g;
-    for (int l = 0; l < nd; ++l) {          // cone/transformer.py:319-342
-        const DecLayer& dl = m->dec[l];
-        RUN(launch_layernorm(f.TGT, 256, dl.n1.g, dl.n1.b, f.TGT1, 256, T, nullptr, 256, s));
-        g = G(m, f.TGT1, 256, dl.sa.in_w, 256, nullptr, f.DQK, 768, T, nullptr, 768, 256, EPI_RESIDUAL);
-        g.R = m->dec_sa_tab[l]; g.ldr = 768; g.r_mod = m->nq;
-        RUN(launch_gemm(g, s));
-        RUN(launch_small_attn(f.DQK, 768, f.DQK + 256, 768, f.DQK + 512, 768, f.DATT, 256, nullptr, B, m->nq, m->nq, s));
-        g = G(m, f.DATT, 256, dl.sa.out.w, 256, dl.sa.out.b, f.TGT, 256, T, nullptr, 256, 256, EPI_RESIDUAL);
-        g.R = f.TGT; g.ldr = 256;
-        RUN(launch_gemm(g, s));
-        RUN(launch_layernorm(f.TGT, 256, dl.n2.g, dl.n2.b, f.TGT1, 256, T, nullptr, 256, s));
-        g = G(m, f.TGT1, 256, dl.ca.in_w, 256, nullptr, f.DQ, 256, T, nullptr, 256, 256, EPI_RESIDUAL);
-        g.R = m->dec_ca_tab[l]; g.ldr = 256; g.r_mod = m->nq;
-        RUN(launch_gemm(g, s));
-        RUN(launch_dec_cross_mfma(f.DQ, xp ? f.XP : nullptr, MEM, xp ? nullptr : l0->pos_rows, vlen, f.off, dl.ca.in_w + 256 * 256,
-                                  m->dec_vT[l], dl.ca.in_b + 512, f.DATT, B, m->nq, Lmax, nullptr, s, 3));
-        TailArgs t = tail_args(&m->dec_tail[l], f.DATT, f.TGT, f.TGT, T, nullptr, ff);
-        t.pre = true; t.OUT2 = f.HS + (size_t)l * T * 256; t.ldo2 = 256;                             // decoder.norm of this layer's rows
-        RUN(launch_layer_tail(m, f, t, s));
-    }
-    return heads_and_taps(m, HeadBufs{f.HS, f.S1, f.S2, f.LG, f.SP, f.off}, MEM, vlen, qlen, B, Lv_max, Lq_max, logits, spans, saliency,
-                          taps, false, s);
-}
-
 // ------------------------------------------------------------------------------ general-shape forward
 // Any supported (d, heads), post-norm and pre-norm (cone/transformer.py:233-260, 296-342), built from plain launches:
 // LayerNorm, row GEMMs with residual / ReLU epilogues, the attention core of general.hip (encoder self-attention over the
@@ -875,27 +902,28 @@ static void carve_gen(const cone_model* m, Carver& c, int B, int Lmax, GenBuffer
     f.HS = c.take<float>(nd * T * d); f.S1 = c.take<float>(nd * T * d); f.S2 = c.take<float>(nd * T * d);
     f.LG = c.take<float>(nd * T * 2); f.SP = c.take<float>(nd * T * 2);
 }
-static size_t gen_ws_bytes(const cone_model* m, int B, int Lmax) {
+// workspace of the body the plan picked
+static size_t fwd_ws_bytes(const cone_model* m, int B, int Lmax, const FwdPlan& p) {
     Carver c(nullptr, ~(size_t)0);
-    GenBuffers f;
-    carve_gen(m, c, B, Lmax, f);
+    FwdBuffers f;
+    GenBuffers g;
+    if (p.body == BODY_GENERAL) carve_gen(m, c, B, Lmax, g);
+    else carve_fwd(m, c, B, Lmax, p, f);
     return c.cur;
 }
 
-static int forward_general(const cone_model* m, const float* vproj, const int* vrow0, const int* vlen, const float* tproj,
-                           const int* trow0, const int* qlen, int B, int Lv_max, int Lq_max, float* logits, float* spans,
-                           float* saliency, const cone_taps* taps, void* ws, size_t ws_bytes, hipStream_t s) {
-    const int d = m->d, hd = m->d / m->heads, nh = m->heads;
-    const int Lmax = Lv_max + Lq_max, Mmax = B * Lmax, T = B * m->nq, nd = m->n_dec, ff = m->ff, nq = m->nq;
+static int forward_general(const cone_model* m, const FwdCall& call, void* ws, size_t ws_bytes, hipStream_t s) {
+    const int d = m->d, hd = m->d / m->heads, nh = m->heads, B = call.B;
+    const int Lmax = call.Lv_max + call.Lq_max, Mmax = B * Lmax, T = B * m->nq, nd = m->n_dec, ff = m->ff, nq = m->nq;
     const bool pre = m->pre_norm != 0;
     Carver c(ws, ws_bytes);
     GenBuffers f;
     carve_gen(m, c, B, Lmax, f);
     if (!c.ok) { set_error("forward: workspace too small (%zu < %zu)", ws_bytes, c.cur); return CONE_E_WORKSPACE; }
     const int* Mdev = f.off + B;
-    RUN(launch_scan_lengths(vlen, qlen, B, f.off, s));
-    RUN(launch_gen_pack_pos(vproj, vrow0, vlen, tproj, trow0, qlen, f.off, m->dim_t, f.X, f.POS, d, B, Lmax, s, m->txt_pos_emb,
-                            m->txt_pos_ln.g, m->txt_pos_ln.b));
+    RUN(launch_scan_lengths(call.vlen, call.qlen, B, f.off, s));
+    RUN(launch_gen_pack_pos(call.vproj, call.vrow0, call.vlen, call.tproj, call.trow0, call.qlen, f.off, m->dim_t, f.X, f.POS, d, B,
+                            Lmax, s, m->txt_pos_emb, m->txt_pos_ln.g, m->txt_pos_ln.b));
     GemmArgs g;
     auto residual = [&](const float* A, int K, const Linear& lin, const float* R, float* C, int M, const int* M_dev) {
         GemmArgs r = G(m, A, K, lin.w, K, lin.b, C, d, M, M_dev, d, K, EPI_RESIDUAL);   // C = A W^T + b + R
@@ -975,99 +1003,86 @@ static int forward_general(const cone_model* m, const float* vproj, const int* v
         }
         RUN(ln(f.TGT, m->dec_norm, f.HS + (size_t)l * T * d));                                            // decoder.norm (intermediate)
     }
-    return heads_and_taps(m, HeadBufs{f.HS, f.S1, f.S2, f.LG, f.SP, f.off}, MEM, vlen, qlen, B, Lv_max, Lq_max, logits, spans, saliency,
-                          taps, true, s);
+    return heads_and_taps(m, call, HeadBufs{f.HS, f.S1, f.S2, f.LG, f.SP, f.off}, MEM, true, s);
 }
 
-static int forward_packed(const cone_model* m, const float* vproj, const int* vrow0, const int* vlen,
-                          const float* tproj, const int* trow0, const int* qlen, int B, int Lv_max, int Lq_max,
-                          float* logits, float* spans, float* saliency, const cone_taps* taps, void* ws,
-                          size_t ws_bytes, hipStream_t s, const cone_layer0* l0 = nullptr) {
+// The forward behind every entry, on the plan its caller made (plan_forward).  Its own body is the 256-wide packed path,
+// post-norm and (p.pre, table path only) pre-norm with the fused tails: the same launches either way -- position tables, ONE
+// N = 768 GEMM per encoder layer, the fused layer tail, the folded decoder cross-attention.  Pre-norm differs in where the
+// LayerNorms sit (Z = the normalised rows the next consumer reads, the tail's second output), in that its first layer reads
+// the row caches all or nothing, and in that it has no first-decoder-layer constants and computes every layer's heads.
+static int forward_packed(const cone_model* m, const FwdCall& c, const FwdPlan& p, void* ws, size_t ws_bytes, hipStream_t s) {
+    const int B = c.B, Lv_max = c.Lv_max, Lq_max = c.Lq_max;
     CONE_REQUIRE(B > 0 && Lv_max > 0 && Lq_max >= 0, "forward: bad sizes B=%d Lv=%d Lq=%d", B, Lv_max, Lq_max);
     const int Lmax = Lv_max + Lq_max;
     CONE_REQUIRE(Lmax <= CONE_MAX_WINDOW_TOKENS, "forward: window length %d + %d exceeds %d tokens", Lv_max, Lq_max,
                  CONE_MAX_WINDOW_TOKENS);
     // beyond 192 tokens only the default path exists (the 256-key forms of the encoder attention and of the folded cross-
     // attention): the A/B forms and the unfolded decoder stop at 192 keys (the general path: any length up to the limit)
-    if (!m->general())
-        CONE_REQUIRE(Lmax <= 192 || (m->opt_dec_fold >= 2 && dec_cross_mfma_supported(m->nq, Lmax, true) && !m->txt_pos_emb &&
-                                     m->opt_pos_tables),
+    if (p.body != BODY_GENERAL)
+        CONE_REQUIRE(Lmax <= 192 || p.long_ok,
                      "forward: windows of %d tokens (> 192) run only on the default table path with 3 / 5 / 8 decoder slots", Lmax);
     CONE_REQUIRE((int64_t)B * Lmax < (1ll << 24), "forward: batch too large (B * L >= 2^24 tokens)");
     if (m->txt_pos_emb)
         CONE_REQUIRE(Lq_max <= m->txt_pos_rows, "forward: %d text tokens but txt_position_embed has %d rows (max_q_l)", Lq_max,
                      m->txt_pos_rows);
-    if (m->general())       // (no layer-0 caches or tables read)
-        return forward_general(m, vproj, vrow0, vlen, tproj, trow0, qlen, B, Lv_max, Lq_max, logits, spans, saliency, taps, ws,
-                               ws_bytes, s);
-    cone_layer0 eff;
-    FwdPlan plan;
-    l0 = resolve_l0(m, l0, Lv_max, Lmax, &eff, &plan);
-    const bool caches = l0 && l0->qkv_vid;
-    if (l0)     // (the handle's own tables or the caller's: either must cover the longest window of the call)
-        CONE_REQUIRE(l0->pos_qk && l0->max_v_l >= Lv_max,
-                     "forward: position tables / layer-0 cache built for a shorter window (%d < %d clips)", l0->max_v_l, Lv_max);
-    Carver c(ws, ws_bytes);
+    if (p.body == BODY_GENERAL) return forward_general(m, c, ws, ws_bytes, s);      // (no layer-0 caches or tables read)
+    const cone_layer0& l0 = p.l0;
+    if (p.have_l0)  // (the handle's own tables or the caller's: either must cover the longest window of the call)
+        CONE_REQUIRE(l0.pos_qk && l0.max_v_l >= Lv_max,
+                     "forward: position tables / layer-0 cache built for a shorter window (%d < %d clips)", l0.max_v_l, Lv_max);
+    Carver cv(ws, ws_bytes);
     FwdBuffers f;
-    carve_fwd(m, c, B, Lmax, plan, f);
-    if (!c.ok) { set_error("forward: workspace too small (%zu < %zu)", ws_bytes, c.cur); return CONE_E_WORKSPACE; }
-    if (m->pre_norm && plan.tables)
-        return forward_packed_prenorm_fused(m, vproj, vrow0, vlen, tproj, trow0, qlen, B, Lv_max, Lq_max, logits, spans, saliency,
-                                            taps, f, s, l0);
-    if (m->pre_norm)
-        return forward_packed_prenorm(m, vproj, vrow0, vlen, tproj, trow0, qlen, B, Lv_max, Lq_max, logits, spans, saliency, taps,
-                                      f, s);
+    carve_fwd(m, cv, B, Lmax, p, f);
+    if (!cv.ok) { set_error("forward: workspace too small (%zu < %zu)", ws_bytes, cv.cur); return CONE_E_WORKSPACE; }
+    if (p.body == BODY_PRENORM_PLAIN) return forward_packed_prenorm(m, c, p, f, s);
     const int Mmax = B * Lmax, T = B * m->nq, nd = m->n_dec, ff = m->ff;
     const int* Mdev = f.off + B;
-    const size_t pos_rows_n = l0 ? (size_t)cone_pos_table_rows(l0->max_v_l) : 0;
+    float* Z = f.X1;                                    // pre: the normalised rows
 
-    RUN(launch_scan_lengths(vlen, qlen, B, f.off, s));
-    const bool gather0 = caches && m->opt_l0_gather;
-    // first layer entirely from the per-clip / per-token rows: attention gathers q|k|v, the fused layer tail gathers its
-    // residual rows through a row index (kept in the X1 region, unused by that path) -- no packed copy of the input
-    const bool gather_res = gather0 && plan.tables && m->opt_ffn_fused >= 2 && m->opt_res_gather && ffn_fused_supported(ff) &&
-                            m->n_enc > 0;
-    int* RIDX = reinterpret_cast<int*>(f.X1);
-    if (gather_res) {
-        RUN(launch_row_index(vrow0, vlen, trow0, qlen, f.off, RIDX, B, Lmax, s));
-    } else if (caches) {
+    RUN(launch_scan_lengths(c.vlen, c.qlen, B, f.off, s));
+    if (p.gather_res) {
+        // first layer entirely from the per-clip / per-token rows: attention gathers q|k|v, the fused layer tail gathers its
+        // residual rows through a row index -- no packed copy of the input
+        RUN(launch_row_index(c.vrow0, c.vlen, c.trow0, c.qlen, f.off, f.RIDX, B, Lmax, s));
+    } else if (p.caches) {
         // X (and, off the table path, POS): the first layer's attention gathers q|k|v from the caches itself; with
         // the gather switched off a packing pass writes them out first
-        RUN(launch_pack_l0(vproj, vrow0, vlen, tproj, trow0, qlen, f.off, m->dim_t, l0->qkv_vid, l0->qkv_txt,
-                           l0->pos_qk, f.X, f.POS, gather0 ? nullptr : f.QKV, gather0 ? nullptr : f.QKV + (size_t)Mmax * 512,
+        RUN(launch_pack_l0(c.vproj, c.vrow0, c.vlen, c.tproj, c.trow0, c.qlen, f.off, m->dim_t, l0.qkv_vid, l0.qkv_txt,
+                           l0.pos_qk, f.X, f.POS, p.gather0 ? nullptr : f.QKV, p.gather0 ? nullptr : f.QKV + (size_t)Mmax * 512,
                            B, Lmax, s));
-    } else if (plan.tables) {
+    } else if (p.tables) {
         // no row caches (a caller that hands over projected rows only): the packed layer input, nothing else -- the first
         // layer then runs like the later ones (one N = 768 GEMM on x, position rows from the table)
-        RUN(launch_pack_l0(vproj, vrow0, vlen, tproj, trow0, qlen, f.off, m->dim_t, nullptr, nullptr, nullptr, f.X, nullptr,
-                           nullptr, nullptr, B, Lmax, s));
+        RUN(launch_pack_l0(c.vproj, c.vrow0, c.vlen, c.tproj, c.trow0, c.qlen, f.off, m->dim_t, nullptr, nullptr, nullptr, f.X,
+                           nullptr, nullptr, nullptr, B, Lmax, s));
     } else {
-        RUN(launch_pack_pos(vproj, vrow0, vlen, tproj, trow0, qlen, f.off, m->dim_t, f.X, f.POS, f.XP, B, Lmax, s,
+        RUN(launch_pack_pos(c.vproj, c.vrow0, c.vlen, c.tproj, c.trow0, c.qlen, f.off, m->dim_t, f.X, f.POS, f.XP, B, Lmax, s,
                             m->txt_pos_emb, m->txt_pos_ln.g, m->txt_pos_ln.b));
     }
+    if (p.pre && !p.gather_res)
+        RUN(launch_layernorm(f.X, 256, m->enc[0].n1.g, m->enc[0].n1.b, Z, 256, Mmax, Mdev, 256, s));    // norm1 of layer 0
 
     bool qkv_fused = false;               // this layer's q | k | v rows were written by the previous layer's tail
-    for (int l = 0; l < m->n_enc; ++l) {  // cone/transformer.py:233-246
+    for (int l = 0; l < m->n_enc; ++l) {  // cone/transformer.py:233-246, pre: :248-260
         const EncLayer& e = m->enc[l];
         AttnSrc src{};
         int mode = ATTN_PACKED;
-        if (l == 0 && gather0) {
+        if (l == 0 && p.gather0) {
             mode = ATTN_GATHER;
-            src.qkv_vid = l0->qkv_vid; src.qkv_txt = l0->qkv_txt; src.pos_qk = l0->pos_qk;
-            src.vrow0 = vrow0; src.vlen = vlen; src.trow0 = trow0; src.pos_zero_row = (int)pos_rows_n - 1;
-            src.txt_pos_qk = l0->txt_pos_qk;                                   // (--use_txt_pos: this layer's = the first image)
-        } else if (l == 0 && caches) {                     // packed by pack_l0: (M, 512) q|k then (M, 256) v
+            src = table_attn_src(c, l0, 0);
+            src.qkv_vid = l0.qkv_vid; src.qkv_txt = l0.qkv_txt; src.vrow0 = c.vrow0; src.trow0 = c.trow0;
+        } else if (l == 0 && p.caches) {                    // packed by pack_l0: (M, 512) q|k then (M, 256) v
             src.Q = f.QKV; src.K = f.QKV + 256; src.V = f.QKV + (size_t)Mmax * 512;
             src.ldq = src.ldk = 512; src.ldv = 256;
-        } else if (plan.tables) {
-            // q | k | v = x W^T + b in ONE N = 768 GEMM on x; the attention adds pos W_qk^T of this layer from the
-            // static table ((x + pos) W^T = x W^T + pos W^T): no x + pos matrix, no second A operand
+        } else if (p.tables) {
+            // q | k | v = x W^T + b in ONE N = 768 GEMM on x (pre: on norm1(x)); the attention adds pos W_qk^T of this layer
+            // from the static table: no x + pos matrix, no second A operand
             if (!qkv_fused)     // (else: written by the previous layer's tail from the registers that held its output rows)
-                RUN(encoder_qkv(m, l, f.X, f.QKV, Mmax, Mdev, s, true));
+                RUN(encoder_qkv(m, l, p.pre ? Z : f.X, f.QKV, Mmax, Mdev, s, !p.pre));
             mode = ATTN_POSADD;
+            src = table_attn_src(c, l0, l);
             src.Q = f.QKV; src.K = f.QKV + 256; src.V = f.QKV + 512; src.ldq = src.ldk = src.ldv = 768;
-            src.pos_qk = l0->pos_qk + (size_t)l * pos_rows_n * 512; src.vlen = vlen; src.pos_zero_row = (int)pos_rows_n - 1;
-            if (l0->txt_pos_qk) { src.txt_pos_qk = l0->txt_pos_qk + (size_t)l * l0->n_txt * 512; src.trow0 = trow0; }
         } else {
             float* QK = f.QKV; float* V = f.QKV + (size_t)Mmax * 512;
             RUN(launch_gemm(G(m, f.XP, 256, e.sa.in_w, 256, e.sa.in_b, QK, 512, Mmax, Mdev, 512, 256), s));  // q | k = (x+pos) W^T
@@ -1078,101 +1093,60 @@ static int forward_packed(const cone_model* m, const float* vproj, const int* vr
         // everything behind the attention: norm2(x1 + ffn(x1)), x1 = norm1(x + attn Wo^T + bo) -- by default ONE launch, in place
         // (a workgroup reads its 128 rows of x before it writes them, and nobody else touches them), in which the next layer's
         // q | k | v projection may ride (its input rows are that kernel's output; ATT and QKV are disjoint parts of the H region)
-        const bool g0 = l == 0 && gather_res;
-        TailArgs t = tail_args(&m->enc_tail[l], f.ATT, g0 ? vproj : f.X, f.X, Mmax, Mdev, ff);
-        if (g0) { t.r_idx = RIDX; t.R2 = tproj; }
-        if (l + 1 < m->n_enc) t.next = &m->enc_tail[l + 1];
-        t.QKV = f.QKV; t.ldq = 768; t.n_qkv = 768;
-        t.X1 = f.X1; t.H = f.H;
-        if (!plan.tables) { t.C2 = f.XP; t.ADD = f.POS; }   // x + pos for the next layer's q/k / the decoder's keys
+        const bool g0 = l == 0 && p.gather_res;
+        TailArgs t = tail_args(&m->enc_tail[l], f.ATT, g0 ? c.vproj : f.X, f.X, Mmax, Mdev, ff);
+        if (g0) { t.r_idx = f.RIDX; t.R2 = c.tproj; }
+        if (p.pre) {
+            t.pre = true; t.OUT2 = Z; t.ldo2 = 256;         // Z = the next consumer's norm of the stream
+        } else {
+            if (l + 1 < m->n_enc) t.next = &m->enc_tail[l + 1];
+            t.QKV = f.QKV; t.ldq = 768; t.n_qkv = 768;
+            t.X1 = f.X1; t.H = f.H;
+            if (!p.tables) { t.C2 = f.XP; t.ADD = f.POS; }  // x + pos for the next layer's q/k / the decoder's keys
+        }
         RUN(launch_layer_tail(m, f, t, s, &qkv_fused));
     }
-    const float* MEM = f.X;
+    const float* MEM = p.pre ? Z : f.X;                     // (pre: encoder.norm(src))
 
-    // decoder (cone/transformer.py:296-317, 117-146).  Default: the memory K / V projections are folded into
+    // decoder (cone/transformer.py:296-317, 117-146, pre: :319-342).  Default: the memory K / V projections are folded into
     // the cross-attention kernel (dec_cross.hip); otherwise memory K/V for all layers in two GEMMs.
-    const bool fold = plan.fold;
-    const bool want_aux = taps && (taps->hs || taps->aux_logits || taps->aux_spans);
-    bool sal_done = false;
-    const int h0 = want_aux ? 0 : nd - 1;               // first decoder layer whose heads are needed
-    const int HT = (nd - h0) * T;
+    const int h0 = p.h0, HT = (nd - h0) * T;
     const size_t hoff = (size_t)h0 * T;
     // only the last layer's heads wanted (the eval pipeline): they write straight into the caller's logits / spans; with the
     // intermediate layers' too, all layers go to the workspace and the last layer's rows are copied out
-    float* LGo = want_aux ? f.LG + hoff * 2 : logits;
-    float* SPo = want_aux ? f.SP + hoff * 2 : spans;
-    // (the chain only where launch_gemm itself would run its 16-row form, and only on the automatic tile family: the A/B
-    // families walk k in other orders)
-    const bool heads_chain = m->opt_chain && m->opt_gemm == GEMM_AUTO && rows_chain_supported(T) &&
-                             !(m->opt_spread && gemm_rows_spread_rows(T));      // (few rows: the spread GEMM launches are faster)
+    float* LGo = p.want_aux ? f.LG + hoff * 2 : c.logits;
+    float* SPo = p.want_aux ? f.SP + hoff * 2 : c.spans;
     // the position rows come from the tables inside the cross-attention kernels -- unless text tokens carry their own
     // (--use_txt_pos): then memory + pos is written once (dec_xp) and the kernels run their x + pos form
-    const bool dec_tab = plan.tables && !plan.dec_xp;
-    if (plan.dec_xp) RUN(launch_add_pos_rows(MEM, f.off, vlen, l0->pos_rows, f.XP, B, Lmax, s, l0->txt_pos, trow0));
-    if (!fold) {
-        if (dec_tab) RUN(launch_add_pos_rows(MEM, f.off, vlen, l0->pos_rows, f.XP, B, Lmax, s));
+    if (p.dec_xp) RUN(launch_add_pos_rows(MEM, f.off, c.vlen, l0.pos_rows, f.XP, B, Lmax, s, l0.txt_pos, c.trow0));
+    if (!p.fold) {
+        if (p.dec_tab) RUN(launch_add_pos_rows(MEM, f.off, c.vlen, l0.pos_rows, f.XP, B, Lmax, s));
         GemmArgs g = G(m, f.XP, 256, m->dec_k.w, 256, m->dec_k.b, f.KD, 256 * nd, Mmax, Mdev, 256 * nd, 256);
         RUN(launch_gemm(g, s));                                                             // k = (memory+pos) W_k^T
         RUN(launch_gemm(G(m, MEM, 256, m->dec_v.w, 256, m->dec_v.b, f.VD, 256 * nd, Mmax, Mdev, 256 * nd, 256), s));
     }
-    if (!m->opt_dec0_const)          // tgt = 0 is only read by the first layer's own projections (constants otherwise)
+    if (!p.dec0)                     // tgt = 0 is only read by the first layer's own projections (constants otherwise)
         CONE_CHECK_HIP(hipMemsetAsync(f.TGT, 0, (size_t)T * 256 * sizeof(float), s));
     for (int l = 0; l < nd; ++l) {
-        const DecLayer& dl = m->dec[l];
-        // Layer 0 starts from tgt = 0 (cone/transformer.py:66): its self-attention block and its cross-attention
-        // queries do not depend on the window.  They are computed for ONE window's nq rows by the same kernels
-        // (rows of a GEMM are independent: identical bits) and replicated, instead of T = B*nq identical rows.
-        const bool dec0 = l == 0 && m->opt_dec0_const;
-        const int Tq = dec0 ? m->nq : T;
-        GemmArgs g;
-        if (dec0) {
-            // the layer's self-attention block and cross-attention queries: per-checkpoint constants (dec0_constants, at
-            // cone_model_create), replicated to the T rows of the batch in one launch
-            RUN(launch_tile_rows2(f.TGT1, m->dec0_tgt1, f.DQ, m->dec0_dq, m->nq, T, s));
-        } else {
-            // q | k | v of the slots in ONE N = 768 GEMM on tgt, the slot-position term from the layer's table
-            g = G(m, f.TGT, 256, dl.sa.in_w, 256, nullptr, f.DQK, 768, T, nullptr, 768, 256, EPI_RESIDUAL);
-            g.R = m->dec_sa_tab[l]; g.ldr = 768; g.r_mod = m->nq;
-            RUN(launch_gemm(g, s));
-            RUN(launch_small_attn(f.DQK, 768, f.DQK + 256, 768, f.DQK + 512, 768, f.DATT, 256, nullptr, B, m->nq, m->nq, s));
-            g = G(m, f.DATT, 256, dl.sa.out.w, 256, dl.sa.out.b, f.TGT1, 256, T, nullptr, 256, 256, EPI_RESIDUAL | EPI_LN);
-            g.R = f.TGT; g.ldr = 256; g.ln_g = dl.n1.g; g.ln_b = dl.n1.b;
-            RUN(launch_gemm(g, s));
-            g = G(m, f.TGT1, 256, dl.ca.in_w, 256, nullptr, f.DQ, 256, T, nullptr, 256, 256, EPI_RESIDUAL);
-            g.R = m->dec_ca_tab[l]; g.ldr = 256; g.r_mod = m->nq;
-            RUN(launch_gemm(g, s));
+        // Layer 0 starts from tgt = 0 (cone/transformer.py:66): its self-attention block and its cross-attention queries do
+        // not depend on the window: per-checkpoint constants (dec0_constants, at cone_model_create, by the same kernels on
+        // ONE window's nq rows: identical bits), replicated to the T rows of the batch in one launch
+        if (l == 0 && p.dec0) RUN(launch_tile_rows2(f.TGT1, m->dec0_tgt1, f.DQ, m->dec0_dq, m->nq, T, s));
+        else RUN(dec_layer_front(m, f, l, B, p.pre, s));
+        RUN(dec_cross_attn(m, c, p, f, l, MEM, s));
+        if (p.pre) {
+            TailArgs t = tail_args(&m->dec_tail[l], f.DATT, f.TGT, f.TGT, T, nullptr, ff);
+            t.pre = true; t.OUT2 = f.HS + (size_t)l * T * 256; t.ldo2 = 256;                // decoder.norm of this layer's rows
+            RUN(launch_layer_tail(m, f, t, s));
+            continue;
         }
-        if (fold && m->opt_dec_fold >= 2) {
-            // the first layer's launch holds every memory row of the batch in registers anyway: the saliency head rides along
-            // (table form of the default kernel; other forms: the separate pass at the end)
-            const bool ride = l == 0 && saliency && dec_tab && (m->opt_dec_fold == 2 || m->opt_dec_fold == 3 || m->opt_dec_fold == 5);
-            if (ride) {
-                CONE_CHECK_HIP(hipMemsetAsync(saliency, 0, (size_t)B * Lv_max * sizeof(float), s));     // padded clips: 0
-                sal_done = true;
-            }
-            RUN(launch_dec_cross_mfma(f.DQ, dec_tab ? nullptr : f.XP, MEM, dec_tab ? l0->pos_rows : nullptr, vlen,
-                                      f.off, dl.ca.in_w + 256 * 256, m->dec_vT[l], dl.ca.in_b + 512, f.DATT, B, m->nq, Lmax,
-                                      Tq != T ? f.QKS : nullptr, s,       // layer 0: the same queries for every window
-                                      // the kernel form.  Default: rows-once for the first layer, two-read behind it -- by
-                                      // LAYER, not by whether this batch shares its slabs (a one-window batch does not): a
-                                      // window's bits must not depend on the batch it rides in
-                                      m->opt_dec_fold == 2 ? (l == 0 ? 5 : 3) : m->opt_dec_fold,
-                                      ride ? m->saliency.w : nullptr, ride ? m->saliency.b : nullptr, ride ? saliency : nullptr,
-                                      ride ? Lv_max : 0));
-        }
-        else if (fold)
-            RUN(launch_dec_cross(f.DQ, dec_tab ? nullptr : f.XP, MEM, dec_tab ? l0->pos_rows : nullptr, vlen,
-                                 f.off, dl.ca.in_w + 256 * 256, m->dec_vT[l], dl.ca.in_b + 512, f.DATT, B, m->nq, Lmax, s));
-        else
-            RUN(launch_small_attn(f.DQ, 256, f.KD + l * 256, 256 * nd, f.VD + l * 256, 256 * nd, f.DATT, 256, f.off, B,
-                                  m->nq, Lmax, s));
         TailArgs t = tail_args(&m->dec_tail[l], f.DATT, f.TGT1, f.TGT, T, nullptr, ff);    // tgt = norm3(x1 + ffn(x1)), x1 = norm2(tgt1 + ca)
         t.X1 = f.TGT2; t.H = f.DH;
         RUN(launch_layer_tail(m, f, t, s));
         // decoder.norm + heads on an intermediate layer only feed aux_outputs / the hs tap (unused by inference,
         // cone/inference.py:54-59): computed on request only
-        if (l == nd - 1 || want_aux) {
-            if (heads_chain) {
+        if (l == nd - 1 || p.want_aux) {
+            if (p.heads_chain) {
                 // few rows: decoder.norm -> class head, span MLP -> span head of THIS layer's rows in one launch (rows_chain.h);
                 // the normalised rows are written only when the hs tap asks for them
                 ChainArgs ca{};
@@ -1180,7 +1154,7 @@ static int forward_packed(const cone_model* m, const float* vproj, const int* vr
                 const size_t ro = (size_t)(l - h0) * T * 2;
                 ChainStage& c0 = ca.st[0];
                 c0.kind = 1; c0.ln_g = m->dec_norm.g; c0.ln_b = m->dec_norm.b;
-                c0.C = taps && taps->hs ? f.HS + (size_t)l * T * 256 : nullptr; c0.ldc = 256;
+                c0.C = c.taps && c.taps->hs ? f.HS + (size_t)l * T * 256 : nullptr; c0.ldc = 256;
                 c0.hw = m->class_embed.w; c0.hb = m->class_embed.b; c0.hout = LGo + ro; c0.hld = 2; c0.hnout = 2; c0.hact = 0;
                 ChainStage& c1 = ca.st[1];
                 c1.kind = 0; c1.K = 256; c1.W = m->span[0].w; c1.bias = m->span[0].b; c1.flags = EPI_RELU;
@@ -1194,22 +1168,23 @@ static int forward_packed(const cone_model* m, const float* vproj, const int* vr
             }
         }
     }
+    if (p.pre) return heads_and_taps(m, c, HeadBufs{f.HS, f.S1, f.S2, f.LG, f.SP, f.off}, MEM, false, s);
     // heads (cone/model.py:112-117); the last layer is the prediction
-    if (!heads_chain) {
+    if (!p.heads_chain) {
         RUN(launch_rowdot(f.HS + hoff * 256, 256, m->class_embed.w, m->class_embed.b, LGo, 2, HT, 2, 0, s));
         RUN(launch_gemm(G(m, f.HS + hoff * 256, 256, m->span[0].w, 256, m->span[0].b, f.S1, 256, HT, nullptr, 256, 256, EPI_RELU), s));
         RUN(launch_gemm(G(m, f.S1, 256, m->span[1].w, 256, m->span[1].b, f.S2, 256, HT, nullptr, 256, 256, EPI_RELU), s));
         RUN(launch_rowdot(f.S2, 256, m->span[2].w, m->span[2].b, SPo, 2, HT, 2, 1, s));
     }
     const size_t last = (size_t)(nd - 1) * T * 2;
-    if (want_aux) {
-        CONE_CHECK_HIP(hipMemcpyAsync(logits, f.LG + last, (size_t)T * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
-        CONE_CHECK_HIP(hipMemcpyAsync(spans, f.SP + last, (size_t)T * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (p.want_aux) {
+        CONE_CHECK_HIP(hipMemcpyAsync(c.logits, f.LG + last, (size_t)T * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
+        CONE_CHECK_HIP(hipMemcpyAsync(c.spans, f.SP + last, (size_t)T * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
-    RUN(copy_taps(taps, f.HS, f.LG, f.SP, nd, T, 256, s));
-    if ((saliency && !sal_done) || (taps && taps->memory))     // saliency == NULL: not wanted (cone/inference.py never reads it)
-        RUN(launch_saliency(MEM, f.off, vlen, qlen, m->saliency.w, m->saliency.b, sal_done ? nullptr : saliency, Lv_max,
-                            taps ? taps->memory : nullptr, Lq_max, B, s));
+    RUN(copy_taps(c.taps, f.HS, f.LG, f.SP, nd, T, 256, s));
+    if ((c.saliency && !p.sal_ride) || (c.taps && c.taps->memory))  // saliency == NULL: not wanted (cone/inference.py never reads it)
+        RUN(launch_saliency(MEM, f.off, c.vlen, c.qlen, m->saliency.w, m->saliency.b, p.sal_ride ? nullptr : c.saliency, Lv_max,
+                            c.taps ? c.taps->memory : nullptr, Lq_max, B, s));
     return 0;
 }
 
@@ -1227,12 +1202,7 @@ extern "C" int cone_abi_version(void) { return CONE_HIP_ABI_VERSION; }
 
 extern "C" int cone_model_create(const cone_weights* w, cone_model** out) { return build_model(w, out); }
 extern "C" void cone_model_destroy(cone_model* m) {
-    if (!m) return;
-    if (m->arena) (void)hipFree(m->arena);
-    if (m->split_img) (void)hipFree(m->split_img);
-    if (m->bf16_img) (void)hipFree(m->bf16_img);
-    if (m->tab_arena) (void)hipFree(m->tab_arena);
-    delete m;
+    if (m) free_model(m);
 }
 
 extern "C" size_t cone_adapter_norm_workspace(const cone_model* m, int64_t n_rows) {
@@ -1279,11 +1249,9 @@ extern "C" int cone_project_tokens(const cone_model* m, int which, const float* 
 
 extern "C" size_t cone_forward_packed_workspace(const cone_model* m, int B, int Lv_max, int Lq_max,
                                                 const cone_layer0* l0) {
-    if (m->general()) return gen_ws_bytes(m, B, Lv_max + Lq_max);
-    cone_layer0 eff;
-    FwdPlan plan;
-    resolve_l0(m, l0, Lv_max, Lv_max + Lq_max, &eff, &plan);
-    return fwd_ws_bytes(m, B, Lv_max + Lq_max, plan);
+    FwdCall c{};
+    c.B = B; c.Lv_max = Lv_max; c.Lq_max = Lq_max;
+    return fwd_ws_bytes(m, B, Lv_max + Lq_max, plan_forward(m, c, l0, false));
 }
 extern "C" int cone_forward_packed(const cone_model* m, const float* vproj, const int32_t* vid_row0,
                                    const int32_t* vid_len, const float* tproj, const int32_t* txt_row0,
@@ -1292,8 +1260,8 @@ extern "C" int cone_forward_packed(const cone_model* m, const float* vproj, cons
                                    void* ws, size_t ws_bytes, void* stream) {
     CONE_REQUIRE(m && vproj && tproj && vid_row0 && vid_len && txt_row0 && txt_len && logits && spans,
                  "forward_packed: null argument");
-    return forward_packed(m, vproj, vid_row0, vid_len, tproj, txt_row0, txt_len, B, Lv_max, Lq_max, logits, spans,
-                          saliency, taps, ws, ws_bytes, (hipStream_t)stream, l0);
+    const FwdCall c{vproj, vid_row0, vid_len, tproj, txt_row0, txt_len, B, Lv_max, Lq_max, logits, spans, saliency, taps};
+    return forward_packed(m, c, plan_forward(m, c, l0, false), ws, ws_bytes, (hipStream_t)stream);
 }
 
 extern "C" int64_t cone_pos_table_rows(int max_v_l) { return pos_table_rows(max_v_l); }
@@ -1348,42 +1316,27 @@ struct PaddedCarve {
     float *vp, *tp, *qv, *qt, *pt, *ptqk;
     char* pws; size_t pw;
 };
-static void carve_padded(const cone_model* m, Carver& c, int B, int Lv_pad, int Lq_pad, bool caches, bool txt_tables,
-                         PaddedCarve& p) {
+static void carve_padded(const cone_model* m, Carver& c, int B, int Lv_pad, int Lq_pad, const FwdPlan& plan, PaddedCarve& p) {
     const size_t nv = (size_t)B * Lv_pad, nt = (size_t)B * Lq_pad;
     p.voff = c.take<int>(B + 1); p.toff = c.take<int>(B + 1);
     p.vidx = c.take<int>(nv); p.tidx = c.take<int>(nt);
     p.vp = c.take<float>(nv * m->d); p.tp = c.take<float>(nt * m->d);
     p.qv = p.qt = p.pt = p.ptqk = nullptr;
-    if (caches) { p.qv = c.take<float>(nv * 768); p.qt = c.take<float>(nt * 768); }
-    if (txt_tables) { p.pt = c.take<float>(nt * 256); p.ptqk = c.take<float>((size_t)m->n_enc * nt * 512); }   // --use_txt_pos
+    if (plan.mk_caches) { p.qv = c.take<float>(nv * 768); p.qt = c.take<float>(nt * 768); }
+    if (plan.mk_txt_pos) { p.pt = c.take<float>(nt * 256); p.ptqk = c.take<float>((size_t)m->n_enc * nt * 512); }   // --use_txt_pos
     p.pw = project_ws_bytes(m, 0, nv);
     const size_t pt = project_ws_bytes(m, 1, nt);
     if (pt > p.pw) p.pw = pt;
     p.pws = c.take<char>(p.pw);
 }
-// What the padded entry runs on: the handle's tables, first-layer row caches it builds itself, and for a --use_txt_pos model
-// the text position rows it builds itself (such a model off the table path: nothing of it -- the general path)
-static FwdPlan padded_plan(const cone_model* m, int Lv_pad, int Lmax, bool* caches, bool* txt_tables) {
-    if (m->general()) {         // the general path: the compact projected rows only
-        *caches = *txt_tables = false;
-        return FwdPlan{};
-    }
-    cone_layer0 eff;
-    const cone_layer0* l0 = effective_l0(m, nullptr, Lv_pad, &eff, true);
-    *caches = l0 && m->opt_pos_tables && m->opt_l0_gather;
-    FwdPlan p = plan_for(m, l0 != nullptr, *caches, Lmax);
-    if (m->txt_pos_emb && !p.tables) { *caches = false; p = plan_for(m, false, false, Lmax); }
-    *txt_tables = m->txt_pos_emb && p.tables;
-    return p;
-}
 extern "C" size_t cone_forward_workspace(const cone_model* m, int B, int Lv_pad, int Lq_pad) {
-    bool caches, txt_tables;
-    const FwdPlan plan = padded_plan(m, Lv_pad, Lv_pad + Lq_pad, &caches, &txt_tables);
+    FwdCall call{};
+    call.B = B; call.Lv_max = Lv_pad; call.Lq_max = Lq_pad;
+    const FwdPlan plan = plan_forward(m, call, nullptr, true);
     Carver c(nullptr, ~(size_t)0);
     PaddedCarve p;
-    carve_padded(m, c, B, Lv_pad, Lq_pad, caches, txt_tables, p);
-    return c.cur + (m->general() ? gen_ws_bytes(m, B, Lv_pad + Lq_pad) : fwd_ws_bytes(m, B, Lv_pad + Lq_pad, plan));
+    carve_padded(m, c, B, Lv_pad, Lq_pad, plan, p);
+    return c.cur + fwd_ws_bytes(m, B, Lv_pad + Lq_pad, plan);
 }
 extern "C" int cone_forward_windows(const cone_model* m, const float* vid, const int32_t* vid_len, const float* txt,
                                     const int32_t* txt_len, int B, int Lv_pad, int Lq_pad, float* logits,
@@ -1394,11 +1347,13 @@ extern "C" int cone_forward_windows(const cone_model* m, const float* vid, const
     CONE_REQUIRE((int64_t)B * Lv_pad < (1ll << 31) && (int64_t)B * Lq_pad < (1ll << 31), "forward_windows: batch too large");
     hipStream_t s = (hipStream_t)stream;
     const size_t nv = (size_t)B * Lv_pad, nt = (size_t)B * Lq_pad;
-    bool caches, txt_tables;
-    padded_plan(m, Lv_pad, Lv_pad + Lq_pad, &caches, &txt_tables);
+    // what the packed forward will run on: the handle's tables, and the first-layer row caches / (--use_txt_pos) the text
+    // position rows this entry builds itself where the plan asks for them
+    FwdCall call{nullptr, nullptr, vid_len, nullptr, nullptr, txt_len, B, Lv_pad, Lq_pad, logits, spans, saliency, taps};
+    FwdPlan plan = plan_forward(m, call, nullptr, true);
     Carver c(ws, ws_bytes);
     PaddedCarve p;
-    carve_padded(m, c, B, Lv_pad, Lq_pad, caches, txt_tables, p);
+    carve_padded(m, c, B, Lv_pad, Lq_pad, plan, p);
     if (!c.ok) { set_error("forward_windows: workspace too small (%zu < %zu)", ws_bytes, c.cur); return CONE_E_WORKSPACE; }
     // compact row lists of the valid clips / tokens: offsets (= the windows' first rows), source-row indices, device counts
     RUN(launch_scan_lengths(vid_len, nullptr, B, p.voff, s));
@@ -1406,18 +1361,18 @@ extern "C" int cone_forward_windows(const cone_model* m, const float* vid, const
     RUN(launch_compact_index(vid_len, p.voff, Lv_pad, p.vidx, txt_len, p.toff, Lq_pad, p.tidx, B, s));
     RUN(project_tokens(m, 0, vid, nv, p.vp, p.pws, p.pw, s, p.vidx, p.voff + B));
     RUN(project_tokens(m, 1, txt, nt, p.tp, p.pws, p.pw, s, p.tidx, p.toff + B));
-    cone_layer0 l0{};
-    if (caches) {   // the first encoder layer's in_proj once per compact row (cone_layer0_project's kernel)
+    cone_layer0& l0 = plan.l0;
+    if (plan.mk_caches) {   // the first encoder layer's in_proj once per compact row (cone_layer0_project's kernel)
         RUN(layer0_rows(m, p.vp, (int)nv, p.voff + B, p.qv, (float*)p.pws, s));     // (scratch: the projections are done with it)
         RUN(layer0_rows(m, p.tp, (int)nt, p.toff + B, p.qt, (float*)p.pws, s));
         l0.qkv_vid = p.qv; l0.qkv_txt = p.qt;
     }
-    if (txt_tables) {   // a compact token row's index in its query = its column in the padded batch (masks are prefixes)
+    if (plan.mk_txt_pos) {   // a compact token row's index in its query = its column in the padded batch (masks are prefixes)
         RUN(text_positions(m, p.tp, nullptr, p.tidx, Lq_pad, (int)nt, p.toff + B, p.pt, p.ptqk, s));
         l0.txt_pos = p.pt; l0.txt_pos_qk = p.ptqk; l0.n_txt = (int64_t)nt;
     }
-    return forward_packed(m, p.vp, p.voff, vid_len, p.tp, p.toff, txt_len, B, Lv_pad, Lq_pad, logits, spans, saliency,
-                          taps, (char*)ws + c.cur, ws_bytes - c.cur, s, caches || txt_tables ? &l0 : nullptr);
+    call.vproj = p.vp; call.vrow0 = p.voff; call.tproj = p.tp; call.trow0 = p.toff;
+    return forward_packed(m, call, plan, (char*)ws + c.cur, ws_bytes - c.cur, s);
 }
 
 extern "C" size_t cone_clip_matching_workspace(const cone_model* m, int B) {
@@ -1473,51 +1428,42 @@ extern "C" int cone_clip_matching(const cone_model* m, const float* cls, const f
                                        (char*)ws + c.cur, ws_bytes - c.cur, stream);
 }
 
+// The options that are a field and a range: value != 0 for a switch, else inclusive bounds.
+struct OptionRow { const char* name; int cone_model::*field; int lo, hi; bool is_switch; };
+static const OptionRow OPTION_ROWS[] = {
+    {"dec_fold", &cone_model::opt_dec_fold, 0, 5, false},
+    {"l0_gather", &cone_model::opt_l0_gather, 0, 1, true},
+    {"dec0_const", &cone_model::opt_dec0_const, 0, 1, true},
+    {"pos_tables", &cone_model::opt_pos_tables, 0, 1, true},
+    {"ffn_fused", &cone_model::opt_ffn_fused, 0, 2, false},
+    {"qkv_fused", &cone_model::opt_qkv_fused, 0, 2, false},
+    // general_shape 1: a 256 / 8 handle runs the general-shape path (A/B parity only); 0: the shipped path (a handle of any
+    // other shape has only the general path, whatever the value)
+    {"general_shape", &cone_model::opt_general, 0, 1, true},
+    {"res_gather", &cone_model::opt_res_gather, 0, 1, true},
+    {"rows_chain", &cone_model::opt_chain, 0, 1, true},
+    {"ffn_spread", &cone_model::opt_spread, 0, 1, true},
+};
 extern "C" int cone_model_set_option(cone_model* m, const char* name, int value) {
     CONE_REQUIRE(m && name, "set_option: null argument");
-    if (!strcmp(name, "dec_fold")) {
-        CONE_REQUIRE(value >= 0 && value <= 5, "set_option: dec_fold %d not in [0, 5]", value);
-        m->opt_dec_fold = value;
+    for (const OptionRow& o : OPTION_ROWS) {
+        if (strcmp(name, o.name)) continue;
+        CONE_REQUIRE(o.is_switch || (value >= o.lo && value <= o.hi), "set_option: %s %d not in [%d, %d]", name, value, o.lo, o.hi);
+        m->*o.field = o.is_switch ? value != 0 : value;
         return 0;
     }
-    if (!strcmp(name, "l0_gather")) { m->opt_l0_gather = value != 0; return 0; }
-    if (!strcmp(name, "dec0_const")) { m->opt_dec0_const = value != 0; return 0; }
-    if (!strcmp(name, "pos_tables")) { m->opt_pos_tables = value != 0; return 0; }
-    if (!strcmp(name, "ffn_fused")) {
-        CONE_REQUIRE(value >= 0 && value <= 2, "set_option: ffn_fused %d not in [0, 2]", value);
-        m->opt_ffn_fused = value;
+    // the two bf16 modes need their weight images and exclude each other
+    const bool split = !strcmp(name, "split_bf16");
+    if (split || !strcmp(name, "bf16")) {
+        const char* other = split ? "bf16" : "split_bf16";
+        CONE_REQUIRE(value == 0 || (split ? m->split_img : m->bf16_img),
+                     "set_option: %s needs hidden_dim 256 with 8 heads and dim_feedforward %% 32 == 0 "
+                     "(<= 2048); this handle is hidden_dim %d with %d heads, dim_feedforward %d", name, m->d, m->heads, m->ff);
+        CONE_REQUIRE(value == 0 || !(split ? m->opt_bf16 : m->opt_split_bf16),
+                     "set_option: %s = 1 while %s = 1: the two modes exclude each other (set %s = 0 first)", name, other, other);
+        (split ? m->opt_split_bf16 : m->opt_bf16) = value != 0;
         return 0;
     }
-    if (!strcmp(name, "qkv_fused")) {
-        CONE_REQUIRE(value >= 0 && value <= 2, "set_option: qkv_fused %d not in [0, 2]", value);
-        m->opt_qkv_fused = value;
-        return 0;
-    }
-    if (!strcmp(name, "general_shape")) {
-        // 1: a 256 / 8 handle runs the general-shape path (A/B parity only); 0: the shipped path (a handle of any other shape
-        // has only the general path, whatever the value)
-        m->opt_general = value != 0;
-        return 0;
-    }
-    if (!strcmp(name, "split_bf16")) {
-        CONE_REQUIRE(value == 0 || m->split_img, "set_option: split_bf16 needs hidden_dim 256 with 8 heads and dim_feedforward %% 32 == 0 "
-                     "(<= 2048); this handle is hidden_dim %d with %d heads, dim_feedforward %d", m->d, m->heads, m->ff);
-        CONE_REQUIRE(value == 0 || !m->opt_bf16, "set_option: split_bf16 = 1 while bf16 = 1: the two modes exclude each other "
-                     "(set bf16 = 0 first)");
-        m->opt_split_bf16 = value != 0;
-        return 0;
-    }
-    if (!strcmp(name, "bf16")) {
-        CONE_REQUIRE(value == 0 || m->bf16_img, "set_option: bf16 needs hidden_dim 256 with 8 heads and dim_feedforward %% 32 == 0 "
-                     "(<= 2048); this handle is hidden_dim %d with %d heads, dim_feedforward %d", m->d, m->heads, m->ff);
-        CONE_REQUIRE(value == 0 || !m->opt_split_bf16, "set_option: bf16 = 1 while split_bf16 = 1: the two modes exclude each other "
-                     "(set split_bf16 = 0 first)");
-        m->opt_bf16 = value != 0;
-        return 0;
-    }
-    if (!strcmp(name, "res_gather")) { m->opt_res_gather = value != 0; return 0; }
-    if (!strcmp(name, "rows_chain")) { m->opt_chain = value != 0; return 0; }
-    if (!strcmp(name, "ffn_spread")) { m->opt_spread = value != 0; return 0; }
     if (!strcmp(name, "gemm")) {
         CONE_REQUIRE(value >= GEMM_AUTO && value <= GEMM_ROWS8, "set_option: gemm tile family %d not in [0, 3]", value);
         m->opt_gemm = value;
