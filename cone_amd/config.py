@@ -52,6 +52,23 @@ def check_model_shape(hidden_dim, nheads) -> None:
         raise ValueError(f"unsupported model shape hidden_dim={d} nheads={h}: supported are {SUPPORTED_SHAPES}")
 
 
+# Window length (max_v_l clips + max_q_l text tokens; WINDOW_LENGTH / --max_v_l / --max_q_l of the reference's scripts): up to
+# MAX_WINDOW_TOKENS on the fused kernels, up to MAX_LONG_WINDOW_TOKENS on the general path with the streaming attention core
+# (the handle's "max_window_tokens" option; include/cone_hip.h: CONE_MAX_WINDOW_TOKENS / CONE_MAX_LONG_WINDOW_TOKENS).
+MAX_WINDOW_TOKENS = 256
+MAX_LONG_WINDOW_TOKENS = 1024
+
+
+def window_token_limit(max_v_l, max_q_l) -> int:
+    """The "max_window_tokens" value a model built for (max_v_l, max_q_l) needs: MAX_WINDOW_TOKENS unless the two exceed it,
+    else their sum.  Raises ValueError beyond MAX_LONG_WINDOW_TOKENS -- on the host, before any GPU work."""
+    v, q = int(max_v_l or 0), int(max_q_l or 0)
+    if v + q > MAX_LONG_WINDOW_TOKENS:
+        raise ValueError(f"unsupported window length: max_v_l={v} + max_q_l={q} = {v + q} tokens per window, the library "
+                         f"runs at most {MAX_LONG_WINDOW_TOKENS}")
+    return max(v + q, MAX_WINDOW_TOKENS)
+
+
 EVAL_DEFAULTS = dict(
     nms_thd=-1.0, max_before_nms=200, max_after_nms=5, no_sort_results=False,
     eval_split_name="val", eval_modality="both", save_all=False, debug=False,

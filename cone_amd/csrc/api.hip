@@ -88,7 +88,13 @@ struct cone_model {
     // handle whose shape is not 256 / 8 (gen_native), or a 256 / 8 handle with option general_shape = 1 (A/B parity only)
     int gen_native = 0;
     int opt_general = 0;
-    bool general() const { return gen_native || opt_general; }
+    // option max_window_tokens (default CONE_MAX_WINDOW_TOKENS; up to CONE_MAX_LONG_WINDOW_TOKENS): the longest window this
+    // handle takes.  Above 256 EVERY forward of the handle runs the general path, whatever the call's own lengths, and its
+    // attention launches carry this value as their key capacity (the streaming core of general.hip) -- a window's bits
+    // depend neither on the batch it rides in nor on the entry it came through
+    int opt_max_tokens = CONE_MAX_WINDOW_TOKENS;
+    bool long_windows() const { return opt_max_tokens > CONE_MAX_WINDOW_TOKENS; }
+    bool general() const { return gen_native || opt_general || long_windows(); }
 };
 
 namespace cone {
@@ -153,7 +159,8 @@ static int build_model(const cone_weights* w, cone_model** out) {
                  "model_create: unsupported model shape hidden_dim=%d nheads=%d -- supported: hidden_dim a multiple of 64 in "
                  "[64, 512] with head_dim = hidden_dim / nheads in {16, 32, 64} (256 / 8, every shipped CONE configuration, runs "
                  "the fused kernels; other shapes the general path); also required: dim_feedforward a multiple of 128, "
-                 "num_queries <= 16, feature dims multiples of 32 up to 1024, at most 256 tokens (clips + words) per window",
+                 "num_queries <= 16, feature dims multiples of 32 up to 1024, at most 256 tokens (clips + words) per window (up to 1024 with "
+                 "option max_window_tokens)",
                  w->hidden_dim, w->nheads);
     CONE_REQUIRE(w->dim_ff % 128 == 0 && w->dim_ff >= 128, "model_create: dim_feedforward=%d must be a multiple of 128", w->dim_ff);
     CONE_REQUIRE(w->enc_layers >= 1 && w->enc_layers <= CONE_MAX_LAYERS && w->dec_layers >= 1 &&
@@ -881,7 +888,7 @@ static TailArgs tail_args(const TailWeights* w, const float* A, const float* R, 
 // ------------------------------------------------------------------------------ general-shape forward
 // Any supported (d, heads), post-norm and pre-norm (cone/transformer.py:233-260, 296-342), built from plain launches:
 // LayerNorm, row GEMMs with residual / ReLU epilogues, the attention core of general.hip (encoder self-attention over the
-// packed tokens, decoder self-attention over the slots, cross-attention to the window's memory: up to 256 keys), and the
+// packed tokens, decoder self-attention over the slots, cross-attention to the window's memory: up to 256 keys resident in LDS, up to 1024 streamed), and the
 // d-wide pack / head / saliency kernels.  What it does not fuse: the LayerNorms (own launches, no GEMM epilogue), the layer
 // tails, the decoder's memory K / V projections (two GEMMs over all layers), the first decoder layer (run per window, from
 // tgt = 0, only the slot-position tables are per-checkpoint constants) -- and it reads no layer-0 caches or position tables:
@@ -916,6 +923,9 @@ static int forward_general(const cone_model* m, const FwdCall& call, void* ws, s
     const int d = m->d, hd = m->d / m->heads, nh = m->heads, B = call.B;
     const int Lmax = call.Lv_max + call.Lq_max, Mmax = B * Lmax, T = B * m->nq, nd = m->n_dec, ff = m->ff, nq = m->nq;
     const bool pre = m->pre_norm != 0;
+    // key capacity of the attention over the window's tokens: the call's bound, or (a long-window handle) the handle's, so
+    // that the kernel form does not depend on the call
+    const int kcap = m->long_windows() ? m->opt_max_tokens : Lmax;
     Carver c(ws, ws_bytes);
     GenBuffers f;
     carve_gen(m, c, B, Lmax, f);
@@ -941,7 +951,7 @@ static int forward_general(const cone_model* m, const FwdCall& call, void* ws, s
         g.A2 = f.POS; g.lda2 = d;
         RUN(launch_gemm(g, s));
         RUN(launch_gemm(G(m, A, d, e.sa.in_w + 2 * d * d, d, e.sa.in_b + 2 * d, f.QKV + 2 * d, 3 * d, Mmax, Mdev, d, d), s));
-        RUN(launch_gen_attn(f.QKV, 3 * d, f.QKV + d, 3 * d, f.QKV + 2 * d, 3 * d, f.ATT, d, f.off, f.off, B, 0, nh, hd, Lmax, s));
+        RUN(launch_gen_attn(f.QKV, 3 * d, f.QKV + d, 3 * d, f.QKV + 2 * d, 3 * d, f.ATT, d, f.off, f.off, B, 0, nh, hd, kcap, s));
         if (pre) {
             RUN(residual(f.ATT, d, e.sa.out, f.X, f.X, Mmax, Mdev));                                      // src += attn
             RUN(launch_layernorm(f.X, d, e.n2.g, e.n2.b, f.X1, d, Mmax, Mdev, d, s));                     // src2 = norm2(src)
@@ -988,7 +998,7 @@ static int forward_general(const cone_model* m, const FwdCall& call, void* ws, s
         g.R = m->dec_ca_tab[l]; g.ldr = d; g.r_mod = nq;
         RUN(launch_gemm(g, s));
         RUN(launch_gen_attn(f.DQ, d, f.KD + (size_t)l * d, d * nd, f.VD + (size_t)l * d, d * nd, f.DATT, d, nullptr, f.off, B, nq, nh,
-                            hd, Lmax, s));
+                            hd, kcap, s));
         if (pre) {
             RUN(residual(f.DATT, d, dl.ca.out, f.TGT, f.TGT, T, nullptr));                                // tgt += ca
             RUN(ln(f.TGT, dl.n3, f.TGT1));                                                                // tgt2 = norm3(tgt)
@@ -1015,8 +1025,12 @@ static int forward_packed(const cone_model* m, const FwdCall& c, const FwdPlan& 
     const int B = c.B, Lv_max = c.Lv_max, Lq_max = c.Lq_max;
     CONE_REQUIRE(B > 0 && Lv_max > 0 && Lq_max >= 0, "forward: bad sizes B=%d Lv=%d Lq=%d", B, Lv_max, Lq_max);
     const int Lmax = Lv_max + Lq_max;
-    CONE_REQUIRE(Lmax <= CONE_MAX_WINDOW_TOKENS, "forward: window length %d + %d exceeds %d tokens", Lv_max, Lq_max,
-                 CONE_MAX_WINDOW_TOKENS);
+    if (m->long_windows())
+        CONE_REQUIRE(Lmax <= m->opt_max_tokens, "forward: window length %d + %d exceeds the handle's max_window_tokens = %d",
+                     Lv_max, Lq_max, m->opt_max_tokens);
+    else
+        CONE_REQUIRE(Lmax <= CONE_MAX_WINDOW_TOKENS, "forward: window length %d + %d exceeds %d tokens", Lv_max, Lq_max,
+                     CONE_MAX_WINDOW_TOKENS);
     // beyond 192 tokens only the default path exists (the 256-key forms of the encoder attention and of the folded cross-
     // attention): the A/B forms and the unfolded decoder stop at 192 keys (the general path: any length up to the limit)
     if (p.body != BODY_GENERAL)
@@ -1452,10 +1466,23 @@ extern "C" int cone_model_set_option(cone_model* m, const char* name, int value)
         m->*o.field = o.is_switch ? value != 0 : value;
         return 0;
     }
+    // the longest window of this handle; above CONE_MAX_WINDOW_TOKENS the handle is a general-path handle (exact fp32 only)
+    if (!strcmp(name, "max_window_tokens")) {
+        CONE_REQUIRE(value >= CONE_MAX_WINDOW_TOKENS && value <= CONE_MAX_LONG_WINDOW_TOKENS,
+                     "set_option: max_window_tokens %d not in [%d, %d]", value, CONE_MAX_WINDOW_TOKENS, CONE_MAX_LONG_WINDOW_TOKENS);
+        CONE_REQUIRE(value == CONE_MAX_WINDOW_TOKENS || !(m->opt_bf16 || m->opt_split_bf16),
+                     "set_option: max_window_tokens %d while bf16 / split_bf16 = 1: windows beyond %d tokens run in exact fp32 "
+                     "only (set the mode to 0 first)", value, CONE_MAX_WINDOW_TOKENS);
+        m->opt_max_tokens = value;
+        return 0;
+    }
     // the two bf16 modes need their weight images and exclude each other
     const bool split = !strcmp(name, "split_bf16");
     if (split || !strcmp(name, "bf16")) {
         const char* other = split ? "bf16" : "split_bf16";
+        CONE_REQUIRE(value == 0 || !m->long_windows(),
+                     "set_option: %s on a handle with max_window_tokens = %d: windows beyond %d tokens run the general path, "
+                     "exact fp32 only", name, m->opt_max_tokens, CONE_MAX_WINDOW_TOKENS);
         CONE_REQUIRE(value == 0 || (split ? m->split_img : m->bf16_img),
                      "set_option: %s needs hidden_dim 256 with 8 heads and dim_feedforward %% 32 == 0 "
                      "(<= 2048); this handle is hidden_dim %d with %d heads, dim_feedforward %d", name, m->d, m->heads, m->ff);

@@ -92,6 +92,167 @@ __global__ __launch_bounds__(256) void gen_attn_kernel(const float* __restrict__
     }
 }
 
+// ------------------------------------------------------------------------------ streaming attention core (> 256 keys)
+// The same (Q, K, V, OUT, ld*, qoff, koff, nq) addressing, for windows of up to kGenMaxStreamKeys keys, in exact fp32 on the
+// matrix cores (v_mfma_f32_16x16x4_f32) in the orientation of enc_attn16_kernel: S^T = K Q^T with the key on accumulator rows
+// (4 lg + r, lg = lane / 16) and the query on lanes (li = lane % 16), so a query's softmax is an in-register reduction plus two
+// cross-group exchanges and the score registers are directly the A operand of P V (k slot lg <-> key 4 lg + r of a 16-key tile).
+// One workgroup (four waves) per (window, head); it walks the window's queries in passes of 64 (one 16-query tile per wave) and,
+// inside a pass, the window's keys in blocks of kGenStreamBlock = 64 through LDS:
+//   K block d-major [HD][LDK], LDK = 64 + 64 / HD: lane group lg reads channel (HD / 4) lg + st, (HD / 4) LDK = 16 mod 64 banks;
+//   V block key-major [64][LDV], LDV = HD + 4: lane group lg reads key 4 lg + r, 4 LDV = 16 mod 64 banks.
+// 16.3 + 17.0 KiB at head_dim 64 (8.3 + 9.0 at 32, 4.3 + 5.0 at 16), whatever the window length: four workgroups fit a CU's LDS.
+// The next block's rows are requested into registers before the current block's MFMAs and written to LDS behind them.
+// Online softmax per query: running maximum m, running sum l (a lane's partial over its own 16 keys of every block, reduced
+// across the four lane groups once at the end), output accumulators rescaled by exp(m_old - m_new) every block; 1 / l once at
+// the end.  Rows of the last block past the window's end re-read its last row (finite) and have their scores masked to -inf
+// (probability exactly 0): no per-tile branch.  exp(-inf - (-inf)) cannot arise: the subtrahend is 0 while the maximum is -inf.
+// The decomposition and the block order depend on the window's own lengths only: a window's bits do not depend on the batch
+// or on kcap.  A window with no query or no key writes nothing.
+constexpr int kGenMaxStreamKeys = 1024;
+constexpr int kGenStreamBlock = 64;
+
+typedef float gen_f32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ float gen_lane_read(float v, int src_lane) {
+    return __int_as_float(__builtin_amdgcn_ds_bpermute(src_lane << 2, __float_as_int(v)));
+}
+
+template <int HD>
+__global__ __launch_bounds__(256) void gen_attn_stream_kernel(const float* __restrict__ Q, int ldq, const float* __restrict__ K,
+                                                              int ldk, const float* __restrict__ V, int ldv,
+                                                              float* __restrict__ OUT, int ldo, const int* __restrict__ qoff,
+                                                              const int* __restrict__ koff, int nq, int kcap, float scale) {
+    constexpr int KB = kGenStreamBlock, LDK = KB + 64 / HD, LDV = HD + 4;
+    constexpr int CS = HD / 4;              // channel steps of S^T: lane group lg owns channels CS lg .. CS lg + CS - 1
+    constexpr int DT = HD / 16;             // 16-channel output tiles
+    constexpr int NLD = HD / 16;            // float4 rows per thread and operand of one block (64 HD / 4 float4 over 256 threads)
+    __shared__ float KsT[HD * LDK];
+    __shared__ __attribute__((aligned(16))) float Vs[KB * LDV];
+    const int b = blockIdx.x, h = blockIdx.y;
+    const int q0 = qoff ? qoff[b] : b * nq, nqr = qoff ? qoff[b + 1] - q0 : nq;
+    const int k0 = koff ? koff[b] : b * nq, nk = koff ? koff[b + 1] - k0 : nq;
+    if (nqr <= 0 || nk <= 0 || nk > kcap) return;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int li = lane & 15, lg = lane >> 4;
+    const int nblk = (nk + KB - 1) / KB;
+    const float* Kb = K + (size_t)k0 * ldk + h * HD;
+    const float* Vb = V + (size_t)k0 * ldv + h * HD;
+    gen_f32x4 kreg[NLD], vreg[NLD];
+    auto load_block = [&](int blk) {        // rows past the window's end: its last row (masked below)
+#pragma unroll
+        for (int it = 0; it < NLD; ++it) {
+            const int idx = tid + 256 * it;
+            const int row = min(blk * KB + idx / CS, nk - 1), c4 = (idx % CS) * 4;
+            kreg[it] = *reinterpret_cast<const gen_f32x4*>(Kb + (size_t)row * ldk + c4);
+            vreg[it] = *reinterpret_cast<const gen_f32x4*>(Vb + (size_t)row * ldv + c4);
+        }
+    };
+    auto store_block = [&]() {
+#pragma unroll
+        for (int it = 0; it < NLD; ++it) {
+            const int idx = tid + 256 * it;
+            const int key = idx / CS, c4 = (idx % CS) * 4;
+            float* kd = KsT + c4 * LDK + key;
+            kd[0] = kreg[it][0]; kd[LDK] = kreg[it][1]; kd[2 * LDK] = kreg[it][2]; kd[3 * LDK] = kreg[it][3];
+            *reinterpret_cast<gen_f32x4*>(Vs + key * LDV + c4) = vreg[it];
+        }
+    };
+    for (int qp = 0; qp < nqr; qp += 64) {              // (workgroup-uniform: every wave meets every barrier)
+        const int qt = qp + 16 * wave;
+        const bool active = qt < nqr;                   // wave-uniform
+        float qv[CS];
+        {
+            const float* qr = Q + (size_t)(q0 + min(qt + li, nqr - 1)) * ldq + h * HD + CS * lg;
+#pragma unroll
+            for (int u = 0; u < CS / 4; ++u) {
+                const gen_f32x4 x = reinterpret_cast<const gen_f32x4*>(qr)[u];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) qv[4 * u + j] = x[j] * scale;
+            }
+        }
+        float m = -INFINITY, l = 0.f;
+        gen_f32x4 o[DT];
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) o[dt] = gen_f32x4{0.f, 0.f, 0.f, 0.f};
+        load_block(0);
+        for (int blk = 0; blk < nblk; ++blk) {
+            __syncthreads();                            // the previous block's reads are done
+            store_block();
+            __syncthreads();
+            if (blk + 1 < nblk) load_block(blk + 1);    // in flight under this block's MFMAs
+            if (!active) continue;
+            gen_f32x4 sc[4];
+#pragma unroll
+            for (int kt = 0; kt < 4; ++kt) sc[kt] = gen_f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int st = 0; st < CS; ++st) {
+                const float* kp = KsT + (CS * lg + st) * LDK + li;
+#pragma unroll
+                for (int kt = 0; kt < 4; ++kt) sc[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(kp[16 * kt], qv[st], sc[kt], 0, 0, 0);
+            }
+            // sc[kt][r] = score of key blk KB + 16 kt + 4 lg + r against query li
+            const int lim = nk - blk * KB - 4 * lg;     // that key is real iff 16 kt + r < lim
+            if ((blk + 1) * KB > nk) {
+#pragma unroll
+                for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) sc[kt][r] = 16 * kt + r < lim ? sc[kt][r] : -INFINITY;
+            }
+            float bm = -INFINITY;
+#pragma unroll
+            for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) bm = fmaxf(bm, sc[kt][r]);
+            bm = fmaxf(bm, gen_lane_read(bm, lane ^ 16));
+            bm = fmaxf(bm, gen_lane_read(bm, lane ^ 32));
+            const float mn = fmaxf(m, bm);
+            const float ms = mn == -INFINITY ? 0.f : mn;    // (a block with no real key: every exponential below is exp(-inf) = 0)
+            const float alpha = expf(m - ms);
+            m = mn;
+            float ps = 0.f;
+#pragma unroll
+            for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    sc[kt][r] = expf(sc[kt][r] - ms);
+                    ps += sc[kt][r];
+                }
+            l = fmaf(l, alpha, ps);
+            // o[dt][r] = output row (query) 4 lg + r: its rescale factor sits in the lanes whose li is that row
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float a = gen_lane_read(alpha, (lane & 48) + 4 * lg + r);
+#pragma unroll
+                for (int dt = 0; dt < DT; ++dt) o[dt][r] *= a;
+            }
+#pragma unroll
+            for (int kt = 0; kt < 4; ++kt) {
+                const float* vp = Vs + (16 * kt + 4 * lg) * LDV + li;
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+#pragma unroll
+                    for (int dt = 0; dt < DT; ++dt)
+                        o[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(sc[kt][r], vp[r * LDV + 16 * dt], o[dt], 0, 0, 0);
+            }
+        }
+        if (!active) continue;
+        l += gen_lane_read(l, lane ^ 16);
+        l += gen_lane_read(l, lane ^ 32);
+        const float inv = 1.0f / l;
+        float* ob = OUT + (size_t)(q0 + qt + 4 * lg) * ldo + h * HD + li;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float s = gen_lane_read(inv, (lane & 48) + 4 * lg + r);
+            if (qt + 4 * lg + r < nqr) {
+#pragma unroll
+                for (int dt = 0; dt < DT; ++dt) ob[(size_t)r * ldo + 16 * dt] = o[dt][r] * s;
+            }
+        }
+    }
+}
+
 bool gen_shape_supported(int d, int heads) {
     if (d < 64 || d > 512 || d % 64 != 0 || heads < 1 || d % heads != 0) return false;
     const int hd = d / heads;
@@ -103,10 +264,22 @@ static size_t gen_attn_lds(int hd, int kcap) { return (size_t)kcap * (2 * hd + 1
 int launch_gen_attn(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* OUT, int ldo,
                     const int* qoff, const int* koff, int B, int nq, int heads, int hd, int kcap, hipStream_t s) {
     CONE_REQUIRE(hd == 16 || hd == 32 || hd == 64, "attention: head_dim %d not in {16, 32, 64}", hd);
-    CONE_REQUIRE(kcap >= 1 && kcap <= kGenMaxKeys, "attention: %d keys not in [1, %d]", kcap, kGenMaxKeys);
+    CONE_REQUIRE(kcap >= 1 && kcap <= kGenMaxStreamKeys, "attention: %d keys not in [1, %d]", kcap, kGenMaxStreamKeys);
     CONE_REQUIRE(koff || kcap >= nq, "attention: slot keys need kcap >= nq");
     CONE_REQUIRE((ldq | ldk | ldv) % 4 == 0 && Q && K && V && OUT && heads >= 1, "attention: bad operands");
     if (B <= 0) return 0;
+    const float scale = (float)(1.0 / sqrt((double)hd));
+    const dim3 grid((unsigned)B, (unsigned)heads);
+    if (kcap > kGenMaxKeys) {   // the streaming core: static LDS, the same for every window length
+        if (hd == 16)
+            hipLaunchKernelGGL(gen_attn_stream_kernel<16>, grid, dim3(256), 0, s, Q, ldq, K, ldk, V, ldv, OUT, ldo, qoff, koff, nq, kcap, scale);
+        else if (hd == 32)
+            hipLaunchKernelGGL(gen_attn_stream_kernel<32>, grid, dim3(256), 0, s, Q, ldq, K, ldk, V, ldv, OUT, ldo, qoff, koff, nq, kcap, scale);
+        else
+            hipLaunchKernelGGL(gen_attn_stream_kernel<64>, grid, dim3(256), 0, s, Q, ldq, K, ldk, V, ldv, OUT, ldo, qoff, koff, nq, kcap, scale);
+        CONE_LAUNCH_CHECK();
+        return 0;
+    }
     static DeviceOnce once;     // the opt-in to > 64 KiB of LDS (head_dim 64, 256 keys: 129 KiB), once per device
     CONE_CHECK_HIP(device_once(once, [] {
         hipError_t rc = hipFuncSetAttribute((const void*)gen_attn_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -119,8 +292,6 @@ int launch_gen_attn(const float* Q, int ldq, const float* K, int ldk, const floa
                                      (int)gen_attn_lds(64, kGenMaxKeys));
         return rc;
     }));
-    const float scale = (float)(1.0 / sqrt((double)hd));
-    const dim3 grid((unsigned)B, (unsigned)heads);
     const size_t lds = gen_attn_lds(hd, kcap);
     if (hd == 16)
         hipLaunchKernelGGL(gen_attn_kernel<16>, grid, dim3(256), lds, s, Q, ldq, K, ldk, V, ldv, OUT, ldo, qoff, koff, nq, kcap, scale);

@@ -528,7 +528,7 @@ def project_video(model, store: FeatureStore, row_range=None, ws=None):
     r0, r1 = row_range if row_range is not None else (0, int(store.vid_raw.shape[0]))
     vproj = model.project(0, store.motion_rows(r0, r1), ws=ws)   # the MOTION source (normalised when it is a second one)
     out = dict(vproj=vproj, vid_base=r0)
-    if getattr(store.opt, "layer0_cache", True):
+    if getattr(store.opt, "layer0_cache", True) and not getattr(model, "long_windows", False):
         out["l0_vid"] = model.layer0_rows(vproj, ws=ws)      # (the position tables are the model handle's own)
     return out
 
@@ -542,7 +542,7 @@ def project_text(model, store: FeatureStore, ws=None):
         tok = ops.l2_normalize(tok, 1e-5)                                   # dataloader :277-278 (normalize_t)
     tproj = model.project(1, tok, ws=ws)
     out = dict(tproj=tproj)
-    if getattr(store.opt, "layer0_cache", True):
+    if getattr(store.opt, "layer0_cache", True) and not getattr(model, "long_windows", False):
         out["l0_txt"] = model.layer0_rows(tproj, ws=ws)
         if getattr(model, "txt_pos_tables", False):     # --use_txt_pos: the tokens' own position rows, once per token as well
             out["txt_pos"], out["txt_pos_qk"] = model.text_positions(tproj, store.index_tensors()["tok_idx"])

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .config import check_model_shape
+from .config import MAX_WINDOW_TOKENS, check_model_shape, window_token_limit
 from .synth import state_dict_spec
 
 import os as _os
@@ -88,6 +88,10 @@ class CONE:
 
     def load_state_dict(self, state_dict, strict: bool = True):
         """Accepts the reference checkpoint's ``ckpt["model"]`` unchanged (cone/inference.py:525-527)."""
+        # windows of more than 256 tokens (max_v_l + max_q_l of build_model's args, as in the reference): the handle's
+        # "max_window_tokens" option; more than the library runs fails here, before any GPU work
+        a = self.args
+        self.max_window_tokens = window_token_limit(getattr(a, "max_v_l", 0), getattr(a, "max_q_l", 0))
         lib = _lib.load()
         if not torch.cuda.is_available():
             raise _lib.ConeHipError("cone_amd needs a GPU: there is no CPU execution path")
@@ -121,6 +125,8 @@ class CONE:
         # ABI 8: the handle's position tables cover windows of up to max_v_l clips (build_model's own parameter, cone/model.py:
         # 468-486); an args object without it gets the 255-clip tables.  Longer windows than that still run (general path)
         w.table_max_v_l = min(int(getattr(a, "max_v_l", 0) or 0), 255)
+        if self.long_windows:       # a general-path handle reads no tables: the smallest there is, never one beyond 255 clips
+            w.table_max_v_l = 1
         p = lambda k: sd[k].data_ptr()
 
         def lin(dst, prefix):
@@ -169,7 +175,15 @@ class CONE:
         torch.cuda.synchronize()
         _lib.check(lib.cone_model_create(C.byref(w), C.byref(h)))
         self._handle = h
+        if self.long_windows:
+            self.set_option("max_window_tokens", self.max_window_tokens)
         return self
+
+    @property
+    def long_windows(self) -> bool:
+        """Built for windows of more than 256 tokens: every forward runs the general path (streaming attention core); no
+        layer-0 caches or position tables are built or read."""
+        return int(getattr(self, "max_window_tokens", MAX_WINDOW_TOKENS)) > MAX_WINDOW_TOKENS
 
     def __del__(self):
         try:
@@ -351,6 +365,8 @@ class CONE:
         """cone_layer0 for forward_packed: the per-row q|k|v caches.  The static position tables are the handle's own
         (built at cone_model_create, ABI 6); ``pos_tables()`` builds caller-owned ones (parity tests).  ``tok_index``: see
         ``text_positions`` -- a --use_txt_pos model needs it to take the table path."""
+        if self.long_windows:       # a long-window handle runs the general path: nothing to cache
+            return None
         l0 = dict(qkv_vid=self.layer0_rows(vproj), qkv_txt=self.layer0_rows(tproj), max_v_l=max_v_l)
         if self.txt_pos_tables and tok_index is not None:
             l0["txt_pos"], l0["txt_pos_qk"] = self.text_positions(tproj, tok_index)

@@ -41,7 +41,11 @@ extern "C" {
 #define CONE_MAX_LAYERS 8
 #define CONE_MAX_PROJ 3
 #define CONE_TABLE_MAX_V_L 255 /* longest window (clips) the handle's own position tables cover */
-#define CONE_MAX_WINDOW_TOKENS 256 /* clips + text tokens of one window (WINDOW_LENGTH + max_q_l of the reference's scripts) */
+#define CONE_MAX_WINDOW_TOKENS 256 /* clips + text tokens of one window (WINDOW_LENGTH + max_q_l of the reference's scripts): the
+                                    * limit of a handle as created, and of the fused kernels (position tables, layer-0 caches,
+                                    * fused tails, folded cross-attention) */
+#define CONE_MAX_LONG_WINDOW_TOKENS 1024 /* the limit a handle can be raised to (cone_model_set_option "max_window_tokens"): such a
+                                          * handle runs every forward on the general path with the streaming attention core */
 
 typedef struct cone_model cone_model;
 
@@ -215,7 +219,8 @@ typedef struct {
  * projection, padding is never projected -- the projections and the first encoder layer's q | k | v rows run once per compact
  * row (device-side row counts), and the windows enter the packed forward below as (row0, len) pairs with those row caches:
  * the SAME launches as the eval driver's arena path (gathering first layer, the handle's position tables, fused layer tails,
- * folded decoder cross-attention), the same bits for the same windows.  Lv_pad + Lq_pad <= CONE_MAX_WINDOW_TOKENS.
+ * folded decoder cross-attention), the same bits for the same windows.  Lv_pad + Lq_pad <= CONE_MAX_WINDOW_TOKENS, or the
+ * handle's "max_window_tokens" option where that was raised (then both entries are the general path, still one path).
  * Outputs: logits (B,Nq,2), spans (B,Nq,2) = sigmoid(center,width), saliency (B,Lv_pad; may be NULL: the
  * saliency head is then skipped -- cone/inference.py computes and never reads it, :54-59; likewise the heads and
  * decoder.norm of the intermediate decoder layers run only when taps ask for hs / aux_logits / aux_spans)
@@ -447,6 +452,14 @@ int64_t cone_prof_collect(double* out, int64_t max_rec);
  *   rows of a few windows) runs as four launches over single-wave workgroups (ffn_wide.hip, fs_*_kernel) instead of one CU
  *   per 16 rows walking the whole block, and a row GEMM of at most 1 024 rows without a LayerNorm epilogue as one wave per
  *   16 x 16 output tile; 0 = the wide form / the workgroup-per-16-rows form.  Bit-identical.
+ * "max_window_tokens" (default 256 = CONE_MAX_WINDOW_TOKENS; 256 .. 1024 = CONE_MAX_LONG_WINDOW_TOKENS, anything else is an
+ *   error): the longest window (clips + text tokens) the handle's forwards accept; one token more is rejected by name.  A
+ *   handle left at 256 is unchanged in every respect.  Above 256 the handle is a general-path handle: EVERY forward, through
+ *   either entry and whatever the call's own Lv_max + Lq_max, runs the general launch sequence (x + pos materialised; no
+ *   position tables, layer-0 caches or fused-path forms are read, and the fused path's A/B options are ignored as on a handle
+ *   of another shape than 256 / 8) with the streaming attention core (general.hip: gen_attn_stream_kernel) for the encoder
+ *   self-attention and the decoder cross-attention, so that a window's bits depend neither on its batch nor on the entry.
+ *   Exact fp32 only: "bf16" / "split_bf16" = 1 are refused on such a handle, and raising the option is refused while one is on.
  * "gemm" (default 0 = by shape): tile family of every dense layer: 1 = register-staged 128x128 / 64x256 tiles,
  *   2 / 3 = 128x256 row-owning LDS-DMA tile with 4 waves x 32 rows (32x32x2) / 8 waves x 16 rows (16x16x4) -- all
  *   exact-fp32 fma chains per output element that walk k in different orders. */
@@ -521,7 +534,9 @@ int cone_test_layernorm(const float* x, const float* g, const float* b, float* o
  * (window b, head).  Query rows qoff[b] .. qoff[b + 1] of Q (qoff == NULL: the nq rows b * nq ..), key / value rows koff[b] ..
  * koff[b + 1] of K / V (koff == NULL: b * nq ..); head h reads / writes columns h * head_dim ..  OUT = softmax(q k^T /
  * sqrt(head_dim)) v per query row, ahead of out_proj; a window without queries or keys writes nothing.  kcap >= the longest key
- * count, <= 256 (CONE_MAX_WINDOW_TOKENS). */
+ * count, <= 1024 (CONE_MAX_LONG_WINDOW_TOKENS).  kcap <= 256 (CONE_MAX_WINDOW_TOKENS): the LDS-resident kernel (all keys and
+ * values of the window staged once, lane-per-key fma chains); kcap > 256: the streaming kernel (64-key blocks through LDS,
+ * online softmax, fp32 matrix cores), whose result for a window depends neither on kcap nor on the other windows of the call. */
 int cone_test_gen_attn(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* OUT, int ldo,
                        const int32_t* qoff, const int32_t* koff, int B, int nq, int heads, int head_dim, int kcap, void* stream);
 
