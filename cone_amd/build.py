@@ -25,7 +25,8 @@ NO_CONTRACT = {"window_ops.hip", "postproc.hip", "metrics.hip", "criterion.hip",
 
 
 def _deps_mtime():
-    hdrs = [os.path.join(CSRC, "common.h"), os.path.join(HERE, "..", "include", "cone_hip.h"), __file__]
+    hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    hdrs += [os.path.join(HERE, "..", "include", "cone_hip.h"), __file__]
     return max(os.path.getmtime(h) for h in hdrs)
 
 

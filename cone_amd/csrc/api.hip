@@ -124,16 +124,10 @@ static void free_model(cone_model* m) {
 
 // One numeric mode's weight images of every layer tail (13 MB split_bf16 / 4.4 MB bf16 at ff = 1024; opt-in paths), one
 // allocation: the encoder layers' q | k | v projections (768 x 256), then per layer (encoder, decoder) [Wo image | FFN image].
-struct TailImageMode {
-    size_t (*proj_bytes)(); size_t (*ffn_bytes)(int); size_t (*rows_bytes)(int);
-    int (*pack)(const float*, const float*, int, void*, hipStream_t);
-};
-static const TailImageMode TAIL_IMAGE_MODES[TAIL_IMG_MODES] = {
-    {ffn_split_proj_image_bytes, ffn_split_image_bytes, rows256_split_image_bytes, launch_ffn_split_pack},
-    {ffn_bf16_proj_image_bytes, ffn_bf16_image_bytes, rows256_bf16_image_bytes, launch_ffn_bf16_pack}};
+static const TailMode* const TAIL_MODES[TAIL_IMG_MODES] = {&TAIL_MODE_SPLIT, &TAIL_MODE_BF16};
 static int build_tail_images(cone_model* m, int mode, char** img) {
-    const TailImageMode& k = TAIL_IMAGE_MODES[mode];
-    const size_t per = k.proj_bytes() + k.ffn_bytes(m->ff), qkv = k.rows_bytes(768);
+    const TailMode& k = *TAIL_MODES[mode];
+    const size_t per = k.proj_image_bytes() + k.ffn_image_bytes(m->ff), qkv = k.rows_image_bytes(768);
     if (hipMalloc((void**)img, per * (size_t)(m->n_enc + m->n_dec) + qkv * (size_t)m->n_enc) != hipSuccess) {
         set_error("model_create: building the split-bf16 / bf16 weight images failed");
         return CONE_E_HIP;
@@ -146,8 +140,8 @@ static int build_tail_images(cone_model* m, int mode, char** img) {
     for (int i = 0; i < m->n_enc + m->n_dec; ++i, ip += per) {
         TailWeights& t = i < m->n_enc ? m->enc_tail[i] : m->dec_tail[i - m->n_enc];
         if (int rc = k.pack(t.Wo, nullptr, 256, ip, nullptr)) return rc;
-        if (int rc = k.pack(t.W1, t.W2, m->ff, ip + k.proj_bytes(), nullptr)) return rc;
-        t.img[mode].wo = ip; t.img[mode].ffn = ip + k.proj_bytes();
+        if (int rc = k.pack(t.W1, t.W2, m->ff, ip + k.proj_image_bytes(), nullptr)) return rc;
+        t.img[mode].wo = ip; t.img[mode].ffn = ip + k.proj_image_bytes();
     }
     return 0;
 }
@@ -321,7 +315,7 @@ static int build_model(const cone_weights* w, cone_model** out) {
         const DecLayer& dl = m->dec[l];
         m->dec_tail[l] = m->pre_norm ? tail(dl.ca.out, dl.l1, dl.l2, dl.n3, m->dec_norm) : tail(dl.ca.out, dl.l1, dl.l2, dl.n2, dl.n3);
     }
-    if (!m->gen_native && ffn_split_supported(m->ff)) {
+    if (!m->gen_native && TAIL_MODES[TAIL_IMG_SPLIT]->ffn_supported(m->ff)) {
         int rc = build_tail_images(m, TAIL_IMG_SPLIT, &m->split_img);
         if (rc == 0) rc = build_tail_images(m, TAIL_IMG_BF16, &m->bf16_img);
         if (rc == 0 && hipDeviceSynchronize() != hipSuccess) {
@@ -446,10 +440,10 @@ static int encoder_qkv(const cone_model* m, int l, const float* X, float* QKV, i
                        bool split_ok) {
     const TailWeights& t = m->enc_tail[l];
     const int d = m->d;
-    if (m->opt_bf16 && m->bf16_img && !m->general())
-        return launch_rows256_bf16(X, 256, t.img[TAIL_IMG_BF16].qkv, t.qb, QKV, 768, M, M_dev, 768, s);
-    if (split_ok && l > 0 && m->opt_split_bf16 && m->split_img)
-        return launch_rows256_split(X, 256, t.img[TAIL_IMG_SPLIT].qkv, t.qb, QKV, 768, M, M_dev, 768, s);
+    const int mode = m->opt_bf16 && m->bf16_img && !m->general()               ? TAIL_IMG_BF16
+                     : split_ok && l > 0 && m->opt_split_bf16 && m->split_img ? TAIL_IMG_SPLIT
+                                                                               : -1;
+    if (mode >= 0) return TAIL_MODES[mode]->rows256(X, 256, t.img[mode].qkv, t.qb, QKV, 768, M, M_dev, 768, s);
     return launch_gemm(G(m, X, d, t.Wq, d, t.qb, QKV, 3 * d, M, M_dev, 3 * d, d), s);
 }
 
@@ -818,13 +812,13 @@ static int forward_packed_prenorm(const cone_model* m, const FwdCall& c, const F
 //
 //   t.pre (the fused pre-norm path; plan_forward admits it only with ffn_fused = 2 and an ff the fused kernels take;
 //   split_bf16 is not consulted; no ride)
-//     1  bf16                                                     launch_proj_ffn_bf16_prenorm
+//     1  bf16                                                     TAIL_MODES[TAIL_IMG_BF16]->proj_ffn_prenorm
 //     2  ffn_spread, scratch, <= 64 row groups, ff % 256 == 0     launch_proj_ffn_spread (pre)
 //     3  ffn_spread, <= 768 row groups, ff the wide form takes    launch_proj_ffn_prenorm_wide (ffn_spread = 0 switches it off too)
 //     4  otherwise                                                launch_proj_ffn_prenorm (persistent 128-row kernel)
 //   post-norm with ffn_fused = 2, an ff the fused kernels take and no x + pos second output wanted (t.C2 == null)
-//     5  bf16                                                     launch_proj_ffn_bf16; rides if qkv_fused >= 1 and it fits the LDS
-//     6  split_bf16                                               launch_proj_ffn_split; rides likewise
+//     5  bf16                                                     TAIL_MODES[TAIL_IMG_BF16]->proj_ffn; rides if qkv_fused >= 1 and it fits the LDS
+//     6  split_bf16                                               TAIL_MODES[TAIL_IMG_SPLIT]->proj_ffn; rides likewise
 //     7  exact fp32, ride offered, qkv_fused = 2, fits the LDS    launch_proj_ffn_fused with the ride (persistent 128-row kernel)
 //     8  exact fp32, ffn_spread, scratch, <= 64 row groups, ...   launch_proj_ffn_spread
 //     9  exact fp32 otherwise                                     launch_proj_ffn_fused: wide form (<= 768 row groups), 64-row
@@ -847,7 +841,7 @@ static int launch_layer_tail(const cone_model* m, const FwdBuffers& f, TailArgs 
     t.scratch = f.SPR;
     *rode = false;
     if (t.pre) {
-        if (bf16) return launch_proj_ffn_bf16_prenorm(t, s);
+        if (bf16) return TAIL_MODES[TAIL_IMG_BF16]->proj_ffn_prenorm(t, s);
         if (spread) return launch_proj_ffn_spread(t, s);
         if (m->opt_spread && (t.M + 15) / 16 <= 768 && ffn_wide_supported(ff)) return launch_proj_ffn_prenorm_wide(t, s);
         return launch_proj_ffn_prenorm(t, s);
@@ -855,9 +849,10 @@ static int launch_layer_tail(const cone_model* m, const FwdBuffers& f, TailArgs 
     const bool block_fused = !t.C2 && m->opt_ffn_fused && ffn_fused_supported(ff);
     if (block_fused && m->opt_ffn_fused >= 2) {
         if (bf16 || split) {
-            *rode = next && m->opt_qkv_fused && (bf16 ? ffn_bf16_qkv_fits(ff, t.n_qkv) : ffn_split_qkv_fits(ff, t.n_qkv));
+            const TailMode& k = *TAIL_MODES[bf16 ? TAIL_IMG_BF16 : TAIL_IMG_SPLIT];
+            *rode = next && m->opt_qkv_fused && k.qkv_fits(ff, t.n_qkv);
             if (*rode) t.next = next;
-            return bf16 ? launch_proj_ffn_bf16(t, s) : launch_proj_ffn_split(t, s);
+            return k.proj_ffn(t, s);
         }
         // (the ride on the exact-fp32 kernel: measured neutral against the separate GEMM launch -- 44.3 vs 44.1 ms of kernel
         // time per step -- so only on request: qkv_fused = 2)
@@ -1539,47 +1534,51 @@ extern "C" int cone_test_proj_ffn_spread(const float* A, const float* Wo, const 
     t.scratch = (float*)scratch;
     return launch_proj_ffn_spread(t, (hipStream_t)stream);
 }
-extern "C" size_t cone_test_ffn_split_image_bytes(int ff) { return ffn_split_supported(ff) ? ffn_split_image_bytes(ff) : 0; }
+// pack: CONE_TEST_SINGLE_PIECE selects the single-piece form (ffn_bf16.hip), which packs only with CONE_TEST_PACK; the split
+// form packs with any non-zero value
+static int test_tail_mode(int pack, bool* do_pack) {
+    const bool single = pack & CONE_TEST_SINGLE_PIECE;
+    *do_pack = single ? pack & CONE_TEST_PACK : pack;
+    return single ? TAIL_IMG_BF16 : TAIL_IMG_SPLIT;
+}
+extern "C" size_t cone_test_ffn_split_image_bytes(int ff) {
+    const TailMode& k = *TAIL_MODES[TAIL_IMG_SPLIT];
+    return k.ffn_supported(ff) ? k.ffn_image_bytes(ff) : 0;
+}
 extern "C" int cone_test_ffn_split(const float* X, const float* W1, const float* b1, const float* W2, const float* b2,
                                    const float* ln_g, const float* ln_b, float* OUT, int M, int ff, void* img, int pack,
                                    void* stream) {
-    if (pack & CONE_TEST_SINGLE_PIECE) {     // the single-piece form (ffn_bf16.hip)
-        if (pack & CONE_TEST_PACK) {
-            const int rc = launch_ffn_bf16_pack(W1, W2, ff, img, (hipStream_t)stream);
-            if (rc) return rc;
-        }
-        return launch_ffn_bf16(X, 256, img, b1, b2, ln_g, ln_b, OUT, 256, M, nullptr, ff, (hipStream_t)stream);
-    }
-    if (pack) {
-        const int rc = launch_ffn_split_pack(W1, W2, ff, img, (hipStream_t)stream);
+    bool do_pack;
+    const TailMode& k = *TAIL_MODES[test_tail_mode(pack, &do_pack)];
+    if (do_pack) {
+        const int rc = k.pack(W1, W2, ff, img, (hipStream_t)stream);
         if (rc) return rc;
     }
-    return launch_ffn_split(X, 256, img, b1, b2, ln_g, ln_b, OUT, 256, M, nullptr, ff, (hipStream_t)stream);
+    return k.ffn(X, 256, img, b1, b2, ln_g, ln_b, OUT, 256, M, nullptr, ff, (hipStream_t)stream);
 }
-extern "C" size_t cone_test_rows_split_image_bytes(int N) { return rows256_split_supported(N) ? rows256_split_image_bytes(N) : 0; }
+extern "C" size_t cone_test_rows_split_image_bytes(int N) {
+    const TailMode& k = *TAIL_MODES[TAIL_IMG_SPLIT];
+    return k.rows_supported(N) ? k.rows_image_bytes(N) : 0;
+}
 extern "C" int cone_test_rows_split(const float* X, const float* W, const float* bias, float* C, int M, int N, void* img,
                                     int pack, void* stream) {
-    if (pack & CONE_TEST_SINGLE_PIECE) {     // the single-piece form
-        if (pack & CONE_TEST_PACK) {
-            const int rc = launch_ffn_bf16_pack(W, nullptr, N, img, (hipStream_t)stream);
-            if (rc) return rc;
-        }
-        return launch_rows256_bf16(X, 256, img, bias, C, N, M, nullptr, N, (hipStream_t)stream);
-    }
-    if (pack) {
-        const int rc = launch_ffn_split_pack(W, nullptr, N, img, (hipStream_t)stream);
+    bool do_pack;
+    const TailMode& k = *TAIL_MODES[test_tail_mode(pack, &do_pack)];
+    if (do_pack) {
+        const int rc = k.pack(W, nullptr, N, img, (hipStream_t)stream);
         if (rc) return rc;
     }
-    return launch_rows256_split(X, 256, img, bias, C, N, M, nullptr, N, (hipStream_t)stream);
+    return k.rows256(X, 256, img, bias, C, N, M, nullptr, N, (hipStream_t)stream);
 }
-extern "C" size_t cone_test_proj_split_image_bytes(void) { return ffn_split_proj_image_bytes(); }
+extern "C" size_t cone_test_proj_split_image_bytes(void) { return TAIL_MODES[TAIL_IMG_SPLIT]->proj_image_bytes(); }
 extern "C" int cone_test_proj_ffn_split(const float* A, const float* Wo, const float* bo, const float* R, const float* pg,
                                         const float* pb, const float* W1, const float* b1, const float* W2,
                                         const float* b2, const float* ln_g, const float* ln_b, float* OUT, int M, int ff,
                                         void* img, void* wo_img, int pack, void* stream) {
-    const bool single = pack & CONE_TEST_SINGLE_PIECE;     // the single-piece form (ffn_bf16.hip)
-    const TailImageMode& k = TAIL_IMAGE_MODES[single ? TAIL_IMG_BF16 : TAIL_IMG_SPLIT];
-    if (single ? pack & CONE_TEST_PACK : pack) {
+    bool do_pack;
+    const int mode = test_tail_mode(pack, &do_pack);
+    const TailMode& k = *TAIL_MODES[mode];
+    if (do_pack) {
         int rc = k.pack(W1, W2, ff, img, (hipStream_t)stream);
         if (rc) return rc;
         rc = k.pack(Wo, nullptr, 256, wo_img, (hipStream_t)stream);
@@ -1587,8 +1586,8 @@ extern "C" int cone_test_proj_ffn_split(const float* A, const float* Wo, const f
     }
     TailWeights w;
     const TailArgs t = test_tail(&w, A, Wo, bo, R, pg, pb, W1, b1, W2, b2, ln_g, ln_b, OUT, M, ff);
-    w.img[single ? TAIL_IMG_BF16 : TAIL_IMG_SPLIT] = TailImages{wo_img, img, nullptr};
-    return single ? launch_proj_ffn_bf16(t, (hipStream_t)stream) : launch_proj_ffn_split(t, (hipStream_t)stream);
+    w.img[mode] = TailImages{wo_img, img, nullptr};
+    return k.proj_ffn(t, (hipStream_t)stream);
 }
 extern "C" int cone_test_enc_attn(int mode, const float* QKV, const float* qkv_vid, const float* qkv_txt,
                                   const float* pos_qk, const int32_t* vrow0, const int32_t* vlen, const int32_t* trow0,

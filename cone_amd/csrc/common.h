@@ -192,43 +192,34 @@ int launch_ffn_wide(const float* X, int ldx, const float* W1, const float* b1, c
                     const float* ln_g, const float* ln_b, float* OUT, int ldo, int M, const int* M_dev, int ff, hipStream_t s,
                     int m_off = 0);
 
-// ---------------------------------------------------------------- the same on the bf16 matrix cores (ffn_split.hip)
-// fp32 products as six partial products of three-piece bf16 operands, fp32 accumulation: fp32-MFMA accuracy (measured),
-// 2.7x its rate.  Wimg = the layer's W1 / W2 split and laid out once by launch_ffn_split_pack
-// (ffn_split_image_bytes(ff) bytes).
-bool ffn_split_supported(int ff);
-size_t ffn_split_image_bytes(int ff);
-int launch_ffn_split_pack(const float* W1, const float* W2, int ff, void* img, hipStream_t s);
-int launch_ffn_split(const float* X, int ldx, const void* Wimg, const float* b1, const float* b2, const float* ln_g,
-                     const float* ln_b, float* OUT, int ldo, int M, const int* M_dev, int ff, hipStream_t s);
-// C (M, N) = X (M, 256) W^T + bias on the same split operands; Wimg = launch_ffn_split_pack(W, nullptr, N, ...)
-bool rows256_split_supported(int N);
-size_t rows256_split_image_bytes(int N);
-int launch_rows256_split(const float* X, int ldx, const void* Wimg, const float* bias, float* C, int ldc, int M,
-                         const int* M_dev, int N, hipStream_t s);
-// launch_proj_ffn_fused's computation on img[TAIL_IMG_SPLIT]: wo = launch_ffn_split_pack(Wo, nullptr, 256, ...)
-// (ffn_split_proj_image_bytes()), ffn as above, the ride's qkv = launch_ffn_split_pack(Wq, nullptr, n_qkv, ...)
-size_t ffn_split_proj_image_bytes();
-bool ffn_split_qkv_fits(int ff, int n_qkv);
-int launch_proj_ffn_split(const TailArgs& t, hipStream_t s);
-
-// ---------------------------------------------------------------- the single-piece form (ffn_bf16.hip)
-// The same kernels with every GEMM operand rounded ONCE to bf16 and one MFMA per operand pair (fp32 accumulation; bias,
-// ReLU, residual -- the unrounded fp32 input -- and LayerNorm in fp32): plain bf16 matrix arithmetic, NOT fp32-accurate.
-// Images (img[TAIL_IMG_BF16]) hold the high piece only (one third of the three-piece images), built by launch_ffn_bf16_pack.
-bool ffn_bf16_supported(int ff);
-size_t ffn_bf16_image_bytes(int ff);
-int launch_ffn_bf16_pack(const float* W1, const float* W2, int ff, void* img, hipStream_t s);
-int launch_ffn_bf16(const float* X, int ldx, const void* Wimg, const float* b1, const float* b2, const float* ln_g,
-                    const float* ln_b, float* OUT, int ldo, int M, const int* M_dev, int ff, hipStream_t s);
-bool rows256_bf16_supported(int N);
-size_t rows256_bf16_image_bytes(int N);
-int launch_rows256_bf16(const float* X, int ldx, const void* Wimg, const float* bias, float* C, int ldc, int M,
-                        const int* M_dev, int N, hipStream_t s);
-size_t ffn_bf16_proj_image_bytes();
-bool ffn_bf16_qkv_fits(int ff, int n_qkv);
-int launch_proj_ffn_bf16(const TailArgs& t, hipStream_t s);
-int launch_proj_ffn_bf16_prenorm(const TailArgs& t, hipStream_t s);    // the --pre_norm form
+// ---------------------------------------------------------------- the same on the bf16 matrix cores
+// Two numeric modes, one interface each (TAIL_MODES[TAIL_IMG_*] in api.hip; the code of both: tail_bf16_common.h):
+//   TAIL_IMG_SPLIT (ffn_split.hip): fp32 products as six partial products of three-piece bf16 operands, fp32 accumulation:
+//                  fp32-MFMA accuracy (measured), 2.7x its rate;
+//   TAIL_IMG_BF16  (ffn_bf16.hip): every GEMM operand rounded ONCE to bf16 and one MFMA per operand pair (fp32 accumulation;
+//                  bias, ReLU, residual -- the unrounded fp32 input -- and LayerNorm in fp32): plain bf16 matrix arithmetic,
+//                  NOT fp32-accurate.  Its images hold the high piece only (one third of the three-piece images).
+struct TailMode {
+    bool (*ffn_supported)(int ff);
+    size_t (*ffn_image_bytes)(int ff);
+    // the layer's W1 / W2 (W2 == null: any (N = ff, 256) weight of a 256-channel product) laid out once for the kernels
+    int (*pack)(const float* W1, const float* W2, int ff, void* img, hipStream_t s);
+    // launch_ffn_fused's computation; Wimg = pack(W1, W2, ff) (ffn_image_bytes(ff) bytes)
+    int (*ffn)(const float* X, int ldx, const void* Wimg, const float* b1, const float* b2, const float* ln_g, const float* ln_b,
+               float* OUT, int ldo, int M, const int* M_dev, int ff, hipStream_t s);
+    // C (M, N) = X (M, 256) W^T + bias on the same operands; Wimg = pack(W, nullptr, N) (rows_image_bytes(N) bytes)
+    bool (*rows_supported)(int N);
+    size_t (*rows_image_bytes)(int N);
+    int (*rows256)(const float* X, int ldx, const void* Wimg, const float* bias, float* C, int ldc, int M, const int* M_dev, int N,
+                   hipStream_t s);
+    // launch_proj_ffn_fused's computation on t.w->img[mode]: wo = pack(Wo, nullptr, 256) (proj_image_bytes()), ffn as
+    // above, the ride's qkv = pack(Wq, nullptr, n_qkv)
+    size_t (*proj_image_bytes)();
+    bool (*qkv_fits)(int ff, int n_qkv);
+    int (*proj_ffn)(const TailArgs& t, hipStream_t s);
+    int (*proj_ffn_prenorm)(const TailArgs& t, hipStream_t s);     // the --pre_norm form; null: the mode has none
+};
+extern const TailMode TAIL_MODE_SPLIT, TAIL_MODE_BF16;
 
 // ---------------------------------------------------------------- row kernels (rowops.hip)
 int launch_layernorm(const float* x, int ldx, const float* g, const float* b, float* out, int ldo,
