@@ -144,6 +144,8 @@ _SIGNATURES = {
                                  C.c_int, C.c_int, C.c_void_p]),
     "cone_test_ffn": (C.c_int, [C.c_void_p] * 8 + [C.c_int, C.c_int, C.c_void_p]),
     "cone_test_proj_ffn": (C.c_int, [C.c_void_p] * 13 + [C.c_int, C.c_int, C.c_void_p]),
+    "cone_test_tail_form": (C.c_int, [C.c_void_p] * 13 + [C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                                               C.c_void_p, C.c_void_p]),
     "cone_test_proj_ffn_spread_scratch_bytes": (C.c_size_t, [C.c_int]),
     "cone_test_proj_ffn_spread": (C.c_int, [C.c_void_p] * 13 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cone_test_ffn_split_image_bytes": (C.c_size_t, [C.c_int]),

@@ -814,14 +814,14 @@ static int forward_packed_prenorm(const cone_model* m, const FwdCall& c, const F
 //   split_bf16 is not consulted; no ride)
 //     1  bf16                                                     TAIL_MODES[TAIL_IMG_BF16]->proj_ffn_prenorm
 //     2  ffn_spread, scratch, <= 64 row groups, ff % 256 == 0     launch_proj_ffn_spread (pre)
-//     3  ffn_spread, <= 768 row groups, ff the wide form takes    launch_proj_ffn_prenorm_wide (ffn_spread = 0 switches it off too)
+//     3  ffn_spread, <= FFN_WIDE_GROUPS row groups, a wide ff     launch_proj_ffn_prenorm_wide (ffn_spread = 0 switches it off too)
 //     4  otherwise                                                launch_proj_ffn_prenorm (persistent 128-row kernel)
 //   post-norm with ffn_fused = 2, an ff the fused kernels take and no x + pos second output wanted (t.C2 == null)
 //     5  bf16                                                     TAIL_MODES[TAIL_IMG_BF16]->proj_ffn; rides if qkv_fused >= 1 and it fits the LDS
 //     6  split_bf16                                               TAIL_MODES[TAIL_IMG_SPLIT]->proj_ffn; rides likewise
 //     7  exact fp32, ride offered, qkv_fused = 2, fits the LDS    launch_proj_ffn_fused with the ride (persistent 128-row kernel)
 //     8  exact fp32, ffn_spread, scratch, <= 64 row groups, ...   launch_proj_ffn_spread
-//     9  exact fp32 otherwise                                     launch_proj_ffn_fused: wide form (<= 768 row groups), 64-row
+//     9  exact fp32 otherwise                                     launch_proj_ffn_fused: wide form (<= FFN_WIDE_GROUPS), 64-row
 //                                                                 form, 128-row form + wide remainder -- chosen INSIDE it (ffn.hip)
 //   post-norm otherwise (ffn_fused = 1 / 0, an ff the fused kernels do not take, or t.C2: the encoder off the table path,
 //   whose next layer reads x + pos -- only the GEMM epilogue writes that)
@@ -843,7 +843,7 @@ static int launch_layer_tail(const cone_model* m, const FwdBuffers& f, TailArgs 
     if (t.pre) {
         if (bf16) return TAIL_MODES[TAIL_IMG_BF16]->proj_ffn_prenorm(t, s);
         if (spread) return launch_proj_ffn_spread(t, s);
-        if (m->opt_spread && (t.M + 15) / 16 <= 768 && ffn_wide_supported(ff)) return launch_proj_ffn_prenorm_wide(t, s);
+        if (m->opt_spread && (t.M + 15) / 16 <= FFN_WIDE_GROUPS && ffn_wide_supported(ff)) return launch_proj_ffn_prenorm_wide(t, s);
         return launch_proj_ffn_prenorm(t, s);
     }
     const bool block_fused = !t.C2 && m->opt_ffn_fused && ffn_fused_supported(ff);
@@ -1533,6 +1533,16 @@ extern "C" int cone_test_proj_ffn_spread(const float* A, const float* Wo, const 
     TailArgs t = test_tail(&w, A, Wo, bo, R, pg, pb, W1, b1, W2, b2, ln_g, ln_b, OUT, M, ff);
     t.scratch = (float*)scratch;
     return launch_proj_ffn_spread(t, (hipStream_t)stream);
+}
+extern "C" int cone_test_tail_form(const float* A, const float* Wo, const float* bo, const float* R, const float* pg,
+                                   const float* pb, const float* W1, const float* b1, const float* W2, const float* b2,
+                                   const float* ln_g, const float* ln_b, float* OUT, int M, int ff, const int32_t* r_idx,
+                                   const float* R2, const int32_t* M_dev, int pre, float* OUT2, int form, int n_cu, void* scratch,
+                                   void* stream) {
+    TailWeights w;
+    TailArgs t = test_tail(&w, A, Wo, bo, R, pg, pb, W1, b1, W2, b2, ln_g, ln_b, OUT, M, ff);
+    t.r_idx = r_idx; t.R2 = R2; t.M_dev = M_dev; t.pre = pre != 0; t.OUT2 = OUT2; t.ldo2 = 256; t.scratch = (float*)scratch;
+    return launch_tail_f32_form(t, form, n_cu, (hipStream_t)stream);
 }
 // pack: CONE_TEST_SINGLE_PIECE selects the single-piece form (ffn_bf16.hip), which packs only with CONE_TEST_PACK; the split
 // form packs with any non-zero value

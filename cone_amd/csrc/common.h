@@ -163,7 +163,8 @@ struct TailArgs {
     float* C2; const float* ADD;          // != null: a second output C2 = OUT + ADD, which only the unfused GEMM epilogue writes
 };
 
-// ---------------------------------------------------------------- fused feed-forward block (ffn.hip)
+// ---------------------------------------------------------------- the exact-fp32 layer tail (ffn.hip, ffn_wide.hip)
+// What api.hip calls; what the two files share is in tail_f32_common.h.
 // OUT = LayerNorm(X + W2 relu(W1 X + b1) + b2): X, OUT (M, 256); W1 (ff, 256); W2 (256, ff).  OUT may alias nothing
 // the kernel reads (X is re-read as the residual from registers only, but other workgroups read other rows).
 bool ffn_fused_supported(int ff);
@@ -176,21 +177,23 @@ int launch_ffn_fused(const float* X, int ldx, const float* W1, const float* b1, 
 int launch_proj_ffn_fused(const TailArgs& t, hipStream_t s);
 int launch_proj_ffn_prenorm(const TailArgs& t, hipStream_t s);     // the pre-norm tail, persistent 128-row kernel only
 bool ffn_fused_qkv_fits(int ff, int n_qkv);
-
-// ---------------------------------------------------------------- wide form for a few row groups (ffn_wide.hip)
-// The same two computations with ONE workgroup per 16 rows whose eight waves split the output elements (projection and
-// GEMM2 by output channels, GEMM1 by hidden units): every element's fma chain is ffn.hip's, results are bit-identical.
+// The wide form (ffn_wide.hip): ONE workgroup per 16 rows whose eight waves split the output elements (projection and GEMM2
+// by output channels, GEMM1 by hidden units): every element's fma chain is ffn.hip's, results are bit-identical.  Launches of
+// at most FFN_WIDE_GROUPS 16-row groups (host bound) take it: 45 - 60 us per round of 256 groups against 160 - 200 us of a
+// wave's serial pass over the weights.  tools/tail_wide_bench.py, out_proj + LN + FFN: 52 / 62 / 124 / 183 us at 16 / 4 096 /
+// 8 192 / 12 288 rows against 168 / 181 / 187 / 194 us; from the fourth round on (12 500 rows: 226 us) the row forms win.
+#ifndef CONE_FFN_WIDE_GROUPS
+#define CONE_FFN_WIDE_GROUPS 768
+#endif
+constexpr int FFN_WIDE_GROUPS = CONE_FFN_WIDE_GROUPS;
 bool ffn_wide_supported(int ff);
+int launch_proj_ffn_prenorm_wide(const TailArgs& t, hipStream_t s);
 // the spread form of the projecting tail for <= 64 row groups (ffn_wide.hip): 4 launches over single-wave workgroups, same bits
 size_t ffn_spread_scratch_floats(int ff);
 bool ffn_spread_supported(int M, int ff);
 int launch_proj_ffn_spread(const TailArgs& t, hipStream_t s);      // post-norm and pre-norm (t.pre)
-int launch_proj_ffn_prenorm_wide(const TailArgs& t, hipStream_t s);
-int launch_proj_ffn_wide(const TailArgs& t, hipStream_t s);
-// m_off: the rows are rows m_off .. m_off + M of a larger job whose device-side row count is *M_dev
-int launch_ffn_wide(const float* X, int ldx, const float* W1, const float* b1, const float* W2, const float* b2,
-                    const float* ln_g, const float* ln_b, float* OUT, int ldo, int M, const int* M_dev, int ff, hipStream_t s,
-                    int m_off = 0);
+// test hook (cone_test_tail_form): the projecting tail in the forced form CONE_TAIL_FORM_*
+int launch_tail_f32_form(const TailArgs& t, int form, int n_cu, hipStream_t s);
 
 // ---------------------------------------------------------------- the same on the bf16 matrix cores
 // Two numeric modes, one interface each (TAIL_MODES[TAIL_IMG_*] in api.hip; the code of both: tail_bf16_common.h):

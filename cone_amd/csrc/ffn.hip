@@ -35,67 +35,20 @@
 // keep the matrix pipe fed; GEMM1 of chunk i and GEMM2 of chunk i-1 share the units of one iteration (software
 // pipelining across chunks), so bias + ReLU never stall a chunk; the epilogue is bias + residual + LayerNorm in
 // registers (a token's 256 channels sit in 4 lanes x 64 registers, two shuffle steps per moment).
+//
+// What this kernel must do exactly as the wide and spread kernels of ffn_wide.hip do (the same bits for a row in every form)
+// is in tail_f32_common.h: the slab primitives, the register LayerNorm and its apply, the gathered residual row, the clamped
+// load row, the row count, the kernel-argument layout, the host fill and the argument checks.  This file keeps the ring, the
+// MFMA schedule (FFN_CHUNK32: the projection's and the q | k | v ride's chunk), the row-kernel launchers and the form ladder.
 #include <mutex>
 
-#include "common.h"
+#include "tail_f32_common.h"
 
 namespace cone {
-
-typedef float f32x4f __attribute__((ext_vector_type(4)));
-
-#define FFN_GLDS16(src, dst) \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src), \
-                                     (__attribute__((address_space(3))) void*)(dst), 16, 0, 0)
-
-__device__ __forceinline__ int ffn_swz16(int row) { return (0x1230 >> (((row >> 2) & 3) * 4)) & 3; }
 
 constexpr int FFN_STAGE = 2 * 16 * 256;           // floats per ring stage: W1 image (16 slabs) + W2 image (16 slabs)
 constexpr int FFN_NST = 4;                        // ring depth: a stage is refilled two barriers after its last read
 // 1-KiB LDS-DMA pieces per wave per chunk: 32 pieces / NW waves (NW = 8: 4, NW = 4: 8)
-
-struct FfnArgs {
-    const float* X; int ldx;                      // (M, 256) block input = residual of the feed-forward block
-    const float* W1; const float* b1;             // (ff, 256), (ff)
-    const float* W2; const float* b2;             // (256, ff), (256)
-    const float* ln_g; const float* ln_b;         // (256)
-    float* OUT; int ldo;                          // (M, 256)
-    int M; const int* M_dev;                      // rows; *M_dev wins when non-null (grid sized by M)
-    int ff;
-    // PROJ: the block input is itself  LayerNorm(R + A Wo^T + bo)  (attention output projection + residual + norm,
-    // cone/transformer.py:239-241, 308-312), computed here instead of being read: A (M, 256) attention output,
-    // R (M, 256) residual; X is unused.
-    const float* A; int lda; const float* R; int ldr;
-    const float* Wo; const float* bo; const float* pg; const float* pb;
-    // r_idx != null: the residual rows are gathered: row i = R[r_idx[i]] (r_idx[i] >= 0) or R2[~r_idx[i]]
-    const int* r_idx; const float* R2;
-    // QKV: the NEXT layer's q | k | v projection of the rows this kernel produces (Wq (n_qkv, 256), qb), computed from the
-    // registers that hold them and written to QKV (M, n_qkv): no second pass over the rows, no extra launch
-    const float* Wq; const float* qb; float* QKV; int ldq; int n_qkv;
-    // PRE (pre-norm layers, cone/transformer.py:248-260 / 319-342; PROJ only): OUT = x1 + W2 relu(W1 LN_p(x1) + b1) + b2 with
-    // x1 = R + A Wo^T + bo -- the residual stream stays un-normalised, (pg, pb) is the norm AHEAD of the feed-forward block --
-    // and OUT2 (may be null) = LayerNorm(OUT; ln_g, ln_b): what the next consumer reads (the next layer's norm1, the
-    // encoder's / decoder's final norm)
-    float* OUT2; int ldo2;
-};
-
-// LayerNorm over a token's 256 channels held as v[16] (channel 16 t + 4 lg + r in v[t][r]): 4 lanes x 64 registers.
-__device__ __forceinline__ void ffn_layernorm_regs(f32x4f (&v)[16], float& rstd) {
-    float s1 = 0.f;
-#pragma unroll
-    for (int t = 0; t < 16; ++t) s1 += (v[t][0] + v[t][1]) + (v[t][2] + v[t][3]);
-    s1 += __shfl_xor(s1, 16, 64);
-    s1 += __shfl_xor(s1, 32, 64);
-    const float mean = s1 * (1.0f / 256.0f);
-    float s2 = 0.f;
-#pragma unroll
-    for (int t = 0; t < 16; ++t) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { v[t][r] -= mean; s2 = fmaf(v[t][r], v[t][r], s2); }
-    }
-    s2 += __shfl_xor(s2, 16, 64);
-    s2 += __shfl_xor(s2, 32, 64);
-    rstd = 1.0f / sqrtf(s2 * (1.0f / 256.0f) + 1e-5f);
-}
 
 // NW = waves per workgroup = 16-row groups per tile.  NW = 8 (128-row tiles, two waves per SIMD) is the throughput form.
 // NW = 4 (64-row tiles, ONE wave per SIMD) is the small-M form: a wave runs the very same instruction sequence on its 16
@@ -107,8 +60,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ffn_fused_kernel(FfnArgs p) {
     constexpr int FFN_ROWS = 16 * NW, FFN_NPIECE = 32 / NW, NT = 64 * NW, HW = NW / 2;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* b1s = smem + FFN_NST * FFN_STAGE;
-    int M = p.M;
-    if (p.M_dev) { const int md = *p.M_dev; M = md < M ? md : M; }
+    TF_LAUNCH_ROWS(M, p, 0)
     // Work items of the persistent loop: full tiles of FFN_ROWS rows, walked round-robin over the grid -- except that the
     // tiles of the LAST round, when they would occupy at most half of the workgroups, are cut into half tiles of 64 rows
     // (waves 0-3; waves 4-7 idle through the item): twice as many CUs finish the ragged end of a launch in 0.18 ms instead of
@@ -141,21 +93,21 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ffn_fused_kernel(FfnArgs p) {
     // (PROJ) bo, pg, pb -- no ordinary global load remains inside the tile loop besides the tile's own rows
     float* prm = b1s + ff;
     for (int i = tid; i < (ff >> 2); i += NT)
-        reinterpret_cast<f32x4f*>(b1s)[i] = reinterpret_cast<const f32x4f*>(p.b1)[i];
+        reinterpret_cast<f32x4*>(b1s)[i] = reinterpret_cast<const f32x4*>(p.b1)[i];
     if (tid < 64) {
-        reinterpret_cast<f32x4f*>(prm)[tid] = reinterpret_cast<const f32x4f*>(p.b2)[tid];
-        reinterpret_cast<f32x4f*>(prm + 256)[tid] = reinterpret_cast<const f32x4f*>(p.ln_g)[tid];
-        reinterpret_cast<f32x4f*>(prm + 512)[tid] = reinterpret_cast<const f32x4f*>(p.ln_b)[tid];
+        reinterpret_cast<f32x4*>(prm)[tid] = reinterpret_cast<const f32x4*>(p.b2)[tid];
+        reinterpret_cast<f32x4*>(prm + 256)[tid] = reinterpret_cast<const f32x4*>(p.ln_g)[tid];
+        reinterpret_cast<f32x4*>(prm + 512)[tid] = reinterpret_cast<const f32x4*>(p.ln_b)[tid];
         if (PROJ) {
-            reinterpret_cast<f32x4f*>(prm + 768)[tid] = reinterpret_cast<const f32x4f*>(p.bo)[tid];
-            reinterpret_cast<f32x4f*>(prm + 1024)[tid] = reinterpret_cast<const f32x4f*>(p.pg)[tid];
-            reinterpret_cast<f32x4f*>(prm + 1280)[tid] = reinterpret_cast<const f32x4f*>(p.pb)[tid];
+            reinterpret_cast<f32x4*>(prm + 768)[tid] = reinterpret_cast<const f32x4*>(p.bo)[tid];
+            reinterpret_cast<f32x4*>(prm + 1024)[tid] = reinterpret_cast<const f32x4*>(p.pg)[tid];
+            reinterpret_cast<f32x4*>(prm + 1280)[tid] = reinterpret_cast<const f32x4*>(p.pb)[tid];
         }
     }
     float* qbs = prm + 1536;
     if (QKV)
         for (int i = tid; i < (p.n_qkv >> 2); i += NT)
-            reinterpret_cast<f32x4f*>(qbs)[i] = reinterpret_cast<const f32x4f*>(p.qb)[i];
+            reinterpret_cast<f32x4*>(qbs)[i] = reinterpret_cast<const f32x4*>(p.qb)[i];
 
     // ---- LDS-DMA pieces.  A feed-forward chunk = 32 slabs of [16 rows][16 floats]; wave w issues slabs 4w .. 4w+3
     // (0-15 = W1, 16-31 = W2); lane -> (row = lane / 4, physical chunk = lane % 4), the source chunk is XOR-swizzled.
@@ -165,7 +117,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ffn_fused_kernel(FfnArgs p) {
     // Addressing: all four pieces of a wave lie on one side (waves 0-3: W1 slabs 4w .. 4w+3, waves 4-7: W2 slabs), so a
     // piece's source is a wave-uniform base (SGPRs) + ONE per-lane offset + scalar multiples of the piece / chunk index.
     const int drow = lane >> 2;
-    const int dch = (lane & 3) ^ ffn_swz16(drow);
+    const int dch = (lane & 3) ^ tf_swz16(drow);
     const bool w2side = wave >= HW;
     const float* fbase = w2side ? p.W2 : p.W1;                         // wave-uniform
     const int foff = w2side ? (16 * FFN_NPIECE * (wave - HW) + drow) * ff + 4 * dch   // W2[16 t + row][h0 + 4 ch ..], t = NPIECE (w - HW) + i
@@ -193,11 +145,11 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ffn_fused_kernel(FfnArgs p) {
                : (pj ? p.Wo + ((size_t)gg * (32 * 256) + 16 * i) : fbase + ((size_t)(gg - NP) * fchunk + (size_t)i * fpiece)));
         const unsigned vo = (unsigned)((pj ? poff : foff) * 4);
         asm volatile("" : "+s"(ub));
-        FFN_GLDS16(ub + vo, dstp);
+        TF_GLDS16(ub + vo, dstp);
     };
 
-    const int rd = li * 16 + ((lg ^ ffn_swz16(li)) << 2);          // this lane's 16-B chunk inside a slab
-#define FFN_RD(stg, off) (*reinterpret_cast<const f32x4f*>((stg) + (off) + rd))
+    const int rd = li * 16 + ((lg ^ tf_swz16(li)) << 2);          // this lane's 16-B chunk inside a slab
+#define FFN_RD(stg, off) (*reinterpret_cast<const f32x4*>((stg) + (off) + rd))
 #define FFN_STAGE_OF(g) (smem + ((sb + (g)) % FFN_NST) * FFN_STAGE)
 #define FFN_SB() __builtin_amdgcn_sched_barrier(0)
     // unit u of a chunk (8 units) issues the wave's share of the next-but-one chunk: every other unit at 4 pieces per wave,
@@ -244,6 +196,36 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ffn_fused_kernel(FfnArgs p) {
         }                                                                             \
     }
 
+    // One chunk of 32 output channels in the projection's slab format (pair g of the output projection, a chunk of the q | k | v
+    // ride) against the register tile B: declares st and ha / hb = two partial chains for each of the chunk's two 16-channel
+    // tiles -- with both tiles interleaved, four MFMAs apart; fully unrolled: B[] is indexed statically
+#define FFN_CHUNK32(gi, B)                                                                                                 \
+    const float* st = FFN_STAGE_OF(gi);                                                                                    \
+    f32x4 ha[2], hb[2];                                                                                                    \
+    ha[0] = f32x4{0.f, 0.f, 0.f, 0.f}; hb[0] = ha[0];                                                                      \
+    ha[1] = ha[0]; hb[1] = ha[0];                                                                                          \
+    wa = FFN_RD(st, 0); wb = FFN_RD(st, 256); va = FFN_RD(st, 4096); vb = FFN_RD(st, 4096 + 256);                          \
+    _Pragma("unroll") for (int u = 0; u < 8; ++u) {                                                                        \
+        FFN_SB();                                                                                                          \
+        asm volatile("" : "+v"(wa), "+v"(wb), "+v"(va), "+v"(vb));                                                         \
+        FFN_SB();                                                                                                          \
+        if (u < 7) {                                                                                                       \
+            na = FFN_RD(st, (2 * u + 2) * 256); nb = FFN_RD(st, (2 * u + 3) * 256);                                        \
+            nva = FFN_RD(st, 4096 + (2 * u + 2) * 256); nvb = FFN_RD(st, 4096 + (2 * u + 3) * 256);                        \
+        }                                                                                                                  \
+        FFN_SB();                                                                                                          \
+        _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                                                    \
+            FFN_MFMA(ha[r & 1], wa[r], B[2 * u][r])                                                                        \
+            FFN_MFMA(hb[r & 1], va[r], B[2 * u][r])                                                                        \
+        }                                                                                                                  \
+        _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                                                    \
+            FFN_MFMA(ha[r & 1], wb[r], B[2 * u + 1][r])                                                                    \
+            FFN_MFMA(hb[r & 1], vb[r], B[2 * u + 1][r])                                                                    \
+        }                                                                                                                  \
+        FFN_STREAM((gi) + 2, u)                 /* the next-but-one chunk's pieces ride behind MFMAs */                    \
+        if (u < 7) { wa = na; wb = nb; va = nva; vb = nvb; }                                                               \
+    }
+
 #pragma unroll
     for (int i = 0; i < FFN_NPIECE; ++i) stream_piece(0, i);
 #pragma unroll
@@ -254,8 +236,8 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ffn_fused_kernel(FfnArgs p) {
     // where hipcc puts its lgkmcnt wait -- BEFORE the next reads are issued, so it never covers a read that was only
     // just issued) after them: LDS latency hides under 512 matrix-pipe cycles.  Loop bodies are straight-line code: the
     // ring is refilled unconditionally (the last iterations re-stream the final chunk into stages nobody reads again).
-    f32x4f wa, wb, na, nb;      // W1-format fragments (current / next unit)
-    f32x4f va, vb, nva, nvb;    // second-half fragments
+    f32x4 wa, wb, na, nb;      // W1-format fragments (current / next unit)
+    f32x4 va, vb, nva, nvb;    // second-half fragments
 
     // Persistent workgroup: one per CU, walking tiles blockIdx.x, + gridDim.x, ...  A tile's fixed costs -- its
     // input rows (16 KiB per wave, 64-B row segments per load), the output stores, the dispatch of a fresh workgroup --
@@ -266,19 +248,19 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ffn_fused_kernel(FfnArgs p) {
     // the residual of the block (PROJ: starts as the residual of the projection, becomes the block input); ar (PROJ) =
     // attention rows, B operand of the projection.  The NEXT tile's rows are requested from the epilogue, ahead of
     // this tile's stores (vmcnt retires in order: loads queued behind stores would wait for the stores' acks).
-    f32x4f xr[16];
-    f32x4f ar[PROJ ? 16 : 1];
+    f32x4 xr[16];
+    f32x4 ar[PROJ ? 16 : 1];
     auto load_tile = [&](int tile) {
         const int row = wave_row0(tile) + li;
-        const size_t ld_row = (size_t)(row < M ? row : M - 1);         // rows past M feed unstored outputs
+        const size_t ld_row = TF_LD_ROW(row, M);
         if (PROJ) {     // the attention rows; the residual rows follow at the top of the tile (load_res)
             const float* ap = p.A + ld_row * p.lda + 4 * lg;
 #pragma unroll
-            for (int q = 0; q < 16; ++q) ar[q] = *reinterpret_cast<const f32x4f*>(ap + 16 * q);
+            for (int q = 0; q < 16; ++q) ar[q] = *reinterpret_cast<const f32x4*>(ap + 16 * q);
         } else {
             const float* xp = p.X + ld_row * p.ldx + 4 * lg;
 #pragma unroll
-            for (int q = 0; q < 16; ++q) xr[q] = *reinterpret_cast<const f32x4f*>(xp + 16 * q);
+            for (int q = 0; q < 16; ++q) xr[q] = *reinterpret_cast<const f32x4*>(xp + 16 * q);
         }
     };
     // PROJ: the residual rows of a tile are requested at its top and consumed at the end of each projection chunk (they
@@ -286,14 +268,10 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ffn_fused_kernel(FfnArgs p) {
     // tiles live together
     auto load_res = [&](int tile) {
         const int row = wave_row0(tile) + li;
-        const size_t ld_row = (size_t)(row < M ? row : M - 1);
-        const float* rp = p.R + ld_row * p.ldr + 4 * lg;
-        if (p.r_idx) {
-            const int ix = p.r_idx[ld_row];
-            rp = (ix >= 0 ? p.R + (size_t)ix * p.ldr : p.R2 + (size_t)(~ix) * p.ldr) + 4 * lg;
-        }
+        const size_t ld_row = TF_LD_ROW(row, M);
+        TF_RES_ROW(rp, p, ld_row, 4 * lg)
 #pragma unroll
-        for (int q = 0; q < 16; ++q) xr[q] = *reinterpret_cast<const f32x4f*>(rp + 16 * q);
+        for (int q = 0; q < 16; ++q) xr[q] = *reinterpret_cast<const f32x4*>(rp + 16 * q);
     };
     load_tile(blockIdx.x);
     bool first = true;
@@ -319,62 +297,29 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ffn_fused_kernel(FfnArgs p) {
         break;
     }
 
-    f32x4f y[16];
+    f32x4 y[16];
     if (PROJ) {
         load_res(tile);
         // ---- attention output projection + residual + LayerNorm: pair g computes channels [32 g, 32 g + 32) of
         // A Wo^T and adds them to xr[2 g], xr[2 g + 1] (the residual rows); fully unrolled: xr[] is indexed statically
 #pragma unroll
         for (int g = 0; g < NP; ++g) {
-            const float* st = FFN_STAGE_OF(g);
-            f32x4f ha[2], hb[2];        // two partial chains per tile: with both tiles interleaved, four MFMAs apart
-            ha[0] = f32x4f{0.f, 0.f, 0.f, 0.f}; hb[0] = ha[0];
-            ha[1] = ha[0]; hb[1] = ha[0];
-            wa = FFN_RD(st, 0); wb = FFN_RD(st, 256); va = FFN_RD(st, 4096); vb = FFN_RD(st, 4096 + 256);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                FFN_SB();
-                asm volatile("" : "+v"(wa), "+v"(wb), "+v"(va), "+v"(vb));
-                FFN_SB();
-                if (u < 7) {
-                    na = FFN_RD(st, (2 * u + 2) * 256); nb = FFN_RD(st, (2 * u + 3) * 256);
-                    nva = FFN_RD(st, 4096 + (2 * u + 2) * 256); nvb = FFN_RD(st, 4096 + (2 * u + 3) * 256);
-                }
-                FFN_SB();
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    FFN_MFMA(ha[r & 1], wa[r], ar[2 * u][r])
-                    FFN_MFMA(hb[r & 1], va[r], ar[2 * u][r])
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    FFN_MFMA(ha[r & 1], wb[r], ar[2 * u + 1][r])
-                    FFN_MFMA(hb[r & 1], vb[r], ar[2 * u + 1][r])
-                }
-                FFN_STREAM(g + 2, u)                               // the next-but-one chunk's pieces ride behind MFMAs
-                if (u < 7) { wa = na; wb = nb; va = nva; vb = nvb; }
-            }
+            FFN_CHUNK32(g, ar)
             xr[2 * g] += ha[0] + ha[1];
             xr[2 * g + 1] += hb[0] + hb[1];
             FFN_END_CHUNK()
         }
         FFN_SB();
 #pragma unroll
-        for (int t = 0; t < 16; ++t) xr[t] += *reinterpret_cast<const f32x4f*>(prm + 768 + 16 * t + 4 * lg);       // + bo
+        for (int t = 0; t < 16; ++t) xr[t] += *reinterpret_cast<const f32x4*>(prm + 768 + 16 * t + 4 * lg);       // + bo
         if (PRE) {      // the un-normalised stream x1 is the block's residual: the output accumulators START from x1 + b2
                         // (no second copy of the tile in registers), then xr becomes the normalised block input
 #pragma unroll
-            for (int t = 0; t < 16; ++t) y[t] = xr[t] + *reinterpret_cast<const f32x4f*>(prm + 16 * t + 4 * lg);
+            for (int t = 0; t < 16; ++t) y[t] = xr[t] + *reinterpret_cast<const f32x4*>(prm + 16 * t + 4 * lg);
         }
         float rstd;
-        ffn_layernorm_regs(xr, rstd);
-#pragma unroll
-        for (int t = 0; t < 16; ++t) {
-            const f32x4f g4 = *reinterpret_cast<const f32x4f*>(prm + 1024 + 16 * t + 4 * lg);
-            const f32x4f b4 = *reinterpret_cast<const f32x4f*>(prm + 1280 + 16 * t + 4 * lg);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) xr[t][r] = xr[t][r] * rstd * g4[r] + b4[r];
-        }
+        tf_layernorm_regs(xr, rstd);
+        TF_LN_APPLY(xr, rstd, prm + 1024, prm + 1280)
         FFN_SB();
     }
 
@@ -383,13 +328,13 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ffn_fused_kernel(FfnArgs p) {
     // units, so the GEMM1 -> bias/ReLU -> GEMM2 dependency spans a whole iteration instead of stalling every chunk.
     if (!PRE) {
 #pragma unroll
-        for (int t = 0; t < 16; ++t) y[t] = f32x4f{0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < 16; ++t) y[t] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    f32x4f h, hp[4];
+    f32x4 h, hp[4];
     {   // iteration 0: GEMM1 of chunk 0 alone
         const float* st = FFN_STAGE_OF(NP);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) hp[r] = f32x4f{0.f, 0.f, 0.f, 0.f};
+        for (int r = 0; r < 4; ++r) hp[r] = f32x4{0.f, 0.f, 0.f, 0.f};
         wa = FFN_RD(st, 0); wb = FFN_RD(st, 256);
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
@@ -404,7 +349,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ffn_fused_kernel(FfnArgs p) {
             if (u < 7) { wa = na; wb = nb; }
         }
         FFN_SB();
-        h = (hp[0] + hp[1]) + (hp[2] + hp[3]) + *reinterpret_cast<const f32x4f*>(b1s + 4 * lg);
+        h = (hp[0] + hp[1]) + (hp[2] + hp[3]) + *reinterpret_cast<const f32x4*>(b1s + 4 * lg);
 #pragma unroll
         for (int r = 0; r < 4; ++r) h[r] = fmaxf(h[r], 0.f);
         FFN_END_CHUNK()
@@ -413,7 +358,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ffn_fused_kernel(FfnArgs p) {
         const float* s1 = FFN_STAGE_OF(NP + i);             // W1 half: chunk i
         const float* s2 = FFN_STAGE_OF(NP + i - 1);         // W2 half: chunk i - 1
 #pragma unroll
-        for (int r = 0; r < 4; ++r) hp[r] = f32x4f{0.f, 0.f, 0.f, 0.f};
+        for (int r = 0; r < 4; ++r) hp[r] = f32x4{0.f, 0.f, 0.f, 0.f};
         wa = FFN_RD(s1, 0); wb = FFN_RD(s1, 256);           // only now visible (the barrier above); GEMM2's first
 #pragma unroll                                              // fragments were requested before it
         for (int u = 0; u < 8; ++u) {
@@ -449,7 +394,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ffn_fused_kernel(FfnArgs p) {
         }
         FFN_SB();
         // hidden tile of chunk i for the next iteration (the last GEMM1 MFMAs finished under the last GEMM2 ones)
-        h = (hp[0] + hp[1]) + (hp[2] + hp[3]) + *reinterpret_cast<const f32x4f*>(b1s + 16 * i + 4 * lg);
+        h = (hp[0] + hp[1]) + (hp[2] + hp[3]) + *reinterpret_cast<const f32x4*>(b1s + 16 * i + 4 * lg);
 #pragma unroll
         for (int r = 0; r < 4; ++r) h[r] = fmaxf(h[r], 0.f);
         FFN_END_CHUNK()
@@ -471,7 +416,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ffn_fused_kernel(FfnArgs p) {
     FFN_SB();
     if (!PRE) {
 #pragma unroll
-        for (int t = 0; t < 16; ++t) y[t] = y[t] + *reinterpret_cast<const f32x4f*>(prm + 16 * t + 4 * lg) + xr[t];
+        for (int t = 0; t < 16; ++t) y[t] = y[t] + *reinterpret_cast<const f32x4*>(prm + 16 * t + 4 * lg) + xr[t];
     }
     FFN_SB();
     // in flight under the LayerNorm + stores (unconditional -- after the last tile a valid tile is simply re-read --
@@ -481,76 +426,32 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ffn_fused_kernel(FfnArgs p) {
     if (PRE && my_row < M) {        // the un-normalised stream
         float* op = p.OUT + (size_t)my_row * p.ldo + 4 * lg;
 #pragma unroll
-        for (int t = 0; t < 16; ++t) *reinterpret_cast<f32x4f*>(op + 16 * t) = y[t];
+        for (int t = 0; t < 16; ++t) *reinterpret_cast<f32x4*>(op + 16 * t) = y[t];
     }
     float rstd;
-    if (!PRE || p.OUT2) ffn_layernorm_regs(y, rstd);
+    if (!PRE || p.OUT2) tf_layernorm_regs(y, rstd);
     if (PRE) {
         if (p.OUT2 && my_row < M) {
             float* op = p.OUT2 + (size_t)my_row * p.ldo2 + 4 * lg;
-#pragma unroll
-            for (int t = 0; t < 16; ++t) {
-                const f32x4f g = *reinterpret_cast<const f32x4f*>(prm + 256 + 16 * t + 4 * lg);
-                const f32x4f be = *reinterpret_cast<const f32x4f*>(prm + 512 + 16 * t + 4 * lg);
-                f32x4f o;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) o[r] = y[t][r] * rstd * g[r] + be[r];
-                *reinterpret_cast<f32x4f*>(op + 16 * t) = o;
-            }
+            TF_LN_STORE(op, y, rstd, prm + 256, prm + 512, true, false)
         }
     } else if (my_row < M) {
         float* op = p.OUT + (size_t)my_row * p.ldo + 4 * lg;
-#pragma unroll
-        for (int t = 0; t < 16; ++t) {
-            const f32x4f g = *reinterpret_cast<const f32x4f*>(prm + 256 + 16 * t + 4 * lg);
-            const f32x4f be = *reinterpret_cast<const f32x4f*>(prm + 512 + 16 * t + 4 * lg);
-            f32x4f o;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) o[r] = y[t][r] * rstd * g[r] + be[r];
-            *reinterpret_cast<f32x4f*>(op + 16 * t) = o;
-            if (QKV) y[t] = o;
-        }
+        TF_LN_STORE(op, y, rstd, prm + 256, prm + 512, true, QKV)
     } else if (QKV) {       // rows past M feed unstored outputs: any finite values
 #pragma unroll
-        for (int t = 0; t < 16; ++t) y[t] = f32x4f{0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < 16; ++t) y[t] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     if (QKV) {
         // ---- the next layer's q | k | v projection of the tile's output rows (still in registers, in the B-operand
         // layout): NQ chunks of 32 output channels in the projection phase's format, stored from the accumulators
         float* qrow = p.QKV + (size_t)my_row * p.ldq + 4 * lg;
         for (int g = 0; g < NQ; ++g) {
-            const float* st = FFN_STAGE_OF(NP + nc + g);
-            f32x4f ha[2], hb[2];
-            ha[0] = f32x4f{0.f, 0.f, 0.f, 0.f}; hb[0] = ha[0];
-            ha[1] = ha[0]; hb[1] = ha[0];
-            wa = FFN_RD(st, 0); wb = FFN_RD(st, 256); va = FFN_RD(st, 4096); vb = FFN_RD(st, 4096 + 256);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                FFN_SB();
-                asm volatile("" : "+v"(wa), "+v"(wb), "+v"(va), "+v"(vb));
-                FFN_SB();
-                if (u < 7) {
-                    na = FFN_RD(st, (2 * u + 2) * 256); nb = FFN_RD(st, (2 * u + 3) * 256);
-                    nva = FFN_RD(st, 4096 + (2 * u + 2) * 256); nvb = FFN_RD(st, 4096 + (2 * u + 3) * 256);
-                }
-                FFN_SB();
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    FFN_MFMA(ha[r & 1], wa[r], y[2 * u][r])
-                    FFN_MFMA(hb[r & 1], va[r], y[2 * u][r])
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    FFN_MFMA(ha[r & 1], wb[r], y[2 * u + 1][r])
-                    FFN_MFMA(hb[r & 1], vb[r], y[2 * u + 1][r])
-                }
-                FFN_STREAM(NP + nc + g + 2, u)
-                if (u < 7) { wa = na; wb = nb; va = nva; vb = nvb; }
-            }
+            FFN_CHUNK32(NP + nc + g, y)
             FFN_SB();
             if (my_row < M) {
-                *reinterpret_cast<f32x4f*>(qrow + 32 * g) = (ha[0] + ha[1]) + *reinterpret_cast<const f32x4f*>(qbs + 32 * g + 4 * lg);
-                *reinterpret_cast<f32x4f*>(qrow + 32 * g + 16) = (hb[0] + hb[1]) + *reinterpret_cast<const f32x4f*>(qbs + 32 * g + 16 + 4 * lg);
+                *reinterpret_cast<f32x4*>(qrow + 32 * g) = (ha[0] + ha[1]) + *reinterpret_cast<const f32x4*>(qbs + 32 * g + 4 * lg);
+                *reinterpret_cast<f32x4*>(qrow + 32 * g + 16) = (hb[0] + hb[1]) + *reinterpret_cast<const f32x4*>(qbs + 32 * g + 16 + 4 * lg);
             }
             FFN_END_CHUNK()
         }
@@ -560,6 +461,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ffn_fused_kernel(FfnArgs p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // no LDS-DMA may outlive the workgroup's LDS
 }
 
+#undef FFN_CHUNK32
 #undef FFN_MM_A
 #undef FFN_MM_Y
 #undef FFN_MM_AY
@@ -572,54 +474,52 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ffn_fused_kernel(FfnArgs p) {
 
 bool ffn_fused_supported(int ff) { return ff >= 32 && ff % 16 == 0 && ff <= 4096; }
 
-// Launches of at most this many 16-row groups (host bound) take the wide form (ffn_wide.hip: one workgroup per group and
-// CU, the eight waves split the output elements): 45 - 60 us per round of 256 groups against 160 - 200 us of a wave's
-// serial pass over the weights.  tools/tail_wide_bench.py, out_proj + LN + FFN: 52 / 62 / 124 / 183 us at 16 / 4 096 /
-// 8 192 / 12 288 rows against 168 / 181 / 187 / 194 us; from the fourth round on (12 500 rows: 226 us) the row forms win.
-#ifndef CONE_FFN_WIDE_GROUPS
-#define CONE_FFN_WIDE_GROUPS 768
-#endif
-constexpr int FFN_WIDE_GROUPS = CONE_FFN_WIDE_GROUPS;
 bool ffn_fused_qkv_fits(int ff, int n_qkv) {
     return ffn_fused_supported(ff) && n_qkv >= 32 && n_qkv % 32 == 0 &&
            (size_t)(FFN_NST * FFN_STAGE + ff + 6 * 256 + n_qkv) * sizeof(float) <= 160 * 1024;
 }
 
+// The CU count: it sizes the persistent grids and picks the form.
+static int ffn_cu_count(int* n_cu) {
+    static DeviceOnce once;
+    CONE_CHECK_HIP(device_once(once, [] { return hipSuccess; }, n_cu));
+    return 0;
+}
+
+// n_cu: the CU count that sizes the grid (0: the device's)
 template <bool PROJ, bool QKV, int NW, bool PRE = false>
-static int launch_ffn_nw(const FfnArgs& a, hipStream_t s, int* n_cu_out) {
+static int launch_ffn_nw(const TailF32Args& a, int n_cu, hipStream_t s) {
     const size_t lds = (size_t)(FFN_NST * FFN_STAGE + a.ff + 6 * 256 + (QKV ? a.n_qkv : 0)) * sizeof(float);
     CONE_REQUIRE(lds <= 160 * 1024, "fused layer tail: %zu bytes of LDS (ff %d, q|k|v %d) exceed 160 KiB", lds, a.ff, a.n_qkv);
     // once per device: the opt-in to > 64 KiB of LDS (a property of the code object) and the CU count that sizes
     // the persistent grid (one workgroup per CU: 132 KiB of LDS, 64 NW threads at <= 256 VGPRs)
     static DeviceOnce once;
-    int n_cu = 0;
+    int dev_cu = 0;
     CONE_CHECK_HIP(device_once(once, [] {
         return hipFuncSetAttribute((const void*)ffn_fused_kernel<PROJ, QKV, NW, PRE>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    160 * 1024);
-    }, &n_cu));
-    if (n_cu_out) { *n_cu_out = n_cu; return 0; }
+    }, &dev_cu));
+    if (!n_cu) n_cu = dev_cu;
     const int tiles = (a.M + 16 * NW - 1) / (16 * NW);
     const int grid = tiles < n_cu ? tiles : n_cu;
     // FLOPs of a record: 4 * M * ff * 256 for the block, + 2 * M * 256 * 256 with the projection
     // (+ 2 * M * n_qkv * 256 with the fused q | k | v projection: booked as n_qkv / 2 extra hidden units)
     ProfScope ps(NW == 8 ? (PROJ ? PK_FFN_PROJ : PK_FFN_FUSED) : (PROJ ? PK_FFN_PROJ_NW4 : PK_FFN_FUSED_NW4), a.M,
                  a.ff + (QKV ? a.n_qkv / 2 : 0), 256, a.M_dev, s);
-    hipLaunchKernelGGL((ffn_fused_kernel<PROJ, QKV, NW, PRE>), dim3((unsigned)grid), dim3(64 * NW), lds, s, a);
+    FfnArgs k;
+    static_cast<TailF32Args&>(k) = a;
+    hipLaunchKernelGGL((ffn_fused_kernel<PROJ, QKV, NW, PRE>), dim3((unsigned)grid), dim3(64 * NW), lds, s, k);
     CONE_LAUNCH_CHECK();
     return 0;
 }
 
-// Tile height by the HOST-known row bound M (never by the device-side count): 64-row tiles (one wave per SIMD) when the
-// 128-row tiles would occupy at most half of the CUs -- every 64-row tile then has a CU to itself and finishes in half the
-// time; the rows' results do not depend on the choice (same per-wave instruction sequence).
-template <bool PROJ, bool QKV>
-static int launch_ffn_t(const FfnArgs& a, hipStream_t s) {
-    int n_cu = 0;
-    const int rc = launch_ffn_nw<PROJ, QKV, 8>(a, s, &n_cu);
-    if (rc) return rc;
-    const int tiles128 = (a.M + 127) / 128;
-    if (!QKV && 2 * tiles128 <= n_cu) return launch_ffn_nw<PROJ, QKV, 4>(a, s, nullptr);
-    return launch_ffn_nw<PROJ, QKV, 8>(a, s, nullptr);
+// The row kernel on filled arguments: nw = 8 (128-row tiles) or 4 (64-row tiles); the ride (a.Wq) and the pre-norm form exist
+// on 8 waves only.
+static int launch_ffn_rows(const TailF32Args& a, bool proj, bool pre, int nw, int n_cu, hipStream_t s) {
+    if (pre) return launch_ffn_nw<true, false, 8, true>(a, n_cu, s);
+    if (a.Wq) return launch_ffn_nw<true, true, 8>(a, n_cu, s);
+    if (nw == 4) return proj ? launch_ffn_nw<true, false, 4>(a, n_cu, s) : launch_ffn_nw<false, false, 4>(a, n_cu, s);
+    return proj ? launch_ffn_nw<true, false, 8>(a, n_cu, s) : launch_ffn_nw<false, false, 8>(a, n_cu, s);
 }
 
 // Rows past the last FULL round of the persistent grid (n_cu tiles of 128 rows) cost the row forms a partial round -- half
@@ -636,6 +536,33 @@ static int ffn_full_round_rows(int M, int n_cu, int ff) {
     return rem > 0 && (rem + 15) / 16 <= CONE_FFN_SPLIT_GROUPS ? (int)full : M;
 }
 
+// The form ladder of the post-norm launches (proj: the projecting tail, else the block on a.X), by the HOST-known row bound
+// a.M, never by the device-side count; the rows' results do not depend on the choice (the same fma chains in every form):
+//   at most wide_groups groups of 16 rows, an ff the wide form takes, no ride   the wide form (ffn_wide.hip)
+//   otherwise the row kernel on the full rounds of n_cu 128-row tiles and the wide form on the rows past them
+//   (ffn_full_round_rows), or the row kernel on all rows: 64-row tiles (one wave per SIMD) when the 128-row tiles would
+//   occupy at most half of the CUs -- every 64-row tile then has a CU to itself and finishes in half the time.
+// n_cu = 0: the device's CU count.
+static int launch_ffn_ladder(TailF32Args a, bool proj, int n_cu, int wide_groups, hipStream_t s) {
+    const int M = a.M;
+    const bool ride = a.Wq != nullptr;
+    if (!ride && (M + 15) / 16 <= wide_groups && ffn_wide_supported(a.ff)) return launch_tail_f32_wide(a, proj, false, s);
+    if (!n_cu)
+        if (int rc = ffn_cu_count(&n_cu)) return rc;
+    const int m1 = ride ? M : ffn_full_round_rows(M, n_cu, a.ff);
+    a.M = m1;
+    if (int rc = launch_ffn_rows(a, proj, false, !ride && 2 * ((m1 + 127) / 128) <= n_cu ? 4 : 8, n_cu, s)) return rc;
+    if (m1 == M) return 0;
+    // the rows past the last full round: the wide form on offset pointers
+    a.M = M - m1; a.m_off = m1; a.OUT += (size_t)m1 * a.ldo;
+    if (!proj) a.X += (size_t)m1 * a.ldx;
+    else {
+        a.A += (size_t)m1 * a.lda;
+        if (a.r_idx) a.r_idx += m1; else a.R += (size_t)m1 * a.ldr;
+    }
+    return launch_tail_f32_wide(a, proj, false, s);
+}
+
 int launch_ffn_fused(const float* X, int ldx, const float* W1, const float* b1, const float* W2, const float* b2,
                      const float* ln_g, const float* ln_b, float* OUT, int ldo, int M, const int* M_dev, int ff,
                      hipStream_t s) {
@@ -643,73 +570,40 @@ int launch_ffn_fused(const float* X, int ldx, const float* W1, const float* b1, 
     CONE_REQUIRE(X && W1 && b1 && W2 && b2 && ln_g && ln_b && OUT, "fused FFN: null argument");
     CONE_REQUIRE(ldx % 4 == 0 && ldo % 4 == 0, "fused FFN: row strides must be multiples of 4");
     if (M <= 0) return 0;
-    if ((M + 15) / 16 <= FFN_WIDE_GROUPS && ffn_wide_supported(ff))     // a few row groups: the wide form (same bits)
-        return launch_ffn_wide(X, ldx, W1, b1, W2, b2, ln_g, ln_b, OUT, ldo, M, M_dev, ff, s);
-    FfnArgs a{};
+    TailF32Args a{};
     a.X = X; a.ldx = ldx; a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2; a.ln_g = ln_g; a.ln_b = ln_b;
     a.OUT = OUT; a.ldo = ldo; a.M = M; a.M_dev = M_dev; a.ff = ff;
-    int n_cu = 0;
-    if (int rc = launch_ffn_nw<false, false, 8>(a, s, &n_cu)) return rc;
-    const int m1 = ffn_full_round_rows(M, n_cu, ff);
-    if (m1 == M) return launch_ffn_t<false, false>(a, s);
-    a.M = m1;
-    if (int rc = launch_ffn_t<false, false>(a, s)) return rc;
-    return launch_ffn_wide(X + (size_t)m1 * ldx, ldx, W1, b1, W2, b2, ln_g, ln_b, OUT + (size_t)m1 * ldo, ldo, M - m1, M_dev, ff,
-                           s, m1);
+    return launch_ffn_ladder(a, false, 0, FFN_WIDE_GROUPS, s);
 }
 
 int launch_proj_ffn_fused(const TailArgs& t, hipStream_t s) {
-    const TailWeights& w = *t.w;
-    const float* Wq = t.next ? t.next->Wq : nullptr;
-    CONE_REQUIRE(!t.r_idx || t.R2, "fused layer tail: a gathered residual needs both source matrices");
-    CONE_REQUIRE(ffn_fused_supported(t.ff), "fused layer tail: dim_feedforward=%d unsupported", t.ff);
-    CONE_REQUIRE(t.A && w.Wo && w.bo && t.R && w.in_g && w.in_b && w.W1 && w.b1 && w.W2 && w.b2 && w.out_g && w.out_b && t.OUT,
-                 "fused layer tail: null argument");
-    CONE_REQUIRE(t.lda % 4 == 0 && t.ldr % 4 == 0 && t.ldo % 4 == 0, "fused layer tail: row strides must be multiples of 4");
-    const int M = t.M;
-    if (M <= 0) return 0;
-    if (!Wq && (M + 15) / 16 <= FFN_WIDE_GROUPS && ffn_wide_supported(t.ff))     // a few row groups: the wide form (same bits)
-        return launch_proj_ffn_wide(t, s);
-    FfnArgs a{};
-    a.A = t.A; a.lda = t.lda; a.Wo = w.Wo; a.bo = w.bo; a.R = t.R; a.ldr = t.ldr; a.pg = w.in_g; a.pb = w.in_b;
-    a.W1 = w.W1; a.b1 = w.b1; a.W2 = w.W2; a.b2 = w.b2; a.ln_g = w.out_g; a.ln_b = w.out_b;
-    a.OUT = t.OUT; a.ldo = t.ldo; a.M = M; a.M_dev = t.M_dev; a.ff = t.ff; a.r_idx = t.r_idx; a.R2 = t.R2;
-    if (Wq) {
-        CONE_REQUIRE(t.next->qb && t.QKV && t.n_qkv >= 32 && t.n_qkv % 32 == 0 && t.ldq % 4 == 0,
-                     "fused layer tail: bad q|k|v arguments");
-        a.Wq = Wq; a.qb = t.next->qb; a.QKV = t.QKV; a.ldq = t.ldq; a.n_qkv = t.n_qkv;
-        return launch_ffn_t<true, true>(a, s);
-    }
-    int n_cu = 0;
-    if (int rc = launch_ffn_nw<true, false, 8>(a, s, &n_cu)) return rc;
-    const int m1 = ffn_full_round_rows(M, n_cu, t.ff);
-    if (m1 == M) return launch_ffn_t<true, false>(a, s);
-    a.M = m1;
-    if (int rc = launch_ffn_t<true, false>(a, s)) return rc;
-    TailArgs rem = t;           // the rows past the last full round: the wide form on offset pointers
-    rem.A += (size_t)m1 * t.lda; rem.OUT += (size_t)m1 * t.ldo; rem.M = M - m1; rem.m_off = m1;
-    if (t.r_idx) rem.r_idx += m1; else rem.R += (size_t)m1 * t.ldr;
-    return launch_proj_ffn_wide(rem, s);
-}
-
-// The pre-norm layer tail (--pre_norm): OUT = x1 + FFN(LN(x1; in_g, in_b)), x1 = R + A Wo^T + bo; OUT2 (may be null) =
-// LN(OUT; out_g, out_b).  The persistent 128-row kernel for every row count (the option is off in every shipped configuration:
-// no wide / 64-row forms).  OUT may be R (in place).
-int launch_proj_ffn_prenorm(const TailArgs& t, hipStream_t s) {
-    const TailWeights& w = *t.w;
-    CONE_REQUIRE(!t.r_idx || t.R2, "pre-norm layer tail: a gathered residual needs both source matrices");
-    CONE_REQUIRE(ffn_fused_supported(t.ff), "pre-norm layer tail: dim_feedforward=%d unsupported", t.ff);
-    CONE_REQUIRE(t.A && w.Wo && w.bo && t.R && w.in_g && w.in_b && w.W1 && w.b1 && w.W2 && w.b2 && t.OUT &&
-                     (!t.OUT2 || (w.out_g && w.out_b)), "pre-norm layer tail: null argument");
-    CONE_REQUIRE(t.lda % 4 == 0 && t.ldr % 4 == 0 && t.ldo % 4 == 0 && t.ldo2 % 4 == 0,
-                 "pre-norm layer tail: row strides must be multiples of 4");
+    if (int rc = tail_f32_check(t, TF_FORM_ROWS, "fused layer tail")) return rc;
     if (t.M <= 0) return 0;
-    FfnArgs a{};
-    a.A = t.A; a.lda = t.lda; a.Wo = w.Wo; a.bo = w.bo; a.R = t.R; a.ldr = t.ldr; a.pg = w.in_g; a.pb = w.in_b;
-    a.W1 = w.W1; a.b1 = w.b1; a.W2 = w.W2; a.b2 = w.b2; a.ln_g = w.out_g ? w.out_g : w.in_g; a.ln_b = w.out_b ? w.out_b : w.in_b;
-    a.OUT = t.OUT; a.ldo = t.ldo; a.OUT2 = t.OUT2; a.ldo2 = t.ldo2; a.M = t.M; a.M_dev = t.M_dev; a.ff = t.ff;
-    a.r_idx = t.r_idx; a.R2 = t.R2;
-    return launch_ffn_nw<true, false, 8, true>(a, s, nullptr);
+    return launch_ffn_ladder(tail_f32_args(t), true, 0, FFN_WIDE_GROUPS, s);
 }
 
+// The pre-norm layer tail (--pre_norm, t.pre): OUT = x1 + FFN(LN(x1; in_g, in_b)), x1 = R + A Wo^T + bo; OUT2 (may be null) =
+// LN(OUT; out_g, out_b).  The persistent 128-row kernel for every row count (the option is off in every shipped configuration:
+// no 64-row form; api.hip picks the wide and spread forms).  OUT may be R (in place).
+int launch_proj_ffn_prenorm(const TailArgs& t, hipStream_t s) {
+    if (int rc = tail_f32_check(t, TF_FORM_ROWS, "pre-norm layer tail")) return rc;
+    if (t.M <= 0) return 0;
+    return launch_ffn_rows(tail_f32_args(t), true, true, 8, 0, s);
+}
+
+// Test hook (cone_test_tail_form): the projecting tail t (post-norm or t.pre) in ONE forced form, or -- CONE_TAIL_FORM_LADDER,
+// post-norm -- by the ladder's row rules for an assumed CU count, so that the full rounds + wide remainder split is reached
+// with a few hundred rows (the few-groups rule is off: such a launch would always go wide).  No production path calls it.
+int launch_tail_f32_form(const TailArgs& t, int form, int n_cu, hipStream_t s) {
+    if (form == CONE_TAIL_FORM_SPREAD) return launch_proj_ffn_spread(t, s);
+    CONE_REQUIRE(form >= CONE_TAIL_FORM_ROWS128 && form <= CONE_TAIL_FORM_LADDER, "tail form hook: unknown form %d", form);
+    CONE_REQUIRE(!t.pre || (form != CONE_TAIL_FORM_ROWS64 && form != CONE_TAIL_FORM_LADDER), "tail form hook: no such pre-norm form");
+    CONE_REQUIRE(form != CONE_TAIL_FORM_LADDER || n_cu > 0, "tail form hook: the ladder needs a CU count");
+    if (int rc = tail_f32_check(t, form == CONE_TAIL_FORM_WIDE ? TF_FORM_WIDE : TF_FORM_ROWS, "tail form hook")) return rc;
+    if (t.M <= 0) return 0;
+    const TailF32Args a = tail_f32_args(t);
+    if (form == CONE_TAIL_FORM_WIDE) return launch_tail_f32_wide(a, true, t.pre, s);
+    if (form == CONE_TAIL_FORM_LADDER) return launch_ffn_ladder(a, true, n_cu, 0, s);
+    return launch_ffn_rows(a, true, t.pre, form == CONE_TAIL_FORM_ROWS64 ? 4 : 8, 0, s);
+}
 }  // namespace cone

@@ -502,6 +502,17 @@ size_t cone_test_proj_ffn_spread_scratch_bytes(int ff);
 int cone_test_proj_ffn_spread(const float* A, const float* Wo, const float* bo, const float* R, const float* pg, const float* pb,
                               const float* W1, const float* b1, const float* W2, const float* b2, const float* ln_g,
                               const float* ln_b, float* OUT, int M, int ff, void* scratch, void* stream);
+/* cone_test_proj_ffn in ONE forced form of the exact-fp32 tail (tests only; no option or production path reads this):
+ * 128-row / 64-row persistent kernel, wide, spread (scratch as above), or the row rules of the launcher's ladder for an
+ * ASSUMED CU count n_cu (full rounds of n_cu 128-row tiles + the wide form on the rows past them; post-norm only).  Optional:
+ * r_idx / R2 (residual row i = R[r_idx[i]] or R2[~r_idx[i]]), M_dev (device-side row count), pre (the pre-norm tail: OUT = the
+ * stream, OUT2 (may be null) = its LayerNorm; no 64-row form). */
+enum { CONE_TAIL_FORM_ROWS128 = 0, CONE_TAIL_FORM_ROWS64 = 1, CONE_TAIL_FORM_WIDE = 2, CONE_TAIL_FORM_LADDER = 3,
+       CONE_TAIL_FORM_SPREAD = 4 };
+int cone_test_tail_form(const float* A, const float* Wo, const float* bo, const float* R, const float* pg, const float* pb,
+                        const float* W1, const float* b1, const float* W2, const float* b2, const float* ln_g,
+                        const float* ln_b, float* OUT, int M, int ff, const int32_t* r_idx, const float* R2,
+                        const int32_t* M_dev, int pre, float* OUT2, int form, int n_cu, void* scratch, void* stream);
 /* cone_test_proj_ffn on the bf16 matrix cores; wo_img = scratch of cone_test_proj_split_image_bytes() bytes. */
 size_t cone_test_proj_split_image_bytes(void);
 int cone_test_proj_ffn_split(const float* A, const float* Wo, const float* bo, const float* R, const float* pg,

@@ -269,6 +269,102 @@ def test_fused_tail_small_m_form_is_bit_identical(ff):
         assert torch.equal(big2[:m], small2), m
 
 
+_TAIL_FORM_ROWS128, _TAIL_FORM_ROWS64, _TAIL_FORM_WIDE, _TAIL_FORM_LADDER, _TAIL_FORM_SPREAD = range(5)     # CONE_TAIL_FORM_*
+_TAIL_FORM_MMAX = 258
+_tail_form_cache = {}
+
+
+def _tail_form_data(ff):
+    """Operands of _TAIL_FORM_MMAX rows (a case takes the first M) with test_fused_ffn_matches_float64's generators and scales,
+    a row index that mixes rows of R and of R2, and the float64 results per residual source: built once per ff."""
+    if ff in _tail_form_cache:
+        return _tail_form_cache[ff]
+    dev, M = _gpu(), _TAIL_FORM_MMAX
+    g = torch.Generator().manual_seed(4711 + ff)
+    R = torch.randn(M + 5, 256, generator=g) * 1.5
+    R2 = torch.randn(M // 2 + 3, 256, generator=g) * 1.5
+    W1 = torch.randn(ff, 256, generator=g) / 16
+    b1 = torch.randn(ff, generator=g) * 0.2
+    W2 = torch.randn(256, ff, generator=g) / ff ** 0.5
+    b2 = torch.randn(256, generator=g) * 0.2
+    lg, lb = torch.rand(256, generator=g) + 0.5, torch.randn(256, generator=g)
+    A = torch.randn(M, 256, generator=g)
+    Wo = torch.randn(256, 256, generator=g) / 16
+    bo = torch.randn(256, generator=g) * 0.2
+    pg, pb = torch.rand(256, generator=g) + 0.5, torch.randn(256, generator=g) * 0.3
+    # row i: even -> a row of R (not its own), odd -> a row of R2 (stored as ~row)
+    src = torch.randperm(M + 5, generator=g)[:M]
+    src2 = torch.randint(0, R2.shape[0], (M,), generator=g)
+    odd = torch.arange(M) % 2 == 1
+    idx = torch.where(odd, ~src2, src).to(torch.int32)
+    res = {False: R[:M], True: torch.where(odd[:, None], R2[src2], R[src])}
+    ln = lambda x, w, b: torch.nn.functional.layer_norm(x, (256,), w.double(), b.double(), 1e-5)
+    ref = {}
+    for gather, r in res.items():
+        x1 = r.double() + A.double() @ Wo.double().t() + bo.double()
+        blk = lambda x: (x @ W1.double().t() + b1.double()).clamp(min=0) @ W2.double().t() + b2.double()
+        post_in = ln(x1, pg, pb)
+        stream = x1 + blk(ln(x1, pg, pb))
+        ref[gather] = {"post": ln(post_in + blk(post_in), lg, lb), "stream": stream, "stream_ln": ln(stream, lg, lb)}
+    d = lambda t: t.to(dev).contiguous()
+    ops = dict(A=d(A), Wo=d(Wo), bo=d(bo), R=d(R), R2=d(R2), pg=d(pg), pb=d(pb), W1=d(W1), b1=d(b1), W2=d(W2), b2=d(b2), lg=d(lg),
+               lb=d(lb), idx=d(idx))
+    _tail_form_cache[ff] = (ops, ref)
+    return _tail_form_cache[ff]
+
+
+@pytest.mark.parametrize("M,cut,n_cu", [(1, 0, 0), (17, 9, 0), (65, 40, 0), (129, 100, 0), (130, 129, 1), (258, 257, 2)])
+@pytest.mark.parametrize("ff", [128, 256])
+def test_tail_forms_forced_are_bit_identical(ff, M, cut, n_cu):
+    """Every form of the exact-fp32 projecting tail, FORCED through cone_test_tail_form on a few rows: the persistent 128-row
+    kernel, the 64-row one (post-norm only), the wide kernel, the spread launches (ff = 256: the smallest ff they take) and --
+    n_cu != 0 -- the launcher's row rules for an assumed CU count; post-norm, pre-norm without and with the second output;
+    without and with a gathered residual whose index mixes rows of R and R2; without and with a device-side row count `cut` < M.
+    M = 1: one ragged group; 17: two groups, the second ragged (cut 9: it empties); 65 / 129: a second 64- / 128-row tile with one
+    row (its other waves idle through the side path); 130 with one assumed CU: ONE persistent workgroup walks both tiles (the
+    ring runs on) -- ffn_full_round_rows never splits on one CU, every round is full; 258 with two assumed CUs: one full round of
+    two tiles + a wide remainder of 2 rows (cut 257: inside the remainder, r_idx and m_off handed over).
+    (a) every result within 3e-5 of a float64 evaluation (test_fused_ffn_matches_float64's bound, generators and scales);
+    (b) all forms the same bits; (c) rows at and past min(M, cut) of the NaN-filled outputs stay NaN."""
+    from cone_amd import _lib
+    dev = _gpu()
+    o, ref = _tail_form_data(ff)
+    lib, P = _lib.load(), _lib.ptr
+    scratch = torch.empty(lib.cone_test_proj_ffn_spread_scratch_bytes(ff), dtype=torch.uint8, device=dev)
+    m_dev = torch.tensor([cut], dtype=torch.int32, device=dev)
+    spread = [_TAIL_FORM_SPREAD] if ff % 256 == 0 else []
+    ladder = [_TAIL_FORM_LADDER] if n_cu else []
+    forms = {"post": [_TAIL_FORM_ROWS128, _TAIL_FORM_ROWS64, _TAIL_FORM_WIDE] + ladder + spread,
+             "pre": [_TAIL_FORM_ROWS128, _TAIL_FORM_WIDE] + spread}
+    for mode, want2 in (("post", False), ("pre", False), ("pre", True)):
+        for gather in (False, True):
+            for counted in (False, True):
+                n = min(M, cut) if counted else M
+                outs = []
+                for form in forms[mode]:
+                    out = torch.full((M + 3, 256), float("nan"), device=dev)
+                    out2 = torch.full((M + 3, 256), float("nan"), device=dev) if want2 else None
+                    _lib.check(lib.cone_test_tail_form(
+                        P(o["A"]), P(o["Wo"]), P(o["bo"]), P(o["R"]), P(o["pg"]), P(o["pb"]), P(o["W1"]), P(o["b1"]), P(o["W2"]),
+                        P(o["b2"]), P(o["lg"]), P(o["lb"]), P(out), M, ff, P(o["idx"]) if gather else None,
+                        P(o["R2"]) if gather else None, P(m_dev) if counted else None, int(mode == "pre"), P(out2), form, n_cu,
+                        P(scratch), _lib.stream()))
+                    outs.append((form, out, out2))
+                torch.cuda.synchronize()
+                what = (mode, want2, gather, counted)
+                r = ref[gather]
+                for form, out, out2 in outs:
+                    err = maxdiff(out[:n], r["post" if mode == "post" else "stream"][:n]) if n else 0.0
+                    err2 = maxdiff(out2[:n], r["stream_ln"][:n]) if want2 and n else 0.0
+                    print(f"tail form {form} {what}: err {err:.2e} {err2:.2e}")
+                    assert err < 3e-5 and err2 < 3e-5, (what, form, err, err2)
+                    assert bool(torch.isnan(out[n:]).all()), (what, form)
+                    assert torch.equal(out[:n], outs[0][1][:n]), (what, form, "vs form", outs[0][0])
+                    if want2:
+                        assert bool(torch.isnan(out2[n:]).all()), (what, form)
+                        assert torch.equal(out2[:n], outs[0][2][:n]), (what, form, "OUT2 vs form", outs[0][0])
+
+
 @pytest.mark.parametrize("n,dim", [(5, 256), (1000, 768), (3, 512), (77, 1024)])
 def test_layernorm_matches_torch(n, dim):
     from cone_amd import _lib
