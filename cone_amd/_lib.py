@@ -87,6 +87,16 @@ _SIGNATURES = {
     "cone_prefilter_batched": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                          C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                          C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    # the opt-in bf16 pre-filter (additive in ABI 8)
+    "cone_rows_to_bf16": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+    "cone_adapter_norm_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                         C.c_void_p]),
+    "cone_prefilter_scores_bf16_workspace": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
+    "cone_prefilter_scores_bf16": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                             C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cone_prefilter_batched_bf16": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                              C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                              C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "cone_topk_windows": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cone_topk_windows_workspace": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),
     "cone_topk_windows_ws": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,

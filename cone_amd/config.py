@@ -18,7 +18,8 @@ from types import SimpleNamespace
 CLI_WINS = ("eval_path", "eval_split_name", "results_root", "num_workers", "nms_thd",
             "debug", "save_all", "max_before_nms", "max_after_nms", "max_pred_l",
             "min_pred_l", "eval_bsz", "data_ratio", "topk_window", "resume",
-            "resume_all", "no_sort_results", "packed_features", "split_bf16", "bf16", "gpus", "dist_backend")
+            "resume_all", "no_sort_results", "packed_features", "split_bf16", "bf16", "prefilter_bf16", "gpus",
+            "dist_backend")
 
 MODEL_DEFAULTS = dict(
     hidden_dim=256, nheads=8, dim_feedforward=1024, enc_layers=2, dec_layers=2,
@@ -118,6 +119,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "matrix-core product each; bias, ReLU, residual, LayerNorm, attention, heads and activations in memory "
                         "stay fp32.  Stage A (pre-filter, window ranking) is unchanged, so the same windows are selected; only "
                         "stage-B values differ, within the reference model's own bf16-autocast error")
+    p.add_argument("--prefilter_bf16", action="store_true",
+                   help="(cone_amd extension, opt-in; a switch of its own, independent of --bf16) stage A with a bf16 context arena "
+                        "and bf16 operands: window score = sum of bf16(ctx) * bf16(cls) products, fp32 accumulation.  NOT "
+                        "fp32-accurate (~2^-8 absolute on unit-norm rows): windows whose scores are closer than that may swap "
+                        "ranks.  Half the arena bytes of the HBM-bound stream; stage B and C are unchanged")
     p.add_argument("--gpus", type=int, default=1,
                    help="(cone_amd extension) evaluate the split sharded over N GPUs of this node: a plain process starts "
                         "N ranks through torch.distributed.run; under torchrun it must equal WORLD_SIZE.  Rank 0 writes the files")

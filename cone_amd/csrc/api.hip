@@ -1246,6 +1246,36 @@ extern "C" int cone_l2_normalize_rows(const float* x, int64_t n_rows, int dim, f
     return launch_l2norm(x, n_rows, dim, eps, out, (hipStream_t)stream, clamp);
 }
 
+extern "C" int cone_rows_to_bf16(const float* x, int64_t n_rows, int dim, uint16_t* out, void* stream) {
+    CONE_REQUIRE(x && out, "rows_to_bf16: null argument");
+    CONE_REQUIRE(n_rows > 0, "rows_to_bf16: bad row count");
+    CONE_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)out & 7) == 0, "rows_to_bf16: x must be 16-B aligned, out 8-B aligned");
+    return launch_rows_to_bf16(x, n_rows, dim, out, (hipStream_t)stream);
+}
+
+// cone_adapter_norm whose LAST stage stores bf16 (the same launches up to it, so the same fp32 values go into the rounding)
+extern "C" int cone_adapter_norm_bf16(const cone_model* m, const float* x, int64_t n_rows, uint16_t* out, int renorm,
+                                      void* ws, size_t ws_bytes, void* stream) {
+    CONE_REQUIRE(m && x && out, "adapter_norm_bf16: null argument");
+    CONE_REQUIRE(n_rows > 0 && n_rows < (1ll << 31), "adapter_norm_bf16: bad row count");
+    CONE_REQUIRE(((uintptr_t)out & 15) == 0, "adapter_norm_bf16: out must be 16-B aligned (the bf16 pre-filter's arena)");
+    hipStream_t s = (hipStream_t)stream;
+    if (!m->has_adapter)    // adapter_module == "none": the features pass through, rounded
+        return launch_rows_to_bf16(x, n_rows, m->dv, out, s);
+    Carver c(ws, ws_bytes);
+    const int d = m->d;
+    float* h = c.take<float>((size_t)n_rows * d);
+    float* y = c.take<float>((size_t)n_rows * m->dv);
+    if (!c.ok) { set_error("adapter_norm_bf16: workspace too small (%zu < %zu)", ws_bytes, c.cur); return CONE_E_WORKSPACE; }
+    RUN(launch_gemm(G(m, x, m->dv, m->adapter[0].w, m->dv, m->adapter[0].b, h, d, (int)n_rows, nullptr, d, m->dv, EPI_RELU), s));
+    GemmArgs g = G(m, h, d, m->adapter[1].w, d, m->adapter[1].b, y, m->dv, (int)n_rows, nullptr, m->dv, d, EPI_RESIDUAL);
+    g.R = x; g.ldr = m->dv;
+    RUN(launch_gemm(g, s));
+    // renorm: the L2 norm's own store is the bf16 one (the normalised fp32 rows never reach memory); the localizer's raw sum
+    // (renorm == 0) is converted from the GEMM's fp32 output
+    return renorm ? launch_l2norm_bf16(y, n_rows, m->dv, 0.f, out, s) : launch_rows_to_bf16(y, n_rows, m->dv, out, s);
+}
+
 extern "C" size_t cone_project_workspace(const cone_model* m, int which, int64_t n_rows) {
     return project_ws_bytes(m, which, n_rows);
 }

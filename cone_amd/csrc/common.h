@@ -229,6 +229,10 @@ int launch_layernorm(const float* x, int ldx, const float* g, const float* b, fl
                      int64_t n_rows, const int* n_rows_dev, int dim, hipStream_t s, const int* src_row = nullptr);
 // src_row != null: output row i normalises input row src_row[i]
 int launch_l2norm(const float* x, int64_t n_rows, int dim, float eps, float* out, hipStream_t s, int clamp = 0);
+// the bf16 context arena of the opt-in bf16 pre-filter: launch_l2norm with a bf16 store (bf16_rne of its fp32 value), and
+// the plain conversion out = bf16_rne(x)
+int launch_l2norm_bf16(const float* x, int64_t n_rows, int dim, float eps, uint16_t* out, hipStream_t s, int clamp = 0);
+int launch_rows_to_bf16(const float* x, int64_t n_rows, int dim, uint16_t* out, hipStream_t s);
 // out[m][n] = act(<X[m], W[n]> + b[n]), n < nout <= 2, K = 256; act 0 none, 1 sigmoid
 int launch_rowdot(const float* X, int ldx, const float* W, const float* b, float* out, int ldo,
                   int64_t n_rows, int nout, int act, hipStream_t s);

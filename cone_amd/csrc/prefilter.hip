@@ -982,6 +982,366 @@ static int launch_frame_scores(const float* vid, int64_t ctx_l, int S, int64_t n
     return 0;
 }
 
+// ---- OPT-IN: the bf16 pre-filter -- bf16 context rows, bf16 operands, fp32 accumulation ------------------------------------
+// ONE arithmetic contract for every form: score[q][f] = sum_c bf16(ctx[f][c]) * bf16(cls[q][c]); both operands rounded once
+// (round to nearest even: the arena by its producer -- cone_rows_to_bf16 / cone_adapter_norm_bf16 --, the query vectors
+// here), every product exact in fp32 (8 x 8 significand bits), the sum in fp32 in the form's own order.  NOT fp32-accurate:
+// ~2^-8 relative per operand.  The arena is half the bytes of the fp32 one (the stream is HBM-bound), and the many-query form
+// needs 16 x fewer matrix instructions per score than v_mfma_f32_16x16x4_f32.  Window scores: the half-window running max,
+// the first-frame term and window_combine_kernel's rule, as above; no frame-score matrix in this mode.
+//   frame_score_bf16_kernel        : the streaming form (frame_score_kernel's shape): a row arrives as 16-B non-temporal lane loads
+//                                    (8 bf16 = lane's channels 8 c .. 8 c + 7, c = lane + 64 v), widened to fp32 by a shift; dv is
+//                                    any multiple of 32 up to 1024 (lanes past dv / 8 hold zeros and load nothing)
+//   frame_score_mq_bf16_kernel     : 16 / 32 / 64 queries per pass on v_mfma_f32_16x16x32_bf16
+//   frame_score_groups_bf16_kernel : the streaming form for a whole split (one video x up to 4 queries per group)
+// From how many queries the matrix-core form takes over: CONE_PF16_MQ_MIN (A/B: compile with another value).  The streaming
+// form costs one pass per 4 queries, the matrix-core form one pass per 64, so 5 is the first count at which the latter saves a
+// whole pass over the arena; below 5 both are one HBM-bound pass and the streaming form (no LDS prologue, 8 workgroups per
+// CU) is kept.  (tools/prefilter_bf16_bench.py measures both sides of it: profiles/prefilter_bf16.txt.)
+#ifndef CONE_PF16_MQ_MIN
+#define CONE_PF16_MQ_MIN 5
+#endif
+
+__device__ __forceinline__ pf_u4 pf16_ld(const uint16_t* p, bool nt) {
+    if (nt) return __builtin_nontemporal_load(reinterpret_cast<const pf_u4*>(p));
+    return *reinterpret_cast<const pf_u4*>(p);
+}
+__device__ __forceinline__ float pf16_rne(float a) { return __uint_as_float(pf_pk(a, 0.f) << 16); }    // fp32 -> bf16 -> fp32
+
+// <x, q> over a lane's 8 channels: two pf_dot4 (the pinned fma chain of the fp32 kernels) on the widened values, added
+__device__ __forceinline__ float pf16_dot8(const pf_u4& x, const float (&q)[8]) {
+#pragma clang fp contract(off)
+    const float4 a = make_float4(__uint_as_float(x[0] << 16), __uint_as_float(x[0] & 0xffff0000u),
+                                 __uint_as_float(x[1] << 16), __uint_as_float(x[1] & 0xffff0000u));
+    const float4 b = make_float4(__uint_as_float(x[2] << 16), __uint_as_float(x[2] & 0xffff0000u),
+                                 __uint_as_float(x[3] << 16), __uint_as_float(x[3] & 0xffff0000u));
+    const float d0 = pf_dot4(a, make_float4(q[0], q[1], q[2], q[3]));
+    const float d1 = pf_dot4(b, make_float4(q[4], q[5], q[6], q[7]));
+    return d0 + d1;
+}
+
+// a query vector's share of this lane, rounded ONCE to bf16 and held widened (zeros past dv)
+template <int VPL>
+__device__ __forceinline__ void pf16_load_query(const float* __restrict__ row, int dv, int lane, float (&q)[VPL][8]) {
+#pragma unroll
+    for (int v = 0; v < VPL; ++v) {
+        const int c = lane + 64 * v;
+        float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
+        if (c * 8 < dv) {
+            a = reinterpret_cast<const float4*>(row)[2 * c];
+            b = reinterpret_cast<const float4*>(row)[2 * c + 1];
+        }
+        q[v][0] = pf16_rne(a.x); q[v][1] = pf16_rne(a.y); q[v][2] = pf16_rne(a.z); q[v][3] = pf16_rne(a.w);
+        q[v][4] = pf16_rne(b.x); q[v][5] = pf16_rne(b.y); q[v][6] = pf16_rne(b.z); q[v][7] = pf16_rne(b.w);
+    }
+}
+
+// One wave over rows sub * RPW, + step * RPW, ... of a half window of n rows at `base`: RPW rows in flight, the NV = RPW * QG
+// (row, query) sums by one butterfly.  Returns the running max of query my_g = (lane / (64 / NV)) % QG over the wave's rows
+// (every lane of that query's groups holds it); `first` = the score of row 0 (held by the lanes with row slot 0 of a wave
+// with sub == 0).  The per-lane chain and the butterfly's pairs do not depend on QG, so a query's bits do not depend on the
+// launch it shares, and the per-video and the grouped kernel produce the same bits.
+template <int VPL, int QG, int RPW, bool NT>
+__device__ __forceinline__ float pf16_half_block(const uint16_t* __restrict__ base, int n, int dv, const float (&q)[QG][VPL][8],
+                                                 int lane, int sub, int step, float& first) {
+    constexpr int NV = RPW * QG;
+    static_assert((RPW & (RPW - 1)) == 0 && (QG & (QG - 1)) == 0 && NV <= 64, "row / query counts: powers of two");
+    const int my_r = (lane / (64 / NV)) / QG;
+    float m = -INFINITY;
+    for (int j0 = sub * RPW; j0 < n; j0 += step * RPW) {
+        pf_u4 x[RPW][VPL];
+#pragma unroll
+        for (int r = 0; r < RPW; ++r) {
+            const int row = min(j0 + r, n - 1);
+#pragma unroll
+            for (int v = 0; v < VPL; ++v) {
+                const int c = lane + 64 * v;
+                x[r][v] = pf_u4{0u, 0u, 0u, 0u};
+                if (c * 8 < dv) x[r][v] = pf16_ld(base + (size_t)row * dv + 8 * c, NT);
+            }
+        }
+        float part[NV];
+#pragma unroll
+        for (int r = 0; r < RPW; ++r)
+#pragma unroll
+            for (int g = 0; g < QG; ++g) {
+                float s = 0.f;
+#pragma unroll
+                for (int v = 0; v < VPL; ++v) s += pf16_dot8(x[r][v], q[g][v]);
+                part[r * QG + g] = s;
+            }
+        const float s = wave_sum_multi<NV>(part, lane);                // = the total of (row j0 + my_r, query my_g)
+        if (j0 + my_r < n) {
+            m = fmaxf(m, s);
+            if (my_r == 0 && j0 == 0) first = s;
+        }
+    }
+    // over the RPW row slots of a query: the lanes that differ in the index's top log2(RPW) bits (lane bits 5, 4, ...)
+#pragma unroll
+    for (int o = 32; o > 32 / RPW; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    return m;
+}
+
+template <int VPL /* 16-B loads per lane and row: dv <= 512 VPL */, int QG, int RPW, int WPH>
+__global__ __launch_bounds__(256) void frame_score_bf16_kernel(const uint16_t* __restrict__ vid, int64_t ctx_l, int dv, int S,
+                                                               int64_t nh, const float* __restrict__ txt, int q0, int nq,
+                                                               float* __restrict__ hm, float* __restrict__ fr) {
+    constexpr int UPB = 4 / WPH, NV = RPW * QG;
+    __shared__ float red[4][QG];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sub = wave % WPH;
+    const int my_j = lane / (64 / NV), my_r = my_j / QG, my_g = my_j % QG;
+    const bool out_lane = (lane & (64 / NV - 1)) == 0 && my_r == 0;    // lane g * (64 / NV): query q0 + g
+    float q[QG][VPL][8];
+#pragma unroll
+    for (int g = 0; g < QG; ++g) pf16_load_query<VPL>(txt + (size_t)min(q0 + g, nq - 1) * dv, dv, lane, q[g]);
+    for (int64_t h = (int64_t)blockIdx.x * UPB + wave / WPH; h < nh; h += (int64_t)gridDim.x * UPB) {
+        const int64_t r_lo = h * S;
+        const int n = (int)min((int64_t)S, ctx_l - r_lo);            // frames of this half window
+        float first = 0.f;
+        const float m = pf16_half_block<VPL, QG, RPW, CONE_PF_NT != 0>(vid + r_lo * dv, n, dv, q, lane, sub, WPH, first);
+        if (out_lane && sub == 0 && q0 + my_g < nq) fr[(size_t)(q0 + my_g) * nh + h] = first;     // the block's first frame
+        if (WPH == 1) {
+            if (out_lane && q0 + my_g < nq) hm[(size_t)(q0 + my_g) * nh + h] = m;
+        } else {                                    // h is uniform over the workgroup: the barriers are too
+            if (out_lane) red[wave][my_g] = m;
+            __syncthreads();
+            if (wave == 0 && lane < QG && q0 + lane < nq)
+                hm[(size_t)(q0 + lane) * nh + h] = fmaxf(fmaxf(red[0][lane], red[1][lane]), fmaxf(red[2][lane], red[3][lane]));
+            __syncthreads();
+        }
+    }
+}
+
+template <int VPL>
+static int launch_frame_scores_bf16(const uint16_t* vid, int64_t ctx_l, int dv, int S, int64_t nh, const float* txt, int nq,
+                                    float* hm, float* fr, hipStream_t s) {
+    constexpr int RPW = CONE_PF_RPW;
+    const bool wide = nh < 4096;            // as launch_frame_scores: short videos give a half window to a whole workgroup
+    int64_t blocks = wide ? nh : (nh + 3) / 4;
+    if (blocks > 256 * CONE_PF_WGS_PER_CU) blocks = 256 * CONE_PF_WGS_PER_CU;
+    for (int q0 = 0; q0 < nq;) {
+        const int rem = nq - q0;
+        const int qg = rem >= 3 ? 4 : (rem >= 2 ? 2 : 1);      // 3 queries ride a 4-query launch (the fourth slot stores nothing)
+        ProfScope ps(PK_FRAME_SCORE, ctx_l, dv, qg, nullptr, s);
+#define CONE_FS16_LAUNCH(QG, WPH)                                                                                          \
+    hipLaunchKernelGGL((frame_score_bf16_kernel<VPL, QG, RPW, WPH>), dim3((unsigned)blocks), dim3(256), 0, s, vid, ctx_l, dv, \
+                       S, nh, txt, q0, nq, hm, fr)
+        if (qg == 4) { if (wide) CONE_FS16_LAUNCH(4, 4); else CONE_FS16_LAUNCH(4, 1); }
+        else if (qg == 2) { if (wide) CONE_FS16_LAUNCH(2, 4); else CONE_FS16_LAUNCH(2, 1); }
+        else { if (wide) CONE_FS16_LAUNCH(1, 4); else CONE_FS16_LAUNCH(1, 1); }
+#undef CONE_FS16_LAUNCH
+        q0 += qg;
+        CONE_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+// Many queries: D[query][frame] tiles of v_mfma_f32_16x16x32_bf16.  k slot (lg, j) of k-step t <-> channel 32 t + 8 lg + j on both
+// operands, so a lane's B fragment (frame li, its 8 k slots) is ONE 16-B load from the arena -- no conversion, no split on the
+// frame side -- and its A fragment one ds_read_b128 from the query image: 1-KiB slabs [16 queries][4 lg][8 bf16] per (query
+// tile, k-step), rounded and laid out once per launch by the workgroup's prologue (64 queries x 1024 channels = 128 KiB: the
+// LDS holds every shape).  A wave owns whole half windows, 16 frames per tile; the loads of the next block of PF16_KS k-steps
+// (256 channels: 512 B of each of the tile's 16 rows) are in flight under the MFMAs of the current one, across tiles and half
+// windows.  dv / 32 need not be a multiple of PF16_KS: the last block is short (uniform guards).  Ordinary loads, as in the fp32
+// kernel (CONE_PF_NT_MQ): a row's 128-B line is fetched by two consecutive instructions.
+constexpr int PF16_KS = 8;
+
+template <int QT /* query tiles of 16 */>
+__global__ __launch_bounds__(MQ_NT, 3) void frame_score_mq_bf16_kernel(const uint16_t* __restrict__ vid, int64_t ctx_l, int dv,
+                                                                     int S, int64_t nh, const float* __restrict__ txt, int q0,
+                                                                     int nq, float* __restrict__ hm, float* __restrict__ fr) {
+    extern __shared__ __attribute__((aligned(16))) char qb[];           // [QT][dv / 32] slabs of 1 KiB
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int li = lane & 15, lg = lane >> 4;
+    const int nks = dv >> 5;                                             // k-steps of 32 channels
+    for (int i = tid; i < QT * 16 * (dv >> 3); i += MQ_NT) {             // (query, 8 channels of its vector)
+        const int qi = i / (dv >> 3), c8 = i % (dv >> 3);
+        const int qg = q0 + qi;
+        pf4 a = pf4{0.f, 0.f, 0.f, 0.f}, b = a;
+        if (qg < nq) {
+            a = *reinterpret_cast<const pf4*>(txt + (size_t)qg * dv + c8 * 8);
+            b = *reinterpret_cast<const pf4*>(txt + (size_t)qg * dv + c8 * 8 + 4);
+        }
+        *reinterpret_cast<pf_u4*>(qb + (((qi >> 4) * nks + (c8 >> 2)) << 10) + (qi & 15) * 64 + (c8 & 3) * 16) =
+            pf_u4{pf_pk(a[0], a[1]), pf_pk(a[2], a[3]), pf_pk(b[0], b[1]), pf_pk(b[2], b[3])};
+    }
+    __syncthreads();
+    const int rd = li * 64 + lg * 16;
+    const int nchunk = (nks + PF16_KS - 1) / PF16_KS;
+    constexpr int NW = MQ_NT / 64;
+    const int64_t h_step = (int64_t)gridDim.x * NW;
+    int64_t h = (int64_t)blockIdx.x * NW + (tid >> 6);
+    if (h >= nh) return;
+    int64_t r_lo = h * S, r_hi = min(r_lo + S, ctx_l);
+    int64_t f0 = r_lo;
+    const uint16_t* fp = vid + min(f0 + li, r_hi - 1) * dv + 8 * lg;
+    pf_u4 cur[PF16_KS];
+#pragma unroll
+    for (int s = 0; s < PF16_KS; ++s) {
+        cur[s] = pf_u4{0u, 0u, 0u, 0u};
+        if (s < nks) cur[s] = pf16_ld(fp + 32 * s, CONE_PF_NT_MQ != 0);
+    }
+    pf4 mx[QT];
+#pragma unroll
+    for (int qt = 0; qt < QT; ++qt) mx[qt] = pf4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    while (true) {
+        // where the stream goes after this tile
+        int64_t h2 = h, f2 = f0 + 16, lo2 = r_lo, hi2 = r_hi;
+        if (f2 >= r_hi) { h2 = h + h_step; lo2 = h2 * S; hi2 = min(lo2 + S, ctx_l); f2 = lo2; }
+        const bool more = h2 < nh;
+        const uint16_t* fp2 = more ? vid + min(f2 + li, hi2 - 1) * dv + 8 * lg : fp;
+        pf4 acc[QT];
+#pragma unroll
+        for (int qt = 0; qt < QT; ++qt) acc[qt] = pf4{0.f, 0.f, 0.f, 0.f};
+        for (int c = 0; c < nchunk; ++c) {
+            const int kb = c * PF16_KS;
+            const bool last = c + 1 == nchunk;
+            const uint16_t* np = last ? fp2 : fp + 32 * (kb + PF16_KS);      // the next block's first k-step of this lane
+            const int n_nxt = last ? nks : nks - (kb + PF16_KS);              // k-steps it has (>= 1)
+            pf_u4 nxt[PF16_KS];
+#pragma unroll
+            for (int s = 0; s < PF16_KS; ++s) {
+                nxt[s] = pf_u4{0u, 0u, 0u, 0u};
+                if (s < n_nxt) nxt[s] = pf16_ld(np + 32 * s, CONE_PF_NT_MQ != 0);
+            }
+#pragma unroll
+            for (int s = 0; s < PF16_KS; ++s) {
+                if (kb + s < nks) {
+                    const pf_s8 bb = __builtin_bit_cast(pf_s8, cur[s]);
+#pragma unroll
+                    for (int qt = 0; qt < QT; ++qt) {
+                        const pf_s8 aa = *reinterpret_cast<const pf_s8*>(qb + ((qt * nks + kb + s) << 10) + rd);
+                        PF_MFMA(acc[qt], aa, bb);
+                    }
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < PF16_KS; ++s) cur[s] = nxt[s];
+        }
+        const bool valid = f0 + li < r_hi;
+        const bool first = f0 == r_lo && li == 0;       // lane li = 0 of the block's first tile = frame hS
+#pragma unroll
+        for (int qt = 0; qt < QT; ++qt) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (valid) mx[qt][r] = fmaxf(mx[qt][r], acc[qt][r]);
+                const int qg = q0 + qt * 16 + 4 * lg + r;
+                if (first && qg < nq) fr[(size_t)qg * nh + h] = acc[qt][r];
+            }
+        }
+        if (f0 + 16 >= r_hi) {                          // half window done: max over its 16 frame lanes, one store per query
+#pragma unroll
+            for (int qt = 0; qt < QT; ++qt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float v = mx[qt][r];
+                    v = fmaxf(v, __shfl_xor(v, 1, 64));
+                    v = fmaxf(v, __shfl_xor(v, 2, 64));
+                    v = fmaxf(v, __shfl_xor(v, 4, 64));
+                    v = fmaxf(v, __shfl_xor(v, 8, 64));
+                    const int qg = q0 + qt * 16 + 4 * lg + r;
+                    if (li == 0 && qg < nq) hm[(size_t)qg * nh + h] = v;
+                    mx[qt][r] = -INFINITY;
+                }
+        }
+        if (!more) break;
+        h = h2; f0 = f2; r_lo = lo2; r_hi = hi2; fp = fp2;
+    }
+}
+
+static int launch_frame_scores_mq_bf16(const uint16_t* vid, int64_t ctx_l, int dv, int S, int64_t nh, const float* txt, int nq,
+                                       float* hm, float* fr, hipStream_t s) {
+    static DeviceOnce once;     // up to 128 KiB of LDS (64 queries x 1024 channels): opt-in once per device; one workgroup per CU
+    int n_cu = 0;
+    if (device_once(once, [] {
+            const void* fns[3] = {(const void*)frame_score_mq_bf16_kernel<4>, (const void*)frame_score_mq_bf16_kernel<2>,
+                                  (const void*)frame_score_mq_bf16_kernel<1>};
+            hipError_t e = hipSuccess;
+            for (int i = 0; i < 3 && e == hipSuccess; ++i)
+                e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+            return e;
+        }, &n_cu) != hipSuccess) {
+        set_error("prefilter (bf16): raising the LDS limit of the many-query kernel failed");
+        return CONE_E_HIP;
+    }
+    int64_t blocks = (nh + MQ_NT / 64 - 1) / (MQ_NT / 64);
+    if (blocks > n_cu) blocks = n_cu;                                  // one workgroup per CU, grid-stride over half windows
+    for (int q0 = 0; q0 < nq; q0 += 64) {
+        const int rem = nq - q0;
+        const int qt = rem > 32 ? 4 : (rem > 16 ? 2 : 1);              // query tiles of this pass: 64 / 32 / 16 queries
+        ProfScope ps(PK_FRAME_SCORE, ctx_l, dv, rem < 16 * qt ? rem : 16 * qt, nullptr, s);
+#define CONE_MQ16_LAUNCH(QT)                                                                                                \
+    hipLaunchKernelGGL((frame_score_mq_bf16_kernel<QT>), dim3((unsigned)blocks), dim3(MQ_NT), (size_t)(QT) * 16 * dv * 2, s, vid, \
+                       ctx_l, dv, S, nh, txt, q0, nq, hm, fr)
+        if (qt == 4) CONE_MQ16_LAUNCH(4); else if (qt == 2) CONE_MQ16_LAUNCH(2); else CONE_MQ16_LAUNCH(1);
+#undef CONE_MQ16_LAUNCH
+        CONE_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+// The grouped form for a whole split: one video x up to 4 of its queries per group (blockIdx.y), a wave per half window --
+// pf16_half_block with four query slots, so the bits of frame_score_bf16_kernel -- and NO intermediate planes: the half-window
+// max goes straight into the two windows that contain the half window, the first-frame score (odd W) into the window before,
+// by atomic max on the window scores (preset to -inf by win_fill_seg_kernel).  max is order-free, so the result is the one
+// window_combine_kernel computes, bit for bit; topk_seg_kernel reads it unchanged.  (Ordinary loads: the video's other groups
+// read the same rows again.)
+__device__ __forceinline__ void pf_atomic_max(float* p, float v) {      // *p = max(*p, v) on the fp32 order; NaN is dropped (fmaxf)
+    if (v != v) return;
+    if (__float_as_int(v) >= 0) atomicMax(reinterpret_cast<int*>(p), __float_as_int(v));
+    else atomicMin(reinterpret_cast<unsigned*>(p), __float_as_uint(v));
+}
+
+__global__ __launch_bounds__(256) void win_fill_seg_kernel(const int64_t* __restrict__ q_win_off, const int* __restrict__ q_ctx_l,
+                                                           int S, float* __restrict__ win) {
+    const int q = blockIdx.y;
+    const int nw = (q_ctx_l[q] + S - 1) / S + 1;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < nw) win[q_win_off[q] + i] = -INFINITY;
+}
+
+template <int VPL>
+__global__ __launch_bounds__(256) void frame_score_groups_bf16_kernel(const uint16_t* __restrict__ arena, int dv,
+                                                                      const float* __restrict__ cls,
+                                                                      const int64_t* __restrict__ g_row0,
+                                                                      const int* __restrict__ g_ctx_l,
+                                                                      const int* __restrict__ g_q,
+                                                                      const int64_t* __restrict__ q_win_off, int S, int odd,
+                                                                      float* __restrict__ win) {
+    constexpr int RPW = 4, QG = 4, NV = RPW * QG;
+    const int g = blockIdx.y;
+    const int ctx_l = g_ctx_l[g];
+    const int nh = (ctx_l + S - 1) / S;
+    const int lane = threadIdx.x & 63;
+    const int wave_id = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int n_waves = gridDim.x * 4;
+    if (wave_id >= nh) return;
+    const uint16_t* vid = arena + g_row0[g] * dv;
+    int qi[QG];
+    float q[QG][VPL][8];
+#pragma unroll
+    for (int j = 0; j < QG; ++j) {
+        qi[j] = g_q[g * 4 + j];
+        pf16_load_query<VPL>(cls + (size_t)(qi[j] >= 0 ? qi[j] : g_q[g * 4]) * dv, dv, lane, q[j]);
+    }
+    const int my_j = lane / (64 / NV), my_r = my_j / QG, my_g = my_j % QG;
+    const bool out_lane = (lane & (64 / NV - 1)) == 0 && my_r == 0;
+    int my_qi = qi[0];
+#pragma unroll
+    for (int j = 1; j < QG; ++j) my_qi = my_g == j ? qi[j] : my_qi;
+    for (int h = wave_id; h < nh; h += n_waves) {
+        const int n = min(S, ctx_l - h * S);
+        float first = 0.f;
+        const float m = pf16_half_block<VPL, QG, RPW, false>(vid + (size_t)h * S * dv, n, dv, q, lane, 0, 1, first);
+        if (out_lane && my_qi >= 0) {
+            float* w = win + q_win_off[my_qi];
+            pf_atomic_max(w + h, m);
+            pf_atomic_max(w + h + 1, m);
+            if (odd && h >= 1) pf_atomic_max(w + h - 1, first);
+        }
+    }
+}
+
 }  // namespace cone
 
 extern "C" int64_t cone_num_windows(int64_t ctx_l, int W) {
@@ -1051,6 +1411,71 @@ extern "C" int cone_prefilter_scores(const float* vid, int64_t ctx_l, int dv, co
 extern "C" int cone_prefilter_scores_split(const float* vid, int64_t ctx_l, int dv, const float* txt, int nq, int W,
                                            int S, float* win_scores, void* ws, size_t ws_bytes, void* stream) {
     return prefilter_scores_impl(vid, ctx_l, dv, txt, nq, W, S, nullptr, win_scores, ws, ws_bytes, stream, true);
+}
+
+// ---- the opt-in bf16 pre-filter: entries ----
+extern "C" size_t cone_prefilter_scores_bf16_workspace(int64_t ctx_l, int nq, int W) {
+    return cone_prefilter_scores_workspace(ctx_l, nq, W);           // the two planes (half-window max, first-frame score)
+}
+
+#define CONE_PF16_REQUIRE_ARENA(name, p, dv)                                                                              \
+    CONE_REQUIRE((dv) > 0 && (dv) % 32 == 0 && (dv) <= 1024, name ": feature dim %d must be a multiple of 32 and <= 1024", dv); \
+    CONE_REQUIRE(((uintptr_t)(p) & 15) == 0, name ": the bf16 arena must be 16-B aligned (16-B lane loads)")
+
+extern "C" int cone_prefilter_scores_bf16(const uint16_t* vid, int64_t ctx_l, int dv, const float* txt, int nq, int W, int S,
+                                          float* win_scores, void* ws, size_t ws_bytes, void* stream) {
+    CONE_REQUIRE(vid && txt && win_scores, "prefilter (bf16): null argument");
+    CONE_REQUIRE(ctx_l > 0 && nq > 0 && W > 0 && S > 0 && S == W / 2, "prefilter (bf16): bad sizes ctx_l=%lld nq=%d W=%d S=%d",
+                 (long long)ctx_l, nq, W, S);
+    CONE_PF16_REQUIRE_ARENA("prefilter (bf16)", vid, dv);
+    CONE_REQUIRE(((uintptr_t)txt & 15) == 0, "prefilter (bf16): the query vectors must be 16-B aligned");
+    const size_t need = cone_prefilter_scores_bf16_workspace(ctx_l, nq, W);
+    CONE_REQUIRE(ws && ws_bytes >= need, "prefilter (bf16): workspace too small (%zu < %zu)", ws_bytes, need);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t nh = (ctx_l + S - 1) / S;
+    float* hm = (float*)ws;
+    float* fr = (float*)((char*)ws + need / 2);
+    int rc;
+    if (nq >= CONE_PF16_MQ_MIN) rc = cone::launch_frame_scores_mq_bf16(vid, ctx_l, dv, S, nh, txt, nq, hm, fr, s);
+    else if (dv <= 512) rc = cone::launch_frame_scores_bf16<1>(vid, ctx_l, dv, S, nh, txt, nq, hm, fr, s);
+    else rc = cone::launch_frame_scores_bf16<2>(vid, ctx_l, dv, S, nh, txt, nq, hm, fr, s);
+    if (rc) return rc;
+    hipLaunchKernelGGL(cone::window_combine_kernel, dim3((unsigned)((nh + 1 + 255) / 256), nq), dim3(256), 0, s, hm, fr, nh,
+                       W & 1, win_scores);
+    CONE_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cone_prefilter_batched_bf16(const uint16_t* arena, int dv, const float* cls, const int64_t* g_row0,
+                                           const int32_t* g_ctx_l, const int32_t* g_q, int ng, int max_ctx_l,
+                                           const int64_t* q_win_off, const int32_t* q_ctx_l, int nq, int W, int S,
+                                           float* win_scores, int k, int32_t* topk_idx, void* stream) {
+    CONE_REQUIRE(arena && cls && g_row0 && g_ctx_l && g_q && q_win_off && q_ctx_l && win_scores && topk_idx,
+                 "prefilter_batched (bf16): null argument");
+    CONE_REQUIRE(ng > 0 && nq > 0 && max_ctx_l > 0 && W > 0 && S > 0 && S == W / 2 && k > 0, "prefilter_batched (bf16): bad sizes");
+    CONE_PF16_REQUIRE_ARENA("prefilter_batched (bf16)", arena, dv);
+    CONE_REQUIRE(((uintptr_t)cls & 15) == 0, "prefilter_batched (bf16): the query vectors must be 16-B aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const int max_nh = (max_ctx_l + S - 1) / S, max_nw = max_nh + 1;
+    hipLaunchKernelGGL(cone::win_fill_seg_kernel, dim3((max_nw + 255) / 256, nq), dim3(256), 0, s, q_win_off, q_ctx_l, S,
+                       win_scores);
+    CONE_LAUNCH_CHECK();
+    int bx = (max_nh + 3) / 4;                  // a wave per half window of the longest video
+    if (bx > 2048) bx = 2048;
+    const dim3 grid((unsigned)bx, ng);
+    {
+        cone::ProfScope ps(cone::PK_FRAME_SCORE, max_ctx_l, dv, ng, nullptr, s);
+        if (dv <= 512)
+            hipLaunchKernelGGL(cone::frame_score_groups_bf16_kernel<1>, grid, dim3(256), 0, s, arena, dv, cls, g_row0, g_ctx_l, g_q,
+                               q_win_off, S, W & 1, win_scores);
+        else
+            hipLaunchKernelGGL(cone::frame_score_groups_bf16_kernel<2>, grid, dim3(256), 0, s, arena, dv, cls, g_row0, g_ctx_l, g_q,
+                               q_win_off, S, W & 1, win_scores);
+    }
+    CONE_LAUNCH_CHECK();
+    hipLaunchKernelGGL(cone::topk_seg_kernel, dim3(nq), dim3(256), 0, s, win_scores, q_win_off, q_ctx_l, S, k, topk_idx);
+    CONE_LAUNCH_CHECK();
+    return 0;
 }
 
 extern "C" int cone_prefilter_batched(const float* arena, int dv, const float* cls, const int64_t* g_row0,

@@ -108,6 +108,74 @@ int launch_l2norm(const float* x, int64_t n_rows, int dim, float eps, float* out
     return 0;
 }
 
+// ---- producers of the bf16 context arena (the opt-in bf16 pre-filter, prefilter.hip) ----------------------------------
+// two floats -> packed bf16 pair, round to nearest even (v_cvt_pk_bf16_f32): what torch.Tensor.bfloat16() stores
+typedef float ro_f2 __attribute__((ext_vector_type(2)));
+typedef __bf16 ro_b2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned ro_pk_bf16(float a, float b) {
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(ro_f2{a, b}, ro_b2));
+}
+
+// l2norm_kernel whose store is bf16: the SAME arithmetic up to the quotient (a copy, statement for statement: the value
+// stored is bf16_rne of what l2norm_kernel stores), 8 B per lane and float4 instead of 16 -- the fp32 normalised rows never
+// exist in memory.
+__global__ __launch_bounds__(256) void l2norm_bf16_kernel(const float* __restrict__ x, int64_t n_rows, int dim,
+                                                          float eps, int clamp, uint16_t* out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n_rows) return;
+    const float* xr = x + row * dim;
+    const int nv = dim >> 2;
+    float4 v[4];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = lane + 64 * i;
+        if (c < nv) {
+            v[i] = reinterpret_cast<const float4*>(xr)[c];
+            s += (v[i].x * v[i].x + v[i].y * v[i].y) + (v[i].z * v[i].z + v[i].w * v[i].w);
+        }
+    }
+    const float nrm = clamp ? fmaxf(sqrtf(wave_sum(s)), eps) : sqrtf(wave_sum(s)) + eps;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = lane + 64 * i;
+        if (c < nv) {
+            float4 o;
+            o.x = v[i].x / nrm; o.y = v[i].y / nrm; o.z = v[i].z / nrm; o.w = v[i].w / nrm;
+            reinterpret_cast<uint2*>(out + row * dim)[c] = make_uint2(ro_pk_bf16(o.x, o.y), ro_pk_bf16(o.z, o.w));
+        }
+    }
+}
+
+int launch_l2norm_bf16(const float* x, int64_t n_rows, int dim, float eps, uint16_t* out, hipStream_t s, int clamp) {
+    CONE_REQUIRE(dim % 4 == 0 && dim <= 1024, "l2norm (bf16 store): dim=%d must be a multiple of 4 and <= 1024", dim);
+    if (n_rows <= 0) return 0;
+    hipLaunchKernelGGL(l2norm_bf16_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, s, x, n_rows, dim, eps,
+                       clamp, out);
+    CONE_LAUNCH_CHECK();
+    return 0;
+}
+
+// out = bf16_rne(x), n4 float4 (n_rows * dim / 4: dim is a multiple of 4): 16 B in, 8 B out per thread and step
+__global__ __launch_bounds__(256) void rows_to_bf16_kernel(const float* __restrict__ x, int64_t n4, uint16_t* __restrict__ out) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        const float4 v = reinterpret_cast<const float4*>(x)[i];
+        reinterpret_cast<uint2*>(out)[i] = make_uint2(ro_pk_bf16(v.x, v.y), ro_pk_bf16(v.z, v.w));
+    }
+}
+
+int launch_rows_to_bf16(const float* x, int64_t n_rows, int dim, uint16_t* out, hipStream_t s) {
+    CONE_REQUIRE(dim > 0 && dim % 4 == 0, "rows_to_bf16: dim=%d must be a positive multiple of 4", dim);
+    if (n_rows <= 0) return 0;
+    const int64_t n4 = n_rows * (dim >> 2);
+    int64_t blocks = (n4 + 255) / 256;
+    if (blocks > 256 * 64) blocks = 256 * 64;           // grid-stride past 64 workgroups per CU
+    hipLaunchKernelGGL(rows_to_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, n4, out);
+    CONE_LAUNCH_CHECK();
+    return 0;
+}
+
 // dst rows [period, n_rows) <- rows (r % period) of the same matrix (256 floats per row): replicates the decoder's
 // window-independent first-layer rows to every window.
 __global__ __launch_bounds__(256) void tile_rows_kernel(float* x, int period, int64_t n_rows) {

@@ -372,7 +372,10 @@ def prefilter(model, store: FeatureStore, opt, k=None, keep=None):
     plan = store.prefilter_plan()
     r0, r1 = plan["band"]
     vid_norm = ops.l2_normalize(store.vid_raw[r0:r1], 1e-5)   # PreFilteringDataset :459
-    ctx = model.adapter_norm(vid_norm)                        # :254-258, all videos in one pass
+    # :254-258, all videos in one pass; opt.prefilter_bf16 (opt-in): the adapter's last stage stores bf16 rows and the batched
+    # entry dispatches on the arena's dtype (cone_prefilter_batched_bf16) -- nothing downstream changes
+    bf16 = bool(getattr(opt, "prefilter_bf16", False))
+    ctx = model.adapter_norm(vid_norm, out_dtype=torch.bfloat16 if bf16 else torch.float32)
     cls_norm = store.cls_raw if store.cls_normalized else ops.l2_normalize(store.cls_raw, 1e-5)     # :473
     if keep is not None:
         keep["cls_norm"] = cls_norm
@@ -873,6 +876,7 @@ def _graph_key(model, opt):
             opt.eval_bsz, opt.max_v_l, opt.nms_thd, opt.max_before_nms, opt.max_after_nms, bool(opt.no_sort_results),
             bool(getattr(opt, "need_saliency", False)), bool(getattr(opt, "need_aux", False)),
             int(getattr(opt, "window_batch", 32768)), float(opt.clip_length),
+            bool(getattr(opt, "prefilter_bf16", False)),       # stage A's arithmetic: a capture holds one mode's launches
             # the handle's option switches (bf16, split_bf16, the A/B switches): flipping one after a capture must not
             # replay the other setting's launches
             tuple(sorted(getattr(model, "_options", {}).items())))

@@ -26,11 +26,15 @@ LOCALIZER_OPT = dict(MODEL_DEFAULTS, v_motion_feat_dim=256, v_appear_feat_dim=25
 
 
 class CONELocalizator:
-    def __init__(self, load_checkpoint_path=None, device="cuda", state_dict=None, hip_graph=False, **overrides):
+    def __init__(self, load_checkpoint_path=None, device="cuda", state_dict=None, hip_graph=False, prefilter_bf16=False,
+                 **overrides):
         """``hip_graph`` (cone_amd extension, opt-in): a call at a (video length, query length) shape seen before replays the
         whole launch sequence as ONE hipGraph launch -- the inputs are copied into the capture's own buffers first, the kept
-        moments are read back as usual; same kernels, same order, same bits as the eager call."""
+        moments are read back as usual; same kernels, same order, same bits as the eager call.
+        ``prefilter_bf16`` (cone_amd extension, opt-in): the window ranking of ``predict_moment`` on bf16 adapted rows and bf16
+        operands (the opt-in bf16 pre-filter: NOT fp32-accurate); everything after the ranking is unchanged."""
         self.hip_graph = bool(hip_graph)
+        self.prefilter_bf16 = bool(prefilter_bf16)
         self.args = SimpleNamespace(**dict(LOCALIZER_OPT, **overrides))
         self.localizator, _ = build_model(self.args)
         if state_dict is None:
@@ -54,14 +58,15 @@ class CONELocalizator:
         """Index metadata of one (video length, query length) shape on the device, built once: the latency path uploads
         nothing per call (a pageable H2D copy waits for the stream to drain)."""
         cache = self.__dict__.setdefault("_consts", {})
-        c = cache.get((ctx_l, n_tok))
+        key = (ctx_l, n_tok, self.prefilter_bf16)       # (the entry holds the shape's captured graph: one per pre-filter mode)
+        c = cache.get(key)
         if c is None:
             if len(cache) > 64:
                 cache.clear()
             dev, a = self.device, self.args
             K = min(a.topk_window, ops.num_windows(ctx_l, a.max_v_l))
             t = lambda v: torch.tensor(v, dtype=torch.int32, device=dev)
-            c = cache[(ctx_l, n_tok)] = dict(
+            c = cache[key] = dict(
                 K=K, q_ctx_l=t([ctx_l]), q_vid_off=t([0]), tok_off=t([0, n_tok]), tok_len=t([n_tok]),
                 batch_pad=t([a.max_v_l]), full_w=torch.full((K,), a.max_v_l, dtype=torch.int32, device=dev),
                 tok_idx=torch.arange(n_tok, dtype=torch.int32, device=dev),
@@ -76,7 +81,8 @@ class CONELocalizator:
         vid = ops.l2_normalize(video_feats, 1e-5, clamp=True)                                  # :129
         tok = ops.l2_normalize(text_token_feats, 1e-5, clamp=True)                             # :133
         cls = text_cls_feat.reshape(1, -1)
-        adapted = m.adapter_norm(vid, renorm=False)                                           # :135-138
+        adapted = m.adapter_norm(vid, renorm=False,                                           # :135-138
+                                 out_dtype=torch.bfloat16 if self.prefilter_bf16 else torch.float32)
         _, ws = ops.prefilter_scores(adapted, cls, W, frame_scores=False)                     # :83-100 (stable tie order)
         widx, _ = ops.topk_windows(ws, K)
         # every window counts as padded to max_v_l (the reference pads each to (max_v_l, max_q_l), :150-170)

@@ -275,17 +275,20 @@ class CONE:
         return match
 
     # ---- arena-level entry points used by the eval driver ---------------------------------------
-    def adapter_norm(self, vid_rows, renorm: bool = True):
+    def adapter_norm(self, vid_rows, renorm: bool = True, out_dtype=torch.float32):
         """cone/inference.py:254-258 over any number of clip rows (n, dv); renorm=False keeps
-        adapter(x)+x un-normalised (run_on_video/cone_localizator.py:135-138)."""
+        adapter(x)+x un-normalised (run_on_video/cone_localizator.py:135-138).  ``out_dtype=torch.bfloat16`` (the opt-in
+        bf16 pre-filter's arena): the last stage stores bf16_rne of the fp32 value (cone_adapter_norm_bf16)."""
         lib, h = _lib.load(), self._h()
+        if out_dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"adapter_norm: out_dtype must be torch.float32 or torch.bfloat16, got {out_dtype}")
         x = self._f32(vid_rows)
         self._check_dim(x, self.args.v_appear_feat_dim, "appearance clip features")
-        out = torch.empty_like(x)
+        out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
         nbytes = lib.cone_adapter_norm_workspace(h, x.shape[0])
         ws = self._ws.get(nbytes, x.device)
-        _lib.check(lib.cone_adapter_norm(h, _lib.ptr(x), x.shape[0], _lib.ptr(out), 1 if renorm else 0, _lib.ptr(ws),
-                                         ws.numel(), _lib.stream()))
+        fn = lib.cone_adapter_norm_bf16 if out_dtype == torch.bfloat16 else lib.cone_adapter_norm
+        _lib.check(fn(h, _lib.ptr(x), x.shape[0], _lib.ptr(out), 1 if renorm else 0, _lib.ptr(ws), ws.numel(), _lib.stream()))
         return out
 
     def project(self, which: int, rows, ws=None):

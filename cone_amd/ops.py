@@ -29,6 +29,16 @@ def l2_normalize(x: torch.Tensor, eps: float = 1e-5, clamp: bool = False) -> tor
     return out.view(x.shape)
 
 
+def rows_to_bf16(x: torch.Tensor) -> torch.Tensor:
+    """bf16 (round to nearest even) copy of fp32 rows (..., dim), dim a multiple of 4: the context arena of the opt-in bf16
+    pre-filter for callers that index a resident video once and query it many times (cone_rows_to_bf16)."""
+    lib = _lib.load()
+    x2 = x.to(torch.float32).contiguous().view(-1, x.shape[-1])
+    out = torch.empty(x2.shape, dtype=torch.bfloat16, device=x2.device)
+    _lib.check(lib.cone_rows_to_bf16(_lib.ptr(x2), x2.shape[0], x2.shape[1], _lib.ptr(out), _lib.stream()))
+    return out.view(x.shape)
+
+
 def num_windows(ctx_l: int, max_v_l: int) -> int:
     return math.ceil(ctx_l / int(max_v_l / 2)) + 1
 
@@ -42,12 +52,29 @@ def prefilter_scores(vid_ctx: torch.Tensor, cls_txt: torch.Tensor, max_v_l: int,
     frame-score stream; ``frame_scores=False`` skips writing the (nq, ctx_l) matrix (returned as None) -- the
     reference only computes it to take the window max, and so does every caller in this package.  ``split_bf16`` (opt-in,
     with ``frame_scores=False``): 8 or more queries run on the bf16 matrix cores, each fp32 product as six partial products of
-    three-piece bf16 operands (fp32 accuracy, HBM-bound at 64 queries)."""
+    three-piece bf16 operands (fp32 accuracy, HBM-bound at 64 queries).
+
+    A **bf16** ``vid_ctx`` (``rows_to_bf16`` / ``model.adapter_norm(..., out_dtype=torch.bfloat16)``) selects the opt-in bf16
+    pre-filter (cone_prefilter_scores_bf16): score = sum of bf16(ctx) * bf16(cls) products in fp32 -- NOT fp32-accurate, window
+    scores only (``frame_scores=False``), and not combinable with ``split_bf16``."""
     lib = _lib.load()
     ctx_l, dv = vid_ctx.shape
     nq = cls_txt.shape[0]
     W, S = max_v_l, int(max_v_l / 2)
     nw = num_windows(ctx_l, max_v_l)
+    if vid_ctx.dtype == torch.bfloat16:
+        if frame_scores:
+            raise ValueError("a bf16 context arena computes the window scores only: frame_scores=True is not available "
+                             "(pass frame_scores=False)")
+        if split_bf16:
+            raise ValueError("a bf16 context arena excludes split_bf16=True: the three-piece form splits fp32 rows")
+        ws = torch.empty(nq, nw, device=vid_ctx.device)
+        nbytes = lib.cone_prefilter_scores_bf16_workspace(ctx_l, nq, W)
+        scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=vid_ctx.device)
+        _lib.check(lib.cone_prefilter_scores_bf16(_lib.ptr(vid_ctx, torch.bfloat16), ctx_l, dv,
+                                                  _lib.ptr(cls_txt, torch.float32), nq, W, S, _lib.ptr(ws),
+                                                  _lib.ptr(scratch), scratch.numel(), _lib.stream()))
+        return None, ws
     fs = torch.empty(nq, ctx_l, device=vid_ctx.device) if frame_scores else None
     ws = torch.empty(nq, nw, device=vid_ctx.device)
     nbytes = (lib.cone_prefilter_scores_split_workspace(ctx_l, nq, W, dv) if split_bf16
@@ -69,10 +96,21 @@ def prefilter_scores(vid_ctx: torch.Tensor, cls_txt: torch.Tensor, max_v_l: int,
 def prefilter_batched(ctx_arena, cls_norm, plan, max_v_l: int, k: int):
     """cone/inference.py:276-301 for every query of a split in three launches.  `plan` is the static
     index metadata built by FeatureStore.prefilter_plan().  Returns (topk_idx (nq,k) int32 with -1
-    padding, frame_scores flat, win_scores flat)."""
+    padding, frame_scores flat, win_scores flat).  A **bf16** arena selects the opt-in bf16 pre-filter
+    (cone_prefilter_batched_bf16): no frame scores (None is returned in their place)."""
     lib = _lib.load()
     dev = ctx_arena.device
     nq = cls_norm.shape[0]
+    if ctx_arena.dtype == torch.bfloat16:
+        ws = torch.empty(plan["win_total"], device=dev)
+        idx = torch.empty(nq, k, dtype=torch.int32, device=dev)
+        _lib.check(lib.cone_prefilter_batched_bf16(
+            _lib.ptr(ctx_arena, torch.bfloat16), ctx_arena.shape[1], _lib.ptr(cls_norm, torch.float32),
+            _lib.ptr(plan["g_row0"], torch.int64), _lib.ptr(plan["g_ctx_l"], torch.int32),
+            _lib.ptr(plan["g_q"], torch.int32), plan["ng"], plan["max_ctx_l"],
+            _lib.ptr(plan["q_win_off"], torch.int64), _lib.ptr(plan["q_ctx_l"], torch.int32), nq, max_v_l,
+            int(max_v_l / 2), _lib.ptr(ws), k, _lib.ptr(idx), _lib.stream()))
+        return idx, None, ws
     fs = torch.empty(plan["fs_total"], device=dev)
     ws = torch.empty(plan["win_total"], device=dev)
     idx = torch.empty(nq, k, dtype=torch.int32, device=dev)

@@ -212,11 +212,16 @@ def merge_topk(vals: torch.Tensor, idxs: torch.Tensor, k: int, topk_fn: Callable
 
 
 def prefilter_ctx_sharded(ctx_local: torch.Tensor, ctx_l: int, cls_norm: torch.Tensor, max_v_l: int, k: int,
-                          group=None, window_scores_fn: Callable = None, topk_fn: Callable = None):
+                          group=None, window_scores_fn: Callable = None, topk_fn: Callable = None,
+                          prefilter_bf16: bool = False):
     """Pre-filter (cone/inference.py:284-299) of ONE video whose clip rows are sharded over the ranks of
     `group` as ``ctx_shard`` prescribes.  Every rank returns the same (idx (nq,k) int32 global window
     ids, -1 padded; val (nq,k)).  One all_gather of k x (4 + 4) B per query (the window ids travel as exact
-    fp32 bit patterns next to the scores) -- no feature row ever moves."""
+    fp32 bit patterns next to the scores) -- no feature row ever moves.
+    ``prefilter_bf16`` (``opt.prefilter_bf16`` / ``--prefilter_bf16``) is refused: the ctx-sharded merge runs in fp32 only."""
+    if prefilter_bf16 or ctx_local.dtype == torch.bfloat16:
+        raise ValueError("prefilter_bf16 (--prefilter_bf16) is not available with the ctx-sharded pre-filter "
+                         "(prefilter_ctx_sharded): run the one-video split without it, or unsharded")
     if window_scores_fn is None or topk_fn is None:
         from . import ops
         window_scores_fn = window_scores_fn or (lambda v, c, w: ops.prefilter_scores(v, c, w, frame_scores=False)[1])
@@ -314,6 +319,9 @@ def prefilter_one_video_ctx_sharded(store, opt, hooks, group=None):
     normalises and scores only the clip rows its window range covers (``ctx_shard``: 1 / world of the video + a W - S
     halo), keeps a local stable top-k, and ONE all_gather of k (score, window) pairs per query yields the same
     (nq, topk) window table on every rank -- bit-identical to the single-GPU pre-filter, ties included."""
+    if getattr(opt, "prefilter_bf16", False):
+        raise ValueError("prefilter_bf16 (--prefilter_bf16) is not available with the ctx-sharded pre-filter "
+                         "(prefilter_one_video_ctx_sharded): run the one-video split without it, or unsharded")
     vids = np.unique(np.asarray(store.q_vid))
     if len(vids) != 1:
         raise ValueError("the ctx-sharded pre-filter takes a split over ONE video; several videos shard by query / window")

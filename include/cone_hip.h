@@ -175,6 +175,48 @@ int cone_prefilter_batched(const float* arena, int dv, const float* cls, const i
                            int nq, int W, int S, float* frame_scores, float* win_scores, int k,
                            int32_t* topk_idx, void* stream);
 
+/* ---- OPT-IN bf16 pre-filter (additive in ABI 8): bf16 context rows, bf16 operands, fp32 accumulation.
+ * ONE arithmetic contract for every entry and every kernel form below:
+ *     score[q][f] = sum_c bf16(ctx[f][c]) * bf16(cls[q][c])
+ * both operands rounded ONCE, round to nearest even (the context rows by the producers below, the query vectors by the
+ * scoring kernels -- the few-query streaming form rounds them too, so a query's ranks do not depend on how many queries
+ * share its launch beyond a summation order); every product is exact in fp32, the sum is fp32 in the form's own order.
+ * Window scores are the max over the same frame ranges as cone_prefilter_scores: win[i] = max over frames
+ * [max((i-1)S,0), min((i-1)S+W, ctx_l)) = max(hm[i-1], hm[i], W odd ? score of frame (i+1)S : -inf) with hm[h] the max over
+ * half window h = frames [hS, (h+1)S) -- the half windows that exist, 0 <= h < ceil(ctx_l/S).  No frame-score matrix.
+ * NOT fp32-accurate: each operand carries a relative error of up to 2^-9, a score of unit-norm rows an absolute error of up
+ * to ~2^-8; a pre-filter only RANKS windows, which is why a caller may accept that for half the arena bytes (and twice the
+ * video length per GB).  The defaults (cone_prefilter_scores, cone_prefilter_batched) stay exact fp32.
+ * Named checks: dv a multiple of 32 and <= 1024 (the model's own rule); the bf16 arena 16-B aligned. */
+
+/* out = bf16_rne(x), x (n_rows, dim) fp32, dim a multiple of 4: for callers that index a resident video once (what
+ * cone/inference.py:254-258 recomputes per call) and query it many times. */
+int cone_rows_to_bf16(const float* x, int64_t n_rows, int dim, uint16_t* out, void* stream);
+
+/* cone_adapter_norm (A2, cone/inference.py:254-258; renorm == 0: run_on_video/cone_localizator.py:135-138) whose LAST stage
+ * stores bf16: out = bf16_rne(the fp32 value cone_adapter_norm stores), bit for bit.  With renorm != 0 the L2 norm's own
+ * store is the bf16 one: the normalised fp32 rows are never written.  ws >= cone_adapter_norm_workspace(m, n_rows). */
+int cone_adapter_norm_bf16(const cone_model* m, const float* x, int64_t n_rows, uint16_t* out, int renorm,
+                           void* ws, size_t ws_bytes, void* stream);
+
+/* A3+A4, cone/inference.py:284-296, under the contract above, for all queries of one video: vid (ctx_l,dv) bf16,
+ * txt (nq,dv) fp32 (rounded here), win_scores (nq,num_window) fp32.  Forms (chosen by nq): 1 - 4 queries stream the rows
+ * once (16-B non-temporal lane loads of 8 bf16, widened by a shift; a query's bits do not depend on the others of the
+ * launch); 5 or more run v_mfma_f32_16x16x32_bf16 tiles of 16 / 32 / 64 queries per pass (another summation order).
+ * ws >= cone_prefilter_scores_bf16_workspace(ctx_l, nq, W) bytes. */
+size_t cone_prefilter_scores_bf16_workspace(int64_t ctx_l, int nq, int W);
+int cone_prefilter_scores_bf16(const uint16_t* vid, int64_t ctx_l, int dv, const float* txt, int nq, int W, int S,
+                               float* win_scores, void* ws, size_t ws_bytes, void* stream);
+
+/* A3+A4 for a whole split (cone/inference.py:276-301) under the contract above: cone_prefilter_batched with a bf16 arena
+ * and without the frame scores (no q_fs_off / frame_scores).  Every group runs the streaming form: a query's window scores
+ * are those of cone_prefilter_scores_bf16 with 1 - 4 queries on the same rows, bit for bit.  win_scores and topk_idx as
+ * in cone_prefilter_batched. */
+int cone_prefilter_batched_bf16(const uint16_t* arena, int dv, const float* cls, const int64_t* g_row0,
+                                const int32_t* g_ctx_l, const int32_t* g_q, int ng, int max_ctx_l,
+                                const int64_t* q_win_off, const int32_t* q_ctx_l, int nq, int W, int S,
+                                float* win_scores, int k, int32_t* topk_idx, void* stream);
+
 /* A5, eval branch of StartEndDataset.__getitem__ + collate (cone/ego4d_mad_dataloader.py:144-159, 229-234, 305-344) as
  * index arithmetic: win_idx (nq, K) int32 holds the ranked window indices of every query, valid entries first (a video of
  * fewer than K windows: the tail is -1 and never read).  Row b of every output is (query row_q[b], rank slot row_slot[b])
