@@ -152,6 +152,11 @@ _SIGNATURES = {
     "cone_test_gemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                  C.c_int, C.c_int, C.c_void_p]),
+    # cone_test_gemm_bf16(<cone_test_gemm's up to flags>, img, ldc, r_mod, M_dev, stream): the row GEMM of option general_bf16
+    "cone_test_gemm_bf16_image_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "cone_test_gemm_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                      C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cone_test_ffn": (C.c_int, [C.c_void_p] * 8 + [C.c_int, C.c_int, C.c_void_p]),
     "cone_test_proj_ffn": (C.c_int, [C.c_void_p] * 13 + [C.c_int, C.c_int, C.c_void_p]),
     "cone_test_tail_form": (C.c_int, [C.c_void_p] * 13 + [C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int, C.c_int,

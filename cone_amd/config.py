@@ -18,7 +18,8 @@ from types import SimpleNamespace
 CLI_WINS = ("eval_path", "eval_split_name", "results_root", "num_workers", "nms_thd",
             "debug", "save_all", "max_before_nms", "max_after_nms", "max_pred_l",
             "min_pred_l", "eval_bsz", "data_ratio", "topk_window", "resume",
-            "resume_all", "no_sort_results", "packed_features", "split_bf16", "bf16", "prefilter_bf16", "gpus",
+            "resume_all", "no_sort_results", "packed_features", "split_bf16", "bf16", "prefilter_bf16", "general_bf16",
+            "gpus",
             "dist_backend")
 
 MODEL_DEFAULTS = dict(
@@ -124,6 +125,13 @@ def build_parser() -> argparse.ArgumentParser:
                         "and bf16 operands: window score = sum of bf16(ctx) * bf16(cls) products, fp32 accumulation.  NOT "
                         "fp32-accurate (~2^-8 absolute on unit-norm rows): windows whose scores are closer than that may swap "
                         "ranks.  Half the arena bytes of the HBM-bound stream; stage B and C are unchanged")
+    p.add_argument("--general_bf16", action="store_true",
+                   help="(cone_amd extension, opt-in; a switch of its own, independent of --bf16) for checkpoints that run the "
+                        "general path -- hidden_dim / nheads other than 256 / 8, or windows of 257 - 1024 tokens: its layer GEMMs "
+                        "(q|k|v, attention output projections, linear1, linear2, the decoder's K / V and query projections) with "
+                        "operands rounded once to bf16 on the bf16 matrix cores, fp32 accumulation.  NOT fp32-accurate: errors are "
+                        "those of bf16 operands, within the reference model's own bf16-autocast error.  LayerNorm, attention, heads "
+                        "and activations in memory stay fp32.  Refused for a 256 / 8 checkpoint with short windows: use --bf16")
     p.add_argument("--gpus", type=int, default=1,
                    help="(cone_amd extension) evaluate the split sharded over N GPUs of this node: a plain process starts "
                         "N ranks through torch.distributed.run; under torchrun it must equal WORLD_SIZE.  Rank 0 writes the files")

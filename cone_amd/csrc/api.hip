@@ -88,6 +88,14 @@ struct cone_model {
     // handle whose shape is not 256 / 8 (gen_native), or a 256 / 8 handle with option general_shape = 1 (A/B parity only)
     int gen_native = 0;
     int opt_general = 0;
+    // OPT-IN (option general_bf16; general path only): its layer GEMMs -- encoder q | k, v, out_proj, linear1 / 2, the stacked
+    // decoder K / V, the decoder's in-projections, out-projections and linear1 / 2 -- with operands rounded ONCE to bf16 on the
+    // bf16 matrix cores (gemm_bf16.hip: NOT fp32-accurate).  Their weight images: one allocation, built at the first
+    // general_bf16 = 1 and kept until the handle is destroyed, found by the fp32 weight's address.
+    int opt_general_bf16 = 0;
+    char* gen_bf16_img = nullptr;
+    struct GenImage { const float* W; const void* img; };
+    std::vector<GenImage> gen_bf16_images;
     // option max_window_tokens (default CONE_MAX_WINDOW_TOKENS; up to CONE_MAX_LONG_WINDOW_TOKENS): the longest window this
     // handle takes.  Above 256 EVERY forward of the handle runs the general path, whatever the call's own lengths, and its
     // attention launches carry this value as their key capacity (the streaming core of general.hip) -- a window's bits
@@ -118,6 +126,7 @@ static void free_model(cone_model* m) {
     if (m->arena) (void)hipFree(m->arena);
     if (m->split_img) (void)hipFree(m->split_img);
     if (m->bf16_img) (void)hipFree(m->bf16_img);
+    if (m->gen_bf16_img) (void)hipFree(m->gen_bf16_img);
     if (m->tab_arena) (void)hipFree(m->tab_arena);
     delete m;
 }
@@ -930,10 +939,19 @@ static int forward_general(const cone_model* m, const FwdCall& call, void* ws, s
     RUN(launch_gen_pack_pos(call.vproj, call.vrow0, call.vlen, call.tproj, call.trow0, call.qlen, f.off, m->dim_t, f.X, f.POS, d, B,
                             Lmax, s, m->txt_pos_emb, m->txt_pos_ln.g, m->txt_pos_ln.b));
     GemmArgs g;
+    // a layer GEMM in the handle's numeric mode: exact fp32, or (general_bf16) the bf16 row GEMM on the weight's image
+    auto gemm = [&](const GemmArgs& a) {
+        if (!m->opt_general_bf16) return launch_gemm(a, s);
+        const void* img = nullptr;
+        for (const cone_model::GenImage& gi : m->gen_bf16_images)
+            if (gi.W == a.W) { img = gi.img; break; }
+        CONE_REQUIRE(img, "forward: general_bf16 is set but a weight has no bf16 image");
+        return launch_gemm_bf16(a, img, s);
+    };
     auto residual = [&](const float* A, int K, const Linear& lin, const float* R, float* C, int M, const int* M_dev) {
         GemmArgs r = G(m, A, K, lin.w, K, lin.b, C, d, M, M_dev, d, K, EPI_RESIDUAL);   // C = A W^T + b + R
         r.R = R; r.ldr = d;
-        return launch_gemm(r, s);
+        return gemm(r);
     };
     for (int l = 0; l < m->n_enc; ++l) {
         const EncLayer& e = m->enc[l];
@@ -944,18 +962,18 @@ static int forward_general(const cone_model* m, const FwdCall& call, void* ws, s
         }
         g = G(m, A, d, e.sa.in_w, d, e.sa.in_b, f.QKV, 3 * d, Mmax, Mdev, 2 * d, d);                    // q | k = (a + pos) W^T
         g.A2 = f.POS; g.lda2 = d;
-        RUN(launch_gemm(g, s));
-        RUN(launch_gemm(G(m, A, d, e.sa.in_w + 2 * d * d, d, e.sa.in_b + 2 * d, f.QKV + 2 * d, 3 * d, Mmax, Mdev, d, d), s));
+        RUN(gemm(g));
+        RUN(gemm(G(m, A, d, e.sa.in_w + 2 * d * d, d, e.sa.in_b + 2 * d, f.QKV + 2 * d, 3 * d, Mmax, Mdev, d, d)));
         RUN(launch_gen_attn(f.QKV, 3 * d, f.QKV + d, 3 * d, f.QKV + 2 * d, 3 * d, f.ATT, d, f.off, f.off, B, 0, nh, hd, kcap, s));
         if (pre) {
             RUN(residual(f.ATT, d, e.sa.out, f.X, f.X, Mmax, Mdev));                                      // src += attn
             RUN(launch_layernorm(f.X, d, e.n2.g, e.n2.b, f.X1, d, Mmax, Mdev, d, s));                     // src2 = norm2(src)
-            RUN(launch_gemm(G(m, f.X1, d, e.l1.w, d, e.l1.b, f.H, ff, Mmax, Mdev, ff, d, EPI_RELU), s));
+            RUN(gemm(G(m, f.X1, d, e.l1.w, d, e.l1.b, f.H, ff, Mmax, Mdev, ff, d, EPI_RELU)));
             RUN(residual(f.H, ff, e.l2, f.X, f.X, Mmax, Mdev));                                           // src += ffn(src2)
         } else {
             RUN(residual(f.ATT, d, e.sa.out, f.X, f.T1, Mmax, Mdev));
             RUN(launch_layernorm(f.T1, d, e.n1.g, e.n1.b, f.X1, d, Mmax, Mdev, d, s));                    // norm1(src + attn)
-            RUN(launch_gemm(G(m, f.X1, d, e.l1.w, d, e.l1.b, f.H, ff, Mmax, Mdev, ff, d, EPI_RELU), s));
+            RUN(gemm(G(m, f.X1, d, e.l1.w, d, e.l1.b, f.H, ff, Mmax, Mdev, ff, d, EPI_RELU)));
             RUN(residual(f.H, ff, e.l2, f.X1, f.T1, Mmax, Mdev));
             RUN(launch_layernorm(f.T1, d, e.n2.g, e.n2.b, f.X, d, Mmax, Mdev, d, s));                     // norm2(src + ffn)
         }
@@ -968,8 +986,8 @@ static int forward_general(const cone_model* m, const FwdCall& call, void* ws, s
     // decoder keys / values of all layers: k = (memory + pos) W_k^T + b_k, v = memory W_v^T + b_v (cone/transformer.py:308-311)
     g = G(m, MEM, d, m->dec_k.w, d, m->dec_k.b, f.KD, d * nd, Mmax, Mdev, d * nd, d);
     g.A2 = f.POS; g.lda2 = d;
-    RUN(launch_gemm(g, s));
-    RUN(launch_gemm(G(m, MEM, d, m->dec_v.w, d, m->dec_v.b, f.VD, d * nd, Mmax, Mdev, d * nd, d), s));
+    RUN(gemm(g));
+    RUN(gemm(G(m, MEM, d, m->dec_v.w, d, m->dec_v.b, f.VD, d * nd, Mmax, Mdev, d * nd, d)));
     CONE_CHECK_HIP(hipMemsetAsync(f.TGT, 0, (size_t)T * d * sizeof(float), s));                          // tgt = 0 (:66)
     auto ln = [&](const float* x, const LNorm& n, float* out) { return launch_layernorm(x, d, n.g, n.b, out, d, T, nullptr, d, s); };
     for (int l = 0; l < nd; ++l) {
@@ -979,7 +997,7 @@ static int forward_general(const cone_model* m, const FwdCall& call, void* ws, s
         if (pre) { RUN(ln(f.TGT, dl.n1, f.TGT1)); A = f.TGT1; }
         g = G(m, A, d, dl.sa.in_w, d, nullptr, f.DQK, 3 * d, T, nullptr, 3 * d, d, EPI_RESIDUAL);
         g.R = m->dec_sa_tab[l]; g.ldr = 3 * d; g.r_mod = nq;
-        RUN(launch_gemm(g, s));
+        RUN(gemm(g));
         RUN(launch_gen_attn(f.DQK, 3 * d, f.DQK + d, 3 * d, f.DQK + 2 * d, 3 * d, f.DATT, d, nullptr, nullptr, B, nq, nh, hd, nq, s));
         if (pre) {
             RUN(residual(f.DATT, d, dl.sa.out, f.TGT, f.TGT, T, nullptr));                                // tgt += sa
@@ -991,18 +1009,18 @@ static int forward_general(const cone_model* m, const FwdCall& call, void* ws, s
         // cross-attention: query (a + query_pos) W_q^T + b_q = a W_q^T + the table; keys / values of this layer from KD / VD
         g = G(m, A, d, dl.ca.in_w, d, nullptr, f.DQ, d, T, nullptr, d, d, EPI_RESIDUAL);
         g.R = m->dec_ca_tab[l]; g.ldr = d; g.r_mod = nq;
-        RUN(launch_gemm(g, s));
+        RUN(gemm(g));
         RUN(launch_gen_attn(f.DQ, d, f.KD + (size_t)l * d, d * nd, f.VD + (size_t)l * d, d * nd, f.DATT, d, nullptr, f.off, B, nq, nh,
                             hd, kcap, s));
         if (pre) {
             RUN(residual(f.DATT, d, dl.ca.out, f.TGT, f.TGT, T, nullptr));                                // tgt += ca
             RUN(ln(f.TGT, dl.n3, f.TGT1));                                                                // tgt2 = norm3(tgt)
-            RUN(launch_gemm(G(m, f.TGT1, d, dl.l1.w, d, dl.l1.b, f.DH, ff, T, nullptr, ff, d, EPI_RELU), s));
+            RUN(gemm(G(m, f.TGT1, d, dl.l1.w, d, dl.l1.b, f.DH, ff, T, nullptr, ff, d, EPI_RELU)));
             RUN(residual(f.DH, ff, dl.l2, f.TGT, f.TGT, T, nullptr));                                     // tgt += ffn(tgt2)
         } else {
             RUN(residual(f.DATT, d, dl.ca.out, f.TGT, f.TGT2, T, nullptr));
             RUN(ln(f.TGT2, dl.n2, f.TGT1));                                                               // tgt = norm2(tgt + ca)
-            RUN(launch_gemm(G(m, f.TGT1, d, dl.l1.w, d, dl.l1.b, f.DH, ff, T, nullptr, ff, d, EPI_RELU), s));
+            RUN(gemm(G(m, f.TGT1, d, dl.l1.w, d, dl.l1.b, f.DH, ff, T, nullptr, ff, d, EPI_RELU)));
             RUN(residual(f.DH, ff, dl.l2, f.TGT1, f.TGT2, T, nullptr));
             RUN(ln(f.TGT2, dl.n3, f.TGT));                                                                // tgt = norm3(tgt + ffn)
         }
@@ -1467,6 +1485,61 @@ extern "C" int cone_clip_matching(const cone_model* m, const float* cls, const f
                                        (char*)ws + c.cur, ws_bytes - c.cur, stream);
 }
 
+// The weight images of option general_bf16: every matrix forward_general's layer GEMMs read, each rounded to nearest even once
+// into the slab layout of gemm_bf16.hip (a few MB; one allocation).  Synchronous, like the constants the gemm option rebuilds.
+static int build_general_bf16_images(cone_model* m) {
+    struct Item { const float* W; int N, K; };
+    std::vector<Item> items;
+    const int d = m->d, ff = m->ff, nd = m->n_dec;
+    for (int l = 0; l < m->n_enc; ++l) {
+        const EncLayer& e = m->enc[l];
+        items.push_back({e.sa.in_w, 2 * d, d});                         // q | k
+        items.push_back({e.sa.in_w + (size_t)2 * d * d, d, d});         // v
+        items.push_back({e.sa.out.w, d, d});
+        items.push_back({e.l1.w, ff, d});
+        items.push_back({e.l2.w, d, ff});
+    }
+    items.push_back({m->dec_k.w, d * nd, d});
+    items.push_back({m->dec_v.w, d * nd, d});
+    for (int l = 0; l < nd; ++l) {
+        const DecLayer& dl = m->dec[l];
+        items.push_back({dl.sa.in_w, 3 * d, d});
+        items.push_back({dl.sa.out.w, d, d});
+        items.push_back({dl.ca.in_w, d, d});                            // the cross-attention query projection
+        items.push_back({dl.ca.out.w, d, d});
+        items.push_back({dl.l1.w, ff, d});
+        items.push_back({dl.l2.w, d, ff});
+    }
+    size_t total = 0;
+    for (const Item& it : items) {
+        CONE_REQUIRE(gemm_bf16_image_bytes(it.N, it.K), "set_option: general_bf16: a %d x %d weight has no bf16 image form", it.N, it.K);
+        total += gemm_bf16_image_bytes(it.N, it.K);
+    }
+    char* base = nullptr;
+    hipError_t e = hipMalloc((void**)&base, total);
+    if (e != hipSuccess) {
+        set_error("set_option: general_bf16: hipMalloc of %zu bytes of weight images failed: %s", total, hipGetErrorString(e));
+        return CONE_E_HIP;
+    }
+    std::vector<cone_model::GenImage> images;
+    char* ip = base;
+    int rc = 0;
+    for (const Item& it : items) {
+        rc = launch_gemm_bf16_pack(it.W, it.K, it.N, it.K, ip, nullptr);
+        if (rc) break;
+        images.push_back({it.W, ip});
+        ip += gemm_bf16_image_bytes(it.N, it.K);
+    }
+    if (rc == 0 && hipDeviceSynchronize() != hipSuccess) {
+        set_error("set_option: general_bf16: building the weight images failed");
+        rc = CONE_E_HIP;
+    }
+    if (rc) { (void)hipFree(base); return rc; }
+    m->gen_bf16_img = base;
+    m->gen_bf16_images.swap(images);
+    return 0;
+}
+
 // The options that are a field and a range: value != 0 for a switch, else inclusive bounds.
 struct OptionRow { const char* name; int cone_model::*field; int lo, hi; bool is_switch; };
 static const OptionRow OPTION_ROWS[] = {
@@ -1516,6 +1589,20 @@ extern "C" int cone_model_set_option(cone_model* m, const char* name, int value)
         (split ? m->opt_split_bf16 : m->opt_bf16) = value != 0;
         return 0;
     }
+    // the general path's bf16 GEMMs: a switch of its own (bf16 keeps its meaning and its refusals); needs a handle that runs
+    // the general path at this moment; the weight images are built at the first 1
+    if (!strcmp(name, "general_bf16")) {
+        if (value == 0) { m->opt_general_bf16 = 0; return 0; }
+        CONE_REQUIRE(m->general(),
+                     "set_option: general_bf16 applies to the general path only; this handle runs the fused path: use bf16 "
+                     "(or general_shape = 1 / max_window_tokens first)");
+        CONE_REQUIRE(m->ff % 32 == 0 && m->ff <= 2048,
+                     "set_option: general_bf16 needs dim_feedforward %% 32 == 0 and <= 2048; this handle has dim_feedforward %d", m->ff);
+        if (!m->gen_bf16_img)
+            if (int rc = build_general_bf16_images(m)) return rc;
+        m->opt_general_bf16 = 1;
+        return 0;
+    }
     if (!strcmp(name, "gemm")) {
         CONE_REQUIRE(value >= GEMM_AUTO && value <= GEMM_ROWS8, "set_option: gemm tile family %d not in [0, 3]", value);
         m->opt_gemm = value;
@@ -1535,6 +1622,19 @@ extern "C" int cone_test_gemm(const float* A, const float* A2, int a2_mod, const
     g.A2 = A2; g.lda2 = K; g.a2_mod = a2_mod; g.R = R; g.ldr = N; g.ln_g = ln_g; g.ln_b = ln_b;
     g.C2 = C2; g.ADD = ADD;
     return launch_gemm(g, (hipStream_t)stream);
+}
+extern "C" size_t cone_test_gemm_bf16_image_bytes(int N, int K) { return gemm_bf16_image_bytes(N, K); }
+// cone_test_gemm's arguments, then: img (cone_test_gemm_bf16_image_bytes(N, K) bytes: W is packed into it first), ldc (0: N),
+// r_mod, M_dev
+extern "C" int cone_test_gemm_bf16(const float* A, const float* A2, int a2_mod, const float* W, const float* bias,
+                                   const float* R, const float* ln_g, const float* ln_b, float* C, float* C2,
+                                   const float* ADD, int M, int N, int K, int flags, void* img, int ldc, int r_mod,
+                                   const int32_t* M_dev, void* stream) {
+    GemmArgs g = G(nullptr, A, K, W, K, bias, C, ldc ? ldc : N, M, M_dev, N, K, flags & 0xff);
+    g.A2 = A2; g.lda2 = K; g.a2_mod = a2_mod; g.R = R; g.ldr = N; g.r_mod = r_mod; g.ln_g = ln_g; g.ln_b = ln_b;
+    g.C2 = C2; g.ADD = ADD;
+    if (int rc = launch_gemm_bf16_pack(W, K, N, K, img, (hipStream_t)stream)) return rc;
+    return launch_gemm_bf16(g, img, (hipStream_t)stream);
 }
 extern "C" int cone_test_ffn(const float* X, const float* W1, const float* b1, const float* W2, const float* b2,
                              const float* ln_g, const float* ln_b, float* OUT, int M, int ff, void* stream) {

@@ -130,6 +130,15 @@ struct GemmArgs {
 enum { GEMM_AUTO = 0, GEMM_SQUARE = 1, GEMM_ROWS4 = 2, GEMM_ROWS8 = 3 };
 int launch_gemm(const GemmArgs& a, hipStream_t s);
 
+// The same computation with both operands rounded once to bf16 on the bf16 matrix cores (gemm_bf16.hip; option general_bf16:
+// NOT fp32-accurate): the GemmArgs subset of forward_general -- A2 / a2_mod, bias, EPI_RELU, EPI_RESIDUAL / r_mod, ldc, M_dev;
+// N % 16 == 0, K % 32 == 0 up to 2048; EPI_LN, C2 / ADD and m_off are refused by name.  a.W is not read: w_img is its image
+// (launch_gemm_bf16_pack, gemm_bf16_image_bytes(N, K) bytes; 0: the shape is unsupported).  One tile form: a row's bits do
+// not depend on M.
+size_t gemm_bf16_image_bytes(int N, int K);
+int launch_gemm_bf16_pack(const float* W, int ldw, int N, int K, void* img, hipStream_t s);
+int launch_gemm_bf16(const GemmArgs& a, const void* w_img, hipStream_t s);
+
 // ---------------------------------------------------------------- the layer tail's descriptor
 // A transformer layer behind its attention: x1 = LN_in(R + A Wo^T + bo), OUT = LN_out(x1 + W2 relu(W1 x1 + b1) + b2)
 // (post-norm), resp. x1 = R + A Wo^T + bo, OUT = x1 + FFN(LN_in(x1)), OUT2 = LN_out(OUT) (pre: --pre_norm).

@@ -1190,6 +1190,12 @@ def setup_model(opt):
         model.set_option("split_bf16", 1)
     if getattr(opt, "bf16", False):         # (with --split_bf16 as well: the library refuses, naming both options)
         model.set_option("bf16", 1)
+    if getattr(opt, "general_bf16", False):     # (by now the handle knows whether it runs the general path; every rank of a
+        from . import _lib, launch              # --gpus run comes through here and sets it on its own handle)
+        try:
+            model.set_option("general_bf16", 1)
+        except _lib.ConeHipError as e:          # the library's refusal, as the CLI's exit message
+            launch.fail(f"--general_bf16: {e}")
     logger.info(f"Loaded model saved at epoch {ckpt.get('epoch')} from checkpoint: {opt.resume}")
     return model, criterion, None, None
 

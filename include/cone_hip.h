@@ -501,7 +501,22 @@ int64_t cone_prof_collect(double* out, int64_t max_rec);
  *   position tables, layer-0 caches or fused-path forms are read, and the fused path's A/B options are ignored as on a handle
  *   of another shape than 256 / 8) with the streaming attention core (general.hip: gen_attn_stream_kernel) for the encoder
  *   self-attention and the decoder cross-attention, so that a window's bits depend neither on its batch nor on the entry.
- *   Exact fp32 only: "bf16" / "split_bf16" = 1 are refused on such a handle, and raising the option is refused while one is on.
+ *   Exact fp32 unless "general_bf16" is set: "bf16" / "split_bf16" = 1 are refused on such a handle, and raising the option is
+ *   refused while one is on.
+ * "general_bf16" (default 0, OPT-IN; a switch of its own, independent of bf16 / split_bf16 / max_window_tokens in either set
+ *   order): the general path's layer GEMMs -- encoder q | k (the x + pos form), v, attention output projection, linear1,
+ *   linear2; the stacked decoder K (memory + pos) and V; the decoder's self-attention in-projection (slot table as row-periodic
+ *   residual) and output projection, cross-attention query and output projections, linear1, linear2; post-norm and pre-norm
+ *   alike -- with both operands rounded ONCE to bf16 (round to nearest even; x + pos is summed in fp32 first), one
+ *   v_mfma_f32_16x16x32_bf16 per operand pair, fp32 accumulation (gemm_bf16.hip).  Bias, ReLU, the residual (never rounded),
+ *   every LayerNorm, both attention cores, the heads and saliency, the per-checkpoint tables, the input projections and the
+ *   adapter stay fp32, and activations stay fp32 in memory (rows are rounded in flight).  NOT fp32-accurate: errors are those
+ *   of bf16 operands (bounded by the reference model's own bf16-autocast error, tests/test_general_bf16_gpu.py).  1 is
+ *   accepted when the handle runs the general path at that moment (another shape than 256 / 8, max_window_tokens above 256,
+ *   or general_shape = 1) and dim_feedforward % 32 == 0 and <= 2048; else it is refused by name (a fused-path handle is
+ *   pointed at "bf16").  The first 1 builds the weights' bf16 images (a few MB, synchronously; kept until
+ *   cone_model_destroy); a failed build returns the error and leaves the option at 0.  0 is always accepted.  A later
+ *   general_shape = 0 leaves the option set and inert: the fused path never reads it.
  * "gemm" (default 0 = by shape): tile family of every dense layer: 1 = register-staged 128x128 / 64x256 tiles,
  *   2 / 3 = 128x256 row-owning LDS-DMA tile with 4 waves x 32 rows (32x32x2) / 8 waves x 16 rows (16x16x4) -- all
  *   exact-fp32 fma chains per output element that walk k in different orders. */
@@ -513,6 +528,18 @@ int cone_model_set_option(cone_model* m, const char* name, int value);
 int cone_test_gemm(const float* A, const float* A2, int a2_mod, const float* W, const float* bias,
                    const float* R, const float* ln_g, const float* ln_b, float* C, float* C2,
                    const float* ADD, int M, int N, int K, int flags, void* stream);
+/* The row GEMM of option "general_bf16" (gemm_bf16.hip): cone_test_gemm's arguments and
+ *   C[m][n] = sum_k bf16(A[m][k] (+ A2[a2_mod ? m % a2_mod : m][k], added in fp32 first)) * bf16(W[n][k])   (fp32 accumulation)
+ *             + bias[n],  then ReLU (flag 1),  then + R[r_mod ? m % r_mod : m][n] (flag 2; the residual is never rounded)
+ * N a multiple of 16, K a multiple of 32 up to 2048 (cone_test_gemm_bf16_image_bytes returns 0 otherwise).  ln_g / ln_b /
+ * flag 4, C2 / ADD are refused by name.  img: cone_test_gemm_bf16_image_bytes(N, K) bytes, into which W's bf16 image is
+ * packed first; ldc: row stride of C (0 = N); r_mod: > 0 = the residual is row-periodic; M_dev: optional device-side row
+ * count (rows past min(M, *M_dev) are not stored).  One tile form: a row's bits do not depend on M. */
+size_t cone_test_gemm_bf16_image_bytes(int N, int K);
+int cone_test_gemm_bf16(const float* A, const float* A2, int a2_mod, const float* W, const float* bias,
+                        const float* R, const float* ln_g, const float* ln_b, float* C, float* C2,
+                        const float* ADD, int M, int N, int K, int flags, void* img, int ldc, int r_mod,
+                        const int32_t* M_dev, void* stream);
 /* OUT = LayerNorm(X + W2 relu(W1 X + b1) + b2), the fused feed-forward block: X, OUT (M, 256), W1 (ff, 256), W2 (256, ff). */
 int cone_test_ffn(const float* X, const float* W1, const float* b1, const float* W2, const float* b2,
                   const float* ln_g, const float* ln_b, float* OUT, int M, int ff, void* stream);
