@@ -152,7 +152,13 @@ int cone_prefilter_scores_split(const float* vid, int64_t ctx_l, int dv, const f
 
 /* A4, cone/inference.py:297-299 (+ [:topk], cone/ego4d_mad_dataloader.py:146): the first k entries
  * of the descending sort of each row of win_scores (nq,num_window); ties -> lower window index
- * first (stable order).  idx (nq,k) int32, val (nq,k) fp32 (val may be NULL). */
+ * first (stable order; -0.0 and +0.0 tie).  idx (nq,k) int32, val (nq,k) fp32 (val may be NULL).
+ * NaN scores: a NaN is NEVER selected, in either form below -- the list is the stable descending order of the row's
+ * numbers (+-inf included); a row with fewer than k numbers ends in (idx -1, val -inf) padding.
+ * (cone_prefilter_batched ranks its short rows -- at most 1 024 windows -- by counting instead, and that ranking orders a NaN
+ * FIRST, ahead of every number, as torch.sort does, so that its ranks stay a permutation.  The two rules never meet: window
+ * scores produced by this library are never NaN -- the window max skips NaN frame scores, a window of NaN frames scores
+ * -inf.  tests/test_index_kernels_gpu.py pins both.) */
 int cone_topk_windows(const float* win_scores, int nq, int64_t num_window, int k,
                       int32_t* idx, float* val, void* stream);
 /* The same with caller-owned scratch: rows longer than 8 192 windows (MAD scale) run as a two-level selection -- a
