@@ -97,6 +97,11 @@ _SIGNATURES = {
     "cone_prefilter_batched_bf16": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                               C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                               C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    # the certified pre-filter (additive in ABI 8): bf16 scan, fp32 rescore, exact top-k windows
+    "cone_prefilter_index_bf16": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cone_prefilter_topk_certified_workspace": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "cone_prefilter_topk_certified": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p] + [C.c_int] * 5
+                                      + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]),
     "cone_topk_windows": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cone_topk_windows_workspace": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),
     "cone_topk_windows_ws": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,

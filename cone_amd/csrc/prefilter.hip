@@ -86,13 +86,33 @@ __device__ __forceinline__ float wave_sum_multi(const float (&v)[N], int lane) {
     }
 }
 
-template <int VPL /* float4 per lane per row: dv = 256*VPL */, int QG, int RPW, int WPH>
-__global__ __launch_bounds__(256) void frame_score_kernel(const float* __restrict__ vid, int64_t ctx_l, int S, int64_t nh,
-                                                          const float* __restrict__ txt, int q0, int nq,
-                                                          float* __restrict__ fs, float* __restrict__ hm,
-                                                          float* __restrict__ fr) {
+// A lane's share of <row, query>: the pf_dot4 chain over its VPL float4, in channel order.  With the butterfly of
+// wave_sum_multi this IS the per-frame arithmetic of the streaming form: frame_score_kernel and pf_rescore_kernel (the
+// certified top-k's rescoring of single windows) both call it, so a frame's score has the same bits in either.
+template <int VPL>
+__device__ __forceinline__ float pf_lane_dot(const float4 (&x)[VPL], const float4 (&q)[VPL]) {
+    float s = 0.f;
+#pragma unroll
+    for (int v = 0; v < VPL; ++v) s += pf_dot4(x[v], q[v]);
+    return s;
+}
+
+// GATED (the certified top-k's fallback, cone_prefilter_topk_certified): gate[q] != 0 says that query q needs no scan; a
+// launch group all of whose queries are gated off returns after reading the flags and touches no arena row.  The ungated
+// instantiation is the kernel as it always was (frame_score_kernel below: same arguments, same code).
+template <int VPL /* float4 per lane per row: dv = 256*VPL */, int QG, int RPW, int WPH, bool GATED>
+__device__ __forceinline__ void frame_score_body(const float* __restrict__ vid, int64_t ctx_l, int S, int64_t nh,
+                                                 const float* __restrict__ txt, int q0, int nq,
+                                                 float* __restrict__ fs, float* __restrict__ hm,
+                                                 float* __restrict__ fr, const int* __restrict__ gate) {
     constexpr int DV = 256 * VPL, UPB = 4 / WPH, NV = RPW * QG;
     static_assert((RPW & (RPW - 1)) == 0 && (QG & (QG - 1)) == 0 && NV <= 64, "row / query counts: powers of two");
+    if constexpr (GATED) {                                           // (uniform over the grid: the flags of this launch's queries)
+        bool any = false;
+#pragma unroll
+        for (int g = 0; g < QG; ++g) any |= gate[min(q0 + g, nq - 1)] == 0;
+        if (!any) return;
+    }
     __shared__ float red[4][QG];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sub = wave % WPH;
     // the (row, query) pair whose total this lane ends up with (wave_sum_multi: value index r * QG + g = the lane's top bits)
@@ -124,12 +144,7 @@ __global__ __launch_bounds__(256) void frame_score_kernel(const float* __restric
 #pragma unroll
             for (int r = 0; r < RPW; ++r)
 #pragma unroll
-                for (int g = 0; g < QG; ++g) {
-                    float s = 0.f;
-#pragma unroll
-                    for (int v = 0; v < VPL; ++v) s += pf_dot4(x[r][v], q[g][v]);
-                    part[r * QG + g] = s;
-                }
+                for (int g = 0; g < QG; ++g) part[r * QG + g] = pf_lane_dot<VPL>(x[r], q[g]);
             const float s = wave_sum_multi<NV>(part, lane);            // = wave_sum of (row j0 + my_r, query q0 + my_g)
             if (j0 + my_r < n) {
                 m = fmaxf(m, s);
@@ -155,19 +170,40 @@ __global__ __launch_bounds__(256) void frame_score_kernel(const float* __restric
     }
 }
 
-// win[q][i] = max(hm[q][i-1], hm[q][i], W odd ? fr[q][i+1] : -inf) over the half-blocks that exist (0 <= h < nh):
-// window i covers frames [max((i-1)S, 0), min((i-1)S + W, ctx_l)), cone/inference.py:286-292.
+template <int VPL, int QG, int RPW, int WPH>
+__global__ __launch_bounds__(256) void frame_score_kernel(const float* __restrict__ vid, int64_t ctx_l, int S, int64_t nh,
+                                                          const float* __restrict__ txt, int q0, int nq,
+                                                          float* __restrict__ fs, float* __restrict__ hm,
+                                                          float* __restrict__ fr) {
+    frame_score_body<VPL, QG, RPW, WPH, false>(vid, ctx_l, S, nh, txt, q0, nq, fs, hm, fr, nullptr);
+}
+
+// (one launch for every group of 4 queries: blockIdx.y = the group; a last group of fewer repeats its last query and stores nothing for the spare slots)
+template <int VPL, int RPW, int WPH>
+__global__ __launch_bounds__(256) void frame_score_gated_kernel(const float* __restrict__ vid, int64_t ctx_l, int S, int64_t nh,
+                                                                const float* __restrict__ txt, int nq,
+                                                                float* __restrict__ hm, float* __restrict__ fr,
+                                                                const int* __restrict__ gate) {
+    frame_score_body<VPL, 4, RPW, WPH, true>(vid, ctx_l, S, nh, txt, 4 * (int)blockIdx.y, nq, nullptr, hm, fr, gate);
+}
+
+// win[i] = max(hm[i-1], hm[i], W odd ? fr[i+1] : -inf) over the half-blocks that exist (0 <= h < nh), a / f = one query's
+// rows of the two planes: window i covers frames [max((i-1)S, 0), min((i-1)S + W, ctx_l)), cone/inference.py:286-292.
+__device__ __forceinline__ float pf_window_of_halves(const float* __restrict__ a, const float* __restrict__ f, int64_t nh,
+                                                     int odd, int64_t i) {
+    float m = -INFINITY;
+    if (i >= 1) m = a[i - 1];
+    if (i < nh) m = fmaxf(m, a[i]);
+    if (odd && i + 1 < nh) m = fmaxf(m, f[i + 1]);
+    return m;
+}
+
 __global__ __launch_bounds__(256) void window_combine_kernel(const float* __restrict__ hm, const float* __restrict__ fr,
                                                              int64_t nh, int odd, float* __restrict__ win) {
     const int q = blockIdx.y;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i > nh) return;                                                  // num_window = nh + 1
-    const float* a = hm + (size_t)q * nh;
-    float m = -INFINITY;
-    if (i >= 1) m = a[i - 1];
-    if (i < nh) m = fmaxf(m, a[i]);
-    if (odd && i + 1 < nh) m = fmaxf(m, fr[(size_t)q * nh + i + 1]);
-    win[(size_t)q * (nh + 1) + i] = m;
+    win[(size_t)q * (nh + 1) + i] = pf_window_of_halves(hm + (size_t)q * nh, fr + (size_t)q * nh, nh, odd, i);
 }
 
 // Two-level stable top-k for long rows: level 1 -- one workgroup per chunk of TK_CH scores extracts the chunk's own
@@ -951,7 +987,7 @@ __global__ __launch_bounds__(256) void topk_seg_kernel(const float* __restrict__
 
 template <int VPL>
 static int launch_frame_scores(const float* vid, int64_t ctx_l, int S, int64_t nh, const float* txt, int nq, float* fs,
-                               float* hm, float* fr, hipStream_t s) {
+                               float* hm, float* fr, hipStream_t s, const int* gate = nullptr /* the gated form (no fs) */) {
 #ifndef CONE_PF_RPW
 #define CONE_PF_RPW 4
 #endif
@@ -963,6 +999,14 @@ static int launch_frame_scores(const float* vid, int64_t ctx_l, int S, int64_t n
     const bool wide = nh < 4096;
     int64_t blocks = wide ? nh : (nh + 3) / 4;
     if (blocks > 256 * CONE_PF_WGS_PER_CU) blocks = 256 * CONE_PF_WGS_PER_CU;
+    if (gate) {         // the gated form: every group of 4 queries in ONE launch (a query's bits do not depend on its group)
+        ProfScope ps(PK_FRAME_SCORE, ctx_l, 256 * VPL, 4, nullptr, s);
+        const dim3 grid((unsigned)blocks, (unsigned)((nq + 3) / 4));
+        if (wide) hipLaunchKernelGGL((frame_score_gated_kernel<VPL, RPW, 4>), grid, dim3(256), 0, s, vid, ctx_l, S, nh, txt, nq, hm, fr, gate);
+        else hipLaunchKernelGGL((frame_score_gated_kernel<VPL, RPW, 1>), grid, dim3(256), 0, s, vid, ctx_l, S, nh, txt, nq, hm, fr, gate);
+        CONE_LAUNCH_CHECK();
+        return 0;
+    }
     for (int q0 = 0; q0 < nq;) {
         const int rem = nq - q0;
         // 3 remaining queries ride a 4-query launch (the fourth slot repeats the last query and stores nothing): one pass over
@@ -1342,6 +1386,341 @@ __global__ __launch_bounds__(256) void frame_score_groups_bf16_kernel(const uint
     }
 }
 
+// ---- the certified pre-filter: bf16 scan, fp32 rescore of a few candidates, a proof per query, a gated fp32 fallback ------
+// cone_prefilter_topk_certified returns the top-k windows of the exact-fp32 streaming form, bit for bit, and reads the bf16
+// shadow (half the bytes) to get there whenever a query's scores are separable:
+//   coarse scan                          : the bf16 forms above, unchanged
+//   pf_cand_chunk / pf_cand_merge_kernel : the n_cand best coarse windows as an unordered set (bisection on the score bits)
+//   pf_rescore_kernel                    : the candidates' window scores in the streaming form's own fp32 arithmetic
+//   pf_certify_kernel                    : the k best candidates by (exact score desc, index asc); certified[q] = 1 iff no
+//                                          window outside the candidate set can precede the k-th: t - c_last > E(q)
+//   frame_score_gated_kernel + pf_fallback_chunk_kernel + pf_fallback_merge_kernel : the full fp32 scan and top-k of the
+//                                          queries that are NOT certified; gated on the device, no host read-back
+// The bound.  R >= max_f |v_f - bf16(v_f)|, N >= max_f max(|v_f|, |bf16(v_f)|) (2-norms; measured by pf_index_kernel), qh =
+// bf16(q), u = 2^-24, g = (dv + 1) u / (1 - (dv + 1) u).  For every frame
+//   |coarse_f - exact_f| <= |fl(vh.qh) - vh.qh| + |(vh - v).qh| + |v.(qh - q)| + |v.q - fl(v.q)|
+//                        <= g N |qh|         + R |qh|        + N |qh - q|   + g N |q|                (Cauchy-Schwarz)
+// in any summation order, and |max_f a_f - max_f b_f| <= max_f |a_f - b_f|, so E = (R |qh| + N |qh - q| + 2 g N max(|q|, |qh|))
+// (1 + 2^-10) + PF_CERT_TINY (1 + |qh| + N) bounds |coarse - exact| of every window.  The last term covers operands, products
+// and partial sums below 2^-126 (flushed or rounded as subnormals: at most 2^-126 each, 2 dv + 64 of them, and 2^-126 |qh|_1
+// resp. 2^-126 |vh|_1 for flushed operands); the factor covers the rounding of E's own evaluation (fp64 here).
+constexpr float PF_CERT_INFLATE = 1.0f + 0x1p-10f;      // over the fp32 rounding of a measured norm (pf_index_kernel)
+constexpr float PF_INDEX_TINY = 0x1p-55f;               // over the squares too small for fp32 (pf_index_kernel)
+constexpr double PF_CERT_TINY = 0x1p-114;               // 2^-126 (2 dv + 64 + 32 |qh| + 32 N) <= this (1 + |qh| + N), dv <= 1024
+constexpr int PF_CERT_MAX_CAND = 256 * TK_PT;           // candidates of a query in the selection's registers (topk_merge_kernel's limit)
+constexpr int PF_INDEX_MAX_DIM = 16384;
+
+// out = bf16_rne(x) (rows_to_bf16_kernel's bits: the same conversion) and, per row, r = |x - bf16(x)|, n = max(|x|, |bf16(x)|):
+// one wave per row, fp32 sums of squares (lane-strided float4, then the butterfly), the maxima over the grid by atomicMax on
+// the bit patterns (non-negative floats order like their bits; a NaN is stored as the positive quiet NaN, above +inf, so it
+// sticks).  x - bf16(x) is exact in fp32 (the low bits of x).  Inflation: PF_CERT_INFLATE over the sums' rounding ((dim / 64
+// + 6) roundings on non-negative terms -- 4 fmas per float4 and lane, then the butterfly --, halved by the square root, plus
+// the root and the inflation themselves: about 2^-17 relative at dim = PF_INDEX_MAX_DIM, against 2^-10), and an
+// absolute PF_INDEX_TINY over squares too small for fp32 (each loses at most 2^-126, flushed or not: sqrt(dim 2^-126) <= 2^-56).
+__global__ __launch_bounds__(256) void pf_index_kernel(const float* __restrict__ x, int64_t n_rows, int dim,
+                                                       uint16_t* __restrict__ out, int* __restrict__ err_bits) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave_id = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (int64_t)gridDim.x * 4;
+    const int n4 = dim >> 2;
+    float mr = 0.f, mn = 0.f;
+    for (int64_t row = wave_id; row < n_rows; row += n_waves) {
+        const float4* src = reinterpret_cast<const float4*>(x + row * dim);
+        uint2* dst = reinterpret_cast<uint2*>(out + row * dim);
+        float sr = 0.f, sx = 0.f, sh = 0.f;
+        for (int c = lane; c < n4; c += 64) {
+            const float4 v = src[c];
+            const unsigned lo = pf_pk(v.x, v.y), hi = pf_pk(v.z, v.w);
+            dst[c] = make_uint2(lo, hi);
+            const float h[4] = {__uint_as_float(lo << 16), __uint_as_float(lo & 0xffff0000u), __uint_as_float(hi << 16),
+                                __uint_as_float(hi & 0xffff0000u)};
+            const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float d = e[j] - h[j];
+                sr = __builtin_fmaf(d, d, sr);
+                sx = __builtin_fmaf(e[j], e[j], sx);
+                sh = __builtin_fmaf(h[j], h[j], sh);
+            }
+        }
+        sr = wave_sum(sr); sx = wave_sum(sx); sh = wave_sum(sh);
+        // (a NaN fails both comparisons: carried over explicitly)
+        const float r = sqrtf(sr), n = sqrtf(fmaxf(sx, sh));
+        mr = (r != r || mr != mr) ? NAN : fmaxf(mr, r);
+        mn = (sx != sx || sh != sh || mn != mn) ? NAN : fmaxf(mn, n);
+    }
+    if (lane == 0 && wave_id < n_rows) {
+        const float R = mr * PF_CERT_INFLATE + PF_INDEX_TINY, N = mn * PF_CERT_INFLATE + PF_INDEX_TINY;
+        atomicMax(err_bits, R == R ? __float_as_int(R) : 0x7fc00000);
+        atomicMax(err_bits + 1, N == N ? __float_as_int(N) : 0x7fc00000);
+    }
+}
+
+// One workgroup per (candidate slot, query): window i = cand[q][slot] covers frames [max((i-1)S, 0), min((i-1)S + W, ctx_l));
+// its sixteen waves take the frames four at a time each (loads of four rows in flight per wave), every frame's score by pf_lane_dot and the
+// butterfly of wave_sum_multi<1> -- the bits frame_score_kernel gives that (frame, query) -- and the max (order-free; fmaxf
+// skips a NaN frame score, a window of NaN frames scores -inf) through LDS.  An empty slot (index < 0) scores -inf.
+// ---- the candidates: the top-k SET of a row, unordered ------------------------------------------------------------------
+// The proof needs the n_cand best coarse windows as a set and the smallest score among them, not their order, and n_cand =
+// 128 is past what the sort-based selection of the top-k kernels handles (k <= 64: tk_wave_select_fast): their pass-based
+// form is n_cand dependent passes per wave, twice per kernel.  Here the workgroup finds the k-th largest key by bisection
+// on the bits -- 32 steps of (one ballot + popcount per register slot, one barrier) -- where key = the score's bit pattern
+// mapped to an unsigned that orders like the float (-0 counted as +0), settles ties at that key by a second bisection on
+// the window index (lower first: the stable order's set), and compacts the chosen pairs by ballot ranks.  The same total
+// order as tk_better, so the same SET as the first k of the stable descending sort.
+__device__ __forceinline__ unsigned pf_key(float v) {
+    const unsigned b = __float_as_uint(v + 0.f);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+template <int PT, class F>
+__device__ __forceinline__ int pf_block_count(F pred, int (*cnt)[4], int& par) {     // over the PT slots of all 256 threads
+    int c = 0;
+#pragma unroll
+    for (int u = 0; u < PT; ++u) c += __popcll(__ballot(pred(u)));
+    if ((threadIdx.x & 63) == 0) cnt[par][threadIdx.x >> 6] = c;
+    __syncthreads();
+    const int t = cnt[par][0] + cnt[par][1] + cnt[par][2] + cnt[par][3];
+    par ^= 1;                           // the next call writes the other set: one barrier per call is enough
+    return t;
+}
+
+// (gv, gi)[0 .. k) <- the k best of the pairs (index 0x7fffffff = empty slot), in no particular order; fewer than k pairs:
+// the tail is (-inf, idx_none).  Every thread of the workgroup calls it (barriers inside).
+template <int PT>
+__device__ __forceinline__ void pf_block_select_set(const float (&v)[PT], const int (&ix)[PT], int k, float* gv, int* gi,
+                                                    int idx_none) {
+    __shared__ int cnt[2][4];
+    __shared__ int w_tot[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int par = 0;
+    unsigned key[PT];
+#pragma unroll
+    for (int u = 0; u < PT; ++u) key[u] = ix[u] != 0x7fffffff ? pf_key(v[u]) : 0u;       // (a valid key is >= pf_key(-inf) > 0)
+    unsigned T = 0;                     // the k-th largest key: the largest T with #{key >= T} >= k (0: fewer than k pairs)
+    for (int b = 31; b >= 0; --b) {
+        const unsigned c = T | (1u << b);
+        if (pf_block_count<PT>([&](int u) { return key[u] >= c; }, cnt, par) >= k) T = c;
+    }
+    const int gt = pf_block_count<PT>([&](int u) { return key[u] > T; }, cnt, par);
+    const int eq = T ? pf_block_count<PT>([&](int u) { return key[u] == T; }, cnt, par) : 0;
+    const int r = k - gt;               // how many of the pairs AT the key are taken: those of the lowest indices
+    int J = 0x7fffffff;                 // ... = the indices <= J, J = the r-th smallest index at the key
+    if (eq > r) {                       // (uniform)
+        J = 0;
+        for (int b = 30; b >= 0; --b) {
+            const int c = J | (1 << b);
+            if (pf_block_count<PT>([&](int u) { return key[u] == T && ix[u] < c; }, cnt, par) < r) J = c;
+        }
+    }
+    auto chosen = [&](int u) { return key[u] > T || (T != 0 && key[u] == T && ix[u] <= J); };
+    int mine = 0;
+#pragma unroll
+    for (int u = 0; u < PT; ++u) mine += __popcll(__ballot(chosen(u)));
+    if (lane == 0) w_tot[wave] = mine;
+    __syncthreads();
+    int pos = 0;
+    for (int w2 = 0; w2 < wave; ++w2) pos += w_tot[w2];
+    const int total = w_tot[0] + w_tot[1] + w_tot[2] + w_tot[3];       // = min(k, pairs)
+#pragma unroll
+    for (int u = 0; u < PT; ++u) {
+        const bool c = chosen(u);
+        const unsigned long long bal = __ballot(c);
+        if (c) {
+            const int at = pos + __popcll(bal & ((1ull << lane) - 1ull));
+            gv[at] = v[u];
+            gi[at] = ix[u];
+        }
+        pos += __popcll(bal);
+    }
+    for (int e = total + threadIdx.x; e < k; e += 256) { gv[e] = -INFINITY; gi[e] = idx_none; }
+}
+
+// level 1: the set of a chunk of TK_CH window scores (topk_chunk_kernel's loads: a NaN is never chosen)
+__global__ __launch_bounds__(256) void pf_cand_chunk_kernel(const float* __restrict__ sc, int64_t n, int k, float* __restrict__ cval,
+                                                            int* __restrict__ cidx, int n_chunks) {
+    const int q = blockIdx.y, ch = blockIdx.x, tid = threadIdx.x;
+    const int64_t base = (int64_t)ch * TK_CH;
+    const int m = (int)min((int64_t)TK_CH, n - base);
+    const float* row = sc + (size_t)q * n + base;
+    float v[TK_PT];
+    int ix[TK_PT];
+#pragma unroll
+    for (int u = 0; u < TK_PT; ++u) {
+        const int j = u * 256 + tid;
+        const float x = j < m ? row[j] : -INFINITY;
+        const bool ok = j < m && x == x;
+        v[u] = ok ? x : -INFINITY;
+        ix[u] = ok ? (int)(base + j) : 0x7fffffff;
+    }
+    pf_block_select_set<TK_PT>(v, ix, k, cval + ((size_t)q * n_chunks + ch) * k, cidx + ((size_t)q * n_chunks + ch) * k, 0x7fffffff);
+}
+
+// level 2: the set of the chunk sets' n_in = n_chunks * k <= 256 * TK_PT pairs -> the query's candidates (index -1: none)
+__global__ __launch_bounds__(256) void pf_cand_merge_kernel(const float* __restrict__ cval, const int* __restrict__ cidx, int n_in,
+                                                            int k, int32_t* __restrict__ cand, float* __restrict__ coarse) {
+    const int q = blockIdx.x, tid = threadIdx.x;
+    float v[TK_PT];
+    int ix[TK_PT];
+#pragma unroll
+    for (int u = 0; u < TK_PT; ++u) {
+        const int j = u * 256 + tid;
+        v[u] = j < n_in ? cval[(size_t)q * n_in + j] : -INFINITY;
+        ix[u] = j < n_in ? cidx[(size_t)q * n_in + j] : 0x7fffffff;
+    }
+    pf_block_select_set<TK_PT>(v, ix, k, coarse + (size_t)q * k, cand + (size_t)q * k, -1);
+}
+
+constexpr int PF_RS_NT = 1024;      // 16 waves x 4 rows: a 125-frame window in two rounds of loads (n_cand workgroups cannot fill the card: latency counts)
+template <int VPL>
+__global__ __launch_bounds__(PF_RS_NT) void pf_rescore_kernel(const float* __restrict__ vid, int64_t ctx_l, int W, int S,
+                                                         const float* __restrict__ txt, const int32_t* __restrict__ cand,
+                                                         int n_cand, float* __restrict__ exact) {
+    constexpr int DV = 256 * VPL, RPW = 4;
+    constexpr int NW = PF_RS_NT / 64;
+    __shared__ float red[NW];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int q = blockIdx.y, slot = blockIdx.x;
+    const int32_t i = cand[(size_t)q * n_cand + slot];
+    float m = -INFINITY;
+    if (i >= 0) {                                                   // (uniform over the workgroup)
+        const int64_t lo = max(((int64_t)i - 1) * S, (int64_t)0), hi = min(((int64_t)i - 1) * S + W, ctx_l);
+        float4 qv[1][VPL];
+#pragma unroll
+        for (int v = 0; v < VPL; ++v) qv[0][v] = reinterpret_cast<const float4*>(txt + (size_t)q * DV)[lane + 64 * v];
+        for (int64_t f0 = lo + wave * RPW; f0 < hi; f0 += NW * RPW) {
+            float4 x[RPW][VPL];
+#pragma unroll
+            for (int r = 0; r < RPW; ++r) {
+                const int64_t row = min(f0 + r, hi - 1);
+#pragma unroll
+                for (int v = 0; v < VPL; ++v) x[r][v] = reinterpret_cast<const float4*>(vid + row * DV)[lane + 64 * v];
+            }
+#pragma unroll
+            for (int r = 0; r < RPW; ++r) {
+                const float part[1] = {pf_lane_dot<VPL>(x[r], qv[0])};
+                const float s = wave_sum_multi<1>(part, lane);
+                if (f0 + r < hi) m = fmaxf(m, s);
+            }
+        }
+    }
+    if (lane == 0) red[wave] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = red[0];
+#pragma unroll
+        for (int w2 = 1; w2 < NW; ++w2) t = fmaxf(t, red[w2]);
+        exact[(size_t)q * n_cand + slot] = t;
+    }
+}
+
+// One workgroup per query.  The k_eff = min(k, num_window) best candidates by (exact score desc, index asc) -> idx / val rows
+// of k entries ((-1, -inf) past k_eff and past the row's numbers: cone_topk_windows' padding); certified[q] = 1 iff every
+// window is a candidate, or t - c_last > E(q) with everything finite: t = the k_eff-th exact score, c_last = the
+// smallest coarse score of the candidate list (in any order) -- every other window's coarse score is <= c_last, its exact score <= c_last
+// + E < t, so it cannot precede any of the k listed windows (strictly: ties cannot arise).  E in fp64 from the fp32 inputs.
+__global__ __launch_bounds__(256) void pf_certify_kernel(const float* __restrict__ txt, int dv, const float* __restrict__ err,
+                                                         const int32_t* __restrict__ cand, const float* __restrict__ coarse,
+                                                         const float* __restrict__ exact, int n_cand, int64_t num_window, int k,
+                                                         int k_eff, int32_t* __restrict__ idx, float* __restrict__ val,
+                                                         int32_t* __restrict__ certified) {
+    __shared__ double nrm[4][3];
+    __shared__ float c_min[4];
+    const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    double s_q = 0., s_h = 0., s_d = 0.;                            // |q|^2, |qh|^2, |qh - q|^2
+    if (tid * 4 < dv) {
+        const float4 a = reinterpret_cast<const float4*>(txt + (size_t)q * dv)[tid];
+        const float e[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double x = e[j], h = pf16_rne(e[j]);
+            s_q += x * x; s_h += h * h; s_d += (h - x) * (h - x);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        s_q += __shfl_xor(s_q, o, 64); s_h += __shfl_xor(s_h, o, 64); s_d += __shfl_xor(s_d, o, 64);
+    }
+    if (lane == 0) { nrm[wave][0] = s_q; nrm[wave][1] = s_h; nrm[wave][2] = s_d; }
+    const float* ex = exact + (size_t)q * n_cand;
+    const float* co = coarse + (size_t)q * n_cand;
+    const int32_t* ci = cand + (size_t)q * n_cand;
+    float v[TK_PT];
+    int ix[TK_PT];
+    float cm = INFINITY;                                            // the smallest coarse score (an empty slot: -inf, never certified)
+#pragma unroll
+    for (int u = 0; u < TK_PT; ++u) {
+        const int j = u * 256 + tid;
+        const int i = j < n_cand ? ci[j] : -1;
+        const float x = i >= 0 ? ex[j] : -INFINITY;
+        const bool ok = i >= 0 && x == x;
+        v[u] = ok ? x : -INFINITY;
+        ix[u] = ok ? i : 0x7fffffff;
+        if (j < n_cand) cm = fminf(cm, i >= 0 ? co[j] : -INFINITY);
+    }
+    cm = -wave_max(-cm);
+    if (lane == 0) c_min[wave] = cm;
+    for (int r = k_eff + tid; r < k; r += 256) { idx[(size_t)q * k + r] = -1; val[(size_t)q * k + r] = -INFINITY; }
+    tk_block_select<TK_PT>(v, ix, k_eff, val + (size_t)q * k, idx + (size_t)q * k, -1);
+    __syncthreads();                                                // wave 0's list (global memory) and the four norm shares
+    if (tid != 0) return;
+    const double n_q = sqrt(nrm[0][0] + nrm[1][0] + nrm[2][0] + nrm[3][0]), n_h = sqrt(nrm[0][1] + nrm[1][1] + nrm[2][1] + nrm[3][1]),
+                 n_d = sqrt(nrm[0][2] + nrm[1][2] + nrm[2][2] + nrm[3][2]);
+    const double R = err[0], N = err[1];
+    const double du = (dv + 1) * 0x1p-24, gam = du / (1. - du);
+    const double E = (R * n_h + N * n_d + 2. * gam * N * fmax(n_q, n_h)) * (1. + 0x1p-10) + PF_CERT_TINY * (1. + n_h + N);
+    const double t = val[(size_t)q * k + k_eff - 1], c_last = fminf(fminf(c_min[0], c_min[1]), fminf(c_min[2], c_min[3]));
+    const bool finite = isfinite(E) && isfinite(t) && isfinite(c_last);
+    certified[q] = (num_window <= n_cand || (finite && t - c_last > E)) ? 1 : 0;
+}
+
+// The fallback's top-k, for the queries with certified[q] == 0 only (the others' workgroups return at once): level 1 = the
+// stable top-k of a chunk of TK_CH windows, the window scores taken from the two planes on the fly (pf_window_of_halves:
+// window_combine_kernel's values; never NaN), level 2.. = merges of up to `group` lists of k (group * k <= 256 * TK_PT values
+// in registers) until one list is left, which goes to the query's rows of idx / val.  topk_chunk_kernel / topk_merge_kernel's
+// selection (tk_block_select) and order, so cone_topk_windows' list.
+__global__ __launch_bounds__(256) void pf_fallback_chunk_kernel(const float* __restrict__ hm, const float* __restrict__ fr,
+                                                                int64_t nh, int odd, int k, float* __restrict__ cval,
+                                                                int* __restrict__ cidx, int n_chunks,
+                                                                const int32_t* __restrict__ certified) {
+    const int q = blockIdx.y, ch = blockIdx.x, tid = threadIdx.x;
+    if (certified[q]) return;
+    const int64_t base = (int64_t)ch * TK_CH, n = nh + 1;
+    const int m = (int)min((int64_t)TK_CH, n - base);
+    float v[TK_PT];
+    int ix[TK_PT];
+#pragma unroll
+    for (int u = 0; u < TK_PT; ++u) {
+        const int j = u * 256 + tid;
+        const float x = j < m ? pf_window_of_halves(hm + (size_t)q * nh, fr + (size_t)q * nh, nh, odd, base + j) : -INFINITY;
+        const bool ok = j < m && x == x;
+        v[u] = ok ? x : -INFINITY;
+        ix[u] = ok ? (int)(base + j) : 0x7fffffff;
+    }
+    tk_block_select<TK_PT>(v, ix, k, cval + ((size_t)q * n_chunks + ch) * k, cidx + ((size_t)q * n_chunks + ch) * k, 0x7fffffff);
+}
+
+__global__ __launch_bounds__(256) void pf_fallback_merge_kernel(const float* __restrict__ cv_in, const int* __restrict__ ci_in,
+                                                                int n_lists, int k, int group, float* __restrict__ cv_out,
+                                                                int* __restrict__ ci_out, int32_t* __restrict__ idx,
+                                                                float* __restrict__ val, const int32_t* __restrict__ certified) {
+    const int q = blockIdx.y, g = blockIdx.x, n_groups = gridDim.x, tid = threadIdx.x;
+    if (certified[q]) return;
+    const int l0 = g * group, m = (min(l0 + group, n_lists) - l0) * k;          // this group's candidates: lists are contiguous
+    const float* cv = cv_in + ((size_t)q * n_lists + l0) * k;
+    const int* ci = ci_in + ((size_t)q * n_lists + l0) * k;
+    float v[TK_PT];
+    int ix[TK_PT];
+#pragma unroll
+    for (int u = 0; u < TK_PT; ++u) {
+        const int j = u * 256 + tid;
+        v[u] = j < m ? cv[j] : -INFINITY;
+        ix[u] = j < m ? ci[j] : 0x7fffffff;
+    }
+    const bool last = n_groups == 1;
+    tk_block_select<TK_PT>(v, ix, k, last ? val + (size_t)q * k : cv_out + ((size_t)q * n_groups + g) * k,
+                           last ? idx + (size_t)q * k : ci_out + ((size_t)q * n_groups + g) * k, last ? -1 : 0x7fffffff);
+}
+
 }  // namespace cone
 
 extern "C" int64_t cone_num_windows(int64_t ctx_l, int W) {
@@ -1443,6 +1822,159 @@ extern "C" int cone_prefilter_scores_bf16(const uint16_t* vid, int64_t ctx_l, in
     hipLaunchKernelGGL(cone::window_combine_kernel, dim3((unsigned)((nh + 1 + 255) / 256), nq), dim3(256), 0, s, hm, fr, nh,
                        W & 1, win_scores);
     CONE_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- the certified pre-filter: entries ----
+extern "C" int cone_prefilter_index_bf16(const float* x, int64_t n_rows, int dim, uint16_t* out, float* err, void* stream) {
+    CONE_REQUIRE(x && out && err, "prefilter_index_bf16: null argument");
+    CONE_REQUIRE(n_rows > 0, "prefilter_index_bf16: bad row count");
+    CONE_REQUIRE(dim > 0 && dim % 4 == 0 && dim <= cone::PF_INDEX_MAX_DIM,
+                 "prefilter_index_bf16: dim=%d must be a positive multiple of 4 and <= %d", dim, cone::PF_INDEX_MAX_DIM);
+    CONE_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)out & 7) == 0 && ((uintptr_t)err & 3) == 0,
+                 "prefilter_index_bf16: x must be 16-B aligned, out 8-B aligned");
+    hipStream_t s = (hipStream_t)stream;
+    CONE_CHECK_HIP(hipMemsetAsync(err, 0, 2 * sizeof(float), s));        // +0.0f: the maxima's neutral element
+    int64_t blocks = (n_rows + 3) / 4;                                      // a wave per row, grid-stride past 64 workgroups per CU
+    if (blocks > 256 * 64) blocks = 256 * 64;
+    hipLaunchKernelGGL(cone::pf_index_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, n_rows, dim, out, (int*)err);
+    CONE_LAUNCH_CHECK();
+    return 0;
+}
+
+namespace {
+// the workspace of cone_prefilter_topk_certified: byte offsets of its parts
+struct CertLayout {
+    int k_eff, n_cand, n_chunks;
+    int64_t nh, nw;
+    bool fast_cand;     // the candidates by pf_cand_chunk_kernel / pf_cand_merge_kernel (their sets fit one merge workgroup)
+    size_t planes, planes_bytes, win, topk, topk_bytes, cand, coarse, exact, lists_a, lists_b, total;
+};
+bool cert_layout(int64_t ctx_l, int nq, int W, int k, int n_cand, CertLayout* L) {
+    const int S = W / 2;
+    if (S <= 0 || ctx_l <= 0 || nq <= 0 || k <= 0 || n_cand < 0) return false;
+    L->nh = (ctx_l + S - 1) / S;
+    L->nw = L->nh + 1;
+    L->k_eff = (int)(k < L->nw ? k : L->nw);
+    if (n_cand == 0) {                                                  // the default: min(num_window, max(4 k, 128))
+        const int64_t d = 4 * (int64_t)k > 128 ? 4 * (int64_t)k : 128;
+        n_cand = (int)(d < L->nw ? d : L->nw);
+    }
+    L->n_cand = n_cand;
+    L->n_chunks = (int)((L->nw + cone::TK_CH - 1) / cone::TK_CH);
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o += cone::align_up(bytes, 256); return at; };
+    L->planes_bytes = cone_prefilter_scores_workspace(ctx_l, nq, W);       // (the bf16 entry's workspace has the same size)
+    L->planes = take(L->planes_bytes);
+    L->win = take((size_t)nq * L->nw * 4);
+    L->fast_cand = (int64_t)L->n_chunks * n_cand <= cone::PF_CERT_MAX_CAND;
+    L->topk_bytes = L->fast_cand ? (size_t)nq * L->n_chunks * n_cand * 8 : cone_topk_windows_workspace(nq, L->nw, n_cand);
+    L->topk = take(L->topk_bytes);
+    L->cand = take((size_t)nq * n_cand * 4);
+    L->coarse = take((size_t)nq * n_cand * 4);
+    L->exact = take((size_t)nq * n_cand * 4);
+    const int group = cone::PF_CERT_MAX_CAND / (k < cone::TK_KMAX ? k : cone::TK_KMAX);
+    L->lists_a = take((size_t)nq * L->n_chunks * k * 8);                   // values, then indices
+    L->lists_b = take((size_t)nq * ((L->n_chunks + group - 1) / group) * k * 8);
+    L->total = o;
+    return true;
+}
+}  // namespace
+
+extern "C" size_t cone_prefilter_topk_certified_workspace(int64_t ctx_l, int nq, int W, int k, int n_cand) {
+    CertLayout L;
+    return cert_layout(ctx_l, nq, W, k, n_cand, &L) ? L.total : 0;
+}
+
+extern "C" int cone_prefilter_topk_certified(const float* vid_f32, const uint16_t* vid_bf16, int64_t ctx_l, int dv,
+                                             const float* txt, int nq, int W, int S, int k, int n_cand, const float* err,
+                                             int32_t* idx, float* val, int32_t* certified, void* ws, size_t ws_bytes,
+                                             void* stream) {
+    CONE_REQUIRE(vid_f32 && vid_bf16 && txt && err && idx && val && certified, "prefilter_topk_certified: null argument");
+    CONE_REQUIRE(ctx_l > 0 && nq > 0 && W > 0 && S > 0 && S == W / 2 && k > 0 && n_cand >= 0,
+                 "prefilter_topk_certified: bad sizes ctx_l=%lld nq=%d W=%d S=%d k=%d n_cand=%d", (long long)ctx_l, nq, W, S, k, n_cand);
+    CONE_REQUIRE(dv == 256 || dv == 512 || dv == 768 || dv == 1024,
+                 "prefilter_topk_certified: feature dim %d not in {256,512,768,1024}", dv);
+    CONE_REQUIRE(((uintptr_t)vid_f32 & 15) == 0 && ((uintptr_t)vid_bf16 & 15) == 0 && ((uintptr_t)txt & 15) == 0,
+                 "prefilter_topk_certified: the arenas and the query vectors must be 16-B aligned");
+    CONE_REQUIRE(k <= cone::TK_KMAX, "prefilter_topk_certified: k=%d exceeds the %d entries of a selection list", k, cone::TK_KMAX);
+    CertLayout L;
+    cert_layout(ctx_l, nq, W, k, n_cand, &L);
+    CONE_REQUIRE(L.nw < 0x7fffffff, "prefilter_topk_certified: %lld windows do not fit an int32 index", (long long)L.nw);
+    // what cone_topk_windows_ws supports for the candidate list (n_cand <= num_window), at most the two-level selection's
+    // PF_CERT_MAX_CAND candidates per row, and no fewer than the k windows asked for
+    CONE_REQUIRE(L.n_cand <= L.nw && L.n_cand <= cone::PF_CERT_MAX_CAND && L.n_cand >= L.k_eff,
+                 "prefilter_topk_certified: n_cand=%d must lie in [min(k, num_window)=%d, min(num_window=%lld, %d)]", L.n_cand,
+                 L.k_eff, (long long)L.nw, cone::PF_CERT_MAX_CAND);
+    CONE_REQUIRE(ws && ws_bytes >= L.total, "prefilter_topk_certified: workspace too small (%zu < %zu)", ws_bytes, L.total);
+    hipStream_t s = (hipStream_t)stream;
+    char* w = (char*)ws;
+    float* win = (float*)(w + L.win);
+    int32_t* cand = (int32_t*)(w + L.cand);
+    float* coarse = (float*)(w + L.coarse);
+    float* exact = (float*)(w + L.exact);
+    // (a) the coarse window scores off the bf16 shadow (the existing entry, unchanged), (b) the n_cand best of them
+    int rc = cone_prefilter_scores_bf16(vid_bf16, ctx_l, dv, txt, nq, W, S, win, w + L.planes, L.planes_bytes, stream);
+    if (rc) return rc;
+    if (L.fast_cand) {      // as an unordered set (all the proof needs): chunk sets, then the set of their union
+        float* cv = (float*)(w + L.topk);
+        int* ci = (int*)(cv + (size_t)nq * L.n_chunks * L.n_cand);
+        hipLaunchKernelGGL(cone::pf_cand_chunk_kernel, dim3((unsigned)L.n_chunks, (unsigned)nq), dim3(256), 0, s, win, L.nw, L.n_cand, cv,
+                           ci, L.n_chunks);
+        CONE_LAUNCH_CHECK();
+        hipLaunchKernelGGL(cone::pf_cand_merge_kernel, dim3(nq), dim3(256), 0, s, cv, ci, L.n_chunks * L.n_cand, L.n_cand, cand, coarse);
+        CONE_LAUNCH_CHECK();
+    } else {                // more than 4 096 chunk-set entries (n_cand x ceil(num_window / 4 096)): the top-k entry's own forms
+        rc = cone_topk_windows_ws(win, nq, L.nw, L.n_cand, cand, coarse, w + L.topk, L.topk_bytes, stream);
+        if (rc) return rc;
+    }
+    // (c) the candidates' exact scores
+    const dim3 rgrid((unsigned)L.n_cand, (unsigned)nq);
+    switch (dv / 256) {
+        case 1: hipLaunchKernelGGL(cone::pf_rescore_kernel<1>, rgrid, dim3(cone::PF_RS_NT), 0, s, vid_f32, ctx_l, W, S, txt, cand, L.n_cand, exact); break;
+        case 2: hipLaunchKernelGGL(cone::pf_rescore_kernel<2>, rgrid, dim3(cone::PF_RS_NT), 0, s, vid_f32, ctx_l, W, S, txt, cand, L.n_cand, exact); break;
+        case 3: hipLaunchKernelGGL(cone::pf_rescore_kernel<3>, rgrid, dim3(cone::PF_RS_NT), 0, s, vid_f32, ctx_l, W, S, txt, cand, L.n_cand, exact); break;
+        default: hipLaunchKernelGGL(cone::pf_rescore_kernel<4>, rgrid, dim3(cone::PF_RS_NT), 0, s, vid_f32, ctx_l, W, S, txt, cand, L.n_cand, exact); break;
+    }
+    CONE_LAUNCH_CHECK();
+    // (d) the k best candidates and the proof
+    hipLaunchKernelGGL(cone::pf_certify_kernel, dim3(nq), dim3(256), 0, s, txt, dv, err, cand, coarse, exact, L.n_cand, L.nw, k,
+                       L.k_eff, idx, val, certified);
+    CONE_LAUNCH_CHECK();
+    if (L.nw <= L.n_cand) return 0;                     // every window is a candidate: every query is certified
+    // (e) the fallback, gated on the device by `certified`: the streaming scan in groups of up to 4 queries (a query's bits
+    // do not depend on its group), the planes of the coarse scan reused (dead by now), then the gated top-k (here k <= n_cand
+    // < num_window, so the rows' stride k is the list length)
+    float* hm = (float*)(w + L.planes);
+    float* fr = (float*)(w + L.planes + L.planes_bytes / 2);
+    switch (dv / 256) {
+        case 1: rc = cone::launch_frame_scores<1>(vid_f32, ctx_l, S, L.nh, txt, nq, nullptr, hm, fr, s, certified); break;
+        case 2: rc = cone::launch_frame_scores<2>(vid_f32, ctx_l, S, L.nh, txt, nq, nullptr, hm, fr, s, certified); break;
+        case 3: rc = cone::launch_frame_scores<3>(vid_f32, ctx_l, S, L.nh, txt, nq, nullptr, hm, fr, s, certified); break;
+        default: rc = cone::launch_frame_scores<4>(vid_f32, ctx_l, S, L.nh, txt, nq, nullptr, hm, fr, s, certified); break;
+    }
+    if (rc) return rc;
+    float* cv_a = (float*)(w + L.lists_a);
+    int* ci_a = (int*)(cv_a + (size_t)nq * L.n_chunks * k);
+    hipLaunchKernelGGL(cone::pf_fallback_chunk_kernel, dim3((unsigned)L.n_chunks, (unsigned)nq), dim3(256), 0, s, hm, fr, L.nh, W & 1, k,
+                       cv_a, ci_a, L.n_chunks, certified);
+    CONE_LAUNCH_CHECK();
+    const int group = cone::PF_CERT_MAX_CAND / k;          // lists per merge workgroup (>= 16)
+    char* out_buf = w + L.lists_b;
+    char* in_buf = w + L.lists_a;
+    for (int n_lists = L.n_chunks;;) {
+        const int n_groups = (n_lists + group - 1) / group;
+        float* cv_in = (float*)in_buf;
+        int* ci_in = (int*)(cv_in + (size_t)nq * n_lists * k);
+        float* cv_out = (float*)out_buf;
+        int* ci_out = (int*)(cv_out + (size_t)nq * n_groups * k);
+        hipLaunchKernelGGL(cone::pf_fallback_merge_kernel, dim3((unsigned)n_groups, (unsigned)nq), dim3(256), 0, s, cv_in, ci_in, n_lists,
+                           k, group, cv_out, ci_out, idx, val, certified);
+        CONE_LAUNCH_CHECK();
+        if (n_groups == 1) break;
+        n_lists = n_groups;                                 // (the lists shrink: each buffer holds every later level too)
+        char* t = in_buf; in_buf = out_buf; out_buf = t;
+    }
     return 0;
 }
 

@@ -166,6 +166,49 @@ def topk_windows(win_scores: torch.Tensor, k: int):
     return idx, val
 
 
+class PrefilterIndex:
+    """One resident video indexed once for the certified pre-filter (cone_prefilter_index_bf16 / cone_prefilter_topk_certified):
+    the fp32 adapted rows (ctx_l, dv), their bf16 shadow and its two measured norms -- 1.5 x the fp32 bytes stay resident.
+    ``topk`` returns the exact-fp32 path's top-k windows, bit for bit, reading the shadow instead of the fp32 rows whenever
+    the query's scores are separable.  dv in {256, 512, 768, 1024}."""
+
+    def __init__(self, vid_ctx: torch.Tensor):
+        lib = _lib.load()
+        self.vid = vid_ctx.to(torch.float32).contiguous()
+        self.ctx_l, self.dv = (int(n) for n in self.vid.shape)
+        self.vid16 = torch.empty(self.vid.shape, dtype=torch.bfloat16, device=self.vid.device)
+        self.err = torch.empty(2, device=self.vid.device)           # R, N: see include/cone_hip.h
+        _lib.check(lib.cone_prefilter_index_bf16(_lib.ptr(self.vid), self.ctx_l, self.dv, _lib.ptr(self.vid16),
+                                                 _lib.ptr(self.err), _lib.stream()))
+        self._scratch = None        # ONE grow-only workspace for eager calls (calls on one stream follow each other)
+        self._captured = []         # the workspaces of calls captured in a graph: a replay needs its own, for good
+
+    def topk(self, cls_txt: torch.Tensor, max_v_l: int, k: int, n_cand=None):
+        """(idx (nq,k) int32, val (nq,k) fp32, certified (nq) int32) for cls_txt (nq, dv): idx / val equal
+        ``topk_windows(prefilter_scores(vid, cls_txt[q:q+1], max_v_l)[1], k)`` row for row ((-1, -inf) padding where k exceeds
+        the number of windows); ``certified[q]`` = 1 where the bf16 scan plus ``n_cand`` rescored windows (default
+        min(num_window, max(4 k, 128))) proved it, 0 where the query fell back to the full fp32 scan.  No host read-back."""
+        lib = _lib.load()
+        nq = int(cls_txt.shape[0])
+        W, S, nc = int(max_v_l), int(max_v_l / 2), int(n_cand or 0)
+        nbytes = max(lib.cone_prefilter_topk_certified_workspace(self.ctx_l, nq, W, int(k), nc), 1)
+        if torch.cuda.is_current_stream_capturing():
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.vid.device)
+            self._captured.append(scratch)
+        else:
+            if self._scratch is None or self._scratch.numel() < nbytes:
+                self._scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.vid.device)
+            scratch = self._scratch
+        idx = torch.empty(nq, k, dtype=torch.int32, device=self.vid.device)
+        val = torch.empty(nq, k, device=self.vid.device)
+        cert = torch.empty(nq, dtype=torch.int32, device=self.vid.device)
+        _lib.check(lib.cone_prefilter_topk_certified(
+            _lib.ptr(self.vid, torch.float32), _lib.ptr(self.vid16, torch.bfloat16), self.ctx_l, self.dv,
+            _lib.ptr(cls_txt, torch.float32), nq, W, S, int(k), nc, _lib.ptr(self.err), _lib.ptr(idx), _lib.ptr(val),
+            _lib.ptr(cert), _lib.ptr(scratch), scratch.numel(), _lib.stream()))
+        return idx, val, cert
+
+
 def window_table_rows(win_idx, q_ctx_l, q_vid_off, tok_off, tok_len, q_base: int, eval_bsz: int, max_v_l: int,
                       batch_pad=None, n_batches: int = 0, row_q=None, row_slot=None):
     """A5 in one launch instead of ~50 index operations.  win_idx (nq, K) int32; the per-query vectors int32.  The window

@@ -223,6 +223,45 @@ int cone_prefilter_batched_bf16(const uint16_t* arena, int dv, const float* cls,
                                 const int64_t* q_win_off, const int32_t* q_ctx_l, int nq, int W, int S,
                                 float* win_scores, int k, int32_t* topk_idx, void* stream);
 
+/* ---- OPT-IN certified pre-filter (additive in ABI 8): the bf16 scan's bytes, the exact-fp32 path's top-k windows.
+ * For callers that index a video once and query it many times.  The fp32 rows stay resident BESIDE their bf16 shadow (1.5 x
+ * the fp32 bytes).  Per call: the coarse window scores off the shadow (cone_prefilter_scores_bf16's forms, unchanged), the
+ * n_cand best of them, those candidates' window scores again in the fp32 streaming form's own arithmetic, and a proof
+ * per query, on the device, that no window outside the candidates can enter the top-k; a query whose proof fails gets the
+ * full fp32 scan, still on the device.  One stream, no host read-back: the call can be captured in a graph.
+ * A note on the contract above: round-to-nearest-even into bf16 (8 significand bits) has a worst relative error of
+ * 2^-8 / (1 + 2^-8) per operand -- fp32 1 + 2^-8 rounds to 1.0 --, not the 2^-9 stated there.  Nothing here relies on
+ * either figure: the index measures the rounding residual of the rows it stores. */
+
+/* cone_rows_to_bf16 (the same bits in `out`) that also measures the shadow: err[0] = R >= max over rows of |x_f - bf16(x_f)|,
+ * err[1] = N >= max over rows of max(|x_f|, |bf16(x_f)|) (2-norms; device memory, 2 floats, initialised here).  fp32 sums,
+ * inflated by (1 + 2^-10) + 2^-55 over their own rounding and underflow.  A non-finite row (or one that rounds to a
+ * non-finite bf16 row) makes R or N non-finite: queries on that index are never certified (and still answered exactly).
+ * dim a multiple of 4, <= 16384. */
+int cone_prefilter_index_bf16(const float* x, int64_t n_rows, int dim, uint16_t* out, float* err, void* stream);
+
+/* The certified top-k.  vid_f32 (ctx_l,dv) fp32 and vid_bf16 = its shadow with err = its measures (cone_prefilter_index_bf16),
+ * txt (nq,dv) fp32; dv in {256,512,768,1024} (the fp32 streaming form's rule); k <= 256.  n_cand = candidates per query:
+ * 0 = the default min(num_window, max(4 k, 128)); otherwise min(k, num_window) <= n_cand <= min(num_window, 4096) (named
+ * check: what the top-k entries support for one selection; while n_cand * ceil(num_window / 4096) <= 4096 the candidates are
+ * selected as an unordered set in microseconds, past that by cone_topk_windows_ws, whose one-level form costs n_cand passes
+ * over the row).  Outputs: idx (nq,k) int32, val (nq,k) fp32 = the fp32 window
+ * scores, laid out and padded like cone_topk_windows' ((-1, -inf) where the row has fewer than k numbers; k may exceed
+ * num_window here), certified (nq) int32.
+ * CONTRACT: idx / val are those of cone_topk_windows on cone_prefilter_scores called with that query ALONE (the streaming
+ * form), bit for bit, whatever certified[q] says.  certified[q] = 1: the query was answered from the bf16 scan and n_cand
+ * rescored windows (every window is a candidate, or t - c_last > E(q) strictly with all quantities finite: t = the k-th
+ * exact score, c_last = the smallest coarse score among the candidates,
+ *     E(q) = (R |qh| + N |qh - q| + 2 g N max(|q|, |qh|)) (1 + 2^-10) + 2^-114 (1 + |qh| + N),
+ * qh = bf16(q), g = (dv+1) u / (1 - (dv+1) u), u = 2^-24: a bound on |coarse - exact| of every window in any summation order,
+ * DESIGN.md 3d).  certified[q] = 0: near-ties, too few candidates or non-finite data; the query's group of up to 4 queries
+ * ran the full fp32 scan (a group of certified queries returns after reading the flags).
+ * ws >= cone_prefilter_topk_certified_workspace(ctx_l, nq, W, k, n_cand) bytes. */
+size_t cone_prefilter_topk_certified_workspace(int64_t ctx_l, int nq, int W, int k, int n_cand);
+int cone_prefilter_topk_certified(const float* vid_f32, const uint16_t* vid_bf16, int64_t ctx_l, int dv, const float* txt,
+                                  int nq, int W, int S, int k, int n_cand, const float* err, int32_t* idx, float* val,
+                                  int32_t* certified, void* ws, size_t ws_bytes, void* stream);
+
 /* A5, eval branch of StartEndDataset.__getitem__ + collate (cone/ego4d_mad_dataloader.py:144-159, 229-234, 305-344) as
  * index arithmetic: win_idx (nq, K) int32 holds the ranked window indices of every query, valid entries first (a video of
  * fewer than K windows: the tail is -1 and never read).  Row b of every output is (query row_q[b], rank slot row_slot[b])
