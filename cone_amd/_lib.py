@@ -177,6 +177,14 @@ _SIGNATURES = {
     "cone_test_enc_attn": (C.c_int, [C.c_int] + [C.c_void_p] * 9 + [C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "cone_test_dec_cross": (C.c_int, [C.c_void_p] * 9 + [C.c_int] * 4 + [C.c_void_p, C.c_void_p]),
     "cone_test_dec_cross_slab_floats": (C.c_size_t, []),
+    # cone_test_enc_attn_txt(mode, QKV, qkv_vid, qkv_txt, pos_qk, txt_pos_qk, vrow0, vlen, trow0, off, OUT, B, Lmax, zero_row, stream)
+    "cone_test_enc_attn_txt": (C.c_int, [C.c_int] + [C.c_void_p] * 10 + [C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    # cone_test_small_attn(Q, ldq, K, ldk, V, ldv, OUT, ldo, off, B, nq, Lmax, stream)
+    "cone_test_small_attn": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                       C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    # cone_test_dec_cross_ex(DQ, XP, X, pos_rows, vlen, off, Wk, WvT, bv, OUT, B, nq, Lmax, variant, qk_slabs, sal_w, sal_b, sal,
+    # sal_ld, stream)
+    "cone_test_dec_cross_ex": (C.c_int, [C.c_void_p] * 10 + [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_int, C.c_void_p]),
     "cone_test_layernorm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
                                       C.c_void_p]),
     # cone_test_gen_attn(Q, ldq, K, ldk, V, ldv, OUT, ldo, qoff, koff, B, nq, heads, head_dim, kcap, stream)

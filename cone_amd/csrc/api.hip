@@ -1748,6 +1748,33 @@ extern "C" int cone_test_dec_cross(const float* DQ, const float* X, const float*
                                  (hipStream_t)stream, variant);
 }
 extern "C" size_t cone_test_dec_cross_slab_floats(void) { return dec_cross_mfma_slab_floats(); }
+extern "C" int cone_test_enc_attn_txt(int mode, const float* QKV, const float* qkv_vid, const float* qkv_txt,
+                                      const float* pos_qk, const float* txt_pos_qk, const int32_t* vrow0,
+                                      const int32_t* vlen, const int32_t* trow0, const int32_t* off, float* OUT, int B,
+                                      int Lmax, int pos_zero_row, void* stream) {
+    AttnSrc a{};
+    a.pos_zero_row = pos_zero_row;
+    a.Q = QKV; a.K = QKV ? QKV + 256 : nullptr; a.V = QKV ? QKV + 512 : nullptr; a.ldq = a.ldk = a.ldv = 768;
+    a.qkv_vid = qkv_vid; a.qkv_txt = qkv_txt; a.pos_qk = pos_qk; a.vrow0 = vrow0; a.vlen = vlen; a.trow0 = trow0;
+    a.txt_pos_qk = txt_pos_qk;                    // non-NULL: the ATTN_GATHER | 4 / ATTN_POSADD | 4 builds
+    a.form = (mode >> 8) & 3;
+    return launch_enc_attn(mode & 0xff, a, OUT, off, B, Lmax, (hipStream_t)stream);
+}
+extern "C" int cone_test_small_attn(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* OUT,
+                                    int ldo, const int32_t* off, int B, int nq, int Lmax, void* stream) {
+    return launch_small_attn(Q, ldq, K, ldk, V, ldv, OUT, ldo, off, B, nq, Lmax, (hipStream_t)stream);
+}
+extern "C" int cone_test_dec_cross_ex(const float* DQ, const float* XP, const float* X, const float* pos_rows,
+                                      const int32_t* vlen, const int32_t* off, const float* Wk, const float* WvT,
+                                      const float* bv, float* OUT, int B, int nq, int Lmax, int variant, float* qk_slabs,
+                                      const float* sal_w, const float* sal_b, float* sal, int sal_ld, void* stream) {
+    if (variant == 1) {
+        CONE_REQUIRE(!sal, "fused decoder cross-attention: the VALU kernel has no saliency ride");
+        return launch_dec_cross(DQ, XP, X, pos_rows, vlen, off, Wk, WvT, bv, OUT, B, nq, Lmax, (hipStream_t)stream);
+    }
+    return launch_dec_cross_mfma(DQ, XP, X, pos_rows, vlen, off, Wk, WvT, bv, OUT, B, nq, Lmax, qk_slabs, (hipStream_t)stream,
+                                 variant, sal_w, sal_b, sal, sal_ld);
+}
 extern "C" int cone_test_layernorm(const float* x, const float* g, const float* b, float* out, int64_t n_rows,
                                    int dim, void* stream) {
     return launch_layernorm(x, dim, g, b, out, dim, n_rows, nullptr, dim, (hipStream_t)stream);

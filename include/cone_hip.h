@@ -653,6 +653,25 @@ int cone_test_dec_cross(const float* DQ, const float* X, const float* pos_rows, 
                         const float* Wk, const float* WvT, const float* bv, float* OUT, int B, int nq, int Lmax,
                         int variant, float* qk_slabs, void* stream);
 size_t cone_test_dec_cross_slab_floats(void);
+/* cone_test_enc_attn plus the text position rows of --use_txt_pos: txt_pos_qk (n_txt, 512) != NULL makes a text token j of
+ * window b add row txt_pos_qk[trow0[b] + j] to its q | k instead of the zero row (modes 1 and 2: the ATTN_GATHER | 4 and
+ * ATTN_POSADD | 4 builds; mode 0 ignores it).  txt_pos_qk == NULL: cone_test_enc_attn. */
+int cone_test_enc_attn_txt(int mode, const float* QKV, const float* qkv_vid, const float* qkv_txt, const float* pos_qk,
+                           const float* txt_pos_qk, const int32_t* vrow0, const int32_t* vlen, const int32_t* trow0,
+                           const int32_t* off, float* OUT, int B, int Lmax, int pos_zero_row, void* stream);
+/* The decoder's small attentions (cone/transformer.py:296-311, 8 heads x 32): nq <= 16 query rows b * nq .. of Q per window.
+ * off == NULL: self-attention over the window's own nq rows of K / V; otherwise cross-attention to rows off[b] .. off[b + 1]
+ * of K / V (<= 192 keys).  ld* = floats per row; OUT row b * nq + i, 256 columns. */
+int cone_test_small_attn(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* OUT, int ldo,
+                         const int32_t* off, int B, int nq, int Lmax, void* stream);
+/* cone_test_dec_cross with the remaining operands of its launchers: XP (M, 256) != NULL = the precomputed memory + pos
+ * rows the keys are projected from (the --use_txt_pos decoder; pos_rows / vlen may then be NULL, X still feeds the values);
+ * sal != NULL (matrix-core table forms): the launch also writes sal[b * sal_ld + p] = <X row of clip p, sal_w> + sal_b[0]
+ * for p < min(vlen[b], sal_ld) and leaves the other entries alone.  What a form does not support it refuses by name. */
+int cone_test_dec_cross_ex(const float* DQ, const float* XP, const float* X, const float* pos_rows, const int32_t* vlen,
+                           const int32_t* off, const float* Wk, const float* WvT, const float* bv, float* OUT, int B, int nq,
+                           int Lmax, int variant, float* qk_slabs, const float* sal_w, const float* sal_b, float* sal,
+                           int sal_ld, void* stream);
 int cone_test_layernorm(const float* x, const float* g, const float* b, float* out, int64_t n_rows,
                         int dim, void* stream);
 /* Attention core of the general-shape path (any hidden_dim / nheads with head_dim in {16, 32, 64}): one workgroup per

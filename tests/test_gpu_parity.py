@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import inputs as gi
+from attention_refs import mha64
 from cone_amd import synth
 from cone_amd.config import make_opt
 from oracle import cone_oracle as O
@@ -2599,10 +2600,7 @@ def test_fused_decoder_cross_attention_other_slot_counts_match_float64(nq, Lcap,
             keys[:lv] += pos[lv * (lv - 1) // 2:lv * (lv - 1) // 2 + lv].double()
         K = keys @ Wk.double().t()
         V = mem @ Wv.double().t() + bv.double()
-        q = DQ[b * nq:(b + 1) * nq].double() * (1.0 / 32 ** 0.5)
-        for h in range(8):
-            sl = slice(32 * h, 32 * h + 32)
-            ref[b * nq:(b + 1) * nq, sl] = torch.softmax(q[:, sl] @ K[:, sl].t(), dim=1) @ V[:, sl]
+        ref[b * nq:(b + 1) * nq] = mha64(DQ[b * nq:(b + 1) * nq], K, V)
     d = lambda t: t.to(dev).contiguous()
     lib = _lib.load()
     out = torch.full((B * nq + 2, 256), float("nan"), device=dev)
@@ -2662,11 +2660,7 @@ def test_fused_decoder_cross_attention_matches_float64(variant, shared, case):
         keys[:lv] += pos[lv * (lv - 1) // 2: lv * (lv - 1) // 2 + lv].double()
         K = keys @ Wk.double().t()
         V = mem @ Wv.double().t() + bv.double()
-        q = DQ[b * nq:(b + 1) * nq].double() * (1.0 / 32 ** 0.5)
-        for h in range(8):
-            sl = slice(32 * h, 32 * h + 32)
-            p = torch.softmax(q[:, sl] @ K[:, sl].t(), dim=1)
-            ref[b * nq:(b + 1) * nq, sl] = p @ V[:, sl]
+        ref[b * nq:(b + 1) * nq] = mha64(DQ[b * nq:(b + 1) * nq], K, V)
     d = lambda t: t.to(dev).contiguous()
     lib = _lib.load()
     out = torch.full((B * nq + 2, 256), float("nan"), device=dev)
@@ -2756,10 +2750,7 @@ def test_encoder_attention_kernel_matches_float64(mode):
     ref = torch.empty(M, 256, dtype=torch.float64)
     for b in range(B):
         r = rows[off[b]:off[b + 1]]
-        for h in range(8):
-            sl = slice(32 * h, 32 * h + 32)
-            p = torch.softmax((r[:, sl] / 32 ** 0.5) @ r[:, 256:512][:, sl].t(), dim=1)
-            ref[off[b]:off[b + 1], sl] = p @ r[:, 512:][:, sl]
+        ref[off[b]:off[b + 1]] = mha64(r[:, :256], r[:, 256:512], r[:, 512:])
     d = lambda t: t.to(dev).contiguous()
     i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=dev)
     out = torch.full((M + 1, 256), float("nan"), device=dev)
