@@ -448,7 +448,11 @@ int cone_matcher_cost(const float* logits, const float* spans, const float* tgt,
  * logits, spans, neg_logits (B, Nq, 2); tgt (sum T, 2) (center, width), tgt_off (B + 1); tgt == NULL: no targets --
  * every slot is background and only loss_label is meaningful (:385-388).  saliency (B, L), pos_idx / neg_idx (B, P).
  * Outputs: assign (B, Nq) int32 (target index inside the window, -1 = unmatched; may be NULL), part (B, 8) scratch,
- * losses (5) = loss_span, loss_giou, loss_label, class_error, loss_saliency. */
+ * losses (5) = loss_span, loss_giou, loss_label, class_error, loss_saliency.
+ * CONTRACT: Nq is checked here (1 .. 8), the target counts are NOT: the kernel trusts tgt_off, which lives on the device,
+ * and a window with tgt_off[b + 1] - tgt_off[b] > 8 (or < 0) overruns the kernel's 8 x 8 cost matrix and its 256 DP
+ * states.  The caller checks 0 <= T_b <= 8 on the host before it builds tgt_off (cone_amd.criterion raises
+ * NotImplementedError); pos_idx / neg_idx must already be wrapped into [0, L). */
 int cone_criterion_forward(const float* logits, const float* spans, const float* tgt, const int32_t* tgt_off,
                            const float* neg_logits, const float* saliency, int L, const int32_t* pos_idx,
                            const int32_t* neg_idx, int P, const float* neg_saliency, int L2, int B, int Nq,
