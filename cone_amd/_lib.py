@@ -190,6 +190,27 @@ _SIGNATURES = {
     # cone_test_gen_attn(Q, ldq, K, ldk, V, ldv, OUT, ldo, qoff, koff, B, nq, heads, head_dim, kcap, stream)
     "cone_test_gen_attn": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                      C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
+    # the glue kernels of stage B, one entry per launcher (include/cone_hip.h: the operand lists)
+    "cone_test_grid_limit_y": (C.c_int, []),
+    "cone_test_scan_lengths": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "cone_test_compact_index": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                          C.c_void_p, C.c_int, C.c_void_p]),
+    "cone_test_pack_pos": (C.c_int, [C.c_void_p] * 11 + [C.c_int, C.c_int] + [C.c_void_p] * 4),
+    "cone_test_gen_pack_pos": (C.c_int, [C.c_void_p] * 10 + [C.c_int] * 3 + [C.c_void_p] * 4),
+    "cone_test_pack_l0": (C.c_int, [C.c_void_p] * 15 + [C.c_int, C.c_int, C.c_void_p]),
+    "cone_test_row_index": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]),
+    "cone_test_add_pos_rows": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int] + [C.c_void_p] * 3),
+    "cone_test_txt_pos_rows": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3),
+    "cone_test_gen_txt_pos_rows": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int,
+                                                                                                    C.c_void_p, C.c_void_p]),
+    "cone_test_saliency": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "cone_test_gen_saliency": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "cone_test_rowdot": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int,
+                                   C.c_void_p]),
+    "cone_test_gen_rowdot": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int,
+                                       C.c_int, C.c_void_p]),
+    "cone_test_tile_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
+    "cone_test_tile_rows2": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int64, C.c_void_p]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

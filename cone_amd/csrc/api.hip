@@ -1029,6 +1029,28 @@ static int forward_general(const cone_model* m, const FwdCall& call, void* ws, s
     return heads_and_taps(m, call, HeadBufs{f.HS, f.S1, f.S2, f.LG, f.SP, f.off}, MEM, true, s);
 }
 
+// Most windows one call may hold: launch_pack_pos, launch_pack_l0, launch_row_index, launch_add_pos_rows, launch_saliency,
+// launch_compact_index and their d-wide forms put the window index in gridDim.y, so B is bounded by the device's
+// maxGridSize[1] -- read from the device properties once per device (0: the query failed).
+static int grid_limit_y() {
+    static std::mutex mu;
+    static int limit[CONE_MAX_DEVICES] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= CONE_MAX_DEVICES) return 0;
+    std::lock_guard<std::mutex> lk(mu);
+    if (limit[dev] <= 0) {
+        int v = 0;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxGridDimY, dev) == hipSuccess) limit[dev] = v;
+    }
+    return limit[dev];
+}
+#define CONE_REQUIRE_GRID_Y(what, B)                                                                                          \
+    do {                                                                                                                       \
+        const int lim_ = grid_limit_y();                                                                                       \
+        CONE_REQUIRE(lim_ > 0, what ": the device's grid limit could not be read");                                            \
+        CONE_REQUIRE((B) <= lim_, what ": %d windows in one call exceed the device's grid limit of %d (gridDim.y)", (B), lim_); \
+    } while (0)
+
 // The forward behind every entry, on the plan its caller made (plan_forward).  Its own body is the 256-wide packed path,
 // post-norm and (p.pre, table path only) pre-norm with the fused tails: the same launches either way -- position tables, ONE
 // N = 768 GEMM per encoder layer, the fused layer tail, the folded decoder cross-attention.  Pre-norm differs in where the
@@ -1037,6 +1059,7 @@ static int forward_general(const cone_model* m, const FwdCall& call, void* ws, s
 static int forward_packed(const cone_model* m, const FwdCall& c, const FwdPlan& p, void* ws, size_t ws_bytes, hipStream_t s) {
     const int B = c.B, Lv_max = c.Lv_max, Lq_max = c.Lq_max;
     CONE_REQUIRE(B > 0 && Lv_max > 0 && Lq_max >= 0, "forward: bad sizes B=%d Lv=%d Lq=%d", B, Lv_max, Lq_max);
+    CONE_REQUIRE_GRID_Y("forward", B);
     const int Lmax = Lv_max + Lq_max;
     if (m->long_windows())
         CONE_REQUIRE(Lmax <= m->opt_max_tokens, "forward: window length %d + %d exceeds the handle's max_window_tokens = %d",
@@ -1401,6 +1424,7 @@ extern "C" int cone_forward_windows(const cone_model* m, const float* vid, const
                                     size_t ws_bytes, void* stream) {
     CONE_REQUIRE(m && vid && txt && vid_len && txt_len && logits && spans, "forward_windows: null argument");
     CONE_REQUIRE(B > 0 && Lv_pad > 0 && Lq_pad > 0, "forward_windows: bad sizes");
+    CONE_REQUIRE_GRID_Y("forward_windows", B);
     CONE_REQUIRE((int64_t)B * Lv_pad < (1ll << 31) && (int64_t)B * Lq_pad < (1ll << 31), "forward_windows: batch too large");
     hipStream_t s = (hipStream_t)stream;
     const size_t nv = (size_t)B * Lv_pad, nt = (size_t)B * Lq_pad;
@@ -1783,4 +1807,78 @@ extern "C" int cone_test_gen_attn(const float* Q, int ldq, const float* K, int l
                                   const int32_t* qoff, const int32_t* koff, int B, int nq, int heads, int head_dim, int kcap,
                                   void* stream) {
     return launch_gen_attn(Q, ldq, K, ldk, V, ldv, OUT, ldo, qoff, koff, B, nq, heads, head_dim, kcap, (hipStream_t)stream);
+}
+
+// The glue kernels of stage B, one entry per launcher, raw operand pointers (tests/test_glue_kernels_gpu.py).  Each entry is
+// the launcher the forward path calls and nothing else: no arithmetic, no checks of its own.
+extern "C" int cone_test_grid_limit_y(void) { return grid_limit_y(); }
+extern "C" int cone_test_scan_lengths(const int32_t* vlen, const int32_t* qlen, int B, int32_t* off, void* stream) {
+    return launch_scan_lengths(vlen, qlen, B, off, (hipStream_t)stream);
+}
+extern "C" int cone_test_compact_index(const int32_t* vlen, const int32_t* voff, int Lv_pad, int32_t* vidx, const int32_t* qlen,
+                                       const int32_t* toff, int Lq_pad, int32_t* tidx, int B, void* stream) {
+    return launch_compact_index(vlen, voff, Lv_pad, vidx, qlen, toff, Lq_pad, tidx, B, (hipStream_t)stream);
+}
+extern "C" int cone_test_pack_pos(const float* vproj, const int32_t* vrow0, const int32_t* vlen, const float* tproj,
+                                  const int32_t* trow0, const int32_t* qlen, const int32_t* off, const float* dim_t, float* X,
+                                  float* POS, float* XP, int B, int Lmax, const float* tpe, const float* tpg, const float* tpb,
+                                  void* stream) {
+    return launch_pack_pos(vproj, vrow0, vlen, tproj, trow0, qlen, off, dim_t, X, POS, XP, B, Lmax, (hipStream_t)stream, tpe, tpg,
+                           tpb);
+}
+extern "C" int cone_test_gen_pack_pos(const float* vproj, const int32_t* vrow0, const int32_t* vlen, const float* tproj,
+                                      const int32_t* trow0, const int32_t* qlen, const int32_t* off, const float* dim_t, float* X,
+                                      float* POS, int d, int B, int Lmax, const float* tpe, const float* tpg, const float* tpb,
+                                      void* stream) {
+    return launch_gen_pack_pos(vproj, vrow0, vlen, tproj, trow0, qlen, off, dim_t, X, POS, d, B, Lmax, (hipStream_t)stream, tpe,
+                               tpg, tpb);
+}
+extern "C" int cone_test_pack_l0(const float* vproj, const int32_t* vrow0, const int32_t* vlen, const float* tproj,
+                                 const int32_t* trow0, const int32_t* qlen, const int32_t* off, const float* dim_t,
+                                 const float* qkv_vid, const float* qkv_txt, const float* pos_qk, float* X, float* POS, float* QK,
+                                 float* V, int B, int Lmax, void* stream) {
+    return launch_pack_l0(vproj, vrow0, vlen, tproj, trow0, qlen, off, dim_t, qkv_vid, qkv_txt, pos_qk, X, POS, QK, V, B, Lmax,
+                          (hipStream_t)stream);
+}
+extern "C" int cone_test_row_index(const int32_t* vrow0, const int32_t* vlen, const int32_t* trow0, const int32_t* qlen,
+                                   const int32_t* off, int32_t* ridx, int B, int Lmax, void* stream) {
+    return launch_row_index(vrow0, vlen, trow0, qlen, off, ridx, B, Lmax, (hipStream_t)stream);
+}
+extern "C" int cone_test_add_pos_rows(const float* MEM, const int32_t* off, const int32_t* vlen, const float* pos_rows, float* XP,
+                                      int B, int Lmax, const float* txt_pos, const int32_t* trow0, void* stream) {
+    return launch_add_pos_rows(MEM, off, vlen, pos_rows, XP, B, Lmax, (hipStream_t)stream, txt_pos, trow0);
+}
+extern "C" int cone_test_txt_pos_rows(const float* tproj, const int32_t* tok_index, const int32_t* src_row, int mod, int n_emb,
+                                      const float* tpe, const float* tpg, const float* tpb, int n, const int32_t* n_dev,
+                                      float* out, void* stream) {
+    return launch_txt_pos_rows(tproj, tok_index, src_row, mod, n_emb, tpe, tpg, tpb, n, n_dev, out, (hipStream_t)stream);
+}
+extern "C" int cone_test_gen_txt_pos_rows(const float* tproj, const int32_t* tok_index, const int32_t* src_row, int mod, int n_emb,
+                                          const float* tpe, const float* tpg, const float* tpb, int n, const int32_t* n_dev, int d,
+                                          float* out, void* stream) {
+    return launch_gen_txt_pos_rows(tproj, tok_index, src_row, mod, n_emb, tpe, tpg, tpb, n, n_dev, d, out, (hipStream_t)stream);
+}
+extern "C" int cone_test_saliency(const float* MEM, const int32_t* off, const int32_t* vlen, const int32_t* qlen, const float* w,
+                                  const float* bias, float* sal, int Lv_out, float* mem_tap, int Lq_out, int B, void* stream) {
+    return launch_saliency(MEM, off, vlen, qlen, w, bias, sal, Lv_out, mem_tap, Lq_out, B, (hipStream_t)stream);
+}
+extern "C" int cone_test_gen_saliency(const float* MEM, const int32_t* off, const int32_t* vlen, const int32_t* qlen,
+                                      const float* w, const float* bias, float* sal, int Lv_out, float* mem_tap, int Lq_out, int B,
+                                      int d, void* stream) {
+    return launch_gen_saliency(MEM, off, vlen, qlen, w, bias, sal, Lv_out, mem_tap, Lq_out, B, d, (hipStream_t)stream);
+}
+extern "C" int cone_test_rowdot(const float* X, int ldx, const float* W, const float* b, float* out, int ldo, int64_t n_rows,
+                                int nout, int act, void* stream) {
+    return launch_rowdot(X, ldx, W, b, out, ldo, n_rows, nout, act, (hipStream_t)stream);
+}
+extern "C" int cone_test_gen_rowdot(const float* X, int ldx, const float* W, const float* b, float* out, int ldo, int64_t n_rows,
+                                    int nout, int act, int d, void* stream) {
+    return launch_gen_rowdot(X, ldx, W, b, out, ldo, n_rows, nout, act, d, (hipStream_t)stream);
+}
+extern "C" int cone_test_tile_rows(float* x, int period, int64_t n_rows, void* stream) {
+    return launch_tile_rows(x, period, n_rows, (hipStream_t)stream);
+}
+extern "C" int cone_test_tile_rows2(float* d0, const float* s0, float* d1, const float* s1, int period, int64_t n_rows,
+                                    void* stream) {
+    return launch_tile_rows2(d0, s0, d1, s1, period, n_rows, (hipStream_t)stream);
 }

@@ -311,7 +311,15 @@ typedef struct {
  * Outputs: logits (B,Nq,2), spans (B,Nq,2) = sigmoid(center,width), saliency (B,Lv_pad; may be NULL: the
  * saliency head is then skipped -- cone/inference.py computes and never reads it, :54-59; likewise the heads and
  * decoder.norm of the intermediate decoder layers run only when taps ask for hs / aux_logits / aux_spans)
- * (entries at padded clips are written as 0; the reference leaves them unspecified/unused). */
+ * (entries at padded clips are written as 0; the reference leaves them unspecified/unused).
+ * CONTRACT (lengths): 0 <= vid_len[b] <= Lv_pad and 0 <= txt_len[b] <= Lq_pad are TRUSTED, not checked: the lengths live on
+ * the device.  The compact row offsets are the prefix sums of the lengths as given, while the source-row lists are written
+ * for min(len, pad) rows per window, so a longer length leaves rows of the compact lists unwritten (read as stale workspace)
+ * and lets the packed forward read past the window's rows.  cone_mask_lengths of an (B, L_pad) mask cannot exceed L_pad; a
+ * caller that builds the lengths itself checks them on the host, as cone_criterion_forward's caller checks tgt_off.
+ * CONTRACT (batch): B is at most the device's maxGridSize[1] (the per-window kernels put the window index in gridDim.y); a
+ * larger B is refused by name ("... exceed the device's grid limit ...") before anything is launched or written.  The same
+ * holds for cone_forward_packed.  Split such a batch into several calls. */
 size_t cone_forward_workspace(const cone_model* m, int B, int Lv_pad, int Lq_pad);
 int cone_forward_windows(const cone_model* m, const float* vid, const int32_t* vid_len,
                          const float* txt, const int32_t* txt_len, int B, int Lv_pad, int Lq_pad,
@@ -687,6 +695,69 @@ int cone_test_layernorm(const float* x, const float* g, const float* b, float* o
  * online softmax, fp32 matrix cores), whose result for a window depends neither on kcap nor on the other windows of the call. */
 int cone_test_gen_attn(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* OUT, int ldo,
                        const int32_t* qoff, const int32_t* koff, int B, int nq, int heads, int head_dim, int kcap, void* stream);
+
+/* The glue kernels of stage B (window_ops.hip, rowops.hip, general.hip), one entry per internal launcher: exactly the launch
+ * the forward path issues, on raw operand pointers, with no arithmetic and no argument checks of its own -- every pointer
+ * must cover what the kernel touches.  All int arrays are int32 on the device.  d-wide ("gen") forms: d % 4 == 0, d <= 512.
+ * Window b holds vlen[b] clip rows then qlen[b] token rows; off (B + 1) is the exclusive prefix sum of vlen + qlen. */
+/* the device's maxGridSize[1] as cone_forward_packed / cone_forward_windows read it (0: the query failed) */
+int cone_test_grid_limit_y(void);
+/* off[0 .. B] = exclusive prefix sum of vlen[b] + qlen[b]; qlen == NULL: of vlen alone (the padded entry's two scans).
+ * Writes exactly B + 1 ints.  One 1024-thread workgroup, any B >= 0. */
+int cone_test_scan_lengths(const int32_t* vlen, const int32_t* qlen, int B, int32_t* off, void* stream);
+/* vidx[voff[b] + p] = b * Lv_pad + p for p < min(vlen[b], Lv_pad), tidx[toff[b] + p] = b * Lq_pad + p for p <
+ * min(qlen[b], Lq_pad); nothing else is written.  B in gridDim.y. */
+int cone_test_compact_index(const int32_t* vlen, const int32_t* voff, int Lv_pad, int32_t* vidx, const int32_t* qlen,
+                            const int32_t* toff, int Lq_pad, int32_t* tidx, int B, void* stream);
+/* d = 256.  Row off[b] + p of X = vproj row vrow0[b] + p (p < vlen[b]) or tproj row trow0[b] + p - vlen[b]; of POS = the
+ * sine row (vlen[b], p) computed per token from dim_t (256 floats) -- any vlen, no table -- or, for a token, zeros (tpe ==
+ * NULL) / LayerNorm(x + tpe[p - vlen[b]]; tpg, tpb); XP = X + POS.  Rows off[B] .. are not written.  Lmax >= the longest
+ * window.  X, POS and XP must all be given. */
+int cone_test_pack_pos(const float* vproj, const int32_t* vrow0, const int32_t* vlen, const float* tproj, const int32_t* trow0,
+                       const int32_t* qlen, const int32_t* off, const float* dim_t, float* X, float* POS, float* XP, int B,
+                       int Lmax, const float* tpe, const float* tpg, const float* tpb, void* stream);
+/* the same d wide, X and POS only (dim_t: d floats) */
+int cone_test_gen_pack_pos(const float* vproj, const int32_t* vrow0, const int32_t* vlen, const float* tproj,
+                           const int32_t* trow0, const int32_t* qlen, const int32_t* off, const float* dim_t, float* X, float* POS,
+                           int d, int B, int Lmax, const float* tpe, const float* tpg, const float* tpb, void* stream);
+/* d = 256.  X as cone_test_pack_pos.  POS != NULL: the sine row / zeros.  QK != NULL (then V too): QK row (512 floats) =
+ * q | k of qkv_vid[clip] (768 floats per row) + pos_qk row vlen (vlen - 1) / 2 + p (512 floats per row), V row = its v part;
+ * a token takes qkv_txt[token] unchanged.  POS == NULL / QK == NULL: that output is not touched and its inputs are not read. */
+int cone_test_pack_l0(const float* vproj, const int32_t* vrow0, const int32_t* vlen, const float* tproj, const int32_t* trow0,
+                      const int32_t* qlen, const int32_t* off, const float* dim_t, const float* qkv_vid, const float* qkv_txt,
+                      const float* pos_qk, float* X, float* POS, float* QK, float* V, int B, int Lmax, void* stream);
+/* ridx[off[b] + p] = vrow0[b] + p for a clip, ~(trow0[b] + p - vlen[b]) for a token */
+int cone_test_row_index(const int32_t* vrow0, const int32_t* vlen, const int32_t* trow0, const int32_t* qlen, const int32_t* off,
+                        int32_t* ridx, int B, int Lmax, void* stream);
+/* d = 256.  XP row off[b] + p = MEM row + pos_rows row vlen (vlen - 1) / 2 + p for a clip; for a token MEM row + txt_pos row
+ * trow0[b] + p - vlen[b], or (txt_pos == NULL: trow0 is then not read) the MEM row unchanged. */
+int cone_test_add_pos_rows(const float* MEM, const int32_t* off, const int32_t* vlen, const float* pos_rows, float* XP, int B,
+                           int Lmax, const float* txt_pos, const int32_t* trow0, void* stream);
+/* out row i = LayerNorm(tproj row i + tpe row j; tpg, tpb), eps 1e-5, for i < (n_dev ? min(*n_dev, n) : n); j = tok_index[i],
+ * or (tok_index == NULL) src_row[i] % mod; j is clamped to [0, n_emb - 1].  Rows past the count are not written. */
+int cone_test_txt_pos_rows(const float* tproj, const int32_t* tok_index, const int32_t* src_row, int mod, int n_emb,
+                           const float* tpe, const float* tpg, const float* tpb, int n, const int32_t* n_dev, float* out,
+                           void* stream);
+int cone_test_gen_txt_pos_rows(const float* tproj, const int32_t* tok_index, const int32_t* src_row, int mod, int n_emb,
+                               const float* tpe, const float* tpg, const float* tpb, int n, const int32_t* n_dev, int d,
+                               float* out, void* stream);
+/* sal (B, Lv_out), may be NULL: <MEM row off[b] + p, w> + bias[0] for p < vlen[b], +0.0 for vlen[b] <= p < Lv_out.  mem_tap
+ * (B, Lv_out + Lq_out, d), may be NULL: rows [0, Lv_out) = the window's clip rows then zero rows, rows [Lv_out, +Lq_out) =
+ * its token rows then zero rows.  Lv_out >= every vlen, Lq_out >= every qlen (TRUSTED). */
+int cone_test_saliency(const float* MEM, const int32_t* off, const int32_t* vlen, const int32_t* qlen, const float* w,
+                       const float* bias, float* sal, int Lv_out, float* mem_tap, int Lq_out, int B, void* stream);
+int cone_test_gen_saliency(const float* MEM, const int32_t* off, const int32_t* vlen, const int32_t* qlen, const float* w,
+                           const float* bias, float* sal, int Lv_out, float* mem_tap, int Lq_out, int B, int d, void* stream);
+/* out[r * ldo + n] = act(<X row r (ldx floats apart, ldx % 4 == 0), W row n> + b[n]), n < nout <= 2; act 1: the sigmoid
+ * 1 / (1 + exp(-s)).  Nothing else of out is written. */
+int cone_test_rowdot(const float* X, int ldx, const float* W, const float* b, float* out, int ldo, int64_t n_rows, int nout,
+                     int act, void* stream);
+int cone_test_gen_rowdot(const float* X, int ldx, const float* W, const float* b, float* out, int ldo, int64_t n_rows, int nout,
+                         int act, int d, void* stream);
+/* 256-float rows.  tile_rows: rows [period, n_rows) of x = row r % period of x (n_rows <= period: nothing is launched).
+ * tile_rows2: rows [0, n_rows) of d0 / d1 = row r % period of s0 / s1. */
+int cone_test_tile_rows(float* x, int period, int64_t n_rows, void* stream);
+int cone_test_tile_rows2(float* d0, const float* s0, float* d1, const float* s1, int period, int64_t n_rows, void* stream);
 
 #ifdef __cplusplus
 }
