@@ -745,8 +745,13 @@ __global__ __launch_bounds__(MQ_NT, 3) void frame_score_mq3_kernel(const float* 
         for (int c = 0; c < nchunk; ++c, ++g) {
             // stage g has landed (this wave's pieces: everything but the 4 pieces of stage g + 1 and, with the loads of the
             // previous step consumed by the compiler's own waits, nothing else); the barrier makes all twelve shares visible
-            // and tells that everybody is done with stage g - 1, which the pieces of stage g + 2 overwrite
-            asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+            // and tells that everybody is done with stage g - 1, which the pieces of stage g + 2 overwrite.  The count is pieces x
+            // stages left in flight: 4 while stage g + 1 follows, 0 on the workgroup's last step -- there nothing younger covers
+            // the four pieces of stage g in a wave that is out of tiles (it issues no frame loads either), and vmcnt(4) would let
+            // it through the barrier with its share of the stage still in the air.  (A live wave needs its frame loads of the
+            // previous step right here anyway: the exact wait costs it nothing.)
+            if (g + 1 < n_steps) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
             pf4 nxt[8];

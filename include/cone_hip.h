@@ -132,7 +132,12 @@ int cone_l2_normalize_rows(const float* x, int64_t n_rows, int dim, float eps, i
  * ws >= cone_prefilter_scores_workspace(ctx_l, nq, W) bytes (two floats per query and half window).
  * Forms (chosen by nq): 1 - 4 queries stream the clip rows once with non-temporal loads, the query vectors in registers (a
  * query's bits do not depend on the others of the launch); 5 or more run fp32-MFMA tiles of 16 / 32 / 64 queries per pass
- * (another summation order: ~1e-7 relative). */
+ * (another summation order: ~1e-7 relative).
+ * NaN: a NaN frame score is skipped by the window max, and a window with no number scores -inf -- nanmax, or -inf where there
+ * is no number.  This is the documented deviation from torch.max, which would return NaN; the frame-score matrix itself keeps
+ * the NaN.  It holds for every form (this entry, cone_prefilter_scores_split, cone_prefilter_batched and the bf16 entries).
+ * Every fp32 form stays within dv u / (1 - dv u) sum_c |a_c b_c| + u |score| of the float64 score, u = 2^-24
+ * (tests/test_prefilter_kernels_gpu.py). */
 int64_t cone_num_windows(int64_t ctx_l, int W);
 size_t cone_prefilter_scores_workspace(int64_t ctx_l, int nq, int W);
 int cone_prefilter_scores(const float* vid, int64_t ctx_l, int dv, const float* txt, int nq,
