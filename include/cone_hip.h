@@ -261,6 +261,8 @@ int cone_prefilter_index_bf16(const float* x, int64_t n_rows, int dim, uint16_t*
  * qh = bf16(q), g = (dv+1) u / (1 - (dv+1) u), u = 2^-24: a bound on |coarse - exact| of every window in any summation order,
  * DESIGN.md 3d).  certified[q] = 0: near-ties, too few candidates or non-finite data; the query's group of up to 4 queries
  * ran the full fp32 scan (a group of certified queries returns after reading the flags).
+ * TRUST: the entry cannot check that its three arenas belong together -- it trusts that vid_bf16 and err are what
+ * cone_prefilter_index_bf16 produced from vid_f32; with any other shadow or measures the proof, and with it the contract, is void.
  * ws >= cone_prefilter_topk_certified_workspace(ctx_l, nq, W, k, n_cand) bytes. */
 size_t cone_prefilter_topk_certified_workspace(int64_t ctx_l, int nq, int W, int k, int n_cand);
 int cone_prefilter_topk_certified(const float* vid_f32, const uint16_t* vid_bf16, int64_t ctx_l, int dv, const float* txt,
