@@ -8,7 +8,13 @@
 //                        The wave keeps the running max of each half-block (S frames) it streams: the window max is
 //                        fused (window_combine_kernel), the frame scores are written only on request.
 //   topk_kernel        : first k entries of the stable descending sort of each score row.
+// The file, in order: the streaming skeleton (PF_LANE_SLOT, pf_slot_max, pf_store_half_max) and its exact-fp32 kernels; the
+// stable top-k family (TK_LOAD_CHUNK, tk_load_list, tk_pass_pick around tk_block_select); the many-query skeleton (PfMqCursor,
+// pf_mq_tile_end, pf_mq_grid) and its three kernels -- exact fp32, split bf16, plain bf16 --, which differ in operand staging
+// and inner product only; the segmented (whole-split) forms; the bf16 streaming forms; the certified pipeline; the C entries
+// and what they share (pf_with_vpl, PfPlanes, launch_window_combine, the CONE_PF_REQUIRE_* checks).  DESIGN.md 3b - 3d.
 #include <mutex>
+#include <type_traits>
 
 #include "common.h"
 
@@ -97,6 +103,41 @@ __device__ __forceinline__ float pf_lane_dot(const float4 (&x)[VPL], const float
     return s;
 }
 
+// ---- the streaming skeleton (fp32 and bf16, per-video and grouped) ------------------------------------------------------
+// Which (row slot, query) total a lane ends up with after wave_sum_multi<RPW * QG>: value index r * QG + g = the lane's top
+// bits -- row slot my_r, query slot my_g.  `writer` = one of the 64 / NV lanes that hold the same total; `out_lane` = lane
+// g * (64 / NV), the one that stores query g's half-window results.  (A macro, not a struct: with a struct hipcc allocates
+// the registers of frame_score_bf16_kernel<1, 2, 4, 4> differently and it loses a wave per SIMD.)
+#define PF_LANE_SLOT(RPW, QG, lane)                                                                                        \
+    static_assert(((RPW) & ((RPW) - 1)) == 0 && ((QG) & ((QG) - 1)) == 0 && (RPW) * (QG) <= 64, "row / query counts: powers of two"); \
+    const int my_j = (lane) / (64 / ((RPW) * (QG))), my_r = my_j / (QG), my_g = my_j % (QG);                                \
+    [[maybe_unused]] const bool writer = ((lane) & (64 / ((RPW) * (QG)) - 1)) == 0, out_lane = writer && my_r == 0
+
+// A wave's max over its rows of a half window (every lane of a (row slot, query) group holds that slot's): over the RPW row
+// slots of a query -- the lanes that differ in the index's top log2(RPW) bits (lane bits 5, 4, ...).
+template <int RPW>
+__device__ __forceinline__ float pf_slot_max(float m) {
+#pragma unroll
+    for (int o = 32; o > 32 / RPW; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    return m;
+}
+
+// hm[q0 + g][h] = the half window's max: the wave's own (WPH = 1) or that of the workgroup's four waves through `red` in LDS
+// (WPH = 4: h is uniform over the workgroup, so the barriers are too).
+template <int QG, int WPH>
+__device__ __forceinline__ void pf_store_half_max(float m, int my_g, bool out_lane, int lane, int wave, float (*red)[QG], int q0, int nq,
+                                                  int64_t nh, int64_t h, float* __restrict__ hm) {
+    if (WPH == 1) {
+        if (out_lane && q0 + my_g < nq) hm[(size_t)(q0 + my_g) * nh + h] = m;
+    } else {
+        if (out_lane) red[wave][my_g] = m;
+        __syncthreads();
+        if (wave == 0 && lane < QG && q0 + lane < nq)
+            hm[(size_t)(q0 + lane) * nh + h] = fmaxf(fmaxf(red[0][lane], red[1][lane]), fmaxf(red[2][lane], red[3][lane]));
+        __syncthreads();
+    }
+}
+
 // GATED (the certified top-k's fallback, cone_prefilter_topk_certified): gate[q] != 0 says that query q needs no scan; a
 // launch group all of whose queries are gated off returns after reading the flags and touches no arena row.  The ungated
 // instantiation is the kernel as it always was (frame_score_kernel below: same arguments, same code).
@@ -106,7 +147,6 @@ __device__ __forceinline__ void frame_score_body(const float* __restrict__ vid, 
                                                  float* __restrict__ fs, float* __restrict__ hm,
                                                  float* __restrict__ fr, const int* __restrict__ gate) {
     constexpr int DV = 256 * VPL, UPB = 4 / WPH, NV = RPW * QG;
-    static_assert((RPW & (RPW - 1)) == 0 && (QG & (QG - 1)) == 0 && NV <= 64, "row / query counts: powers of two");
     if constexpr (GATED) {                                           // (uniform over the grid: the flags of this launch's queries)
         bool any = false;
 #pragma unroll
@@ -115,9 +155,7 @@ __device__ __forceinline__ void frame_score_body(const float* __restrict__ vid, 
     }
     __shared__ float red[4][QG];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sub = wave % WPH;
-    // the (row, query) pair whose total this lane ends up with (wave_sum_multi: value index r * QG + g = the lane's top bits)
-    const int my_j = lane / (64 / NV), my_r = my_j / QG, my_g = my_j % QG;
-    const bool writer = (lane & (64 / NV - 1)) == 0;                   // one of the 64 / NV lanes that hold the same total
+    PF_LANE_SLOT(RPW, QG, lane);
     float4 q[QG][VPL];
 #pragma unroll
     for (int g = 0; g < QG; ++g)
@@ -131,6 +169,8 @@ __device__ __forceinline__ void frame_score_body(const float* __restrict__ vid, 
         const int n = (int)min((int64_t)S, ctx_l - r_lo);            // frames of this half-block
         const float* base = vid + r_lo * DV;
         float m = -INFINITY;                                         // running max of this lane's (row slot, query)
+        // (the row loop of pf16_half_block, with the frame-score and first-frame stores inside: as a function of its own it
+        // costs every instantiation 4 - 10 VGPRs and <2, 1, 4, 1>, the one-query stream, a wave per SIMD)
         for (int j0 = sub * RPW; j0 < n; j0 += WPH * RPW) {
             float4 x[RPW][VPL];
 #pragma unroll
@@ -154,19 +194,8 @@ __device__ __forceinline__ void frame_score_body(const float* __restrict__ vid, 
                 }
             }
         }
-        // over the RPW row slots of a query: the lanes that differ in the index's top log2(RPW) bits (lane bits 5, 4, ...)
-#pragma unroll
-        for (int o = 32; o > 32 / RPW; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-        const bool out_lane = writer && my_r == 0;                     // lane g * (64 / NV): query q0 + g
-        if (WPH == 1) {
-            if (out_lane && q0 + my_g < nq) hm[(size_t)(q0 + my_g) * nh + h] = m;
-        } else {                                    // h is uniform over the workgroup: the barriers are too
-            if (out_lane) red[wave][my_g] = m;
-            __syncthreads();
-            if (wave == 0 && lane < QG && q0 + lane < nq)
-                hm[(size_t)(q0 + lane) * nh + h] = fmaxf(fmaxf(red[0][lane], red[1][lane]), fmaxf(red[2][lane], red[3][lane]));
-            __syncthreads();
-        }
+        m = pf_slot_max<RPW>(m);
+        pf_store_half_max<QG, WPH>(m, my_g, out_lane, lane, wave, red, q0, nq, nh, h, hm);
     }
 }
 
@@ -346,22 +375,39 @@ __device__ __forceinline__ void tk_block_select(const float (&v)[PT], const int 
     }
 }
 
+// The two register loaders of the chunked selections (thread tid's slot u = element u * 256 + tid; index 0x7fffffff = empty).
+// A chunk: windows base .. base + m - 1 of a row into v[] / ix[], SCORE = the score of window base + j as an expression in j
+// (a row's element, or the two planes through pf_window_of_halves); a NaN score is never chosen (as in the one-level kernel);
+// global window indices, ascending with j.  (A macro: as a function taking the score as a callable it costs topk_chunk_kernel
+// and pf_fallback_chunk_kernel 9 VGPRs and with them a wave per SIMD.)
+#define TK_LOAD_CHUNK(v, ix, base, m, SCORE)                        \
+    float v[TK_PT];                                                 \
+    int ix[TK_PT];                                                  \
+    _Pragma("unroll") for (int u = 0; u < TK_PT; ++u) {             \
+        const int j = u * 256 + (int)threadIdx.x;                   \
+        const float x = j < (m) ? (SCORE) : -INFINITY;              \
+        const bool ok = j < (m) && x == x;                          \
+        v[u] = ok ? x : -INFINITY;                                  \
+        ix[u] = ok ? (int)((base) + j) : 0x7fffffff;                \
+    }
+// A list of n <= 256 * TK_PT (value, index) pairs, as a selection left them.
+__device__ __forceinline__ void tk_load_list(const float* __restrict__ cv, const int* __restrict__ ci, int n, float (&v)[TK_PT],
+                                             int (&ix)[TK_PT]) {
+#pragma unroll
+    for (int u = 0; u < TK_PT; ++u) {
+        const int j = u * 256 + threadIdx.x;
+        v[u] = j < n ? cv[j] : -INFINITY;
+        ix[u] = j < n ? ci[j] : 0x7fffffff;
+    }
+}
+
 __global__ __launch_bounds__(256) void topk_chunk_kernel(const float* __restrict__ sc, int64_t n, int k,
                                                          float* __restrict__ cval, int* __restrict__ cidx, int n_chunks) {
-    const int q = blockIdx.y, ch = blockIdx.x, tid = threadIdx.x;
+    const int q = blockIdx.y, ch = blockIdx.x;
     const int64_t base = (int64_t)ch * TK_CH;
     const int m = (int)min((int64_t)TK_CH, n - base);
     const float* row = sc + (size_t)q * n + base;
-    float v[TK_PT];
-    int ix[TK_PT];
-#pragma unroll
-    for (int u = 0; u < TK_PT; ++u) {
-        const int j = u * 256 + tid;
-        const float x = j < m ? row[j] : -INFINITY;
-        const bool ok = j < m && x == x;                    // a NaN score is never selected (as in the one-level kernel)
-        v[u] = ok ? x : -INFINITY;
-        ix[u] = ok ? (int)(base + j) : 0x7fffffff;          // global window index: ascending with j
-    }
+    TK_LOAD_CHUNK(v, ix, base, m, row[j]);
     tk_block_select<TK_PT>(v, ix, k, cval + ((size_t)q * n_chunks + ch) * k, cidx + ((size_t)q * n_chunks + ch) * k, 0x7fffffff);
 }
 
@@ -370,19 +416,46 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float* __restrict
                                                          int n_cand, int k, int32_t* __restrict__ idx,
                                                          float* __restrict__ val) {
     __shared__ float o_v[TK_KMAX];
-    const int q = blockIdx.x, tid = threadIdx.x;
-    const float* cv = cval + (size_t)q * n_cand;
-    const int* ci = cidx + (size_t)q * n_cand;
+    const int q = blockIdx.x;
     float v[TK_PT];
     int ix[TK_PT];
-#pragma unroll
-    for (int u = 0; u < TK_PT; ++u) {
-        const int j = u * 256 + tid;
-        v[u] = j < n_cand ? cv[j] : -INFINITY;
-        ix[u] = j < n_cand ? ci[j] : 0x7fffffff;
-    }
+    tk_load_list(cval + (size_t)q * n_cand, cidx + (size_t)q * n_cand, n_cand, v, ix);
     float* ov = val ? val + (size_t)q * k : o_v;
     tk_block_select<TK_PT>(v, ix, k, ov, idx + (size_t)q * k, -1);
+}
+
+// The end of one pass of the pass-based kernels (topk_kernel, topk_seg_kernel's long rows): every thread brings the best
+// (bv, bi) of its share; the wave arg-max by shuffles, the NW wave winners through LDS, thread 0 picks the pass's winner
+// and stores it (index 0x7fffffff = nothing left: -1), and every thread leaves with it in (last_v, last_i).
+template <int NW>
+__device__ __forceinline__ void tk_pass_pick(float bv, int bi, int32_t* __restrict__ idx_out, float* __restrict__ val_out,
+                                             float& last_v, int& last_i) {
+    __shared__ float s_v[NW];
+    __shared__ int s_i[NW];
+    __shared__ float best_v;
+    __shared__ int best_i;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (tk_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+    if (lane == 0) { s_v[wave] = bv; s_i[wave] = bi; }
+    __syncthreads();
+    if (tid == 0) {
+        float v = s_v[0];
+        int i = s_i[0];
+        for (int w = 1; w < NW; ++w)
+            if (tk_better(s_v[w], s_i[w], v, i)) { v = s_v[w]; i = s_i[w]; }
+        best_v = v; best_i = i;
+        *idx_out = i == 0x7fffffff ? -1 : i;
+        if (val_out) *val_out = v;
+    }
+    __syncthreads();
+    last_v = best_v;
+    last_i = best_i;
+    __syncthreads();
 }
 
 // Stable descending top-k: pass p picks the largest (score, then lowest index) strictly after the
@@ -390,12 +463,7 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float* __restrict
 template <int NT>
 __global__ __launch_bounds__(NT) void topk_kernel(const float* __restrict__ sc, int64_t n, int k,
                                                   int32_t* __restrict__ idx, float* __restrict__ val) {
-    constexpr int NW = NT / 64;
-    __shared__ float s_v[NW];
-    __shared__ int s_i[NW];
-    __shared__ float best_v;
-    __shared__ int best_i;
-    const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int q = blockIdx.x, tid = threadIdx.x;
     const float* row = sc + (size_t)q * n;
     float last_v = INFINITY;
     int last_i = -1;
@@ -413,31 +481,10 @@ __global__ __launch_bounds__(NT) void topk_kernel(const float* __restrict__ sc, 
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int64_t j = j0 + (int64_t)u * NT;
-                const bool after = (v[u] < last_v) || (v[u] == last_v && (int)j > last_i);
-                if (j < n && after && (v[u] > bv || (v[u] == bv && (int)j < bi))) { bv = v[u]; bi = (int)j; }
+                if (j < n && tk_after(v[u], (int)j, last_v, last_i) && tk_better(v[u], (int)j, bv, bi)) { bv = v[u]; bi = (int)j; }
             }
         }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            const float ov = __shfl_xor(bv, o, 64);
-            const int oi = __shfl_xor(bi, o, 64);
-            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-        }
-        if (lane == 0) { s_v[wave] = bv; s_i[wave] = bi; }
-        __syncthreads();
-        if (tid == 0) {
-            float v = s_v[0];
-            int i = s_i[0];
-            for (int w = 1; w < NW; ++w)
-                if (s_v[w] > v || (s_v[w] == v && s_i[w] < i)) { v = s_v[w]; i = s_i[w]; }
-            best_v = v; best_i = i;
-            idx[(size_t)q * k + p] = i == 0x7fffffff ? -1 : i;
-            if (val) val[(size_t)q * k + p] = v;
-        }
-        __syncthreads();
-        last_v = best_v;
-        last_i = best_i;
-        __syncthreads();
+        tk_pass_pick<NT / 64>(bv, bi, idx + (size_t)q * k + p, val ? val + (size_t)q * k + p : nullptr, last_v, last_i);
     }
 }
 
@@ -466,6 +513,79 @@ __device__ __forceinline__ pf4 pf_mq_ld(const float* p) {       // a frame's 16-
 
 constexpr int MQ_NT = 768;     // 12 waves: the one workgroup a CU holds (128 KiB of LDS) runs three waves per SIMD
 
+// ---- the many-query skeleton: what frame_score_mq_kernel, frame_score_mq3_kernel and frame_score_mq_bf16_kernel share ----
+// A wave owns whole half windows (frames [hS, (h+1)S)): ceil(S / 16) tiles of 16 frames, the last one partial (its spare
+// lanes re-read the half window's last frame and are masked), running max per (query, lane) in registers, one value per
+// (query, half window) out.  The waves of a workgroup take consecutive half windows, so their 4-B results of one query fall
+// into one cache line; a wave's next half window is h_step = 12 x gridDim.x further on.  The stream is software-pipelined
+// across tiles AND half windows: the kernels differ in their operand staging and inner product only.
+//
+// The cursor: this tile (half window h, frames f0 .. f0 + 15 of [r_lo, r_hi), fp = lane (li, lg)'s row at its channel
+// offset) and, after look_ahead(), the tile after it (h2 ..., fp2; more = there is one; fp2 = fp when there is none, so a
+// prefetch stays in bounds).  A wave that is not live (frame_score_mq3_kernel's: no half window at all, or none left) points
+// at frame 0 and has no next tile.
+template <class T /* the arena's element */>
+struct PfMqCursor {
+    const T* vid;
+    int64_t ctx_l, nh, h_step;
+    int dv, S, li, off;
+    int64_t h, f0, r_lo, r_hi, h2, f2, lo2, hi2;
+    const T *fp, *fp2;
+    bool more;
+    __device__ __forceinline__ PfMqCursor(const T* vid_, int64_t ctx_l_, int dv_, int S_, int64_t nh_, int64_t h_step_, int li_, int off_,
+                                          int64_t h_, bool live = true)
+        : vid(vid_), ctx_l(ctx_l_), nh(nh_), h_step(h_step_), dv(dv_), S(S_), li(li_), off(off_), h(h_) {
+        r_lo = live ? h * S : 0;
+        r_hi = live ? min(r_lo + S, ctx_l) : 1;
+        f0 = r_lo;
+        fp = vid + min(f0 + li, r_hi - 1) * dv + off;
+    }
+    __device__ __forceinline__ void look_ahead(bool live = true) {       // where the stream goes after this tile
+        h2 = h; f2 = f0 + 16; lo2 = r_lo; hi2 = r_hi;
+        if (f2 >= r_hi) { h2 = h + h_step; lo2 = h2 * S; hi2 = min(lo2 + S, ctx_l); f2 = lo2; }
+        more = live && h2 < nh;
+        fp2 = more ? vid + min(f2 + li, hi2 - 1) * dv + off : fp;
+    }
+    __device__ __forceinline__ void advance() { h = h2; f0 = f2; r_lo = lo2; r_hi = hi2; fp = fp2; }
+};
+
+// The end of a tile.  Accumulator register r of lane (li, lg) = the score of (query q0 + 16 qt + 4 lg + r, frame f0 + li):
+// into the running max, the frame-score matrix (FS) and -- frame hS, i.e. lane li = 0 of the half window's first tile -- the
+// first-frame plane; on the half window's last tile the max over the 16 frame lanes, one hm store per query, and the
+// running max starts over.  (The cursor comes BY VALUE: by reference hipcc does not split the struct before it inlines, and the
+// four-tile forms of all three kernels spill.)
+template <int QT, bool FS, class T>
+__device__ __forceinline__ void pf_mq_tile_end(const PfMqCursor<T> cu, const pf4 (&acc)[QT], pf4 (&mx)[QT], int lg, int q0, int nq,
+                                               float* __restrict__ fs, float* __restrict__ hm, float* __restrict__ fr) {
+    const bool valid = cu.f0 + cu.li < cu.r_hi;
+    const bool first = cu.f0 == cu.r_lo && cu.li == 0;
+#pragma unroll
+    for (int qt = 0; qt < QT; ++qt) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            if (valid) mx[qt][r] = fmaxf(mx[qt][r], acc[qt][r]);
+            const int qg = q0 + qt * 16 + 4 * lg + r;
+            if (FS && valid && qg < nq) fs[(size_t)qg * cu.ctx_l + cu.f0 + cu.li] = acc[qt][r];
+            if (first && qg < nq) fr[(size_t)qg * cu.nh + cu.h] = acc[qt][r];
+        }
+    }
+    if (cu.f0 + 16 >= cu.r_hi) {
+#pragma unroll
+        for (int qt = 0; qt < QT; ++qt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float v = mx[qt][r];
+                v = fmaxf(v, __shfl_xor(v, 1, 64));
+                v = fmaxf(v, __shfl_xor(v, 2, 64));
+                v = fmaxf(v, __shfl_xor(v, 4, 64));
+                v = fmaxf(v, __shfl_xor(v, 8, 64));
+                const int qg = q0 + qt * 16 + 4 * lg + r;
+                if (cu.li == 0 && qg < nq) hm[(size_t)qg * cu.nh + cu.h] = v;
+                mx[qt][r] = -INFINITY;
+            }
+    }
+}
+
 template <int QT /* query tiles of 16 */, bool FS /* also write the frame scores */>
 __global__ __launch_bounds__(MQ_NT, 3) void frame_score_mq_kernel(const float* __restrict__ vid, int64_t ctx_l, int dv,
                                                                 int S, int64_t nh, const float* __restrict__ txt, int q0,
@@ -487,29 +607,17 @@ __global__ __launch_bounds__(MQ_NT, 3) void frame_score_mq_kernel(const float* _
     const int rd = li * 16 + ((lg ^ pf_swz16(li)) << 2);
     const int nchunk = dv >> 7;                                          // 128-channel chunks (8 slabs)
     constexpr int NW = MQ_NT / 64;
-    // A wave owns whole half-blocks (frames [hS, (h+1)S)): ceil(S / 16) tiles of 16 frames, the last one partial (its spare
-    // lanes re-read the block's last frame and are masked), running max per (query, lane) in registers, one value per
-    // (query, half-block) out.  The waves of a workgroup take consecutive half-blocks, so their 4-B results of one query
-    // fall into one cache line.  The stream is software-pipelined across tiles AND half-blocks: the first 128 channels of
-    // the next tile are in flight under the last chunk of this one.
-    const int64_t h_step = (int64_t)gridDim.x * NW;
-    int64_t h = (int64_t)blockIdx.x * NW + (tid >> 6);
-    if (h >= nh) return;
-    int64_t r_lo = h * S, r_hi = min(r_lo + S, ctx_l);
-    int64_t f0 = r_lo;
-    const float* fp = vid + min(f0 + li, r_hi - 1) * dv + 4 * lg;
+    const int64_t h0 = (int64_t)blockIdx.x * NW + (tid >> 6);
+    if (h0 >= nh) return;
+    PfMqCursor<float> cu(vid, ctx_l, dv, S, nh, (int64_t)gridDim.x * NW, li, 4 * lg, h0);
     pf4 cur[8];
 #pragma unroll
-    for (int s = 0; s < 8; ++s) cur[s] = pf_mq_ld(fp + 16 * s);
+    for (int s = 0; s < 8; ++s) cur[s] = pf_mq_ld(cu.fp + 16 * s);
     pf4 mx[QT];
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) mx[qt] = pf4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
     while (true) {
-        // where the stream goes after this tile
-        int64_t h2 = h, f2 = f0 + 16, lo2 = r_lo, hi2 = r_hi;
-        if (f2 >= r_hi) { h2 = h + h_step; lo2 = h2 * S; hi2 = min(lo2 + S, ctx_l); f2 = lo2; }
-        const bool more = h2 < nh;
-        const float* fp2 = more ? vid + min(f2 + li, hi2 - 1) * dv + 4 * lg : fp;
+        cu.look_ahead();
         pf4 acc[QT];
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) acc[qt] = pf4{0.f, 0.f, 0.f, 0.f};
@@ -519,7 +627,7 @@ __global__ __launch_bounds__(MQ_NT, 3) void frame_score_mq_kernel(const float* _
         // 4.07 - 4.10.  PMC: 84 % MFMA-busy at an effective 1.85 GHz -- the exact-fp32 matrix pipe under a 3.4 TB/s stream
         // is power-limited, three waves per SIMD already cover each other's LDS and memory waits.
         for (int c = 0; c < nchunk; ++c) {
-            const float* np = c + 1 < nchunk ? fp + 128 * (c + 1) : fp2;
+            const float* np = c + 1 < nchunk ? cu.fp + 128 * (c + 1) : cu.fp2;
             pf4 nxt[8];
 #pragma unroll
             for (int s = 0; s < 8; ++s) nxt[s] = pf_mq_ld(np + 16 * s);
@@ -536,74 +644,56 @@ __global__ __launch_bounds__(MQ_NT, 3) void frame_score_mq_kernel(const float* _
 #pragma unroll
             for (int s = 0; s < 8; ++s) cur[s] = nxt[s];
         }
-        const bool valid = f0 + li < r_hi;
-        const bool first = f0 == r_lo && li == 0;       // lane li = 0 of the block's first tile = frame hS
-#pragma unroll
-        for (int qt = 0; qt < QT; ++qt) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (valid) mx[qt][r] = fmaxf(mx[qt][r], acc[qt][r]);
-                const int qg = q0 + qt * 16 + 4 * lg + r;
-                if (FS && valid && qg < nq) fs[(size_t)qg * ctx_l + f0 + li] = acc[qt][r];
-                if (first && qg < nq) fr[(size_t)qg * nh + h] = acc[qt][r];
-            }
-        }
-        if (f0 + 16 >= r_hi) {                          // half-block done: max over its 16 frame lanes, one store per query
-#pragma unroll
-            for (int qt = 0; qt < QT; ++qt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float v = mx[qt][r];
-                    v = fmaxf(v, __shfl_xor(v, 1, 64));
-                    v = fmaxf(v, __shfl_xor(v, 2, 64));
-                    v = fmaxf(v, __shfl_xor(v, 4, 64));
-                    v = fmaxf(v, __shfl_xor(v, 8, 64));
-                    const int qg = q0 + qt * 16 + 4 * lg + r;
-                    if (li == 0 && qg < nq) hm[(size_t)qg * nh + h] = v;
-                    mx[qt][r] = -INFINITY;
-                }
-        }
-        if (!more) break;
-        h = h2; f0 = f2; r_lo = lo2; r_hi = hi2; fp = fp2;
+        pf_mq_tile_end<QT, FS>(cu, acc, mx, lg, q0, nq, fs, hm, fr);
+        if (!cu.more) break;
+        cu.advance();
     }
 }
 
-static int prefilter_grid_setup(int* n_cu_out) {
-    static DeviceOnce once;     // the many-query kernel's 128 KiB of LDS: opt-in once per device; its grid = one workgroup per CU
-    const hipError_t rc = device_once(once, [] {
-        const void* fns[6] = {(const void*)frame_score_mq_kernel<4, false>, (const void*)frame_score_mq_kernel<4, true>,
-                              (const void*)frame_score_mq_kernel<2, false>, (const void*)frame_score_mq_kernel<2, true>,
-                              (const void*)frame_score_mq_kernel<1, false>, (const void*)frame_score_mq_kernel<1, true>};
-        hipError_t e = hipSuccess;
-        for (int i = 0; i < 6 && e == hipSuccess; ++i)
-            e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        return e;
-    }, n_cu_out);
-    return rc == hipSuccess ? 0 : -1;
+// The many-query launchers' common part: opt the listed kernels into `lds_bytes` of dynamic LDS (past the 64 KiB default:
+// once per device) and size the grid -- the one workgroup a CU holds, grid-stride over the half windows, twelve per step.
+template <size_t N>
+static int pf_mq_grid(DeviceOnce& once, const void* const (&fns)[N], int lds_bytes, int64_t nh, const char* what, unsigned* blocks) {
+    int n_cu = 0;
+    if (device_once(once, [&] {
+            hipError_t e = hipSuccess;
+            for (size_t i = 0; i < N && e == hipSuccess; ++i)
+                e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+            return e;
+        }, &n_cu) != hipSuccess) {
+        set_error("%s: raising the LDS limit of the many-query kernel failed", what);
+        return CONE_E_HIP;
+    }
+    const int64_t b = (nh + MQ_NT / 64 - 1) / (MQ_NT / 64);
+    *blocks = (unsigned)(b < n_cu ? b : n_cu);
+    return 0;
 }
+// query tiles of 16 for a pass over `rem` remaining queries: 4 (where the form has room for 64 queries), 2, or 1 for <= 16 --
+// half the matrix work of two, and the stream is HBM-bound.  A pass takes 16 x tiles queries.
+static int pf_mq_tiles(int rem, int max_tiles) { return max_tiles == 4 && rem > 32 ? 4 : (rem > 16 ? 2 : 1); }
 
 static int launch_frame_scores_mq(const float* vid, int64_t ctx_l, int dv, int S, int64_t nh, const float* txt, int nq,
                                   float* fs, float* hm, float* fr, hipStream_t s) {
+    static DeviceOnce once;
+    const void* const fns[6] = {(const void*)frame_score_mq_kernel<4, false>, (const void*)frame_score_mq_kernel<4, true>,
+                                (const void*)frame_score_mq_kernel<2, false>, (const void*)frame_score_mq_kernel<2, true>,
+                                (const void*)frame_score_mq_kernel<1, false>, (const void*)frame_score_mq_kernel<1, true>};
+    unsigned blocks = 0;
+    if (int rc = pf_mq_grid(once, fns, 128 * 1024, nh, "prefilter", &blocks)) return rc;
     // 64 queries per launch while their vectors fit the LDS next to nothing else (64 x 512 x 4 B = 128 KiB), else 32
-    const int qpl = dv <= 512 ? 64 : 32;
-    int n_cu = 0;
-    if (prefilter_grid_setup(&n_cu)) { set_error("prefilter: raising the LDS limit of the many-query kernel failed"); return CONE_E_HIP; }
-    int64_t blocks = (nh + MQ_NT / 64 - 1) / (MQ_NT / 64);
-    if (blocks > n_cu) blocks = n_cu;                                  // one workgroup per CU, grid-stride over half-blocks
+    const int max_tiles = dv <= 512 ? 4 : 2;
     for (int q0 = 0; q0 < nq;) {
-        const int rem = nq - q0;
-        const bool wide = qpl == 64 && rem > 32;                           // 4 query tiles, else 2, or 1 for <= 16 queries:
-        const bool one = rem <= 16;                                        // half the matrix work of two, the stream is HBM-bound
-        ProfScope ps(PK_FRAME_SCORE, ctx_l, dv, rem < (wide ? 64 : 32) ? rem : (wide ? 64 : 32), nullptr, s);
-#define CONE_MQ_LAUNCH(QT, FS, QN)                                                                                      \
-    hipLaunchKernelGGL((frame_score_mq_kernel<QT, FS>), dim3((unsigned)blocks), dim3(MQ_NT), (size_t)(QN) * dv * 4, s, vid, \
-                       ctx_l, dv, S, nh, txt, q0, nq, fs, hm, fr)
-        if (wide) { if (fs) CONE_MQ_LAUNCH(4, true, 64); else CONE_MQ_LAUNCH(4, false, 64); }
-        else if (one) { if (fs) CONE_MQ_LAUNCH(1, true, 16); else CONE_MQ_LAUNCH(1, false, 16); }
-        else { if (fs) CONE_MQ_LAUNCH(2, true, 32); else CONE_MQ_LAUNCH(2, false, 32); }
+        const int rem = nq - q0, qt = pf_mq_tiles(rem, max_tiles);
+        ProfScope ps(PK_FRAME_SCORE, ctx_l, dv, rem < 16 * qt ? rem : 16 * qt, nullptr, s);
+#define CONE_MQ_LAUNCH(QT, FS)                                                                                             \
+    hipLaunchKernelGGL((frame_score_mq_kernel<QT, FS>), dim3(blocks), dim3(MQ_NT), (size_t)(QT) * 16 * dv * 4, s, vid, ctx_l, dv, S, \
+                       nh, txt, q0, nq, fs, hm, fr)
+        if (qt == 4) { if (fs) CONE_MQ_LAUNCH(4, true); else CONE_MQ_LAUNCH(4, false); }
+        else if (qt == 2) { if (fs) CONE_MQ_LAUNCH(2, true); else CONE_MQ_LAUNCH(2, false); }
+        else { if (fs) CONE_MQ_LAUNCH(1, true); else CONE_MQ_LAUNCH(1, false); }
 #undef CONE_MQ_LAUNCH
         CONE_LAUNCH_CHECK();
-        q0 += wide ? 64 : 32;
+        q0 += 16 * qt;
     }
     return 0;
 }
@@ -720,25 +810,20 @@ __global__ __launch_bounds__(MQ_NT, 3) void frame_score_mq3_kernel(const float* 
     stream(0);
     if (n_steps > 1) stream(1);
 
-    int64_t h = (int64_t)blockIdx.x * NW + wave;
-    bool live = h < nh;
-    int64_t r_lo = live ? h * S : 0, r_hi = live ? min(r_lo + S, ctx_l) : 1;
-    int64_t f0 = r_lo;
-    const float* fp = vid + min(f0 + li, r_hi - 1) * dv + 4 * lg;
+    const int64_t h0 = (int64_t)blockIdx.x * NW + wave;
+    bool live = h0 < nh;
+    PfMqCursor<float> cu(vid, ctx_l, dv, S, nh, h_step, li, 4 * lg, h0, live);
     pf4 cur[8];
     if (live) {
 #pragma unroll
-        for (int s = 0; s < 8; ++s) cur[s] = pf_mq_ld(fp + 16 * s);
+        for (int s = 0; s < 8; ++s) cur[s] = pf_mq_ld(cu.fp + 16 * s);
     }
     pf4 mx[QT];
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) mx[qt] = pf4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
     int64_t g = 0;
     for (int64_t slot = 0; slot < slots; ++slot) {
-        int64_t h2 = h, f2 = f0 + 16, lo2 = r_lo, hi2 = r_hi;
-        if (f2 >= r_hi) { h2 = h + h_step; lo2 = h2 * S; hi2 = min(lo2 + S, ctx_l); f2 = lo2; }
-        const bool more = live && h2 < nh;
-        const float* fp2 = more ? vid + min(f2 + li, hi2 - 1) * dv + 4 * lg : fp;
+        cu.look_ahead(live);
         pf4 acc[QT];
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) acc[qt] = pf4{0.f, 0.f, 0.f, 0.f};
@@ -756,7 +841,7 @@ __global__ __launch_bounds__(MQ_NT, 3) void frame_score_mq3_kernel(const float* 
             asm volatile("" ::: "memory");
             pf4 nxt[8];
             if (live) {
-                const float* np = c + 1 < nchunk ? fp + 128 * (c + 1) : fp2;
+                const float* np = c + 1 < nchunk ? cu.fp + 128 * (c + 1) : cu.fp2;
 #pragma unroll
                 for (int s = 0; s < 8; ++s) nxt[s] = pf_mq_ld(np + 16 * s);
             }
@@ -786,34 +871,9 @@ __global__ __launch_bounds__(MQ_NT, 3) void frame_score_mq3_kernel(const float* 
             }
         }
         if (!live) continue;
-        const bool valid = f0 + li < r_hi;
-        const bool first = f0 == r_lo && li == 0;       // lane li = 0 of the block's first tile = frame hS
-#pragma unroll
-        for (int qt = 0; qt < QT; ++qt) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (valid) mx[qt][r] = fmaxf(mx[qt][r], acc[qt][r]);
-                const int qg = q0 + qt * 16 + 4 * lg + r;
-                if (first && qg < nq) fr[(size_t)qg * nh + h] = acc[qt][r];
-            }
-        }
-        if (f0 + 16 >= r_hi) {                          // half-block done: max over its 16 frame lanes, one store per query
-#pragma unroll
-            for (int qt = 0; qt < QT; ++qt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float v = mx[qt][r];
-                    v = fmaxf(v, __shfl_xor(v, 1, 64));
-                    v = fmaxf(v, __shfl_xor(v, 2, 64));
-                    v = fmaxf(v, __shfl_xor(v, 4, 64));
-                    v = fmaxf(v, __shfl_xor(v, 8, 64));
-                    const int qg = q0 + qt * 16 + 4 * lg + r;
-                    if (li == 0 && qg < nq) hm[(size_t)qg * nh + h] = v;
-                    mx[qt][r] = -INFINITY;
-                }
-        }
-        if (!more) { live = false; continue; }
-        h = h2; f0 = f2; r_lo = lo2; r_hi = hi2; fp = fp2;
+        pf_mq_tile_end<QT, false>(cu, acc, mx, lg, q0, nq, nullptr, hm, fr);
+        if (!cu.more) { live = false; continue; }
+        cu.advance();
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // no LDS-DMA may outlive the workgroup's LDS
 }
@@ -823,23 +883,16 @@ bool frame_scores_split_supported(int dv, int nq) { return nq >= 8 && dv % 128 =
 static int launch_frame_scores_mq3(const float* vid, int64_t ctx_l, int dv, int S, int64_t nh, const float* txt, int nq, float* hm,
                                    float* fr, char* img, hipStream_t s) {
     static DeviceOnce once;
-    int n_cu = 0;
-    if (device_once(once, [] {
-            return hipFuncSetAttribute((const void*)frame_score_mq3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       MQ3_NBUF * MQ3_CHUNK);
-        }, &n_cu) != hipSuccess) {
-        set_error("prefilter: raising the LDS limit of the split many-query kernel failed");
-        return CONE_E_HIP;
-    }
-    int64_t blocks = (nh + MQ_NT / 64 - 1) / (MQ_NT / 64);
-    if (blocks > n_cu) blocks = n_cu;                                  // one workgroup per CU, grid-stride over half-blocks
+    const void* const fns[1] = {(const void*)frame_score_mq3_kernel};
+    unsigned blocks = 0;
+    if (int rc = pf_mq_grid(once, fns, MQ3_NBUF * MQ3_CHUNK, nh, "prefilter (split)", &blocks)) return rc;
     for (int q0 = 0; q0 < nq; q0 += 64) {
         const int rem = nq - q0;
         hipLaunchKernelGGL(pf_split_queries_kernel, dim3((unsigned)((MQ3_QT * 16 * (dv >> 2) + 255) / 256)), dim3(256), 0, s, txt, dv,
                            q0, nq, img);
         CONE_LAUNCH_CHECK();
         ProfScope ps(PK_FRAME_SCORE, ctx_l, dv, rem < 64 ? rem : 64, nullptr, s);
-        hipLaunchKernelGGL(frame_score_mq3_kernel, dim3((unsigned)blocks), dim3(MQ_NT), MQ3_NBUF * MQ3_CHUNK, s, vid, ctx_l, dv, S, nh,
+        hipLaunchKernelGGL(frame_score_mq3_kernel, dim3(blocks), dim3(MQ_NT), MQ3_NBUF * MQ3_CHUNK, s, vid, ctx_l, dv, S, nh,
                            (const char*)img, q0, nq, hm, fr);
         CONE_LAUNCH_CHECK();
     }
@@ -886,19 +939,14 @@ __global__ __launch_bounds__(256) void frame_score_groups_kernel(const float* __
 #pragma unroll
         for (int r = 0; r < RPW; ++r)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float s = 0.f;
-#pragma unroll
-                for (int v = 0; v < VPL; ++v) s += pf_dot4(x[r][v], q[j][v]);
-                part[r * 4 + j] = s;
-            }
+            for (int j = 0; j < 4; ++j) part[r * 4 + j] = pf_lane_dot<VPL>(x[r], q[j]);
         // the 16 sums by one butterfly (wave_sum_multi): lane l ends up with the total of (row l / 16, query (l / 4) % 4)
         const float s = wave_sum_multi<RPW * 4>(part, lane);
-        const int my_r = lane >> 4;
+        PF_LANE_SLOT(RPW, 4, lane);
         int my_qi = qi[0];
 #pragma unroll
-        for (int j = 1; j < 4; ++j) my_qi = ((lane >> 2) & 3) == j ? qi[j] : my_qi;
-        if ((lane & 3) == 0 && r0 + my_r < ctx_l && my_qi >= 0) fs[q_fs_off[my_qi] + r0 + my_r] = s;
+        for (int j = 1; j < 4; ++j) my_qi = my_g == j ? qi[j] : my_qi;
+        if (writer && r0 + my_r < ctx_l && my_qi >= 0) fs[q_fs_off[my_qi] + r0 + my_r] = s;
     }
 }
 
@@ -923,11 +971,7 @@ __global__ __launch_bounds__(256) void topk_seg_kernel(const float* __restrict__
                                                        const int64_t* __restrict__ q_win_off,
                                                        const int* __restrict__ q_ctx_l, int S, int k,
                                                        int32_t* __restrict__ idx) {
-    __shared__ float s_v[4];
-    __shared__ int s_i[4];
-    __shared__ float best_v;
-    __shared__ int best_i;
-    const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int q = blockIdx.x, tid = threadIdx.x;
     const int n = (q_ctx_l[q] + S - 1) / S + 1;
     const float* row = win + q_win_off[q];
     if (n <= 1024) {
@@ -964,70 +1008,67 @@ __global__ __launch_bounds__(256) void topk_seg_kernel(const float* __restrict__
         int bi = 0x7fffffff;
         for (int j = tid; j < n; j += 256) {
             const float v = row[j];
-            const bool after = (v < last_v) || (v == last_v && j > last_i);
-            if (after && (v > bv || (v == bv && j < bi))) { bv = v; bi = j; }
+            if (tk_after(v, j, last_v, last_i) && tk_better(v, j, bv, bi)) { bv = v; bi = j; }
         }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            const float ov = __shfl_xor(bv, o, 64);
-            const int oi = __shfl_xor(bi, o, 64);
-            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-        }
-        if (lane == 0) { s_v[wave] = bv; s_i[wave] = bi; }
-        __syncthreads();
-        if (tid == 0) {
-            float v = s_v[0];
-            int i = s_i[0];
-            for (int w = 1; w < 4; ++w)
-                if (s_v[w] > v || (s_v[w] == v && s_i[w] < i)) { v = s_v[w]; i = s_i[w]; }
-            best_v = v; best_i = i;
-            idx[(size_t)q * k + p] = i == 0x7fffffff ? -1 : i;
-        }
-        __syncthreads();
-        last_v = best_v;
-        last_i = best_i;
-        __syncthreads();
+        tk_pass_pick<4>(bv, bi, idx + (size_t)q * k + p, nullptr, last_v, last_i);
     }
 }
 
-template <int VPL>
-static int launch_frame_scores(const float* vid, int64_t ctx_l, int S, int64_t nh, const float* txt, int nq, float* fs,
-                               float* hm, float* fr, hipStream_t s, const int* gate = nullptr /* the gated form (no fs) */) {
 #ifndef CONE_PF_RPW
 #define CONE_PF_RPW 4
 #endif
 #ifndef CONE_PF_WGS_PER_CU
 #define CONE_PF_WGS_PER_CU 8
 #endif
-    constexpr int RPW = CONE_PF_RPW;
-    // long videos: one wave per half-block, 8 workgroups per CU grid-striding; short ones: a workgroup per half-block
-    const bool wide = nh < 4096;
-    int64_t blocks = wide ? nh : (nh + 3) / 4;
-    if (blocks > 256 * CONE_PF_WGS_PER_CU) blocks = 256 * CONE_PF_WGS_PER_CU;
-    if (gate) {         // the gated form: every group of 4 queries in ONE launch (a query's bits do not depend on its group)
-        ProfScope ps(PK_FRAME_SCORE, ctx_l, 256 * VPL, 4, nullptr, s);
-        const dim3 grid((unsigned)blocks, (unsigned)((nq + 3) / 4));
-        if (wide) hipLaunchKernelGGL((frame_score_gated_kernel<VPL, RPW, 4>), grid, dim3(256), 0, s, vid, ctx_l, S, nh, txt, nq, hm, fr, gate);
-        else hipLaunchKernelGGL((frame_score_gated_kernel<VPL, RPW, 1>), grid, dim3(256), 0, s, vid, ctx_l, S, nh, txt, nq, hm, fr, gate);
-        CONE_LAUNCH_CHECK();
-        return 0;
+template <int N> using pf_int = std::integral_constant<int, N>;
+
+// The streaming forms' grid, both element types.  Long videos: one wave per half window (WPH = 1), 8 workgroups per CU
+// grid-striding; short ones (`wide`): a workgroup per half window (WPH = 4).
+struct PfStreamGrid {
+    bool wide;
+    unsigned blocks;
+    explicit PfStreamGrid(int64_t nh) : wide(nh < 4096) {
+        const int64_t b = wide ? nh : (nh + 3) / 4;
+        blocks = (unsigned)(b > 256 * CONE_PF_WGS_PER_CU ? 256 * CONE_PF_WGS_PER_CU : b);
     }
+};
+// ... and their passes over the video: 4, 2 or 1 queries each.  3 remaining queries ride a 4-query launch (the fourth slot
+// repeats the last query and stores nothing): one pass instead of two; a query's bits do not depend on the launch it shares
+// (pf_dot4, wave_sum_multi).  launch(QG, WPH, blocks, q0) with QG, WPH as pf_int<> enqueues the kernel instantiation.
+template <class L>
+static int pf_stream_passes(int64_t ctx_l, int dv, int64_t nh, int nq, hipStream_t s, L launch) {
+    const PfStreamGrid g(nh);
     for (int q0 = 0; q0 < nq;) {
         const int rem = nq - q0;
-        // 3 remaining queries ride a 4-query launch (the fourth slot repeats the last query and stores nothing): one pass over
-        // the video instead of two; a query's bits do not depend on the launch it shares (pf_dot4, wave_sum_multi)
         const int qg = rem >= 3 ? 4 : (rem >= 2 ? 2 : 1);
-        ProfScope ps(PK_FRAME_SCORE, ctx_l, 256 * VPL, qg, nullptr, s);
-#define CONE_FS_LAUNCH(QG, WPH)                                                                                        \
-    hipLaunchKernelGGL((frame_score_kernel<VPL, QG, RPW, WPH>), dim3((unsigned)blocks), dim3(256), 0, s, vid, ctx_l, S, \
-                       nh, txt, q0, nq, fs, hm, fr)
-        if (qg == 4) { if (wide) CONE_FS_LAUNCH(4, 4); else CONE_FS_LAUNCH(4, 1); }
-        else if (qg == 2) { if (wide) CONE_FS_LAUNCH(2, 4); else CONE_FS_LAUNCH(2, 1); }
-        else { if (wide) CONE_FS_LAUNCH(1, 4); else CONE_FS_LAUNCH(1, 1); }
-#undef CONE_FS_LAUNCH
+        ProfScope ps(PK_FRAME_SCORE, ctx_l, dv, qg, nullptr, s);
+        auto go = [&](auto QG) { if (g.wide) launch(QG, pf_int<4>{}, g.blocks, q0); else launch(QG, pf_int<1>{}, g.blocks, q0); };
+        if (qg == 4) go(pf_int<4>{}); else if (qg == 2) go(pf_int<2>{}); else go(pf_int<1>{});
         q0 += qg;
         CONE_LAUNCH_CHECK();
     }
+    return 0;
+}
+
+template <int VPL>
+static int launch_frame_scores(const float* vid, int64_t ctx_l, int S, int64_t nh, const float* txt, int nq, float* fs,
+                               float* hm, float* fr, hipStream_t s) {
+    return pf_stream_passes(ctx_l, 256 * VPL, nh, nq, s, [&](auto QG, auto WPH, unsigned blocks, int q0) {
+        hipLaunchKernelGGL((frame_score_kernel<VPL, decltype(QG)::value, CONE_PF_RPW, decltype(WPH)::value>), dim3(blocks), dim3(256), 0,
+                           s, vid, ctx_l, S, nh, txt, q0, nq, fs, hm, fr);
+    });
+}
+
+// the gated form: every group of 4 queries in ONE launch (a query's bits do not depend on its group); no frame scores
+template <int VPL>
+static int launch_frame_scores_gated(const float* vid, int64_t ctx_l, int S, int64_t nh, const float* txt, int nq, float* hm,
+                                     float* fr, const int* gate, hipStream_t s) {
+    const PfStreamGrid g(nh);
+    ProfScope ps(PK_FRAME_SCORE, ctx_l, 256 * VPL, 4, nullptr, s);
+    const dim3 grid(g.blocks, (unsigned)((nq + 3) / 4));
+    if (g.wide) hipLaunchKernelGGL((frame_score_gated_kernel<VPL, CONE_PF_RPW, 4>), grid, dim3(256), 0, s, vid, ctx_l, S, nh, txt, nq, hm, fr, gate);
+    else hipLaunchKernelGGL((frame_score_gated_kernel<VPL, CONE_PF_RPW, 1>), grid, dim3(256), 0, s, vid, ctx_l, S, nh, txt, nq, hm, fr, gate);
+    CONE_LAUNCH_CHECK();
     return 0;
 }
 
@@ -1094,7 +1135,6 @@ template <int VPL, int QG, int RPW, bool NT>
 __device__ __forceinline__ float pf16_half_block(const uint16_t* __restrict__ base, int n, int dv, const float (&q)[QG][VPL][8],
                                                  int lane, int sub, int step, float& first) {
     constexpr int NV = RPW * QG;
-    static_assert((RPW & (RPW - 1)) == 0 && (QG & (QG - 1)) == 0 && NV <= 64, "row / query counts: powers of two");
     const int my_r = (lane / (64 / NV)) / QG;
     float m = -INFINITY;
     for (int j0 = sub * RPW; j0 < n; j0 += step * RPW) {
@@ -1125,21 +1165,17 @@ __device__ __forceinline__ float pf16_half_block(const uint16_t* __restrict__ ba
             if (my_r == 0 && j0 == 0) first = s;
         }
     }
-    // over the RPW row slots of a query: the lanes that differ in the index's top log2(RPW) bits (lane bits 5, 4, ...)
-#pragma unroll
-    for (int o = 32; o > 32 / RPW; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    return m;
+    return pf_slot_max<RPW>(m);
 }
 
 template <int VPL /* 16-B loads per lane and row: dv <= 512 VPL */, int QG, int RPW, int WPH>
 __global__ __launch_bounds__(256) void frame_score_bf16_kernel(const uint16_t* __restrict__ vid, int64_t ctx_l, int dv, int S,
                                                                int64_t nh, const float* __restrict__ txt, int q0, int nq,
                                                                float* __restrict__ hm, float* __restrict__ fr) {
-    constexpr int UPB = 4 / WPH, NV = RPW * QG;
+    constexpr int UPB = 4 / WPH;
     __shared__ float red[4][QG];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sub = wave % WPH;
-    const int my_j = lane / (64 / NV), my_r = my_j / QG, my_g = my_j % QG;
-    const bool out_lane = (lane & (64 / NV - 1)) == 0 && my_r == 0;    // lane g * (64 / NV): query q0 + g
+    PF_LANE_SLOT(RPW, QG, lane);
     float q[QG][VPL][8];
 #pragma unroll
     for (int g = 0; g < QG; ++g) pf16_load_query<VPL>(txt + (size_t)min(q0 + g, nq - 1) * dv, dv, lane, q[g]);
@@ -1149,40 +1185,17 @@ __global__ __launch_bounds__(256) void frame_score_bf16_kernel(const uint16_t* _
         float first = 0.f;
         const float m = pf16_half_block<VPL, QG, RPW, CONE_PF_NT != 0>(vid + r_lo * dv, n, dv, q, lane, sub, WPH, first);
         if (out_lane && sub == 0 && q0 + my_g < nq) fr[(size_t)(q0 + my_g) * nh + h] = first;     // the block's first frame
-        if (WPH == 1) {
-            if (out_lane && q0 + my_g < nq) hm[(size_t)(q0 + my_g) * nh + h] = m;
-        } else {                                    // h is uniform over the workgroup: the barriers are too
-            if (out_lane) red[wave][my_g] = m;
-            __syncthreads();
-            if (wave == 0 && lane < QG && q0 + lane < nq)
-                hm[(size_t)(q0 + lane) * nh + h] = fmaxf(fmaxf(red[0][lane], red[1][lane]), fmaxf(red[2][lane], red[3][lane]));
-            __syncthreads();
-        }
+        pf_store_half_max<QG, WPH>(m, my_g, out_lane, lane, wave, red, q0, nq, nh, h, hm);
     }
 }
 
 template <int VPL>
 static int launch_frame_scores_bf16(const uint16_t* vid, int64_t ctx_l, int dv, int S, int64_t nh, const float* txt, int nq,
                                     float* hm, float* fr, hipStream_t s) {
-    constexpr int RPW = CONE_PF_RPW;
-    const bool wide = nh < 4096;            // as launch_frame_scores: short videos give a half window to a whole workgroup
-    int64_t blocks = wide ? nh : (nh + 3) / 4;
-    if (blocks > 256 * CONE_PF_WGS_PER_CU) blocks = 256 * CONE_PF_WGS_PER_CU;
-    for (int q0 = 0; q0 < nq;) {
-        const int rem = nq - q0;
-        const int qg = rem >= 3 ? 4 : (rem >= 2 ? 2 : 1);      // 3 queries ride a 4-query launch (the fourth slot stores nothing)
-        ProfScope ps(PK_FRAME_SCORE, ctx_l, dv, qg, nullptr, s);
-#define CONE_FS16_LAUNCH(QG, WPH)                                                                                          \
-    hipLaunchKernelGGL((frame_score_bf16_kernel<VPL, QG, RPW, WPH>), dim3((unsigned)blocks), dim3(256), 0, s, vid, ctx_l, dv, \
-                       S, nh, txt, q0, nq, hm, fr)
-        if (qg == 4) { if (wide) CONE_FS16_LAUNCH(4, 4); else CONE_FS16_LAUNCH(4, 1); }
-        else if (qg == 2) { if (wide) CONE_FS16_LAUNCH(2, 4); else CONE_FS16_LAUNCH(2, 1); }
-        else { if (wide) CONE_FS16_LAUNCH(1, 4); else CONE_FS16_LAUNCH(1, 1); }
-#undef CONE_FS16_LAUNCH
-        q0 += qg;
-        CONE_LAUNCH_CHECK();
-    }
-    return 0;
+    return pf_stream_passes(ctx_l, dv, nh, nq, s, [&](auto QG, auto WPH, unsigned blocks, int q0) {
+        hipLaunchKernelGGL((frame_score_bf16_kernel<VPL, decltype(QG)::value, CONE_PF_RPW, decltype(WPH)::value>), dim3(blocks), dim3(256),
+                           0, s, vid, ctx_l, dv, S, nh, txt, q0, nq, hm, fr);
+    });
 }
 
 // Many queries: D[query][frame] tiles of v_mfma_f32_16x16x32_bf16.  k slot (lg, j) of k-step t <-> channel 32 t + 8 lg + j on both
@@ -1218,34 +1231,27 @@ __global__ __launch_bounds__(MQ_NT, 3) void frame_score_mq_bf16_kernel(const uin
     const int rd = li * 64 + lg * 16;
     const int nchunk = (nks + PF16_KS - 1) / PF16_KS;
     constexpr int NW = MQ_NT / 64;
-    const int64_t h_step = (int64_t)gridDim.x * NW;
-    int64_t h = (int64_t)blockIdx.x * NW + (tid >> 6);
-    if (h >= nh) return;
-    int64_t r_lo = h * S, r_hi = min(r_lo + S, ctx_l);
-    int64_t f0 = r_lo;
-    const uint16_t* fp = vid + min(f0 + li, r_hi - 1) * dv + 8 * lg;
+    const int64_t h0 = (int64_t)blockIdx.x * NW + (tid >> 6);
+    if (h0 >= nh) return;
+    PfMqCursor<uint16_t> cu(vid, ctx_l, dv, S, nh, (int64_t)gridDim.x * NW, li, 8 * lg, h0);
     pf_u4 cur[PF16_KS];
 #pragma unroll
     for (int s = 0; s < PF16_KS; ++s) {
         cur[s] = pf_u4{0u, 0u, 0u, 0u};
-        if (s < nks) cur[s] = pf16_ld(fp + 32 * s, CONE_PF_NT_MQ != 0);
+        if (s < nks) cur[s] = pf16_ld(cu.fp + 32 * s, CONE_PF_NT_MQ != 0);
     }
     pf4 mx[QT];
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) mx[qt] = pf4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
     while (true) {
-        // where the stream goes after this tile
-        int64_t h2 = h, f2 = f0 + 16, lo2 = r_lo, hi2 = r_hi;
-        if (f2 >= r_hi) { h2 = h + h_step; lo2 = h2 * S; hi2 = min(lo2 + S, ctx_l); f2 = lo2; }
-        const bool more = h2 < nh;
-        const uint16_t* fp2 = more ? vid + min(f2 + li, hi2 - 1) * dv + 8 * lg : fp;
+        cu.look_ahead();
         pf4 acc[QT];
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) acc[qt] = pf4{0.f, 0.f, 0.f, 0.f};
         for (int c = 0; c < nchunk; ++c) {
             const int kb = c * PF16_KS;
             const bool last = c + 1 == nchunk;
-            const uint16_t* np = last ? fp2 : fp + 32 * (kb + PF16_KS);      // the next block's first k-step of this lane
+            const uint16_t* np = last ? cu.fp2 : cu.fp + 32 * (kb + PF16_KS);      // the next block's first k-step of this lane
             const int n_nxt = last ? nks : nks - (kb + PF16_KS);              // k-steps it has (>= 1)
             pf_u4 nxt[PF16_KS];
 #pragma unroll
@@ -1267,64 +1273,29 @@ __global__ __launch_bounds__(MQ_NT, 3) void frame_score_mq_bf16_kernel(const uin
 #pragma unroll
             for (int s = 0; s < PF16_KS; ++s) cur[s] = nxt[s];
         }
-        const bool valid = f0 + li < r_hi;
-        const bool first = f0 == r_lo && li == 0;       // lane li = 0 of the block's first tile = frame hS
-#pragma unroll
-        for (int qt = 0; qt < QT; ++qt) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (valid) mx[qt][r] = fmaxf(mx[qt][r], acc[qt][r]);
-                const int qg = q0 + qt * 16 + 4 * lg + r;
-                if (first && qg < nq) fr[(size_t)qg * nh + h] = acc[qt][r];
-            }
-        }
-        if (f0 + 16 >= r_hi) {                          // half window done: max over its 16 frame lanes, one store per query
-#pragma unroll
-            for (int qt = 0; qt < QT; ++qt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float v = mx[qt][r];
-                    v = fmaxf(v, __shfl_xor(v, 1, 64));
-                    v = fmaxf(v, __shfl_xor(v, 2, 64));
-                    v = fmaxf(v, __shfl_xor(v, 4, 64));
-                    v = fmaxf(v, __shfl_xor(v, 8, 64));
-                    const int qg = q0 + qt * 16 + 4 * lg + r;
-                    if (li == 0 && qg < nq) hm[(size_t)qg * nh + h] = v;
-                    mx[qt][r] = -INFINITY;
-                }
-        }
-        if (!more) break;
-        h = h2; f0 = f2; r_lo = lo2; r_hi = hi2; fp = fp2;
+        pf_mq_tile_end<QT, false>(cu, acc, mx, lg, q0, nq, nullptr, hm, fr);
+        if (!cu.more) break;
+        cu.advance();
     }
 }
 
 static int launch_frame_scores_mq_bf16(const uint16_t* vid, int64_t ctx_l, int dv, int S, int64_t nh, const float* txt, int nq,
                                        float* hm, float* fr, hipStream_t s) {
-    static DeviceOnce once;     // up to 128 KiB of LDS (64 queries x 1024 channels): opt-in once per device; one workgroup per CU
-    int n_cu = 0;
-    if (device_once(once, [] {
-            const void* fns[3] = {(const void*)frame_score_mq_bf16_kernel<4>, (const void*)frame_score_mq_bf16_kernel<2>,
-                                  (const void*)frame_score_mq_bf16_kernel<1>};
-            hipError_t e = hipSuccess;
-            for (int i = 0; i < 3 && e == hipSuccess; ++i)
-                e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-            return e;
-        }, &n_cu) != hipSuccess) {
-        set_error("prefilter (bf16): raising the LDS limit of the many-query kernel failed");
-        return CONE_E_HIP;
-    }
-    int64_t blocks = (nh + MQ_NT / 64 - 1) / (MQ_NT / 64);
-    if (blocks > n_cu) blocks = n_cu;                                  // one workgroup per CU, grid-stride over half windows
-    for (int q0 = 0; q0 < nq; q0 += 64) {
-        const int rem = nq - q0;
-        const int qt = rem > 32 ? 4 : (rem > 16 ? 2 : 1);              // query tiles of this pass: 64 / 32 / 16 queries
+    static DeviceOnce once;     // up to 128 KiB of LDS (64 queries x 1024 channels)
+    const void* const fns[3] = {(const void*)frame_score_mq_bf16_kernel<4>, (const void*)frame_score_mq_bf16_kernel<2>,
+                                (const void*)frame_score_mq_bf16_kernel<1>};
+    unsigned blocks = 0;
+    if (int rc = pf_mq_grid(once, fns, 128 * 1024, nh, "prefilter (bf16)", &blocks)) return rc;
+    for (int q0 = 0; q0 < nq;) {
+        const int rem = nq - q0, qt = pf_mq_tiles(rem, 4);             // 64 / 32 / 16 queries: the LDS holds every shape
         ProfScope ps(PK_FRAME_SCORE, ctx_l, dv, rem < 16 * qt ? rem : 16 * qt, nullptr, s);
 #define CONE_MQ16_LAUNCH(QT)                                                                                                \
-    hipLaunchKernelGGL((frame_score_mq_bf16_kernel<QT>), dim3((unsigned)blocks), dim3(MQ_NT), (size_t)(QT) * 16 * dv * 2, s, vid, \
-                       ctx_l, dv, S, nh, txt, q0, nq, hm, fr)
+    hipLaunchKernelGGL((frame_score_mq_bf16_kernel<QT>), dim3(blocks), dim3(MQ_NT), (size_t)(QT) * 16 * dv * 2, s, vid, ctx_l, dv, S, \
+                       nh, txt, q0, nq, hm, fr)
         if (qt == 4) CONE_MQ16_LAUNCH(4); else if (qt == 2) CONE_MQ16_LAUNCH(2); else CONE_MQ16_LAUNCH(1);
 #undef CONE_MQ16_LAUNCH
         CONE_LAUNCH_CHECK();
+        q0 += 16 * qt;
     }
     return 0;
 }
@@ -1357,7 +1328,7 @@ __global__ __launch_bounds__(256) void frame_score_groups_bf16_kernel(const uint
                                                                       const int* __restrict__ g_q,
                                                                       const int64_t* __restrict__ q_win_off, int S, int odd,
                                                                       float* __restrict__ win) {
-    constexpr int RPW = 4, QG = 4, NV = RPW * QG;
+    constexpr int RPW = 4, QG = 4;
     const int g = blockIdx.y;
     const int ctx_l = g_ctx_l[g];
     const int nh = (ctx_l + S - 1) / S;
@@ -1373,8 +1344,7 @@ __global__ __launch_bounds__(256) void frame_score_groups_bf16_kernel(const uint
         qi[j] = g_q[g * 4 + j];
         pf16_load_query<VPL>(cls + (size_t)(qi[j] >= 0 ? qi[j] : g_q[g * 4]) * dv, dv, lane, q[j]);
     }
-    const int my_j = lane / (64 / NV), my_r = my_j / QG, my_g = my_j % QG;
-    const bool out_lane = (lane & (64 / NV - 1)) == 0 && my_r == 0;
+    PF_LANE_SLOT(RPW, QG, lane);
     int my_qi = qi[0];
 #pragma unroll
     for (int j = 1; j < QG; ++j) my_qi = my_g == j ? qi[j] : my_qi;
@@ -1540,38 +1510,24 @@ __device__ __forceinline__ void pf_block_select_set(const float (&v)[PT], const 
     for (int e = total + threadIdx.x; e < k; e += 256) { gv[e] = -INFINITY; gi[e] = idx_none; }
 }
 
-// level 1: the set of a chunk of TK_CH window scores (topk_chunk_kernel's loads: a NaN is never chosen)
+// level 1: the set of a chunk of TK_CH window scores (TK_LOAD_CHUNK: a NaN is never chosen)
 __global__ __launch_bounds__(256) void pf_cand_chunk_kernel(const float* __restrict__ sc, int64_t n, int k, float* __restrict__ cval,
                                                             int* __restrict__ cidx, int n_chunks) {
-    const int q = blockIdx.y, ch = blockIdx.x, tid = threadIdx.x;
+    const int q = blockIdx.y, ch = blockIdx.x;
     const int64_t base = (int64_t)ch * TK_CH;
     const int m = (int)min((int64_t)TK_CH, n - base);
     const float* row = sc + (size_t)q * n + base;
-    float v[TK_PT];
-    int ix[TK_PT];
-#pragma unroll
-    for (int u = 0; u < TK_PT; ++u) {
-        const int j = u * 256 + tid;
-        const float x = j < m ? row[j] : -INFINITY;
-        const bool ok = j < m && x == x;
-        v[u] = ok ? x : -INFINITY;
-        ix[u] = ok ? (int)(base + j) : 0x7fffffff;
-    }
+    TK_LOAD_CHUNK(v, ix, base, m, row[j]);
     pf_block_select_set<TK_PT>(v, ix, k, cval + ((size_t)q * n_chunks + ch) * k, cidx + ((size_t)q * n_chunks + ch) * k, 0x7fffffff);
 }
 
 // level 2: the set of the chunk sets' n_in = n_chunks * k <= 256 * TK_PT pairs -> the query's candidates (index -1: none)
 __global__ __launch_bounds__(256) void pf_cand_merge_kernel(const float* __restrict__ cval, const int* __restrict__ cidx, int n_in,
                                                             int k, int32_t* __restrict__ cand, float* __restrict__ coarse) {
-    const int q = blockIdx.x, tid = threadIdx.x;
+    const int q = blockIdx.x;
     float v[TK_PT];
     int ix[TK_PT];
-#pragma unroll
-    for (int u = 0; u < TK_PT; ++u) {
-        const int j = u * 256 + tid;
-        v[u] = j < n_in ? cval[(size_t)q * n_in + j] : -INFINITY;
-        ix[u] = j < n_in ? cidx[(size_t)q * n_in + j] : 0x7fffffff;
-    }
+    tk_load_list(cval + (size_t)q * n_in, cidx + (size_t)q * n_in, n_in, v, ix);
     pf_block_select_set<TK_PT>(v, ix, k, coarse + (size_t)q * k, cand + (size_t)q * k, -1);
 }
 
@@ -1687,20 +1643,11 @@ __global__ __launch_bounds__(256) void pf_fallback_chunk_kernel(const float* __r
                                                                 int64_t nh, int odd, int k, float* __restrict__ cval,
                                                                 int* __restrict__ cidx, int n_chunks,
                                                                 const int32_t* __restrict__ certified) {
-    const int q = blockIdx.y, ch = blockIdx.x, tid = threadIdx.x;
+    const int q = blockIdx.y, ch = blockIdx.x;
     if (certified[q]) return;
     const int64_t base = (int64_t)ch * TK_CH, n = nh + 1;
     const int m = (int)min((int64_t)TK_CH, n - base);
-    float v[TK_PT];
-    int ix[TK_PT];
-#pragma unroll
-    for (int u = 0; u < TK_PT; ++u) {
-        const int j = u * 256 + tid;
-        const float x = j < m ? pf_window_of_halves(hm + (size_t)q * nh, fr + (size_t)q * nh, nh, odd, base + j) : -INFINITY;
-        const bool ok = j < m && x == x;
-        v[u] = ok ? x : -INFINITY;
-        ix[u] = ok ? (int)(base + j) : 0x7fffffff;
-    }
+    TK_LOAD_CHUNK(v, ix, base, m, pf_window_of_halves(hm + (size_t)q * nh, fr + (size_t)q * nh, nh, odd, base + j));
     tk_block_select<TK_PT>(v, ix, k, cval + ((size_t)q * n_chunks + ch) * k, cidx + ((size_t)q * n_chunks + ch) * k, 0x7fffffff);
 }
 
@@ -1708,23 +1655,61 @@ __global__ __launch_bounds__(256) void pf_fallback_merge_kernel(const float* __r
                                                                 int n_lists, int k, int group, float* __restrict__ cv_out,
                                                                 int* __restrict__ ci_out, int32_t* __restrict__ idx,
                                                                 float* __restrict__ val, const int32_t* __restrict__ certified) {
-    const int q = blockIdx.y, g = blockIdx.x, n_groups = gridDim.x, tid = threadIdx.x;
+    const int q = blockIdx.y, g = blockIdx.x, n_groups = gridDim.x;
     if (certified[q]) return;
     const int l0 = g * group, m = (min(l0 + group, n_lists) - l0) * k;          // this group's candidates: lists are contiguous
-    const float* cv = cv_in + ((size_t)q * n_lists + l0) * k;
-    const int* ci = ci_in + ((size_t)q * n_lists + l0) * k;
     float v[TK_PT];
     int ix[TK_PT];
-#pragma unroll
-    for (int u = 0; u < TK_PT; ++u) {
-        const int j = u * 256 + tid;
-        v[u] = j < m ? cv[j] : -INFINITY;
-        ix[u] = j < m ? ci[j] : 0x7fffffff;
-    }
+    tk_load_list(cv_in + ((size_t)q * n_lists + l0) * k, ci_in + ((size_t)q * n_lists + l0) * k, m, v, ix);
     const bool last = n_groups == 1;
     tk_block_select<TK_PT>(v, ix, k, last ? val + (size_t)q * k : cv_out + ((size_t)q * n_groups + g) * k,
                            last ? idx + (size_t)q * k : ci_out + ((size_t)q * n_groups + g) * k, last ? -1 : 0x7fffffff);
 }
+
+// ---- what the C entries share ---------------------------------------------------------------------------------------------
+// f(pf_int<VPL>) for the exact-fp32 streaming kernels' VPL = dv / 256 (dv in {256, 512, 768, 1024}: CONE_PF_REQUIRE_DIM)
+template <class F>
+static int pf_with_vpl(int dv, F f) {
+    switch (dv / 256) {
+        case 1: return f(pf_int<1>{});
+        case 2: return f(pf_int<2>{});
+        case 3: return f(pf_int<3>{});
+        default: return f(pf_int<4>{});
+    }
+}
+
+// the two planes of a score workspace of `bytes` (cone_prefilter_scores_workspace): half-window max, first-frame score
+struct PfPlanes {
+    int64_t nh;
+    float *hm, *fr;
+    PfPlanes(void* ws, size_t bytes, int64_t ctx_l, int S) : nh((ctx_l + S - 1) / S), hm((float*)ws), fr((float*)((char*)ws + bytes / 2)) {}
+};
+
+static int launch_window_combine(const PfPlanes& p, int nq, int W, float* win, hipStream_t s) {
+    hipLaunchKernelGGL(window_combine_kernel, dim3((unsigned)((p.nh + 1 + 255) / 256), nq), dim3(256), 0, s, p.hm, p.fr, p.nh, W & 1, win);
+    CONE_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_frame_scores_gated(const float* vid, int64_t ctx_l, int dv, int S, int64_t nh, const float* txt, int nq, float* hm, float* fr,
+                              const int* gate, hipStream_t s) {
+    return pf_with_vpl(dv, [&](auto VPL) { return launch_frame_scores_gated<decltype(VPL)::value>(vid, ctx_l, S, nh, txt, nq, hm, fr, gate, s); });
+}
+
+// One wording per condition, every entry (`name` = the entry's prefix in the message).
+#define CONE_PF_REQUIRE_SIZES(name, ctx_l, nq, W, S)                                                                       \
+    CONE_REQUIRE((ctx_l) > 0 && (nq) > 0 && (W) > 0 && (S) > 0 && (S) == (W) / 2, name ": bad sizes ctx_l=%lld nq=%d W=%d S=%d", \
+                 (long long)(ctx_l), nq, W, S)
+#define CONE_PF_REQUIRE_DIM(name, dv) \
+    CONE_REQUIRE((dv) == 256 || (dv) == 512 || (dv) == 768 || (dv) == 1024, name ": feature dim %d not in {256,512,768,1024}", dv)
+#define CONE_PF16_REQUIRE_ARENA(name, p, dv)                                                                              \
+    CONE_REQUIRE((dv) > 0 && (dv) % 32 == 0 && (dv) <= 1024, name ": feature dim %d must be a multiple of 32 and <= 1024", dv); \
+    CONE_REQUIRE(((uintptr_t)(p) & 15) == 0, name ": the bf16 arena must be 16-B aligned (16-B lane loads)")
+#define CONE_TK_REQUIRE_SIZES(nq, num_window, k)                                                          \
+    CONE_REQUIRE((nq) > 0 && (num_window) > 0 && (k) > 0 && (k) <= (num_window) && (num_window) < 0x7fffffff, \
+                 "topk: bad sizes nq=%d num_window=%lld k=%d", nq, (long long)(num_window), k)
+#define CONE_PF_REQUIRE_WS(name, ws, ws_bytes, need) \
+    CONE_REQUIRE((ws) && (ws_bytes) >= (need), name ": workspace too small (%zu < %zu)", (size_t)(ws_bytes), (size_t)(need))
 
 }  // namespace cone
 
@@ -1749,41 +1734,29 @@ extern "C" size_t cone_prefilter_scores_split_workspace(int64_t ctx_l, int nq, i
 static int prefilter_scores_impl(const float* vid, int64_t ctx_l, int dv, const float* txt, int nq, int W, int S,
                                  float* frame_scores, float* win_scores, void* ws, size_t ws_bytes, void* stream, bool split) {
     CONE_REQUIRE(vid && txt && win_scores, "prefilter: null argument");
-    CONE_REQUIRE(ctx_l > 0 && nq > 0 && W > 0 && S > 0 && S == W / 2, "prefilter: bad sizes ctx_l=%lld nq=%d W=%d S=%d",
-                 (long long)ctx_l, nq, W, S);
-    CONE_REQUIRE(dv == 256 || dv == 512 || dv == 768 || dv == 1024,
-                 "prefilter: feature dim %d not in {256,512,768,1024}", dv);
+    CONE_PF_REQUIRE_SIZES("prefilter", ctx_l, nq, W, S);
+    CONE_PF_REQUIRE_DIM("prefilter", dv);
     const size_t need = cone_prefilter_scores_workspace(ctx_l, nq, W);
-    CONE_REQUIRE(ws && ws_bytes >= need, "prefilter: workspace too small (%zu < %zu)", ws_bytes, need);
+    CONE_PF_REQUIRE_WS("prefilter", ws, ws_bytes, need);
     hipStream_t s = (hipStream_t)stream;
-    const int64_t nh = (ctx_l + S - 1) / S;
-    float* hm = (float*)ws;
-    float* fr = (float*)((char*)ws + need / 2);
+    const cone::PfPlanes p(ws, need, ctx_l, S);
     int rc;
     if (split && !frame_scores && cone::frame_scores_split_supported(dv, nq)) {
         // opt-in: the same stream on the bf16 matrix cores (three-piece operands, six partial products: fp32 accuracy); the
         // split query image lives behind the two score planes of the workspace
-        CONE_REQUIRE(ws_bytes >= need + cone::frame_scores_split_image_bytes(dv), "prefilter (split): workspace too small (%zu < %zu)",
-                     ws_bytes, need + cone::frame_scores_split_image_bytes(dv));
-        rc = cone::launch_frame_scores_mq3(vid, ctx_l, dv, S, nh, txt, nq, hm, fr, (char*)ws + need, s);
+        CONE_PF_REQUIRE_WS("prefilter (split)", ws, ws_bytes, need + cone::frame_scores_split_image_bytes(dv));
+        rc = cone::launch_frame_scores_mq3(vid, ctx_l, dv, S, p.nh, txt, nq, p.hm, p.fr, (char*)ws + need, s);
     } else if (nq >= CONE_PF_MQ_MIN) {
         // Many queries over one video: the clip arena is read once for up to 64 queries by the fp32-MFMA kernel
         // (BASELINE configs 3 / 5) instead of nq / 4 VALU passes over the features.  From 5 queries on: they would be two
         // passes of the streaming kernel (3.9 ms on the 12.7 GB video), one 16-query tile of this one is a single pass.
-        rc = cone::launch_frame_scores_mq(vid, ctx_l, dv, S, nh, txt, nq, frame_scores, hm, fr, s);
+        rc = cone::launch_frame_scores_mq(vid, ctx_l, dv, S, p.nh, txt, nq, frame_scores, p.hm, p.fr, s);
     } else {
-        switch (dv / 256) {
-            case 1: rc = cone::launch_frame_scores<1>(vid, ctx_l, S, nh, txt, nq, frame_scores, hm, fr, s); break;
-            case 2: rc = cone::launch_frame_scores<2>(vid, ctx_l, S, nh, txt, nq, frame_scores, hm, fr, s); break;
-            case 3: rc = cone::launch_frame_scores<3>(vid, ctx_l, S, nh, txt, nq, frame_scores, hm, fr, s); break;
-            default: rc = cone::launch_frame_scores<4>(vid, ctx_l, S, nh, txt, nq, frame_scores, hm, fr, s); break;
-        }
+        rc = cone::pf_with_vpl(dv, [&](auto VPL) {
+            return cone::launch_frame_scores<decltype(VPL)::value>(vid, ctx_l, S, p.nh, txt, nq, frame_scores, p.hm, p.fr, s);
+        });
     }
-    if (rc) return rc;
-    hipLaunchKernelGGL(cone::window_combine_kernel, dim3((unsigned)((nh + 1 + 255) / 256), nq), dim3(256), 0, s, hm, fr, nh,
-                       W & 1, win_scores);
-    CONE_LAUNCH_CHECK();
-    return 0;
+    return rc ? rc : cone::launch_window_combine(p, nq, W, win_scores, s);
 }
 
 extern "C" int cone_prefilter_scores(const float* vid, int64_t ctx_l, int dv, const float* txt, int nq, int W,
@@ -1802,32 +1775,21 @@ extern "C" size_t cone_prefilter_scores_bf16_workspace(int64_t ctx_l, int nq, in
     return cone_prefilter_scores_workspace(ctx_l, nq, W);           // the two planes (half-window max, first-frame score)
 }
 
-#define CONE_PF16_REQUIRE_ARENA(name, p, dv)                                                                              \
-    CONE_REQUIRE((dv) > 0 && (dv) % 32 == 0 && (dv) <= 1024, name ": feature dim %d must be a multiple of 32 and <= 1024", dv); \
-    CONE_REQUIRE(((uintptr_t)(p) & 15) == 0, name ": the bf16 arena must be 16-B aligned (16-B lane loads)")
-
 extern "C" int cone_prefilter_scores_bf16(const uint16_t* vid, int64_t ctx_l, int dv, const float* txt, int nq, int W, int S,
                                           float* win_scores, void* ws, size_t ws_bytes, void* stream) {
     CONE_REQUIRE(vid && txt && win_scores, "prefilter (bf16): null argument");
-    CONE_REQUIRE(ctx_l > 0 && nq > 0 && W > 0 && S > 0 && S == W / 2, "prefilter (bf16): bad sizes ctx_l=%lld nq=%d W=%d S=%d",
-                 (long long)ctx_l, nq, W, S);
+    CONE_PF_REQUIRE_SIZES("prefilter (bf16)", ctx_l, nq, W, S);
     CONE_PF16_REQUIRE_ARENA("prefilter (bf16)", vid, dv);
     CONE_REQUIRE(((uintptr_t)txt & 15) == 0, "prefilter (bf16): the query vectors must be 16-B aligned");
     const size_t need = cone_prefilter_scores_bf16_workspace(ctx_l, nq, W);
-    CONE_REQUIRE(ws && ws_bytes >= need, "prefilter (bf16): workspace too small (%zu < %zu)", ws_bytes, need);
+    CONE_PF_REQUIRE_WS("prefilter (bf16)", ws, ws_bytes, need);
     hipStream_t s = (hipStream_t)stream;
-    const int64_t nh = (ctx_l + S - 1) / S;
-    float* hm = (float*)ws;
-    float* fr = (float*)((char*)ws + need / 2);
+    const cone::PfPlanes p(ws, need, ctx_l, S);
     int rc;
-    if (nq >= CONE_PF16_MQ_MIN) rc = cone::launch_frame_scores_mq_bf16(vid, ctx_l, dv, S, nh, txt, nq, hm, fr, s);
-    else if (dv <= 512) rc = cone::launch_frame_scores_bf16<1>(vid, ctx_l, dv, S, nh, txt, nq, hm, fr, s);
-    else rc = cone::launch_frame_scores_bf16<2>(vid, ctx_l, dv, S, nh, txt, nq, hm, fr, s);
-    if (rc) return rc;
-    hipLaunchKernelGGL(cone::window_combine_kernel, dim3((unsigned)((nh + 1 + 255) / 256), nq), dim3(256), 0, s, hm, fr, nh,
-                       W & 1, win_scores);
-    CONE_LAUNCH_CHECK();
-    return 0;
+    if (nq >= CONE_PF16_MQ_MIN) rc = cone::launch_frame_scores_mq_bf16(vid, ctx_l, dv, S, p.nh, txt, nq, p.hm, p.fr, s);
+    else if (dv <= 512) rc = cone::launch_frame_scores_bf16<1>(vid, ctx_l, dv, S, p.nh, txt, nq, p.hm, p.fr, s);
+    else rc = cone::launch_frame_scores_bf16<2>(vid, ctx_l, dv, S, p.nh, txt, nq, p.hm, p.fr, s);
+    return rc ? rc : cone::launch_window_combine(p, nq, W, win_scores, s);
 }
 
 // ---- the certified pre-filter: entries ----
@@ -1896,10 +1858,9 @@ extern "C" int cone_prefilter_topk_certified(const float* vid_f32, const uint16_
                                              int32_t* idx, float* val, int32_t* certified, void* ws, size_t ws_bytes,
                                              void* stream) {
     CONE_REQUIRE(vid_f32 && vid_bf16 && txt && err && idx && val && certified, "prefilter_topk_certified: null argument");
-    CONE_REQUIRE(ctx_l > 0 && nq > 0 && W > 0 && S > 0 && S == W / 2 && k > 0 && n_cand >= 0,
-                 "prefilter_topk_certified: bad sizes ctx_l=%lld nq=%d W=%d S=%d k=%d n_cand=%d", (long long)ctx_l, nq, W, S, k, n_cand);
-    CONE_REQUIRE(dv == 256 || dv == 512 || dv == 768 || dv == 1024,
-                 "prefilter_topk_certified: feature dim %d not in {256,512,768,1024}", dv);
+    CONE_PF_REQUIRE_SIZES("prefilter_topk_certified", ctx_l, nq, W, S);
+    CONE_REQUIRE(k > 0 && n_cand >= 0, "prefilter_topk_certified: bad sizes k=%d n_cand=%d", k, n_cand);
+    CONE_PF_REQUIRE_DIM("prefilter_topk_certified", dv);
     CONE_REQUIRE(((uintptr_t)vid_f32 & 15) == 0 && ((uintptr_t)vid_bf16 & 15) == 0 && ((uintptr_t)txt & 15) == 0,
                  "prefilter_topk_certified: the arenas and the query vectors must be 16-B aligned");
     CONE_REQUIRE(k <= cone::TK_KMAX, "prefilter_topk_certified: k=%d exceeds the %d entries of a selection list", k, cone::TK_KMAX);
@@ -1911,7 +1872,7 @@ extern "C" int cone_prefilter_topk_certified(const float* vid_f32, const uint16_
     CONE_REQUIRE(L.n_cand <= L.nw && L.n_cand <= cone::PF_CERT_MAX_CAND && L.n_cand >= L.k_eff,
                  "prefilter_topk_certified: n_cand=%d must lie in [min(k, num_window)=%d, min(num_window=%lld, %d)]", L.n_cand,
                  L.k_eff, (long long)L.nw, cone::PF_CERT_MAX_CAND);
-    CONE_REQUIRE(ws && ws_bytes >= L.total, "prefilter_topk_certified: workspace too small (%zu < %zu)", ws_bytes, L.total);
+    CONE_PF_REQUIRE_WS("prefilter_topk_certified", ws, ws_bytes, L.total);
     hipStream_t s = (hipStream_t)stream;
     char* w = (char*)ws;
     float* win = (float*)(w + L.win);
@@ -1934,13 +1895,11 @@ extern "C" int cone_prefilter_topk_certified(const float* vid_f32, const uint16_
         if (rc) return rc;
     }
     // (c) the candidates' exact scores
-    const dim3 rgrid((unsigned)L.n_cand, (unsigned)nq);
-    switch (dv / 256) {
-        case 1: hipLaunchKernelGGL(cone::pf_rescore_kernel<1>, rgrid, dim3(cone::PF_RS_NT), 0, s, vid_f32, ctx_l, W, S, txt, cand, L.n_cand, exact); break;
-        case 2: hipLaunchKernelGGL(cone::pf_rescore_kernel<2>, rgrid, dim3(cone::PF_RS_NT), 0, s, vid_f32, ctx_l, W, S, txt, cand, L.n_cand, exact); break;
-        case 3: hipLaunchKernelGGL(cone::pf_rescore_kernel<3>, rgrid, dim3(cone::PF_RS_NT), 0, s, vid_f32, ctx_l, W, S, txt, cand, L.n_cand, exact); break;
-        default: hipLaunchKernelGGL(cone::pf_rescore_kernel<4>, rgrid, dim3(cone::PF_RS_NT), 0, s, vid_f32, ctx_l, W, S, txt, cand, L.n_cand, exact); break;
-    }
+    cone::pf_with_vpl(dv, [&](auto VPL) {
+        hipLaunchKernelGGL(cone::pf_rescore_kernel<decltype(VPL)::value>, dim3((unsigned)L.n_cand, (unsigned)nq), dim3(cone::PF_RS_NT), 0, s,
+                           vid_f32, ctx_l, W, S, txt, cand, L.n_cand, exact);
+        return 0;
+    });
     CONE_LAUNCH_CHECK();
     // (d) the k best candidates and the proof
     hipLaunchKernelGGL(cone::pf_certify_kernel, dim3(nq), dim3(256), 0, s, txt, dv, err, cand, coarse, exact, L.n_cand, L.nw, k,
@@ -1950,18 +1909,12 @@ extern "C" int cone_prefilter_topk_certified(const float* vid_f32, const uint16_
     // (e) the fallback, gated on the device by `certified`: the streaming scan in groups of up to 4 queries (a query's bits
     // do not depend on its group), the planes of the coarse scan reused (dead by now), then the gated top-k (here k <= n_cand
     // < num_window, so the rows' stride k is the list length)
-    float* hm = (float*)(w + L.planes);
-    float* fr = (float*)(w + L.planes + L.planes_bytes / 2);
-    switch (dv / 256) {
-        case 1: rc = cone::launch_frame_scores<1>(vid_f32, ctx_l, S, L.nh, txt, nq, nullptr, hm, fr, s, certified); break;
-        case 2: rc = cone::launch_frame_scores<2>(vid_f32, ctx_l, S, L.nh, txt, nq, nullptr, hm, fr, s, certified); break;
-        case 3: rc = cone::launch_frame_scores<3>(vid_f32, ctx_l, S, L.nh, txt, nq, nullptr, hm, fr, s, certified); break;
-        default: rc = cone::launch_frame_scores<4>(vid_f32, ctx_l, S, L.nh, txt, nq, nullptr, hm, fr, s, certified); break;
-    }
+    const cone::PfPlanes p(w + L.planes, L.planes_bytes, ctx_l, S);
+    rc = cone::launch_frame_scores_gated(vid_f32, ctx_l, dv, S, p.nh, txt, nq, p.hm, p.fr, certified, s);
     if (rc) return rc;
     float* cv_a = (float*)(w + L.lists_a);
     int* ci_a = (int*)(cv_a + (size_t)nq * L.n_chunks * k);
-    hipLaunchKernelGGL(cone::pf_fallback_chunk_kernel, dim3((unsigned)L.n_chunks, (unsigned)nq), dim3(256), 0, s, hm, fr, L.nh, W & 1, k,
+    hipLaunchKernelGGL(cone::pf_fallback_chunk_kernel, dim3((unsigned)L.n_chunks, (unsigned)nq), dim3(256), 0, s, p.hm, p.fr, p.nh, W & 1, k,
                        cv_a, ci_a, L.n_chunks, certified);
     CONE_LAUNCH_CHECK();
     const int group = cone::PF_CERT_MAX_CAND / k;          // lists per merge workgroup (>= 16)
@@ -2023,20 +1976,18 @@ extern "C" int cone_prefilter_batched(const float* arena, int dv, const float* c
     CONE_REQUIRE(arena && cls && g_row0 && g_ctx_l && g_q && q_fs_off && q_win_off && q_ctx_l && frame_scores &&
                      win_scores && topk_idx, "prefilter_batched: null argument");
     CONE_REQUIRE(ng > 0 && nq > 0 && max_ctx_l > 0 && W > 0 && S > 0 && k > 0, "prefilter_batched: bad sizes");
-    CONE_REQUIRE(dv == 256 || dv == 512 || dv == 768 || dv == 1024,
-                 "prefilter: feature dim %d not in {256,512,768,1024}", dv);
+    CONE_PF_REQUIRE_DIM("prefilter", dv);
     hipStream_t s = (hipStream_t)stream;
     int64_t bx = ((int64_t)max_ctx_l + 15) / 16;
     if (bx > 2048) bx = 2048;
     dim3 grid((unsigned)bx, ng);
     {
         cone::ProfScope ps(cone::PK_FRAME_SCORE, max_ctx_l, dv, ng, nullptr, s);
-        switch (dv / 256) {
-            case 1: hipLaunchKernelGGL(cone::frame_score_groups_kernel<1>, grid, dim3(256), 0, s, arena, cls, g_row0, g_ctx_l, g_q, q_fs_off, frame_scores); break;
-            case 2: hipLaunchKernelGGL(cone::frame_score_groups_kernel<2>, grid, dim3(256), 0, s, arena, cls, g_row0, g_ctx_l, g_q, q_fs_off, frame_scores); break;
-            case 3: hipLaunchKernelGGL(cone::frame_score_groups_kernel<3>, grid, dim3(256), 0, s, arena, cls, g_row0, g_ctx_l, g_q, q_fs_off, frame_scores); break;
-            default: hipLaunchKernelGGL(cone::frame_score_groups_kernel<4>, grid, dim3(256), 0, s, arena, cls, g_row0, g_ctx_l, g_q, q_fs_off, frame_scores); break;
-        }
+        cone::pf_with_vpl(dv, [&](auto VPL) {
+            hipLaunchKernelGGL(cone::frame_score_groups_kernel<decltype(VPL)::value>, grid, dim3(256), 0, s, arena, cls, g_row0, g_ctx_l, g_q,
+                               q_fs_off, frame_scores);
+            return 0;
+        });
     }
     CONE_LAUNCH_CHECK();
     const int max_nw = (max_ctx_l + S - 1) / S + 1;
@@ -2057,14 +2008,13 @@ extern "C" size_t cone_topk_windows_workspace(int nq, int64_t num_window, int k)
 
 extern "C" int cone_topk_windows_ws(const float* win_scores, int nq, int64_t num_window, int k, int32_t* idx, float* val,
                                     void* ws, size_t ws_bytes, void* stream) {
-    CONE_REQUIRE(nq > 0 && num_window > 0 && k > 0 && k <= num_window && num_window < 0x7fffffff,
-                 "topk: bad sizes nq=%d num_window=%lld k=%d", nq, (long long)num_window, k);
+    CONE_TK_REQUIRE_SIZES(nq, num_window, k);
     const size_t need = cone_topk_windows_workspace(nq, num_window, k);
     const int64_t n_chunks = (num_window + cone::TK_CH - 1) / cone::TK_CH;
     // two-level selection: lists of <= TK_KMAX per wave, all candidates of a row in the merge workgroup's registers
     if (need == 0 || k > cone::TK_KMAX || n_chunks * k > 256 * cone::TK_PT)
         return cone_topk_windows(win_scores, nq, num_window, k, idx, val, stream);
-    CONE_REQUIRE(ws && ws_bytes >= need, "topk: workspace too small (%zu < %zu)", ws_bytes, need);
+    CONE_PF_REQUIRE_WS("topk", ws, ws_bytes, need);
     float* cval = (float*)ws;
     int* cidx = (int*)((char*)ws + need / 2);
     hipStream_t s = (hipStream_t)stream;
@@ -2078,8 +2028,7 @@ extern "C" int cone_topk_windows_ws(const float* win_scores, int nq, int64_t num
 
 extern "C" int cone_topk_windows(const float* win_scores, int nq, int64_t num_window, int k, int32_t* idx,
                                  float* val, void* stream) {
-    CONE_REQUIRE(nq > 0 && num_window > 0 && k > 0 && k <= num_window && num_window < 0x7fffffff,
-                 "topk: bad sizes nq=%d num_window=%lld k=%d", nq, (long long)num_window, k);
+    CONE_TK_REQUIRE_SIZES(nq, num_window, k);
     if (num_window > 4096)      // long video (MAD scale): 16 waves per row
         hipLaunchKernelGGL(cone::topk_kernel<1024>, dim3(nq), dim3(1024), 0, (hipStream_t)stream, win_scores,
                            num_window, k, idx, val);
