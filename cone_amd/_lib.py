@@ -157,6 +157,10 @@ _SIGNATURES = {
     "cone_test_gemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                  C.c_int, C.c_int, C.c_void_p]),
+    # cone_test_gemm_tall(<cone_test_gemm's up to flags>, lda, ldc, M_dev, n_cu, stream): the row GEMM's tall form
+    "cone_test_gemm_tall": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     # cone_test_gemm_bf16(<cone_test_gemm's up to flags>, img, ldc, r_mod, M_dev, stream): the row GEMM of option general_bf16
     "cone_test_gemm_bf16_image_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "cone_test_gemm_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,

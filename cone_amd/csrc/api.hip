@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "common.h"
+#include "gemm_tall.h"
 #include "rows_chain.h"
 
 namespace cone {
@@ -67,6 +68,7 @@ struct cone_model {
     int opt_l0_gather = 1;    // first encoder layer's attention gathers q|k|v from the layer-0 caches itself
     int opt_pos_tables = 1;   // later layers / decoder keys take the position term from the static tables
     int opt_gemm = 0;         // GEMM tile family forced for every dense layer (GEMM_AUTO = by shape)
+    int opt_gemm_tall_min = -1;   // row threshold of the row GEMM's tall form (gemm_tall.hip): -1 = the built-in value, 0 = off
     // derived: every layer tail's operands (launch_layer_tail) -- the fp32 pointers and (d = 256, ff % 32 == 0) the weight
     // images of the two bf16 modes, each mode's in one allocation [encoder q | k | v images | per layer: Wo image, FFN image]:
     // split_img the three-piece images of ffn_split.hip, bf16_img the single-piece ones of ffn_bf16.hip (one third of the bytes)
@@ -377,7 +379,7 @@ static GemmArgs G(const cone_model* m, const float* A, int lda, const float* W, 
     GemmArgs g{};
     g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.C = C; g.ldc = ldc;
     g.M = M; g.M_dev = M_dev; g.N = N; g.K = K; g.flags = flags;
-    g.variant = m ? m->opt_gemm : GEMM_AUTO;
+    g.variant = m ? m->opt_gemm | ((m->opt_gemm_tall_min + 1) << GEMM_TALL_MIN_SHIFT) : GEMM_AUTO;
     if (m && !m->opt_spread) g.flags |= GEMM_NO_SPREAD;        // option ffn_spread = 0: no spread forms anywhere
     return g;
 }
@@ -1579,6 +1581,7 @@ static const OptionRow OPTION_ROWS[] = {
     {"res_gather", &cone_model::opt_res_gather, 0, 1, true},
     {"rows_chain", &cone_model::opt_chain, 0, 1, true},
     {"ffn_spread", &cone_model::opt_spread, 0, 1, true},
+    {"gemm_tall_min_rows", &cone_model::opt_gemm_tall_min, -1, GEMM_TALL_MIN_MAX, false},
 };
 extern "C" int cone_model_set_option(cone_model* m, const char* name, int value) {
     CONE_REQUIRE(m && name, "set_option: null argument");
@@ -1628,7 +1631,7 @@ extern "C" int cone_model_set_option(cone_model* m, const char* name, int value)
         return 0;
     }
     if (!strcmp(name, "gemm")) {
-        CONE_REQUIRE(value >= GEMM_AUTO && value <= GEMM_ROWS8, "set_option: gemm tile family %d not in [0, 3]", value);
+        CONE_REQUIRE(value >= GEMM_AUTO && value <= GEMM_TALL, "set_option: gemm tile family %d not in [0, 4]", value);
         m->opt_gemm = value;
         // the first decoder layer's constants come from these GEMMs: keep them what a step would compute
         if (dec0_constants(m, nullptr) != 0 || hipDeviceSynchronize() != hipSuccess) return CONE_E_HIP;
@@ -1646,6 +1649,20 @@ extern "C" int cone_test_gemm(const float* A, const float* A2, int a2_mod, const
     g.A2 = A2; g.lda2 = K; g.a2_mod = a2_mod; g.R = R; g.ldr = N; g.ln_g = ln_g; g.ln_b = ln_b;
     g.C2 = C2; g.ADD = ADD;
     return launch_gemm(g, (hipStream_t)stream);
+}
+// cone_test_gemm's arguments (bits 8-10 of flags: the tile family, 4 = the tall form; bit 11: an automatic launch never takes the
+// tall form), then lda / ldc (0: K / N), M_dev and n_cu: n_cu > 0 runs the tall form itself on a persistent grid sized for that
+// many CUs, n_cu == 0 goes through the dispatcher
+extern "C" int cone_test_gemm_tall(const float* A, const float* A2, int a2_mod, const float* W, const float* bias,
+                                   const float* R, const float* ln_g, const float* ln_b, float* C, float* C2,
+                                   const float* ADD, int M, int N, int K, int flags, int lda, int ldc, const int32_t* M_dev,
+                                   int n_cu, void* stream) {
+    GemmArgs g = G(nullptr, A, lda ? lda : K, W, K, bias, C, ldc ? ldc : N, M, M_dev, N, K, flags & 0xff);
+    g.variant = ((flags >> 8) & 7) | (((flags >> 11) & 1) << GEMM_TALL_MIN_SHIFT);
+    g.A2 = A2; g.lda2 = K; g.a2_mod = a2_mod; g.R = R; g.ldr = ldc ? ldc : N; g.ln_g = ln_g; g.ln_b = ln_b;
+    g.C2 = C2; g.ADD = ADD;
+    CONE_REQUIRE(n_cu >= 0, "gemm tall hook: negative CU count");
+    return n_cu > 0 ? launch_gemm_tall(g, n_cu, (hipStream_t)stream) : launch_gemm(g, (hipStream_t)stream);
 }
 extern "C" size_t cone_test_gemm_bf16_image_bytes(int N, int K) { return gemm_bf16_image_bytes(N, K); }
 // cone_test_gemm's arguments, then: img (cone_test_gemm_bf16_image_bytes(N, K) bytes: W is packed into it first), ldc (0: N),

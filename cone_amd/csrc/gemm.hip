@@ -18,6 +18,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "gemm_tall.h"
 #include "rows_chain.h"
 
 #ifndef CONE_GEMM_NT_STORE
@@ -1003,11 +1004,24 @@ constexpr int RS_MAX_WGS = CONE_RS_MAX_WGS;
 #define CONE_RS_SPLIT_WGS 256
 #endif
 
-int launch_gemm(const GemmArgs& a, hipStream_t s) {
+int launch_gemm(const GemmArgs& a_in, hipStream_t s) {
+    GemmArgs a = a_in;
+    const int tall_code = a.variant >> GEMM_TALL_MIN_SHIFT;     // gemm_tall.h: the launch's own row threshold of the tall form
+    a.variant &= GEMM_VARIANT_MASK;
     CONE_REQUIRE(a.K > 0 && a.K % BK == 0, "gemm: K=%d must be a multiple of %d", a.K, BK);
     CONE_REQUIRE(a.lda % 4 == 0 && a.ldw % 4 == 0, "gemm: lda/ldw must be multiples of 4");
     CONE_REQUIRE(!(a.flags & EPI_RESIDUAL) || a.R, "gemm: residual flag without R");
     if (a.M <= 0) return 0;
+    // The tall form (gemm_tall.hip; K = 256, many rows): forced by GEMM_TALL, else taken by an automatic launch that it can run
+    // from a row threshold on -- the HOST-known bound, never the device-side count, so a launch's form stays a function of
+    // shape and host bound (below).  It runs the 8-wave row tile's fma chains and epilogue arithmetic: same bits.
+    if (a.variant == GEMM_TALL) return launch_gemm_tall(a, 0, s);
+    if (a.variant == GEMM_AUTO) {
+        // (the built-in rule leaves residual launches where they were: not measured at N = 768, behind the row tile at N = 256)
+        const bool take = tall_code == 0 ? gemm_tall_builtin_rule(a.M, a.N) && !(a.flags & EPI_RESIDUAL)
+                                         : tall_code > 1 && a.M >= tall_code - 1;
+        if (take && !gemm_tall_refusal(a)) return launch_gemm_tall(a, 0, s);
+    }
     if (a.flags & EPI_LN) CONE_REQUIRE(a.N == 256 && a.ln_g && a.ln_b, "gemm: LayerNorm epilogue needs N == 256");
     const bool rows_ok = a.N % 256 == 0 && !a.A2;
     // The tile family is a function of the SHAPE and of a.variant only (never of M or of process state), so a row

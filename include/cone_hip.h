@@ -503,7 +503,9 @@ int cone_eval_window_recall(const int32_t* win_idx, int nq, int k, const double*
  * (M rows, ff, 256): 4*M*ff*256 FLOPs; kind 9 = the same with the output projection: + 2*M*256*256.  One kind per KERNEL:
  * kinds 10 / 11 = kinds 8 / 9 computed by the wide form (ffn_wide_kernel: launches of a few row groups and the rows past the
  * last full round of a big launch -- a record of its own, with the rows it covered); 12 / 13 = the 64-row / 4-wave form;
- * 14 = the row GEMM's small form (16-row tiles).  Returns the record count.  Not thread-safe. */
+ * 14 = the row GEMM's small form (16-row tiles).  The row GEMM's tall form (gemm_tall.hip: K = 256, many rows) books its launches
+ * under kind 6 too: it computes what the 8-wave row tile computes, bit for bit, and the FLOP accounting by shape (M, N, K) of
+ * that kind stays complete.  Returns the record count.  Not thread-safe. */
 int cone_prof_enable(int on);
 int64_t cone_prof_collect(double* out, int64_t max_rec);
 
@@ -583,7 +585,11 @@ int64_t cone_prof_collect(double* out, int64_t max_rec);
  *   general_shape = 0 leaves the option set and inert: the fused path never reads it.
  * "gemm" (default 0 = by shape): tile family of every dense layer: 1 = register-staged 128x128 / 64x256 tiles,
  *   2 / 3 = 128x256 row-owning LDS-DMA tile with 4 waves x 32 rows (32x32x2) / 8 waves x 16 rows (16x16x4) -- all
- *   exact-fp32 fma chains per output element that walk k in different orders. */
+ *   exact-fp32 fma chains per output element that walk k in different orders; 4 = the tall form of the row GEMM
+ *   (gemm_tall.hip: K = 256, N % 32 == 0, no addend / second output / LayerNorm epilogue / periodic residual; the bits of 3),
+ *   a launch it cannot run is refused by name.
+ * "gemm_tall_min_rows" (default -1 = the built-in threshold): automatic launches of at least this many rows (host bound) that
+ *   the tall form can run take it; 0 = never.  The bits do not depend on it. */
 int cone_model_set_option(cone_model* m, const char* name, int value);
 /* C = epi((A [+ A2]) W^T + bias); flags: 1 relu, 2 add residual R, 4 LayerNorm(g,b) (N must be 256), 8 = keep a launch of a few
  * row groups on the workgroup-per-16-rows form (else: one wave per 16 x 16 output tile, same bits);
@@ -592,6 +598,14 @@ int cone_model_set_option(cone_model* m, const char* name, int value);
 int cone_test_gemm(const float* A, const float* A2, int a2_mod, const float* W, const float* bias,
                    const float* R, const float* ln_g, const float* ln_b, float* C, float* C2,
                    const float* ADD, int M, int N, int K, int flags, void* stream);
+/* cone_test_gemm with row strides lda / ldc (0: K / N; R shares ldc), a device-side row count M_dev (may be null) and, in bits
+ * 8-10 of flags, the tile family including 4 = the tall form (gemm_tall.hip); bit 11 keeps an automatic launch (family 0) off the
+ * tall form whatever its row count (the shipped forms, for A/B timing).  n_cu > 0: the tall form itself on a persistent
+ * grid sized for n_cu CUs, so that a few hundred rows make a workgroup walk several tiles; n_cu == 0: through the dispatcher. */
+int cone_test_gemm_tall(const float* A, const float* A2, int a2_mod, const float* W, const float* bias,
+                        const float* R, const float* ln_g, const float* ln_b, float* C, float* C2,
+                        const float* ADD, int M, int N, int K, int flags, int lda, int ldc, const int32_t* M_dev,
+                        int n_cu, void* stream);
 /* The row GEMM of option "general_bf16" (gemm_bf16.hip): cone_test_gemm's arguments and
  *   C[m][n] = sum_k bf16(A[m][k] (+ A2[a2_mod ? m % a2_mod : m][k], added in fp32 first)) * bf16(W[n][k])   (fp32 accumulation)
  *             + bias[n],  then ReLU (flag 1),  then + R[r_mod ? m % r_mod : m][n] (flag 2; the residual is never rounded)

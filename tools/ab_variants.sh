@@ -3,6 +3,9 @@
 #   tools/ab_variants.sh <source.hip> "<command>" "<flags of variant A>" "<flags of variant B>" ...
 # Each variant: rebuild cone_amd/csrc/<source.hip> with CONE_HIPCC_FLAGS=<flags>, run <command>, print its stdout.
 # The default build is restored at the end (also when a variant fails).
+# Switches (-D macros): the thresholds named in the sources, among them CONE_GEMM_TALL_MIN_ROWS (gemm.hip: the row GEMM's tall
+# form from that many rows on at N = 768; 0 = off), e.g.
+#   tools/ab_variants.sh gemm.hip "python bench.py --gpus 1 --steps 20 --warmup 3" "-DCONE_GEMM_TALL_MIN_ROWS=0" ""
 src=$1; cmd=$2; shift 2
 restore() { touch cone_amd/csrc/$src; CONE_HIPCC_FLAGS="" python3 -m cone_amd.build > /dev/null 2>&1; }
 trap restore EXIT
