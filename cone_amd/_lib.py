@@ -67,6 +67,26 @@ class Taps(C.Structure):
                 ("aux_spans", C.c_void_p)]
 
 
+# video sessions (additive in ABI 8): cone_model_dims, cone_session, cone_session_params
+SESSION_BF16, SESSION_CERTIFIED, SESSION_MAX_QUERIES = 1, 2, 64
+
+
+class ModelDims(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("hidden_dim", "num_queries", "enc_layers", "t_dim", "v_dim", "v_motion_dim", "txt_pos",
+                                         "long_windows")]
+
+
+class Session(C.Structure):
+    _fields_ = [("model", C.c_void_p), ("ctx_l", C.c_int64), ("flags", C.c_int32), ("v_dim", C.c_int32),
+                ("hidden_dim", C.c_int32), ("vid_norm", C.c_void_p), ("adapted", C.c_void_p), ("adapted_bf16", C.c_void_p),
+                ("err", C.c_void_p), ("vproj", C.c_void_p), ("qkv_vid", C.c_void_p)]
+
+
+class SessionParams(C.Structure):
+    _fields_ = [("max_v_l", C.c_int32), ("max_q_l", C.c_int32), ("clip_length", C.c_float), ("nms_thd", C.c_double),
+                ("max_before", C.c_int32), ("max_after", C.c_int32)]
+
+
 _SIGNATURES = {
     "cone_last_error": (C.c_char_p, []),
     "cone_abi_version": (C.c_int, []),
@@ -153,6 +173,21 @@ _SIGNATURES = {
     "cone_eval_window_recall": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_void_p,
                                           C.c_int, C.c_void_p, C.c_void_p]),
     "cone_model_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
+    # video sessions (additive in ABI 8): the video half once, the query half as one call
+    "cone_model_get_dims": (C.c_int, [C.c_void_p, C.POINTER(ModelDims)]),
+    "cone_session_arena_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int]),
+    "cone_session_workspace": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int]),
+    "cone_session_index": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                     C.POINTER(Session), C.c_void_p]),
+    # cone_session_query_layout(tok_len (host), nq, max_q_l, ctx_l, K, Nq, max_v_l, <8 int32 outputs>, stream)
+    "cone_session_query_layout": (C.c_int, [C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int]
+                                  + [C.c_void_p] * 8 + [C.c_void_p]),
+    "cone_session_localize_workspace": (C.c_size_t, [C.c_void_p, C.POINTER(Session), C.POINTER(C.c_int32), C.c_int, C.c_int,
+                                                     C.c_int, C.POINTER(SessionParams)]),
+    # cone_session_localize(m, session, tok, tok_len (host), nq, cls, K, n_cand, params, kept, n_kept, certified, ws, ws_bytes, stream)
+    "cone_session_localize": (C.c_int, [C.c_void_p, C.POINTER(Session), C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_void_p,
+                                        C.c_int, C.c_int, C.POINTER(SessionParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_size_t, C.c_void_p]),
     # cone_test_gemm(A, A2, a2_mod, W, bias, R, ln_g, ln_b, C, C2, ADD, M, N, K, flags, stream)
     "cone_test_gemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,

@@ -1641,6 +1641,16 @@ extern "C" int cone_model_set_option(cone_model* m, const char* name, int value)
     return CONE_E_INVALID;
 }
 
+// what a sequencing entry outside this file (session.hip) has to know of the opaque handle to size its buffers
+extern "C" int cone_model_get_dims(const cone_model* m, cone_model_dims* out) {
+    CONE_REQUIRE(m && out, "model_get_dims: null argument");
+    out->hidden_dim = m->d; out->num_queries = m->nq; out->enc_layers = m->n_enc;
+    out->t_dim = m->dt; out->v_dim = m->dv; out->v_motion_dim = m->dvm;
+    out->txt_pos = m->txt_pos_emb != nullptr;
+    out->long_windows = m->long_windows();
+    return 0;
+}
+
 extern "C" int cone_test_gemm(const float* A, const float* A2, int a2_mod, const float* W, const float* bias,
                               const float* R, const float* ln_g, const float* ln_b, float* C, float* C2,
                               const float* ADD, int M, int N, int K, int flags, void* stream) {

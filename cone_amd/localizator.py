@@ -119,6 +119,16 @@ class CONELocalizator:
         g[0].replay()
         return g[2]
 
+    def open_video(self, video_feats, certified=False, n_cand=None, step="python"):
+        """cone_amd extension: index ``video_feats`` once and answer query batches on it (``cone_amd.session.VideoSession``).
+        The session does the video half of ``_enqueue`` (normalised clips, adapted rows, ``input_vid_proj``, the first encoder
+        layer's q | k | v rows) once and keeps it resident; ``session.predict_moment(text_feats)`` /
+        ``session.predict_moments([text_feats, ...])`` return this class's ``predict_moment`` results, ``==``.
+        ``certified``: window ranking through ``ops.PrefilterIndex`` (bf16 scan, fp32 rescore, the exact ranking; ``n_cand``
+        candidates per query); ``step``: "python" (one ctypes call per launcher) or "c" (``cone_session_localize``)."""
+        from .session import VideoSession
+        return VideoSession(self, video_feats, certified=certified, n_cand=n_cand, step=step)
+
     @torch.no_grad()
     def predict_moment(self, video_feats, text_feats):
         """run_on_video/cone_localizator.py:121-221 on the eval driver's kernels, enqueued without a host round trip until

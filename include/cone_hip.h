@@ -476,6 +476,94 @@ int cone_criterion_forward(const float* logits, const float* spans, const float*
 /* loss_adapter (cone/model.py:249-264): (CE(sim / T, diag) + CE(sim^T / T, diag)) / 2 for sim (n, n); loss (1). */
 int cone_adapter_nce(const float* sim, int n, float temperature, float* loss, void* stream);
 
+/* ------------------------------------------------------------ video sessions (additive in ABI 8)
+ * One resident video, indexed once, answering batches of queries: run_on_video/cone_localizator.py:121-221
+ * (CONELocalizator.predict_moment) split into its video half (:129, :135-138, and the per-clip rows of :150-190: input_vid_proj
+ * and the first encoder layer's q | k | v) and its query half.  CONTRACT: nothing new is computed -- both entries only
+ * sequence the launchers above, with the arguments cone_amd/localizator.py passes them, so the kept moments carry the bits
+ * of predict_moment on the same video and query (tests/test_session_gpu.py compares them with ==).  All memory is the caller's:
+ * the resident rows live in ONE arena, every call's scratch in ONE workspace; nothing is allocated here, one stream, no host
+ * read-back (both entries can be captured in a graph). */
+
+/* What a caller sizing buffers around the opaque handle needs to know of it.  long_windows follows the handle's
+ * "max_window_tokens" option at the moment of the call. */
+typedef struct {
+    int32_t hidden_dim, num_queries, enc_layers, t_dim, v_dim, v_motion_dim;
+    int32_t txt_pos;       /* a --use_txt_pos checkpoint */
+    int32_t long_windows;  /* max_window_tokens above CONE_MAX_WINDOW_TOKENS: every forward on the general path */
+} cone_model_dims;
+int cone_model_get_dims(const cone_model* m, cone_model_dims* out);
+
+#define CONE_SESSION_BF16 1       /* the adapted rows are kept in bf16 only: the opt-in bf16 pre-filter (NOT fp32-accurate) */
+#define CONE_SESSION_CERTIFIED 2  /* fp32 adapted rows + their bf16 shadow + its measures: the certified pre-filter; excludes BF16 */
+#define CONE_SESSION_MAX_QUERIES 64
+
+/* The resident half of a video: a plain host struct of device pointers into the caller's arena, filled by cone_session_index.
+ * The library keeps no reference to it; it is valid while the arena and the handle it was indexed with live. */
+typedef struct {
+    const cone_model* model;        /* the handle it was indexed with: cone_session_localize refuses any other */
+    int64_t ctx_l;                  /* clips */
+    int32_t flags;                  /* CONE_SESSION_* */
+    int32_t v_dim, hidden_dim;      /* row widths of the arrays below */
+    const float* vid_norm;          /* (ctx_l, v_dim) F.normalize of the clips (:129) */
+    const float* adapted;           /* (ctx_l, v_dim) adapter(x) + x, NOT re-normalised (:135-138); NULL with CONE_SESSION_BF16 */
+    const uint16_t* adapted_bf16;   /* CONE_SESSION_BF16: the adapted rows in bf16; CONE_SESSION_CERTIFIED: their shadow */
+    const float* err;               /* CONE_SESSION_CERTIFIED: the shadow's two measures (cone_prefilter_index_bf16) */
+    const float* vproj;             /* (ctx_l, hidden_dim) input_vid_proj of the clips */
+    const float* qkv_vid;           /* (ctx_l, 3 hidden_dim) first encoder layer's q | k | v rows; NULL on a long-window handle */
+} cone_session;
+
+/* The video half of run_on_video/cone_localizator.py:121-221, once per video: cone_l2_normalize_rows (eps 1e-5, clamp),
+ * cone_adapter_norm / cone_adapter_norm_bf16 with renorm == 0, with CONE_SESSION_CERTIFIED cone_prefilter_index_bf16 on the
+ * fp32 adapted rows, cone_project_tokens of the video side, and (not on a long-window handle) cone_layer0_project.
+ * raw_vid (ctx_l, v_dim) fp32 with v_dim == v_motion_dim (the localizer feeds one feature to both sides).
+ * arena >= cone_session_arena_bytes, 256-B aligned; ws >= cone_session_workspace (free again when the call's work is done).
+ * Resident bytes per clip at 256 / 256: 1 KiB normalised + 1 KiB adapted (0.5 KiB bf16; 1.5 KiB certified) + 1 KiB projected
+ * + 3 KiB q | k | v.  Refused by name: null arguments, flags with both modes, v_dim != v_motion_dim, a short arena or workspace. */
+size_t cone_session_arena_bytes(const cone_model* m, int64_t ctx_l, int flags);
+size_t cone_session_workspace(const cone_model* m, int64_t ctx_l, int flags);
+int cone_session_index(const cone_model* m, const float* raw_vid, int64_t ctx_l, int flags, void* arena, size_t arena_bytes,
+                       void* ws, size_t ws_bytes, cone_session* session, void* stream);
+
+/* The per-call index metadata of nq queries on one video -- the shapes run_on_video/cone_localizator.py:121-221 builds on the
+ * host per call (:150-170 pads every window to max_v_l, :191 scales by it) --, written on the device by ONE small launch with
+ * no upload (what cone_amd/localizator.py keeps per shape in _const): the token lengths travel as kernel arguments.  tok_len is a HOST array
+ * of nq lengths.  Outputs (device, int32): tok_off (nq + 1) exclusive prefix sums; tok_len_dev (nq); tok_idx (sum of the
+ * lengths) = index of every token row inside its query, restarting at 0 per query (cone_layer0_text_positions); q_ctx_l (nq)
+ * = ctx_l; q_vid_off (nq) = 0; batch_pad (nq) = max_v_l and full_w (nq * K) = max_v_l: every window counts as padded to
+ * max_v_l (:150-170, :191); n_valid (nq) = K * Nq candidate rows per query.  Nothing else is written.
+ * Refused by name: nq outside [1, CONE_SESSION_MAX_QUERIES]; a length outside [1, max_q_l]; K < 1; ctx_l outside [1, 2^31). */
+int cone_session_query_layout(const int32_t* tok_len, int nq, int max_q_l, int64_t ctx_l, int K, int Nq, int max_v_l,
+                              int32_t* tok_off, int32_t* tok_len_dev, int32_t* tok_idx, int32_t* q_ctx_l, int32_t* q_vid_off,
+                              int32_t* batch_pad, int32_t* full_w, int32_t* n_valid, void* stream);
+
+/* What the localizer fixes besides the checkpoint (run_on_video/cone_localizator.py:12-37, :200-219). */
+typedef struct {
+    int32_t max_v_l, max_q_l;   /* window length in clips (slide = max_v_l / 2), longest query in tokens */
+    float clip_length;          /* seconds per clip */
+    double nms_thd;             /* 0.5 */
+    int32_t max_before, max_after;  /* 100, 5 */
+} cone_session_params;
+
+/* The query half of run_on_video/cone_localizator.py:121-221 for nq <= CONE_SESSION_MAX_QUERIES queries in ONE call:
+ * cone_session_query_layout; cone_l2_normalize_rows of the token rows (:133); stage A -- cone_prefilter_scores (resp.
+ * cone_prefilter_scores_bf16) in launches of at most 4 queries, the streaming form whose bits do not depend on the launch, then
+ * cone_topk_windows_ws; or, on a CONE_SESSION_CERTIFIED session, cone_prefilter_topk_certified with n_cand (0: its default) --;
+ * cone_window_table (eval_bsz 1, one batch per query); cone_project_tokens of the text side; cone_layer0_project and, for a
+ * --use_txt_pos checkpoint, cone_layer0_text_positions; ONE cone_forward_packed over all nq * K windows (no saliency);
+ * cone_clip_matching_gathered; cone_compose_rows (sort 0); cone_fuse_nms with a row per query.
+ * tok: the queries' token rows back to back (sum of tok_len, t_dim) fp32, NOT normalised; tok_len: HOST array; cls (nq, v_dim)
+ * raw cls vectors; K = windows per query, 1 <= K <= min(num_window, 256) (the localizer: min(topk_window, num_window)).
+ * kept (3, nq, max_after, 5) fp64 and n_kept (3, nq) int32 are laid out as cone_fuse_nms writes them (the localizer reads
+ * plane 0, the fused ranking).  certified (nq) int32, may be NULL: the flags of cone_prefilter_topk_certified (written only on
+ * a certified session).  ws >= cone_session_localize_workspace for the same arguments: ONE function lays out both, every
+ * buffer and every launcher's scratch has a region of its own (no two alias).  A workspace one byte short is refused by name. */
+size_t cone_session_localize_workspace(const cone_model* m, const cone_session* session, const int32_t* tok_len, int nq, int K,
+                                       int n_cand, const cone_session_params* params);
+int cone_session_localize(const cone_model* m, const cone_session* session, const float* tok, const int32_t* tok_len, int nq,
+                          const float* cls, int K, int n_cand, const cone_session_params* params, double* kept,
+                          int32_t* n_kept, int32_t* certified, void* ws, size_t ws_bytes, void* stream);
+
 /* -------------------------------------------------------------------- metrics on the device
  * Recall@K / IoU counts from the kept rows (layout of cone_fuse_nms: rows (nq, max_after, 5) fp64 [st, ed, ...],
  * n (nq) valid rows) and one target span per query gt (nq, 2) fp64 seconds -- device pointers.  thresholds /
