@@ -87,6 +87,13 @@ class SessionParams(C.Structure):
                 ("max_before", C.c_int32), ("max_after", C.c_int32)]
 
 
+# video libraries (additive in ABI 8): cone_library
+class Library(C.Structure):
+    _fields_ = [("model", C.c_void_p), ("capacity", C.c_int64), ("flags", C.c_int32), ("v_dim", C.c_int32),
+                ("hidden_dim", C.c_int32), ("vid_norm", C.c_void_p), ("adapted", C.c_void_p), ("adapted_bf16", C.c_void_p),
+                ("vproj", C.c_void_p), ("qkv_vid", C.c_void_p)]
+
+
 _SIGNATURES = {
     "cone_last_error": (C.c_char_p, []),
     "cone_abi_version": (C.c_int, []),
@@ -188,6 +195,20 @@ _SIGNATURES = {
     "cone_session_localize": (C.c_int, [C.c_void_p, C.POINTER(Session), C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_void_p,
                                         C.c_int, C.c_int, C.POINTER(SessionParams), C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_size_t, C.c_void_p]),
+    # video libraries (additive in ABI 8): many videos in one arena, one call for (video, query) pairs on any mix of them
+    "cone_library_arena_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int]),
+    "cone_library_open": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(Library)]),
+    "cone_library_add_workspace": (C.c_size_t, [C.c_void_p, C.c_int64]),
+    "cone_library_add": (C.c_int, [C.c_void_p, C.POINTER(Library), C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t,
+                                   C.c_void_p]),
+    # cone_library_query_layout(tok_len, q_row0, q_ctx_l (host), nq, max_q_l, K, Nq, max_v_l, <8 int32 outputs>, stream)
+    "cone_library_query_layout": (C.c_int, [C.POINTER(C.c_int32)] * 3 + [C.c_int] * 5 + [C.c_void_p] * 8 + [C.c_void_p]),
+    "cone_library_localize_workspace": (C.c_size_t, [C.c_void_p, C.POINTER(Library)] + [C.POINTER(C.c_int32)] * 3
+                                        + [C.c_int, C.c_int, C.POINTER(SessionParams)]),
+    # cone_library_localize(m, lib, q_row0, q_ctx_l (host), tok, tok_len (host), nq, cls, K, params, kept, n_kept, ws, ws_bytes, stream)
+    "cone_library_localize": (C.c_int, [C.c_void_p, C.POINTER(Library), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p,
+                                        C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_int, C.POINTER(SessionParams), C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     # cone_test_gemm(A, A2, a2_mod, W, bias, R, ln_g, ln_b, C, C2, ADD, M, N, K, flags, stream)
     "cone_test_gemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,

@@ -1,9 +1,11 @@
 // Video sessions (include/cone_hip.h, "video sessions"): one resident video, indexed once, answering batches of queries.
+// Video libraries ("video libraries"): many videos in the rows of one arena, one call for queries on any mix of them.
 //
-// Nothing is computed here.  cone_session_index and cone_session_localize only SEQUENCE the library's own extern "C"
-// launchers -- the calls cone_amd/localizator.py issues one by one through ctypes for run_on_video/cone_localizator.py:121-221
-// -- and carve their operands out of the caller's arena / workspace.  The one kernel of this file writes a call's index
-// metadata (what the localizer keeps per shape in _const) from lengths that travel as kernel arguments.
+// Nothing is computed here.  cone_session_index / cone_library_add and cone_session_localize / cone_library_localize only
+// SEQUENCE the library's own extern "C" launchers -- the calls cone_amd/localizator.py issues one by one through ctypes for
+// run_on_video/cone_localizator.py:121-221 -- and carve their operands out of the caller's arena / workspace.  The two kernels
+// of this file (one body) write a call's index metadata (what the localizer keeps per shape in _const) from lengths, row
+// offsets and clip counts that travel as kernel arguments.
 #include "common.h"
 
 namespace cone {
@@ -64,28 +66,63 @@ static IndexWs index_ws(const cone_model* m, int64_t n) {
     return w;
 }
 
+// The video half on n rows: the ONE launcher chain behind cone_session_index (the whole arena, row 0) and cone_library_add
+// (rows [row0, row0 + n) of a library's arena: the caller passes the regions already offset).  Every launcher works row by
+// row, so a row's bits depend on the launch's n alone, never on where the rows live.
+struct IndexRows { float* vid_norm; float* adapted; uint16_t* adapted_bf16; float* err; float* vproj; float* qkv_vid; };
+static int index_rows(const cone_model* m, const cone_model_dims& d, int flags, const float* raw, int64_t n, const IndexRows& o,
+                      char* s, const IndexWs& w, void* stream) {
+    RUN(cone_l2_normalize_rows(raw, n, d.v_dim, 1e-5f, 1, o.vid_norm, stream));                              // :129
+    if (flags & CONE_SESSION_BF16)                                                                           // :135-138
+        RUN(cone_adapter_norm_bf16(m, o.vid_norm, n, o.adapted_bf16, 0, s + w.adapter, w.adapter_bytes, stream));
+    else
+        RUN(cone_adapter_norm(m, o.vid_norm, n, o.adapted, 0, s + w.adapter, w.adapter_bytes, stream));
+    if (flags & CONE_SESSION_CERTIFIED) RUN(cone_prefilter_index_bf16(o.adapted, n, d.v_dim, o.adapted_bf16, o.err, stream));
+    RUN(cone_project_tokens(m, 0, o.vid_norm, n, o.vproj, s + w.proj, w.proj_bytes, stream));
+    if (o.qkv_vid) RUN(cone_layer0_project(m, o.vproj, n, o.qkv_vid, w.l0_bytes ? s + w.l0 : nullptr, w.l0_bytes, stream));
+    return 0;
+}
+
+// What the query half reads of the resident rows: a session's one video, or a library's arena of many.
+struct Resident {
+    const cone_model* model;
+    int32_t flags, v_dim, hidden_dim;
+    const float *vid_norm, *adapted;
+    const uint16_t* adapted_bf16;
+    const float *err, *vproj, *qkv_vid;
+};
+static Resident resident_of(const cone_session& S) {
+    return {S.model, S.flags, S.v_dim, S.hidden_dim, S.vid_norm, S.adapted, S.adapted_bf16, S.err, S.vproj, S.qkv_vid};
+}
+static Resident resident_of(const cone_library& B) {
+    return {B.model, B.flags, B.v_dim, B.hidden_dim, B.vid_norm, B.adapted, B.adapted_bf16, nullptr, B.vproj, B.qkv_vid};
+}
+
 // ------------------------------------------------------------------------------ the query half
 struct QueryLens { int32_t len[CONE_SESSION_MAX_QUERIES]; };
 
+struct QueryPairs { int32_t len[CONE_SESSION_MAX_QUERIES], row0[CONE_SESSION_MAX_QUERIES], ctx_l[CONE_SESSION_MAX_QUERIES]; };
+
 // One workgroup.  Every output element has one writer; nothing outside the documented extents is touched:
 // tok_off [0, nq], the per-query arrays [0, nq), full_w [0, nq K), tok_idx [0, sum of the lengths).
-__global__ __launch_bounds__(256) void session_layout_kernel(QueryLens L, int nq, int max_q_l, int ctx_l, int K, int n_cand_rows,
-                                                             int W, int* __restrict__ tok_off, int* __restrict__ tok_len,
-                                                             int* __restrict__ tok_idx, int* __restrict__ q_ctx_l,
-                                                             int* __restrict__ q_vid_off, int* __restrict__ batch_pad,
-                                                             int* __restrict__ full_w, int* __restrict__ n_valid) {
+// in_len: the token lengths (kernel arguments); ctx_of / off_of: query -> clips of its video / first arena row of its video.
+template <class CtxOf, class OffOf>
+__device__ __forceinline__ void layout_body(const int32_t* in_len, CtxOf ctx_of, OffOf off_of, int nq, int max_q_l, int K,
+                                            int n_cand_rows, int W, int* __restrict__ tok_off, int* __restrict__ tok_len,
+                                            int* __restrict__ tok_idx, int* __restrict__ q_ctx_l, int* __restrict__ q_vid_off,
+                                            int* __restrict__ batch_pad, int* __restrict__ full_w, int* __restrict__ n_valid) {
     __shared__ int off[CONE_SESSION_MAX_QUERIES + 1];
     __shared__ int len[CONE_SESSION_MAX_QUERIES];
     const int t = threadIdx.x;
     if (t == 0) {
         int a = 0;
-        for (int q = 0; q < nq; ++q) { off[q] = a; len[q] = L.len[q]; a += L.len[q]; }
+        for (int q = 0; q < nq; ++q) { off[q] = a; len[q] = in_len[q]; a += in_len[q]; }
         off[nq] = a;
     }
     __syncthreads();
     for (int q = t; q < nq; q += blockDim.x) {
         tok_off[q] = off[q]; tok_len[q] = len[q];
-        q_ctx_l[q] = ctx_l; q_vid_off[q] = 0; batch_pad[q] = W; n_valid[q] = n_cand_rows;
+        q_ctx_l[q] = ctx_of(q); q_vid_off[q] = off_of(q); batch_pad[q] = W; n_valid[q] = n_cand_rows;
     }
     if (t == 0) tok_off[nq] = off[nq];
     for (int i = t; i < nq * K; i += blockDim.x) full_w[i] = W;
@@ -93,6 +130,26 @@ __global__ __launch_bounds__(256) void session_layout_kernel(QueryLens L, int nq
         const int q = i / max_q_l, j = i - q * max_q_l;
         if (j < len[q]) tok_idx[off[q] + j] = j;
     }
+}
+
+__global__ __launch_bounds__(256) void session_layout_kernel(QueryLens L, int nq, int max_q_l, int ctx_l, int K, int n_cand_rows,
+                                                             int W, int* __restrict__ tok_off, int* __restrict__ tok_len,
+                                                             int* __restrict__ tok_idx, int* __restrict__ q_ctx_l,
+                                                             int* __restrict__ q_vid_off, int* __restrict__ batch_pad,
+                                                             int* __restrict__ full_w, int* __restrict__ n_valid) {
+    layout_body(L.len, [=](int) { return ctx_l; }, [](int) { return 0; }, nq, max_q_l, K, n_cand_rows, W, tok_off, tok_len, tok_idx,
+                q_ctx_l, q_vid_off, batch_pad, full_w, n_valid);
+}
+
+// The library's form: every query brings the clips and the first arena row of ITS video.
+__global__ __launch_bounds__(256) void library_layout_kernel(QueryPairs P, int nq, int max_q_l, int K, int n_cand_rows, int W,
+                                                             int* __restrict__ tok_off, int* __restrict__ tok_len,
+                                                             int* __restrict__ tok_idx, int* __restrict__ q_ctx_l,
+                                                             int* __restrict__ q_vid_off, int* __restrict__ batch_pad,
+                                                             int* __restrict__ full_w, int* __restrict__ n_valid) {
+    const int32_t *ctx = P.ctx_l, *row0 = P.row0;
+    layout_body(P.len, [=](int q) { return ctx[q]; }, [=](int q) { return row0[q]; }, nq, max_q_l, K, n_cand_rows, W, tok_off,
+                tok_len, tok_idx, q_ctx_l, q_vid_off, batch_pad, full_w, n_valid);
 }
 
 static int check_queries(const char* who, const int32_t* tok_len, int nq, int max_q_l, int64_t* total) {
@@ -109,9 +166,33 @@ static int check_queries(const char* who, const int32_t* tok_len, int nq, int ma
     return 0;
 }
 
-// Every buffer and every launcher's scratch of one cone_session_localize call: the ONE function behind the workspace-size
-// entry and the entry itself.  Each take() is a region of its own.
+// The (video, query) pairs of a library call, on the host, before any pointer into the device is read: every query's video
+// lies inside [0, rows) (rows < 0: only inside the int32 row range) and has at least K windows.
+static int check_pairs(const char* who, const int32_t* q_row0, const int32_t* q_ctx_l, int nq, int64_t rows, int K, int max_v_l) {
+    CONE_REQUIRE(q_row0 && q_ctx_l, "%s: null argument", who);
+    CONE_REQUIRE(max_v_l >= 2, "%s: max_v_l=%d", who, max_v_l);
+    for (int q = 0; q < nq; ++q) {
+        CONE_REQUIRE(q_ctx_l[q] >= 1, "%s: q_ctx_l[%d]=%d < 1", who, q, q_ctx_l[q]);
+        CONE_REQUIRE(q_row0[q] >= 0, "%s: q_row0[%d]=%d < 0", who, q, q_row0[q]);
+        const int64_t end = (int64_t)q_row0[q] + q_ctx_l[q];
+        if (rows >= 0)
+            CONE_REQUIRE(end <= rows, "%s: q_row0[%d] + q_ctx_l[%d] = %lld > capacity=%lld", who, q, q, (long long)end, (long long)rows);
+        else
+            CONE_REQUIRE(end < (1ll << 31), "%s: q_row0[%d] + q_ctx_l[%d] = %lld not below 2^31", who, q, q, (long long)end);
+        const int64_t nw = cone_num_windows(q_ctx_l[q], max_v_l);
+        CONE_REQUIRE(K >= 1 && K <= nw && K <= 256, "%s: K=%d not in [1, min(num_window=%lld, 256)] for query %d", who, K, (long long)nw, q);
+    }
+    return 0;
+}
+
+// Consecutive queries of one video: one stage A.  A session is one run.
+struct Run { int q0, n; int64_t row0, ctx_l, nw; size_t score_off; };
+
+// Every buffer and every launcher's scratch of one cone_session_localize / cone_library_localize call: the ONE function
+// behind the workspace-size entries and the entries themselves.  Each take() is a region of its own.
 struct LocalizeLayout {
+    Run runs[CONE_SESSION_MAX_QUERIES];
+    int n_runs;
     size_t tok_off, tok_len, tok_idx, q_ctx_l, q_vid_off, batch_pad, full_w, n_valid;      // int32 metadata
     size_t tok_norm, scores, widx, wval, cert, wt, tproj, qkv_txt, txt_pos, txt_pos_qk, logits, spans, match, rows, nms_idx;
     size_t pf_ws, pf_bytes, topk_ws, topk_bytes, proj_ws, proj_bytes, l0_ws, l0_bytes, fwd_ws, fwd_bytes, match_ws, match_bytes;
@@ -120,25 +201,39 @@ struct LocalizeLayout {
     int B;
     bool use_l0, use_txt_pos;
 };
-static int localize_layout(const cone_model* m, const cone_model_dims& d, const cone_session* ses, const int32_t* tok_len, int nq,
-                           int K, int n_cand, const cone_session_params* p, LocalizeLayout* out) {
-    const char* who = "session_localize";
+// rows: the session's ctx_l, or the library's capacity; q_row0 / q_ctx_l: NULL for a session (one run over all of its rows).
+static int localize_layout(const char* who, const char* what, const cone_model* m, const cone_model_dims& d, const Resident* ses,
+                           int64_t rows, const int32_t* q_row0, const int32_t* q_ctx_l, const int32_t* tok_len, int nq, int K,
+                           int n_cand, const cone_session_params* p, LocalizeLayout* out) {
     CONE_REQUIRE(m && ses && p, "%s: null argument", who);
-    CONE_REQUIRE(ses->model == m, "%s: the session was indexed with another handle", who);
-    CONE_REQUIRE(flags_ok(ses->flags), "%s: bad session flags %d", who, ses->flags);
-    CONE_REQUIRE(ses->v_dim == d.v_dim && ses->hidden_dim == d.hidden_dim, "%s: the session's row widths %d / %d are not the handle's %d / %d",
-                 who, ses->v_dim, ses->hidden_dim, d.v_dim, d.hidden_dim);
+    CONE_REQUIRE(ses->model == m, "%s: the %s was indexed with another handle", who, what);
+    CONE_REQUIRE(flags_ok(ses->flags), "%s: bad %s flags %d", who, what, ses->flags);
+    CONE_REQUIRE(ses->v_dim == d.v_dim && ses->hidden_dim == d.hidden_dim, "%s: the %s's row widths %d / %d are not the handle's %d / %d",
+                 who, what, ses->v_dim, ses->hidden_dim, d.v_dim, d.hidden_dim);
     CONE_REQUIRE(p->max_v_l >= 2 && p->max_after >= 1 && p->max_before >= 1, "%s: bad params (max_v_l=%d, max_before=%d, max_after=%d)",
                  who, p->max_v_l, p->max_before, p->max_after);
     LocalizeLayout L{};
     RUN(check_queries(who, tok_len, nq, p->max_q_l, &L.T));
-    CONE_REQUIRE(ses->ctx_l >= 1 && ses->ctx_l < (1ll << 31), "%s: ctx_l=%lld not in [1, 2^31)", who, (long long)ses->ctx_l);
-    L.nw = cone_num_windows(ses->ctx_l, p->max_v_l);
-    CONE_REQUIRE(K >= 1 && K <= L.nw && K <= 256, "%s: K=%d not in [1, min(num_window=%lld, 256)]", who, K, (long long)L.nw);
+    const bool cert = (ses->flags & CONE_SESSION_CERTIFIED) != 0;
+    size_t n_scores = 0;
+    if (q_row0) {       // (library_precheck has vetted the pairs, K and the capacity)
+        for (int q = 0; q < nq; ++q) {
+            if (q == 0 || q_row0[q] != q_row0[q - 1] || q_ctx_l[q] != q_ctx_l[q - 1])
+                L.runs[L.n_runs++] = Run{q, 0, q_row0[q], q_ctx_l[q], cone_num_windows(q_ctx_l[q], p->max_v_l), n_scores};
+            Run& r = L.runs[L.n_runs - 1];
+            r.n += 1;
+            n_scores += (size_t)r.nw;
+        }
+    } else {
+        CONE_REQUIRE(rows >= 1 && rows < (1ll << 31), "%s: ctx_l=%lld not in [1, 2^31)", who, (long long)rows);
+        L.nw = cone_num_windows(rows, p->max_v_l);
+        CONE_REQUIRE(K >= 1 && K <= L.nw && K <= 256, "%s: K=%d not in [1, min(num_window=%lld, 256)]", who, K, (long long)L.nw);
+        L.runs[L.n_runs++] = Run{0, nq, 0, rows, L.nw, 0};
+        n_scores = (size_t)nq * L.nw;
+    }
     CONE_REQUIRE(n_cand >= 0, "%s: n_cand=%d", who, n_cand);
     L.B = nq * K;
     const size_t T = (size_t)L.T, B = (size_t)L.B, Nq = (size_t)d.num_queries, dh = (size_t)d.hidden_dim;
-    const bool cert = (ses->flags & CONE_SESSION_CERTIFIED) != 0;
     L.use_l0 = ses->qkv_vid != nullptr && !d.long_windows;
     L.use_txt_pos = L.use_l0 && d.txt_pos;
     Regions r;
@@ -146,7 +241,7 @@ static int localize_layout(const cone_model* m, const cone_model_dims& d, const 
     L.q_ctx_l = r.take(nq * 4); L.q_vid_off = r.take(nq * 4); L.batch_pad = r.take(nq * 4);
     L.full_w = r.take(B * 4); L.n_valid = r.take(nq * 4);
     L.tok_norm = r.take(T * d.t_dim * 4);
-    if (!cert) L.scores = r.take((size_t)nq * L.nw * 4);
+    if (!cert) L.scores = r.take(n_scores * 4);
     L.widx = r.take(B * 4); L.wval = r.take(B * 4); L.cert = r.take(nq * 4);
     L.wt = r.take(7 * align_up(B * 4, SES_ALIGN));
     L.tproj = r.take(T * dh * 4);
@@ -156,13 +251,19 @@ static int localize_layout(const cone_model* m, const cone_model_dims& d, const 
     L.match = r.take(B * Nq * 4); L.rows = r.take(B * Nq * 4 * 4);
     L.nms_idx = r.take((size_t)3 * nq * p->max_after * 4);
     if (cert) {
-        L.pf_bytes = cone_prefilter_topk_certified_workspace(ses->ctx_l, nq, p->max_v_l, K, n_cand);
+        L.pf_bytes = cone_prefilter_topk_certified_workspace(rows, nq, p->max_v_l, K, n_cand);
         CONE_REQUIRE(L.pf_bytes, "%s: n_cand=%d is not a candidate count the certified pre-filter takes for %lld windows and K=%d", who,
                      n_cand, (long long)L.nw, K);
     } else {
-        L.pf_bytes = ses->flags & CONE_SESSION_BF16 ? cone_prefilter_scores_bf16_workspace(ses->ctx_l, nq < 4 ? nq : 4, p->max_v_l)
-                                                    : cone_prefilter_scores_workspace(ses->ctx_l, nq < 4 ? nq : 4, p->max_v_l);
-        L.topk_bytes = cone_topk_windows_workspace(nq, L.nw, K);
+        for (int i = 0; i < L.n_runs; ++i) {        // the runs follow each other on one stream: they share the largest scratch
+            const Run& u = L.runs[i];
+            const int n = u.n < 4 ? u.n : 4;
+            const size_t pf = ses->flags & CONE_SESSION_BF16 ? cone_prefilter_scores_bf16_workspace(u.ctx_l, n, p->max_v_l)
+                                                             : cone_prefilter_scores_workspace(u.ctx_l, n, p->max_v_l);
+            const size_t tk = cone_topk_windows_workspace(u.n, u.nw, K);
+            L.pf_bytes = pf > L.pf_bytes ? pf : L.pf_bytes;
+            L.topk_bytes = tk > L.topk_bytes ? tk : L.topk_bytes;
+        }
     }
     L.pf_ws = r.take(L.pf_bytes); L.topk_ws = r.take(L.topk_bytes);
     L.proj_bytes = cone_project_workspace(m, 1, L.T); L.proj_ws = r.take(L.proj_bytes);
@@ -217,14 +318,7 @@ extern "C" int cone_session_index(const cone_model* m, const float* raw_vid, int
     float* err = A.has_err ? (float*)(a + A.err) : nullptr;
     float* vproj = (float*)(a + A.vproj);
     float* qkv_vid = A.has_qkv ? (float*)(a + A.qkv_vid) : nullptr;
-    RUN(cone_l2_normalize_rows(raw_vid, ctx_l, d.v_dim, 1e-5f, 1, vid_norm, stream));                       // :129
-    if (flags & CONE_SESSION_BF16)                                                                           // :135-138
-        RUN(cone_adapter_norm_bf16(m, vid_norm, ctx_l, adapted16, 0, s + w.adapter, w.adapter_bytes, stream));
-    else
-        RUN(cone_adapter_norm(m, vid_norm, ctx_l, adapted, 0, s + w.adapter, w.adapter_bytes, stream));
-    if (flags & CONE_SESSION_CERTIFIED) RUN(cone_prefilter_index_bf16(adapted, ctx_l, d.v_dim, adapted16, err, stream));
-    RUN(cone_project_tokens(m, 0, vid_norm, ctx_l, vproj, s + w.proj, w.proj_bytes, stream));
-    if (qkv_vid) RUN(cone_layer0_project(m, vproj, ctx_l, qkv_vid, w.l0_bytes ? s + w.l0 : nullptr, w.l0_bytes, stream));
+    RUN(index_rows(m, d, flags, raw_vid, ctx_l, IndexRows{vid_norm, adapted, adapted16, err, vproj, qkv_vid}, s, w, stream));
     *session = cone_session{m, ctx_l, flags, d.v_dim, d.hidden_dim, vid_norm, adapted, adapted16, err, vproj, qkv_vid};
     return 0;
 }
@@ -247,27 +341,32 @@ extern "C" int cone_session_query_layout(const int32_t* tok_len, int nq, int max
     return 0;
 }
 
-extern "C" size_t cone_session_localize_workspace(const cone_model* m, const cone_session* session, const int32_t* tok_len, int nq,
-                                                  int K, int n_cand, const cone_session_params* params) {
-    cone_model_dims d;
-    LocalizeLayout L;
-    if (!m || cone_model_get_dims(m, &d) || localize_layout(m, d, session, tok_len, nq, K, n_cand, params, &L)) return 0;
-    return L.total;
+extern "C" int cone_library_query_layout(const int32_t* tok_len, const int32_t* q_row0, const int32_t* q_ctx_l, int nq, int max_q_l,
+                                         int K, int Nq, int max_v_l, int32_t* tok_off, int32_t* tok_len_dev, int32_t* tok_idx,
+                                         int32_t* q_ctx_l_dev, int32_t* q_vid_off, int32_t* batch_pad, int32_t* full_w,
+                                         int32_t* n_valid, void* stream) {
+    const char* who = "library_query_layout";
+    int64_t T = 0;
+    RUN(check_queries(who, tok_len, nq, max_q_l, &T));
+    RUN(check_pairs(who, q_row0, q_ctx_l, nq, -1, K, max_v_l));
+    CONE_REQUIRE(tok_off && tok_len_dev && tok_idx && q_ctx_l_dev && q_vid_off && batch_pad && full_w && n_valid, "%s: null argument", who);
+    CONE_REQUIRE(Nq >= 1 && Nq <= 16 && max_q_l <= 1024, "%s: bad sizes Nq=%d max_q_l=%d", who, Nq, max_q_l);
+    QueryPairs P{};
+    for (int q = 0; q < nq; ++q) { P.len[q] = tok_len[q]; P.row0[q] = q_row0[q]; P.ctx_l[q] = q_ctx_l[q]; }
+    hipLaunchKernelGGL(library_layout_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, P, nq, max_q_l, K, K * Nq, max_v_l, tok_off,
+                       tok_len_dev, tok_idx, q_ctx_l_dev, q_vid_off, batch_pad, full_w, n_valid);
+    CONE_LAUNCH_CHECK();
+    return 0;
 }
 
-extern "C" int cone_session_localize(const cone_model* m, const cone_session* session, const float* tok, const int32_t* tok_len,
-                                     int nq, const float* cls, int K, int n_cand, const cone_session_params* params, double* kept,
-                                     int32_t* n_kept, int32_t* certified, void* ws, size_t ws_bytes, void* stream) {
-    CONE_REQUIRE(m && session && tok && tok_len && cls && params && kept && n_kept && ws, "session_localize: null argument");
-    CONE_REQUIRE(((uintptr_t)ws & (SES_ALIGN - 1)) == 0, "session_localize: the workspace must be 256-B aligned");
-    cone_model_dims d;
-    RUN(cone_model_get_dims(m, &d));
-    LocalizeLayout L;
-    RUN(localize_layout(m, d, session, tok_len, nq, K, n_cand, params, &L));
-    if (ws_bytes < L.total) { set_error("session_localize: workspace too small (%zu < %zu)", ws_bytes, L.total); return CONE_E_WORKSPACE; }
-    const cone_session& S = *session;
-    const cone_session_params& P = *params;
-    char* w = (char*)ws;
+namespace cone {
+
+// The query half for both kinds of resident rows: q_row0 / q_ctx_l == NULL is a session (one video at row 0, `rows` clips),
+// otherwise a library call (every query names its video's rows inside an arena of `rows`).  Nothing differs after stage A.
+static int localize(const char* who, const cone_model* m, const cone_model_dims& d, const Resident& S, int64_t rows,
+                    const LocalizeLayout& L, const int32_t* q_row0, const int32_t* q_ctx_l, const float* tok, const int32_t* tok_len,
+                    int nq, const float* cls, int K, int n_cand, const cone_session_params& P, double* kept, int32_t* n_kept,
+                    int32_t* certified, char* w, void* stream) {
     auto I = [&](size_t at) { return (int32_t*)(w + at); };
     auto F = [&](size_t at) { return (float*)(w + at); };
     auto scratch = [&](size_t at, size_t bytes) { return bytes ? (void*)(w + at) : nullptr; };
@@ -276,25 +375,35 @@ extern "C" int cone_session_localize(const cone_model* m, const cone_session* se
     int32_t *vid_row0 = I(L.wt), *vid_len = I(L.wt + col), *video_start = I(L.wt + 2 * col), *pad_len = I(L.wt + 3 * col),
             *txt_row0 = I(L.wt + 4 * col), *txt_len = I(L.wt + 5 * col), *cls_row = I(L.wt + 6 * col);
 
-    RUN(cone_session_query_layout(tok_len, nq, P.max_q_l, S.ctx_l, K, Nq, W, I(L.tok_off), I(L.tok_len), I(L.tok_idx), I(L.q_ctx_l),
-                                  I(L.q_vid_off), I(L.batch_pad), I(L.full_w), I(L.n_valid), stream));
+    if (q_row0)
+        RUN(cone_library_query_layout(tok_len, q_row0, q_ctx_l, nq, P.max_q_l, K, Nq, W, I(L.tok_off), I(L.tok_len), I(L.tok_idx),
+                                      I(L.q_ctx_l), I(L.q_vid_off), I(L.batch_pad), I(L.full_w), I(L.n_valid), stream));
+    else
+        RUN(cone_session_query_layout(tok_len, nq, P.max_q_l, rows, K, Nq, W, I(L.tok_off), I(L.tok_len), I(L.tok_idx), I(L.q_ctx_l),
+                                      I(L.q_vid_off), I(L.batch_pad), I(L.full_w), I(L.n_valid), stream));
     RUN(cone_l2_normalize_rows(tok, L.T, d.t_dim, 1e-5f, 1, F(L.tok_norm), stream));                          // :133
     // stage A (:83-100, stable tie order): the raw cls vectors against the adapted rows
     if (S.flags & CONE_SESSION_CERTIFIED) {
-        RUN(cone_prefilter_topk_certified(S.adapted, S.adapted_bf16, S.ctx_l, dv, cls, nq, W, Sl, K, n_cand, S.err, I(L.widx),
+        RUN(cone_prefilter_topk_certified(S.adapted, S.adapted_bf16, rows, dv, cls, nq, W, Sl, K, n_cand, S.err, I(L.widx),
                                           F(L.wval), certified ? certified : I(L.cert), w + L.pf_ws, L.pf_bytes, stream));
     } else {
-        for (int q0 = 0; q0 < nq; q0 += 4) {        // at most 4 queries a launch: the streaming form, whatever nq is
-            const int n = nq - q0 < 4 ? nq - q0 : 4;
-            float* sc = F(L.scores) + (size_t)q0 * L.nw;
-            if (S.flags & CONE_SESSION_BF16)
-                RUN(cone_prefilter_scores_bf16(S.adapted_bf16, S.ctx_l, dv, cls + (size_t)q0 * dv, n, W, Sl, sc, w + L.pf_ws,
-                                               L.pf_bytes, stream));
-            else
-                RUN(cone_prefilter_scores(S.adapted, S.ctx_l, dv, cls + (size_t)q0 * dv, n, W, Sl, nullptr, sc, w + L.pf_ws,
-                                          L.pf_bytes, stream));
+        for (int i = 0; i < L.n_runs; ++i) {        // one video a run, in the form and with the arguments of a session on it
+            const Run& u = L.runs[i];
+            float* scores = F(L.scores) + u.score_off;
+            for (int q0 = 0; q0 < u.n; q0 += 4) {   // at most 4 queries a launch: the streaming form, whatever the run's length
+                const int n = u.n - q0 < 4 ? u.n - q0 : 4;
+                float* sc = scores + (size_t)q0 * u.nw;
+                const float* c = cls + (size_t)(u.q0 + q0) * dv;
+                if (S.flags & CONE_SESSION_BF16)
+                    RUN(cone_prefilter_scores_bf16(S.adapted_bf16 + (size_t)u.row0 * dv, u.ctx_l, dv, c, n, W, Sl, sc, w + L.pf_ws,
+                                                   L.pf_bytes, stream));
+                else
+                    RUN(cone_prefilter_scores(S.adapted + (size_t)u.row0 * dv, u.ctx_l, dv, c, n, W, Sl, nullptr, sc, w + L.pf_ws,
+                                              L.pf_bytes, stream));
+            }
+            RUN(cone_topk_windows_ws(scores, u.n, u.nw, K, I(L.widx) + (size_t)u.q0 * K, F(L.wval) + (size_t)u.q0 * K, w + L.topk_ws,
+                                     L.topk_bytes, stream));
         }
-        RUN(cone_topk_windows_ws(F(L.scores), nq, L.nw, K, I(L.widx), F(L.wval), w + L.topk_ws, L.topk_bytes, stream));
     }
     // every window counts as padded to max_v_l (:150-170): one reference batch per query, its padding max_v_l
     RUN(cone_window_table(I(L.widx), nq, K, nullptr, nullptr, B, I(L.q_ctx_l), I(L.q_vid_off), I(L.tok_off), I(L.tok_len), 0, 1, W,
@@ -318,3 +427,147 @@ extern "C" int cone_session_localize(const cone_model* m, const cone_session* se
     return cone_fuse_nms(F(L.rows), nullptr, I(L.n_valid), nq, K * Nq, P.nms_thd, P.max_before, P.max_after, kept, n_kept,
                          I(L.nms_idx), stream);                                                               // :200-219
 }
+
+}  // namespace cone
+
+extern "C" size_t cone_session_localize_workspace(const cone_model* m, const cone_session* session, const int32_t* tok_len, int nq,
+                                                  int K, int n_cand, const cone_session_params* params) {
+    cone_model_dims d;
+    LocalizeLayout L;
+    if (!m || cone_model_get_dims(m, &d)) return 0;
+    const Resident S = session ? resident_of(*session) : Resident{};
+    if (localize_layout("session_localize", "session", m, d, session ? &S : nullptr, session ? session->ctx_l : 0, nullptr, nullptr,
+                        tok_len, nq, K, n_cand, params, &L))
+        return 0;
+    return L.total;
+}
+
+extern "C" int cone_session_localize(const cone_model* m, const cone_session* session, const float* tok, const int32_t* tok_len,
+                                     int nq, const float* cls, int K, int n_cand, const cone_session_params* params, double* kept,
+                                     int32_t* n_kept, int32_t* certified, void* ws, size_t ws_bytes, void* stream) {
+    const char* who = "session_localize";
+    CONE_REQUIRE(m && session && tok && tok_len && cls && params && kept && n_kept && ws, "%s: null argument", who);
+    CONE_REQUIRE(((uintptr_t)ws & (SES_ALIGN - 1)) == 0, "%s: the workspace must be 256-B aligned", who);
+    cone_model_dims d;
+    RUN(cone_model_get_dims(m, &d));
+    const Resident S = resident_of(*session);
+    LocalizeLayout L;
+    RUN(localize_layout(who, "session", m, d, &S, session->ctx_l, nullptr, nullptr, tok_len, nq, K, n_cand, params, &L));
+    if (ws_bytes < L.total) { set_error("%s: workspace too small (%zu < %zu)", who, ws_bytes, L.total); return CONE_E_WORKSPACE; }
+    return localize(who, m, d, S, session->ctx_l, L, nullptr, nullptr, tok, tok_len, nq, cls, K, n_cand, *params, kept, n_kept,
+                    certified, (char*)ws, stream);
+}
+
+// ------------------------------------------------------------------------------ video libraries
+namespace cone {
+
+static bool library_flags_ok(int flags) { return flags == 0 || flags == CONE_SESSION_BF16; }
+
+// The refusals a library call makes from host values alone, in this order, before the handle is looked at.
+static int library_precheck(const char* who, const cone_library* lib, const int32_t* q_row0, const int32_t* q_ctx_l,
+                            const int32_t* tok_len, int nq, int K, const cone_session_params* p) {
+    CONE_REQUIRE(lib && q_row0 && q_ctx_l && tok_len && p, "%s: null argument", who);
+    CONE_REQUIRE(!(lib->flags & CONE_SESSION_CERTIFIED), "%s: CONE_SESSION_CERTIFIED libraries are not supported", who);
+    CONE_REQUIRE(lib->capacity >= 1 && lib->capacity < (1ll << 31), "%s: capacity=%lld not in [1, 2^31)", who, (long long)lib->capacity);
+    int64_t T = 0;
+    RUN(check_queries(who, tok_len, nq, p->max_q_l, &T));
+    return check_pairs(who, q_row0, q_ctx_l, nq, lib->capacity, K, p->max_v_l);
+}
+static int library_handle(const char* who, const cone_model* m, const cone_library* lib) {
+    CONE_REQUIRE(m, "%s: null argument", who);
+    CONE_REQUIRE(lib->model == m, "%s: the library was opened with another handle", who);
+    return 0;
+}
+
+}  // namespace cone
+
+extern "C" size_t cone_library_arena_bytes(const cone_model* m, int64_t capacity, int flags) {
+    cone_model_dims d;
+    if (flags & CONE_SESSION_CERTIFIED) { set_error("library_arena_bytes: CONE_SESSION_CERTIFIED libraries are not supported"); return 0; }
+    if (capacity <= 0 || capacity >= (1ll << 31) || !library_flags_ok(flags) || cone_model_get_dims(m, &d)) return 0;
+    return arena_layout(d, capacity, flags).total;
+}
+
+extern "C" int cone_library_open(const cone_model* m, int64_t capacity, int flags, void* arena, size_t arena_bytes, cone_library* out) {
+    const char* who = "library_open";
+    CONE_REQUIRE(m && arena && out, "%s: null argument", who);
+    CONE_REQUIRE(!(flags & CONE_SESSION_CERTIFIED), "%s: CONE_SESSION_CERTIFIED libraries are not supported", who);
+    CONE_REQUIRE(library_flags_ok(flags), "%s: flags=%d (0 or CONE_SESSION_BF16)", who, flags);
+    CONE_REQUIRE(capacity >= 1 && capacity < (1ll << 31), "%s: capacity=%lld not in [1, 2^31)", who, (long long)capacity);
+    CONE_REQUIRE(((uintptr_t)arena & (SES_ALIGN - 1)) == 0, "%s: the arena must be 256-B aligned", who);
+    cone_model_dims d;
+    RUN(cone_model_get_dims(m, &d));
+    CONE_REQUIRE(d.v_dim == d.v_motion_dim, "%s: the localizer feeds one clip feature to both sides, v_dim=%d != v_motion_dim=%d", who,
+                 d.v_dim, d.v_motion_dim);
+    const ArenaLayout A = arena_layout(d, capacity, flags);
+    if (arena_bytes < A.total) { set_error("%s: arena too small (%zu < %zu)", who, arena_bytes, A.total); return CONE_E_WORKSPACE; }
+    char* a = (char*)arena;
+    *out = cone_library{m, capacity, flags, d.v_dim, d.hidden_dim, (float*)(a + A.vid_norm), A.has_f32 ? (float*)(a + A.adapted) : nullptr,
+                        A.has_bf16 ? (uint16_t*)(a + A.adapted_bf16) : nullptr, (float*)(a + A.vproj),
+                        A.has_qkv ? (float*)(a + A.qkv_vid) : nullptr};
+    return 0;
+}
+
+extern "C" size_t cone_library_add_workspace(const cone_model* m, int64_t n_rows) {
+    if (!m || n_rows <= 0) return 0;
+    return index_ws(m, n_rows).total;
+}
+
+extern "C" int cone_library_add(const cone_model* m, const cone_library* lib, int64_t row0, const float* raw_clips, int64_t n_rows,
+                                void* ws, size_t ws_bytes, void* stream) {
+    const char* who = "library_add";
+    CONE_REQUIRE(m && lib && raw_clips && ws, "%s: null argument", who);
+    RUN(library_handle(who, m, lib));
+    CONE_REQUIRE(library_flags_ok(lib->flags), "%s: bad library flags %d", who, lib->flags);
+    CONE_REQUIRE(row0 >= 0 && n_rows >= 1 && row0 + n_rows <= lib->capacity, "%s: rows [%lld, %lld + %lld) are not inside [0, capacity=%lld)",
+                 who, (long long)row0, (long long)row0, (long long)n_rows, (long long)lib->capacity);
+    CONE_REQUIRE(((uintptr_t)ws & (SES_ALIGN - 1)) == 0, "%s: the workspace must be 256-B aligned", who);
+    cone_model_dims d;
+    RUN(cone_model_get_dims(m, &d));
+    CONE_REQUIRE(lib->v_dim == d.v_dim && lib->hidden_dim == d.hidden_dim, "%s: the library's row widths %d / %d are not the handle's %d / %d",
+                 who, lib->v_dim, lib->hidden_dim, d.v_dim, d.hidden_dim);
+    CONE_REQUIRE(lib->vid_norm && lib->vproj && (lib->flags & CONE_SESSION_BF16 ? lib->adapted_bf16 != nullptr : lib->adapted != nullptr),
+                 "%s: the library handle misses a region (not one cone_library_open filled)", who);
+    const IndexWs w = index_ws(m, n_rows);
+    if (ws_bytes < w.total) { set_error("%s: workspace too small (%zu < %zu)", who, ws_bytes, w.total); return CONE_E_WORKSPACE; }
+    const size_t r = (size_t)row0, dv = (size_t)d.v_dim, dh = (size_t)d.hidden_dim;
+    const IndexRows o{lib->vid_norm + r * dv, lib->adapted ? lib->adapted + r * dv : nullptr,
+                      lib->adapted_bf16 ? lib->adapted_bf16 + r * dv : nullptr, nullptr, lib->vproj + r * dh,
+                      lib->qkv_vid ? lib->qkv_vid + r * 3 * dh : nullptr};
+    return index_rows(m, d, lib->flags, raw_clips, n_rows, o, (char*)ws, w, stream);
+}
+
+extern "C" size_t cone_library_localize_workspace(const cone_model* m, const cone_library* lib, const int32_t* q_row0,
+                                                  const int32_t* q_ctx_l, const int32_t* tok_len, int nq, int K,
+                                                  const cone_session_params* params) {
+    const char* who = "library_localize";
+    cone_model_dims d;
+    LocalizeLayout L;
+    if (library_precheck(who, lib, q_row0, q_ctx_l, tok_len, nq, K, params)) return 0;
+    if (library_handle(who, m, lib) || cone_model_get_dims(m, &d)) return 0;
+    const Resident S = resident_of(*lib);
+    if (localize_layout(who, "library", m, d, &S, lib->capacity, q_row0, q_ctx_l, tok_len, nq, K, 0, params, &L)) return 0;
+    return L.total;
+}
+
+extern "C" int cone_library_localize(const cone_model* m, const cone_library* lib, const int32_t* q_row0, const int32_t* q_ctx_l,
+                                     const float* tok, const int32_t* tok_len, int nq, const float* cls, int K,
+                                     const cone_session_params* params, double* kept, int32_t* n_kept, void* ws, size_t ws_bytes,
+                                     void* stream) {
+    const char* who = "library_localize";
+    CONE_REQUIRE(m && lib && q_row0 && q_ctx_l && tok && tok_len && cls && params && kept && n_kept && ws, "%s: null argument", who);
+    CONE_REQUIRE(((uintptr_t)ws & (SES_ALIGN - 1)) == 0, "%s: the workspace must be 256-B aligned", who);
+    RUN(library_precheck(who, lib, q_row0, q_ctx_l, tok_len, nq, K, params));
+    RUN(library_handle(who, m, lib));
+    cone_model_dims d;
+    RUN(cone_model_get_dims(m, &d));
+    const Resident S = resident_of(*lib);
+    LocalizeLayout L;
+    RUN(localize_layout(who, "library", m, d, &S, lib->capacity, q_row0, q_ctx_l, tok_len, nq, K, 0, params, &L));
+    CONE_REQUIRE(S.vid_norm && S.vproj && (S.flags & CONE_SESSION_BF16 ? S.adapted_bf16 != nullptr : S.adapted != nullptr),
+                 "%s: the library handle misses a region (not one cone_library_open filled)", who);
+    if (ws_bytes < L.total) { set_error("%s: workspace too small (%zu < %zu)", who, ws_bytes, L.total); return CONE_E_WORKSPACE; }
+    return localize(who, m, d, S, lib->capacity, L, q_row0, q_ctx_l, tok, tok_len, nq, cls, K, 0, *params, kept, n_kept, nullptr,
+                    (char*)ws, stream);
+}
+

@@ -129,6 +129,16 @@ class CONELocalizator:
         from .session import VideoSession
         return VideoSession(self, video_feats, certified=certified, n_cand=n_cand, step=step)
 
+    def open_library(self, capacity_clips):
+        """cone_amd extension: one arena for ``capacity_clips`` clip rows that holds many indexed videos
+        (``cone_amd.library.VideoLibrary``).  ``lib.add(video_feats)`` indexes a video into free rows and returns its id,
+        ``lib.remove(id)`` frees them; ``lib.predict_moments([(id, text_feats), ...])`` answers pairs on any mix of the videos in
+        one C call per 64 pairs (``cone_library_localize``) and one read-back, each answer ``==`` this class's ``predict_moment``
+        on that video and query.  With ``prefilter_bf16`` the library keeps bf16 adapted rows.  No certified ranking, no growth,
+        no compaction."""
+        from .library import VideoLibrary
+        return VideoLibrary(self, capacity_clips)
+
     @torch.no_grad()
     def predict_moment(self, video_feats, text_feats):
         """run_on_video/cone_localizator.py:121-221 on the eval driver's kernels, enqueued without a host round trip until

@@ -564,6 +564,79 @@ int cone_session_localize(const cone_model* m, const cone_session* session, cons
                           const float* cls, int K, int n_cand, const cone_session_params* params, double* kept,
                           int32_t* n_kept, int32_t* certified, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------ video libraries (additive in ABI 8)
+ * Many resident videos in the rows of ONE arena, added and removed while it lives, and one call for a list of
+ * (video, query) pairs on any mix of them: run_on_video/cone_localizator.py:121-221 with its video half done once per video
+ * (as in a session) and its query half done for up to CONE_SESSION_MAX_QUERIES pairs at once.  CONTRACT: nothing new is
+ * computed -- the entries sequence the launchers a session sequences, with a session's arguments, so every pair's kept moments
+ * carry the bits of predict_moment on that video and query (tests/test_library_gpu.py compares them with ==).  A video is a
+ * range of arena rows [row0, row0 + ctx_l); WHO owns which rows is the caller's business (cone_amd/library.py keeps a
+ * first-fit free list), the entries only check that a range lies inside the arena.  The rules are the sessions': all memory
+ * is the caller's, arena and workspaces 256-B aligned, one stream, nothing allocated, no host read-back, refusals by name on
+ * the host before any pointer is read.  Out of scope: CONE_SESSION_CERTIFIED libraries (refused by name), growing a video in
+ * place, compaction. */
+
+/* A plain host struct of device pointers into the caller's arena, like cone_session; filled by cone_library_open. */
+typedef struct {
+    const cone_model* model;        /* the handle it was opened with: the other entries refuse any other */
+    int64_t capacity;               /* clip rows the arena holds */
+    int32_t flags;                  /* 0 or CONE_SESSION_BF16 */
+    int32_t v_dim, hidden_dim;      /* row widths of the arrays below */
+    float* vid_norm;                /* (capacity, v_dim) F.normalize of the clips (:129) */
+    float* adapted;                 /* (capacity, v_dim) adapter(x) + x (:135-138); NULL with CONE_SESSION_BF16 */
+    uint16_t* adapted_bf16;         /* CONE_SESSION_BF16: the adapted rows in bf16; NULL otherwise */
+    float* vproj;                   /* (capacity, hidden_dim) input_vid_proj of the clips */
+    float* qkv_vid;                 /* (capacity, 3 hidden_dim) first encoder layer's q | k | v rows; NULL on a long-window handle */
+} cone_library;
+
+/* Lays the regions of an arena for `capacity` rows out (the layout function of cone_session_arena_bytes, with capacity for
+ * ctx_l) and fills *out; launches nothing, writes nothing to the arena (run_on_video/cone_localizator.py:121-221 keeps no
+ * state; this is where the video half's results of many calls live).  Refused by name: null arguments, CONE_SESSION_CERTIFIED,
+ * other flags than 0 / CONE_SESSION_BF16, capacity outside [1, 2^31), a misaligned or short arena, v_dim != v_motion_dim. */
+size_t cone_library_arena_bytes(const cone_model* m, int64_t capacity, int flags);
+int cone_library_open(const cone_model* m, int64_t capacity, int flags, void* arena, size_t arena_bytes, cone_library* out);
+
+/* The video half of run_on_video/cone_localizator.py:121-221 for ONE video, written to rows [row0, row0 + n_rows) of the
+ * arena: the launcher chain of cone_session_index (one function runs both; cone_session_index is the chain at row0 = 0) on
+ * n_rows rows -- cone_l2_normalize_rows, cone_adapter_norm / cone_adapter_norm_bf16 with renorm == 0, cone_project_tokens of
+ * the video side, cone_layer0_project unless the handle is a long-window handle.  Nothing outside those rows is written.
+ * raw_clips (n_rows, v_dim) fp32; ws >= cone_library_add_workspace, free again when the call's work is done.
+ * Refused by name: null arguments, another handle than the library's, row0 < 0, n_rows < 1, row0 + n_rows > capacity, a
+ * misaligned or short workspace. */
+size_t cone_library_add_workspace(const cone_model* m, int64_t n_rows);
+int cone_library_add(const cone_model* m, const cone_library* lib, int64_t row0, const float* raw_clips, int64_t n_rows, void* ws,
+                     size_t ws_bytes, void* stream);
+
+/* cone_session_query_layout with a video per query (run_on_video/cone_localizator.py:121-221: the shapes :150-170 and :191
+ * build on the host): tok_len, q_row0, q_ctx_l are HOST arrays of nq entries and travel as kernel arguments, nothing is
+ * uploaded; ONE one-workgroup launch, one writer per element.  Outputs as there, except q_ctx_l_dev (nq) = q_ctx_l and
+ * q_vid_off (nq) = q_row0; n_valid = K * Nq, batch_pad = full_w = max_v_l.  Nothing else is written.
+ * Refused by name: nq outside [1, CONE_SESSION_MAX_QUERIES]; a length outside [1, max_q_l]; q_ctx_l[q] < 1; q_row0[q] < 0;
+ * q_row0[q] + q_ctx_l[q] >= 2^31; K outside [1, min(num_window of query q, 256)] (the message names q). */
+int cone_library_query_layout(const int32_t* tok_len, const int32_t* q_row0, const int32_t* q_ctx_l, int nq, int max_q_l, int K,
+                              int Nq, int max_v_l, int32_t* tok_off, int32_t* tok_len_dev, int32_t* tok_idx, int32_t* q_ctx_l_dev,
+                              int32_t* q_vid_off, int32_t* batch_pad, int32_t* full_w, int32_t* n_valid, void* stream);
+
+/* The query half of run_on_video/cone_localizator.py:121-221 for nq <= CONE_SESSION_MAX_QUERIES (video, query) pairs in ONE
+ * call: cone_session_localize, except that query q runs on the video at rows [q_row0[q], q_row0[q] + q_ctx_l[q]).
+ * Stage A runs per RUN of consecutive queries with the same (q_row0, q_ctx_l) -- cone_prefilter_scores (resp.
+ * cone_prefilter_scores_bf16) on that video's adapted rows in launches of at most 4 queries, then one cone_topk_windows_ws,
+ * in the form and with the arguments of a session on that video: that is what makes the bits predict_moment's (callers sort
+ * by video to keep the runs few).  Everything after stage A is one launch over all nq * K windows as in a session:
+ * cone_window_table, the text projection and layer-0 text rows / positions, ONE cone_forward_packed with the arena's vproj /
+ * qkv_vid as bases, cone_clip_matching_gathered on vid_norm, cone_compose_rows, cone_fuse_nms with a row per query.
+ * ONE K per call, 1 <= K <= min(num_window of every query's video, 256); q_row0, q_ctx_l, tok_len: HOST arrays; tok, cls,
+ * kept, n_kept as in cone_session_localize.  ws >= cone_library_localize_workspace for the same arguments (ONE function lays
+ * out both; 0 and cone_last_error on a refusal).
+ * Refused by name, on the host, the pairs first: null arguments; nq outside [1, 64]; a length outside [1, max_q_l];
+ * q_ctx_l[q] < 1; q_row0[q] < 0; q_row0[q] + q_ctx_l[q] > capacity; K outside the range above (the message names the query);
+ * another handle than the library's; a misaligned or short workspace. */
+size_t cone_library_localize_workspace(const cone_model* m, const cone_library* lib, const int32_t* q_row0, const int32_t* q_ctx_l,
+                                       const int32_t* tok_len, int nq, int K, const cone_session_params* params);
+int cone_library_localize(const cone_model* m, const cone_library* lib, const int32_t* q_row0, const int32_t* q_ctx_l,
+                          const float* tok, const int32_t* tok_len, int nq, const float* cls, int K,
+                          const cone_session_params* params, double* kept, int32_t* n_kept, void* ws, size_t ws_bytes, void* stream);
+
 /* -------------------------------------------------------------------- metrics on the device
  * Recall@K / IoU counts from the kept rows (layout of cone_fuse_nms: rows (nq, max_after, 5) fp64 [st, ed, ...],
  * n (nq) valid rows) and one target span per query gt (nq, 2) fp64 seconds -- device pointers.  thresholds /
