@@ -209,6 +209,21 @@ _SIGNATURES = {
     "cone_library_localize": (C.c_int, [C.c_void_p, C.POINTER(Library), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p,
                                         C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_int, C.POINTER(SessionParams), C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # library search (additive in ABI 8): stage A over many videos in one pass, the query half on the scanned lists
+    "cone_library_scan_workspace": (C.c_size_t, [C.POINTER(Library), C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int]),
+    # cone_library_scan(m, lib, v_row0, v_ctx_l, v_hb_off (device), n_videos, total_hb, cls, nq, K, n_rank, params, widx, wval,
+    # rank_slot, rank_val, ws, ws_bytes, stream)
+    "cone_library_scan": (C.c_int, [C.c_void_p, C.POINTER(Library)] + [C.c_void_p] * 3 + [C.c_int64, C.c_int64, C.c_void_p, C.c_int,
+                                    C.c_int, C.c_int, C.POINTER(SessionParams)] + [C.c_void_p] * 4 + [C.c_void_p, C.c_size_t,
+                                                                                                    C.c_void_p]),
+    "cone_library_localize_ranked_workspace": (C.c_size_t, [C.c_void_p, C.POINTER(Library)] + [C.POINTER(C.c_int32)] * 3
+                                               + [C.c_int, C.c_int, C.POINTER(SessionParams)]),
+    # cone_library_localize_ranked(<cone_library_localize's up to params>, pair_query, pair_slot (host), scan_widx, scan_wval
+    # (device), scan_nq, scan_n_videos, scan_K, kept, n_kept, ws, ws_bytes, stream)
+    "cone_library_localize_ranked": (C.c_int, [C.c_void_p, C.POINTER(Library), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p,
+                                               C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_int, C.POINTER(SessionParams),
+                                               C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_int, C.c_int64,
+                                               C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     # cone_test_gemm(A, A2, a2_mod, W, bias, R, ln_g, ln_b, C, C2, ADD, M, N, K, flags, stream)
     "cone_test_gemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,

@@ -11,8 +11,9 @@
 // The file, in order: the streaming skeleton (PF_LANE_SLOT, pf_slot_max, pf_store_half_max) and its exact-fp32 kernels; the
 // stable top-k family (TK_LOAD_CHUNK, tk_load_list, tk_pass_pick around tk_block_select); the many-query skeleton (PfMqCursor,
 // pf_mq_tile_end, pf_mq_grid) and its three kernels -- exact fp32, split bf16, plain bf16 --, which differ in operand staging
-// and inner product only; the segmented (whole-split) forms; the bf16 streaming forms; the certified pipeline; the C entries
-// and what they share (pf_with_vpl, PfPlanes, launch_window_combine, the CONE_PF_REQUIRE_* checks).  DESIGN.md 3b - 3d.
+// and inner product only; the segmented (whole-split) forms; the bf16 streaming forms; the certified pipeline; the library
+// search's scan over many videos (library_scan_kernel, library_topk_kernel: DESIGN.md 4c); the C entries and what they share
+// (pf_with_vpl, PfPlanes, launch_window_combine, the CONE_PF_REQUIRE_* checks).  DESIGN.md 3b - 3d.
 #include <mutex>
 #include <type_traits>
 
@@ -1666,6 +1667,124 @@ __global__ __launch_bounds__(256) void pf_fallback_merge_kernel(const float* __r
                            last ? idx + (size_t)q * k : ci_out + ((size_t)q * n_groups + g) * k, last ? -1 : 0x7fffffff);
 }
 
+// ---- library search: stage A over MANY videos of one arena in one pass (cone_library_scan) ---------------------
+// The streaming form (frame_score_body: the same loads, pf_lane_dot, wave_sum_multi, so a frame's score has the same bits) over
+// a flat list of half-blocks: unit g = half-block h of video v, rows [row0_v + h S, row0_v + min((h + 1) S, ctx_l_v)).  The
+// list is not materialised: v is the last video with v_hb_off[v] <= g, found by a binary search over the V + 1 prefix sums --
+// wave-uniform (scalar loads of a table that stays in the scalar cache / L2), log2 V dependent loads per 45-row half-block that
+// the SIMD's other waves stream through.  (An owner entry per half-block would be one load, but a table as long as the list,
+// rebuilt and re-uploaded for every subset.)  Half-blocks restart at every video's first row, so neither a half-block nor a
+// window ever holds a row of the next video; rows outside the listed videos are never addressed.  The planes are (nq, total_hb)
+// with video v's half-blocks at column v_hb_off[v]; no frame score is written.
+//   QG queries a pass, blockIdx.y = the pass (a last pass of fewer repeats its last query and stores nothing for the spares);
+//   WPH as in frame_score_kernel (1: a wave per unit; 4: the workgroup's four waves share one, for short lists).
+template <int VPL, int QG, int RPW, int WPH>
+__global__ __launch_bounds__(256) void library_scan_kernel(const float* __restrict__ arena, int64_t capacity,
+                                                           const int64_t* __restrict__ v_row0, const int32_t* __restrict__ v_ctx_l,
+                                                           const int64_t* __restrict__ v_hb_off, int n_videos, int64_t total_hb,
+                                                           int S, const float* __restrict__ txt, int nq, float* __restrict__ hm,
+                                                           float* __restrict__ fr) {
+    constexpr int DV = 256 * VPL, UPB = 4 / WPH, NV = RPW * QG;
+    __shared__ float red[4][QG];
+    const int q0 = QG * (int)blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), sub = wave % WPH;
+    PF_LANE_SLOT(RPW, QG, lane);
+    float4 q[QG][VPL];
+#pragma unroll
+    for (int g = 0; g < QG; ++g)
+#pragma unroll
+        for (int v = 0; v < VPL; ++v) {
+            const int qi = min(q0 + g, nq - 1);
+            q[g][v] = reinterpret_cast<const float4*>(txt + (size_t)qi * DV)[lane + 64 * v];
+        }
+    for (int64_t g = (int64_t)blockIdx.x * UPB + wave / WPH; g < total_hb; g += (int64_t)gridDim.x * UPB) {
+        int lo = 0, hi = n_videos - 1;                                   // the last video whose first unit is at or before g
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (v_hb_off[mid] <= g) lo = mid; else hi = mid - 1;
+        }
+        const int64_t h = g - v_hb_off[lo], row0 = v_row0[lo], ctx_l = v_ctx_l[lo], r_lo = h * S;
+        int n = (int)min((int64_t)S, ctx_l - r_lo);                      // frames of this half-block
+        if (h < 0 || row0 < 0 || ctx_l > capacity - row0) n = 0;         // a video outside the arena is not read: -inf
+        const float* base = arena + (row0 + r_lo) * DV;
+        float m = -INFINITY;
+        for (int j0 = sub * RPW; j0 < n; j0 += WPH * RPW) {              // (frame_score_body's row loop, without the fs store)
+            float4 x[RPW][VPL];
+#pragma unroll
+            for (int r = 0; r < RPW; ++r) {
+                const int row = min(j0 + r, n - 1);
+#pragma unroll
+                for (int v = 0; v < VPL; ++v)
+                    x[r][v] = pf_stream_ld(reinterpret_cast<const float4*>(base + (size_t)row * DV) + lane + 64 * v);
+            }
+            float part[NV];
+#pragma unroll
+            for (int r = 0; r < RPW; ++r)
+#pragma unroll
+                for (int g2 = 0; g2 < QG; ++g2) part[r * QG + g2] = pf_lane_dot<VPL>(x[r], q[g2]);
+            const float s = wave_sum_multi<NV>(part, lane);
+            if (j0 + my_r < n) {
+                m = fmaxf(m, s);
+                if (writer && q0 + my_g < nq && my_r == 0 && j0 == 0) fr[(size_t)(q0 + my_g) * total_hb + g] = s;
+            }
+        }
+        if (n <= 0 && sub == 0 && out_lane && q0 + my_g < nq) fr[(size_t)(q0 + my_g) * total_hb + g] = -INFINITY;
+        m = pf_slot_max<RPW>(m);
+        pf_store_half_max<QG, WPH>(m, my_g, out_lane, lane, wave, red, q0, nq, total_hb, g, hm);
+    }
+}
+
+// Combine + stable top-k of one (query, video): win[i] = pf_window_of_halves over the video's OWN nh half-blocks (the odd-W
+// term fr[i + 1] exists only inside the video), then the first K entries of the order of cone_topk_windows_ws -- score
+// descending, ties to the lower index -- into widx / wval[(q V + v) K ..], -1 / -inf where the video has fewer than K windows,
+// and best[q V + v] = the first value.  Up to 1 024 windows (45 000 clips at W = 90) by counting ranks in LDS, as
+// topk_seg_kernel does; above that K selection passes that recompute the window from the planes: the window scores of a scan
+// exist nowhere.  (A window score is never NaN: the half-block max starts from -inf and fmaxf drops a NaN frame score, so an
+// all-NaN video scores -inf everywhere and lists its windows 0 .. K - 1; the counting order and the selection order agree.)
+__global__ __launch_bounds__(256) void library_topk_kernel(const float* __restrict__ hm, const float* __restrict__ fr,
+                                                           const int64_t* __restrict__ v_hb_off, int n_videos, int64_t total_hb,
+                                                           int odd, int K, int32_t* __restrict__ widx, float* __restrict__ wval,
+                                                           float* __restrict__ best) {
+    const int v = blockIdx.x, q = blockIdx.y, tid = threadIdx.x;
+    const int64_t off = v_hb_off[v], nh = v_hb_off[v + 1] - off;
+    const float* a = hm + (size_t)q * total_hb + off;
+    const float* f = fr + (size_t)q * total_hb + off;
+    const size_t pair = (size_t)q * n_videos + v;
+    int32_t* oi = widx + pair * K;
+    float* ov = wval + pair * K;
+    const int n = nh < 1 ? 0 : (int)min(nh + 1, (int64_t)0x7ffffffe);       // windows of this video (nh < 1: a broken table)
+    if (n == 0 && tid == 0) best[pair] = -INFINITY;
+    if (n <= 1024) {
+        __shared__ float s_row[1024];
+        for (int j = tid; j < n; j += 256) s_row[j] = pf_window_of_halves(a, f, nh, odd, j);
+        for (int p = n + tid; p < K; p += 256) { oi[p] = -1; ov[p] = -INFINITY; }
+        __syncthreads();
+        for (int j = tid; j < n; j += 256) {
+            const float x = s_row[j];
+            int rank = 0;
+            for (int i = 0; i < n; ++i) {           // (every thread reads the same address: LDS broadcast)
+                const float y = s_row[i];
+                rank += (y > x) || (y == x && i < j);
+            }
+            if (rank < K) { oi[rank] = j; ov[rank] = x; }
+            if (rank == 0) best[pair] = x;
+        }
+        return;
+    }
+    float last_v = INFINITY;
+    int last_i = -1;
+    for (int p = 0; p < K; ++p) {
+        float bv = -INFINITY;
+        int bi = 0x7fffffff;
+        for (int j = tid; j < n; j += 256) {
+            const float x = pf_window_of_halves(a, f, nh, odd, j);
+            if (tk_after(x, j, last_v, last_i) && tk_better(x, j, bv, bi)) { bv = x; bi = j; }
+        }
+        tk_pass_pick<4>(bv, bi, oi + p, ov + p, last_v, last_i);
+        if (p == 0 && tid == 0) best[pair] = last_v;
+    }
+}
+
 // ---- what the C entries share ---------------------------------------------------------------------------------------------
 // f(pf_int<VPL>) for the exact-fp32 streaming kernels' VPL = dv / 256 (dv in {256, 512, 768, 1024}: CONE_PF_REQUIRE_DIM)
 template <class F>
@@ -2037,4 +2156,92 @@ extern "C" int cone_topk_windows(const float* win_scores, int nq, int64_t num_wi
                            num_window, k, idx, val);
     CONE_LAUNCH_CHECK();
     return 0;
+}
+
+// ---- library search: entries ----
+namespace cone {
+
+// the regions of a scan's workspace: the two planes, best, the ranking's scratch (each 256-B aligned)
+struct ScanLayout { size_t hm, fr, best, rank_ws, rank_bytes, total; };
+static ScanLayout scan_layout(int64_t n_videos, int64_t total_hb, int nq, int n_rank) {
+    ScanLayout L{};
+    const size_t plane = align_up((size_t)nq * (size_t)total_hb * 4, 256);
+    L.hm = 0; L.fr = plane; L.best = 2 * plane;
+    L.rank_ws = L.best + align_up((size_t)nq * (size_t)n_videos * 4, 256);
+    L.rank_bytes = cone_topk_windows_workspace(nq, n_videos, n_rank);
+    L.total = L.rank_ws + align_up(L.rank_bytes, 256);
+    return L;
+}
+
+// The refusals a scan makes from host values alone, in this order, before any pointer or the handle is looked at.
+static int scan_precheck(const cone_library* lib, int64_t n_videos, int64_t total_hb, int nq, int K, int n_rank, int max_v_l) {
+    const char* who = "library_scan";
+    CONE_REQUIRE(lib, "%s: null argument", who);
+    CONE_REQUIRE(nq >= 1 && nq <= CONE_SESSION_MAX_QUERIES, "%s: nq=%d not in [1, %d]", who, nq, CONE_SESSION_MAX_QUERIES);
+    CONE_REQUIRE(n_videos >= 1, "%s: n_videos=%lld < 1", who, (long long)n_videos);
+    CONE_REQUIRE(lib->capacity >= 1 && lib->capacity < (1ll << 31), "%s: capacity=%lld not in [1, 2^31)", who, (long long)lib->capacity);
+    CONE_REQUIRE(total_hb >= n_videos && total_hb <= lib->capacity,
+                 "%s: total_hb=%lld not in [n_videos=%lld, capacity=%lld] (a video has at least one half-block, a half-block at least one row)",
+                 who, (long long)total_hb, (long long)n_videos, (long long)lib->capacity);
+    CONE_REQUIRE(K >= 1 && K <= 256, "%s: K=%d not in [1, 256]", who, K);
+    CONE_REQUIRE(n_rank >= 1 && n_rank <= n_videos, "%s: n_rank=%d not in [1, n_videos=%lld]", who, n_rank, (long long)n_videos);
+    CONE_REQUIRE(max_v_l >= 2, "%s: max_v_l=%d", who, max_v_l);
+    CONE_REQUIRE(!(lib->flags & CONE_SESSION_CERTIFIED), "%s: CONE_SESSION_CERTIFIED libraries are not supported", who);
+    CONE_REQUIRE(!(lib->flags & CONE_SESSION_BF16), "%s: CONE_SESSION_BF16 libraries are not supported", who);
+    return 0;
+}
+
+template <int VPL>
+static int launch_library_scan(const float* arena, int64_t capacity, const int64_t* v_row0, const int32_t* v_ctx_l,
+                               const int64_t* v_hb_off, int n_videos, int64_t total_hb, int S, const float* txt, int nq, float* hm,
+                               float* fr, hipStream_t s) {
+    const PfStreamGrid g(total_hb);
+    const int qg = nq >= 3 ? 4 : nq;                        // 3 queries ride a 4-query pass, as in pf_stream_passes
+    ProfScope ps(PK_FRAME_SCORE, total_hb * S, 256 * VPL, qg, nullptr, s);
+    const dim3 grid(g.blocks, (unsigned)((nq + qg - 1) / qg));
+#define CONE_SCAN_LAUNCH(QG, WPH)                                                                                            \
+    hipLaunchKernelGGL((library_scan_kernel<VPL, QG, CONE_PF_RPW, WPH>), grid, dim3(256), 0, s, arena, capacity, v_row0, v_ctx_l, \
+                       v_hb_off, n_videos, total_hb, S, txt, nq, hm, fr)
+    if (g.wide) { if (qg == 4) CONE_SCAN_LAUNCH(4, 4); else if (qg == 2) CONE_SCAN_LAUNCH(2, 4); else CONE_SCAN_LAUNCH(1, 4); }
+    else { if (qg == 4) CONE_SCAN_LAUNCH(4, 1); else if (qg == 2) CONE_SCAN_LAUNCH(2, 1); else CONE_SCAN_LAUNCH(1, 1); }
+#undef CONE_SCAN_LAUNCH
+    CONE_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace cone
+
+extern "C" size_t cone_library_scan_workspace(const cone_library* lib, int64_t n_videos, int64_t total_hb, int nq, int K, int n_rank) {
+    if (cone::scan_precheck(lib, n_videos, total_hb, nq, K, n_rank, 2)) return 0;
+    return cone::scan_layout(n_videos, total_hb, nq, n_rank).total;
+}
+
+extern "C" int cone_library_scan(const cone_model* m, const cone_library* lib, const int64_t* v_row0, const int32_t* v_ctx_l,
+                                 const int64_t* v_hb_off, int64_t n_videos, int64_t total_hb, const float* cls, int nq, int K,
+                                 int n_rank, const cone_session_params* params, int32_t* widx, float* wval, int32_t* rank_slot,
+                                 float* rank_val, void* ws, size_t ws_bytes, void* stream) {
+    const char* who = "library_scan";
+    CONE_REQUIRE(lib && params, "%s: null argument", who);
+    if (int rc = cone::scan_precheck(lib, n_videos, total_hb, nq, K, n_rank, params->max_v_l)) return rc;
+    CONE_REQUIRE(m && v_row0 && v_ctx_l && v_hb_off && cls && widx && wval && rank_slot && rank_val && ws, "%s: null argument", who);
+    CONE_REQUIRE(lib->model == m, "%s: the library was opened with another handle", who);
+    CONE_PF_REQUIRE_DIM("library_scan", lib->v_dim);
+    CONE_REQUIRE(lib->adapted, "%s: the library handle misses a region (not one cone_library_open filled)", who);
+    CONE_REQUIRE(((uintptr_t)ws & 255) == 0, "%s: the workspace must be 256-B aligned", who);
+    const cone::ScanLayout L = cone::scan_layout(n_videos, total_hb, nq, n_rank);
+    if (ws_bytes < L.total) { cone::set_error("%s: workspace too small (%zu < %zu)", who, ws_bytes, L.total); return CONE_E_WORKSPACE; }
+    hipStream_t s = (hipStream_t)stream;
+    char* w = (char*)ws;
+    float *hm = (float*)(w + L.hm), *fr = (float*)(w + L.fr), *best = (float*)(w + L.best);
+    const int W = params->max_v_l, S = W / 2, V = (int)n_videos;
+    if (int rc = cone::pf_with_vpl(lib->v_dim, [&](auto VPL) {
+            return cone::launch_library_scan<decltype(VPL)::value>(lib->adapted, lib->capacity, v_row0, v_ctx_l, v_hb_off, V, total_hb, S,
+                                                                   cls, nq, hm, fr, s);
+        }))
+        return rc;
+    hipLaunchKernelGGL(cone::library_topk_kernel, dim3((unsigned)V, (unsigned)nq), dim3(256), 0, s, hm, fr, v_hb_off, V, total_hb, W & 1,
+                       K, widx, wval, best);
+    CONE_LAUNCH_CHECK();
+    // the videos' order: the existing stable top-k on best (nq, V) -- slots, ties to the lower one
+    return cone_topk_windows_ws(best, nq, n_videos, n_rank, rank_slot, rank_val, L.rank_bytes ? w + L.rank_ws : nullptr, L.rank_bytes, stream);
 }

@@ -1,5 +1,6 @@
 // Video sessions (include/cone_hip.h, "video sessions"): one resident video, indexed once, answering batches of queries.
 // Video libraries ("video libraries"): many videos in the rows of one arena, one call for queries on any mix of them.
+// Library search ("library search"): the query half on the window lists of a cone_library_scan (csrc/prefilter.hip).
 //
 // Nothing is computed here.  cone_session_index / cone_library_add and cone_session_localize / cone_library_localize only
 // SEQUENCE the library's own extern "C" launchers -- the calls cone_amd/localizator.py issues one by one through ctypes for
@@ -204,7 +205,7 @@ struct LocalizeLayout {
 // rows: the session's ctx_l, or the library's capacity; q_row0 / q_ctx_l: NULL for a session (one run over all of its rows).
 static int localize_layout(const char* who, const char* what, const cone_model* m, const cone_model_dims& d, const Resident* ses,
                            int64_t rows, const int32_t* q_row0, const int32_t* q_ctx_l, const int32_t* tok_len, int nq, int K,
-                           int n_cand, const cone_session_params* p, LocalizeLayout* out) {
+                           int n_cand, const cone_session_params* p, LocalizeLayout* out, bool ranked = false) {
     CONE_REQUIRE(m && ses && p, "%s: null argument", who);
     CONE_REQUIRE(ses->model == m, "%s: the %s was indexed with another handle", who, what);
     CONE_REQUIRE(flags_ok(ses->flags), "%s: bad %s flags %d", who, what, ses->flags);
@@ -241,7 +242,7 @@ static int localize_layout(const char* who, const char* what, const cone_model* 
     L.q_ctx_l = r.take(nq * 4); L.q_vid_off = r.take(nq * 4); L.batch_pad = r.take(nq * 4);
     L.full_w = r.take(B * 4); L.n_valid = r.take(nq * 4);
     L.tok_norm = r.take(T * d.t_dim * 4);
-    if (!cert) L.scores = r.take(n_scores * 4);
+    if (!cert && !ranked) L.scores = r.take(n_scores * 4);        // (ranked: the lists come from a scan -- no stage A here)
     L.widx = r.take(B * 4); L.wval = r.take(B * 4); L.cert = r.take(nq * 4);
     L.wt = r.take(7 * align_up(B * 4, SES_ALIGN));
     L.tproj = r.take(T * dh * 4);
@@ -254,7 +255,7 @@ static int localize_layout(const char* who, const char* what, const cone_model* 
         L.pf_bytes = cone_prefilter_topk_certified_workspace(rows, nq, p->max_v_l, K, n_cand);
         CONE_REQUIRE(L.pf_bytes, "%s: n_cand=%d is not a candidate count the certified pre-filter takes for %lld windows and K=%d", who,
                      n_cand, (long long)L.nw, K);
-    } else {
+    } else if (!ranked) {
         for (int i = 0; i < L.n_runs; ++i) {        // the runs follow each other on one stream: they share the largest scratch
             const Run& u = L.runs[i];
             const int n = u.n < 4 ? u.n : 4;
@@ -361,12 +362,35 @@ extern "C" int cone_library_query_layout(const int32_t* tok_len, const int32_t* 
 
 namespace cone {
 
+// "The lists are here": the window lists of a cone_library_scan -- (scan_nq, n_videos, scan_K) on the device -- and, per pair of
+// this call, the scan's query index and table slot (host values: kernel arguments, nothing is uploaded).
+struct RankedPairs { int32_t query[CONE_SESSION_MAX_QUERIES], slot[CONE_SESSION_MAX_QUERIES]; };
+struct RankedLists {
+    const int32_t* widx;
+    const float* wval;
+    int64_t n_videos;
+    int scan_K;
+    RankedPairs pairs;
+};
+// pair p's first K entries of the list of (query[p], slot[p]) -> the call's window list; one writer per element
+__global__ __launch_bounds__(256) void library_gather_lists_kernel(RankedPairs P, int nq, int K, int64_t n_videos, int scan_K,
+                                                                   const int32_t* __restrict__ scan_widx,
+                                                                   const float* __restrict__ scan_wval, int32_t* __restrict__ widx,
+                                                                   float* __restrict__ wval) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= nq * K) return;
+    const int p = i / K, j = i - p * K;
+    const size_t src = ((size_t)P.query[p] * n_videos + P.slot[p]) * scan_K + j;
+    widx[i] = scan_widx[src];
+    wval[i] = scan_wval[src];
+}
+
 // The query half for both kinds of resident rows: q_row0 / q_ctx_l == NULL is a session (one video at row 0, `rows` clips),
 // otherwise a library call (every query names its video's rows inside an arena of `rows`).  Nothing differs after stage A.
 static int localize(const char* who, const cone_model* m, const cone_model_dims& d, const Resident& S, int64_t rows,
                     const LocalizeLayout& L, const int32_t* q_row0, const int32_t* q_ctx_l, const float* tok, const int32_t* tok_len,
                     int nq, const float* cls, int K, int n_cand, const cone_session_params& P, double* kept, int32_t* n_kept,
-                    int32_t* certified, char* w, void* stream) {
+                    int32_t* certified, char* w, void* stream, const RankedLists* lists = nullptr) {
     auto I = [&](size_t at) { return (int32_t*)(w + at); };
     auto F = [&](size_t at) { return (float*)(w + at); };
     auto scratch = [&](size_t at, size_t bytes) { return bytes ? (void*)(w + at) : nullptr; };
@@ -383,7 +407,11 @@ static int localize(const char* who, const cone_model* m, const cone_model_dims&
                                       I(L.q_vid_off), I(L.batch_pad), I(L.full_w), I(L.n_valid), stream));
     RUN(cone_l2_normalize_rows(tok, L.T, d.t_dim, 1e-5f, 1, F(L.tok_norm), stream));                          // :133
     // stage A (:83-100, stable tie order): the raw cls vectors against the adapted rows
-    if (S.flags & CONE_SESSION_CERTIFIED) {
+    if (lists) {        // a scan has ranked the windows (cone_library_scan: the same lists, bit for bit): copy each pair's
+        hipLaunchKernelGGL(library_gather_lists_kernel, dim3((unsigned)((nq * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                           lists->pairs, nq, K, lists->n_videos, lists->scan_K, lists->widx, lists->wval, I(L.widx), F(L.wval));
+        CONE_LAUNCH_CHECK();
+    } else if (S.flags & CONE_SESSION_CERTIFIED) {
         RUN(cone_prefilter_topk_certified(S.adapted, S.adapted_bf16, rows, dv, cls, nq, W, Sl, K, n_cand, S.err, I(L.widx),
                                           F(L.wval), certified ? certified : I(L.cert), w + L.pf_ws, L.pf_bytes, stream));
     } else {
@@ -571,3 +599,61 @@ extern "C" int cone_library_localize(const cone_model* m, const cone_library* li
                     (char*)ws, stream);
 }
 
+
+// ------------------------------------------------------------------------------ library search: the query half on scanned lists
+namespace cone {
+
+static int ranked_precheck(const char* who, const cone_library* lib, const int32_t* q_row0, const int32_t* q_ctx_l,
+                           const int32_t* tok_len, int nq, int K, const cone_session_params* p) {
+    RUN(library_precheck(who, lib, q_row0, q_ctx_l, tok_len, nq, K, p));
+    CONE_REQUIRE(!(lib->flags & CONE_SESSION_BF16), "%s: CONE_SESSION_BF16 libraries are not supported", who);
+    return 0;
+}
+
+}  // namespace cone
+
+extern "C" size_t cone_library_localize_ranked_workspace(const cone_model* m, const cone_library* lib, const int32_t* q_row0,
+                                                         const int32_t* q_ctx_l, const int32_t* tok_len, int nq, int K,
+                                                         const cone_session_params* params) {
+    const char* who = "library_localize_ranked";
+    cone_model_dims d;
+    LocalizeLayout L;
+    if (ranked_precheck(who, lib, q_row0, q_ctx_l, tok_len, nq, K, params)) return 0;
+    if (library_handle(who, m, lib) || cone_model_get_dims(m, &d)) return 0;
+    const Resident S = resident_of(*lib);
+    if (localize_layout(who, "library", m, d, &S, lib->capacity, q_row0, q_ctx_l, tok_len, nq, K, 0, params, &L, true)) return 0;
+    return L.total;
+}
+
+extern "C" int cone_library_localize_ranked(const cone_model* m, const cone_library* lib, const int32_t* q_row0, const int32_t* q_ctx_l,
+                                            const float* tok, const int32_t* tok_len, int nq, const float* cls, int K,
+                                            const cone_session_params* params, const int32_t* pair_query, const int32_t* pair_slot,
+                                            const int32_t* scan_widx, const float* scan_wval, int scan_nq, int64_t scan_n_videos,
+                                            int scan_K, double* kept, int32_t* n_kept, void* ws, size_t ws_bytes, void* stream) {
+    const char* who = "library_localize_ranked";
+    RUN(ranked_precheck(who, lib, q_row0, q_ctx_l, tok_len, nq, K, params));
+    CONE_REQUIRE(pair_query && pair_slot, "%s: null argument", who);
+    CONE_REQUIRE(scan_nq >= 1 && scan_n_videos >= 1 && scan_K >= 1 && K <= scan_K, "%s: K=%d not in [1, scan_K=%d] (scan_nq=%d, scan_n_videos=%lld)",
+                 who, K, scan_K, scan_nq, (long long)scan_n_videos);
+    RankedLists lists{scan_widx, scan_wval, scan_n_videos, scan_K, {}};
+    for (int q = 0; q < nq; ++q) {
+        CONE_REQUIRE(pair_query[q] >= 0 && pair_query[q] < scan_nq, "%s: pair_query[%d]=%d not in [0, scan_nq=%d)", who, q, pair_query[q],
+                     scan_nq);
+        CONE_REQUIRE(pair_slot[q] >= 0 && pair_slot[q] < scan_n_videos, "%s: pair_slot[%d]=%d not in [0, scan_n_videos=%lld)", who, q,
+                     pair_slot[q], (long long)scan_n_videos);
+        lists.pairs.query[q] = pair_query[q];
+        lists.pairs.slot[q] = pair_slot[q];
+    }
+    CONE_REQUIRE(m && tok && cls && scan_widx && scan_wval && kept && n_kept && ws, "%s: null argument", who);
+    CONE_REQUIRE(((uintptr_t)ws & (SES_ALIGN - 1)) == 0, "%s: the workspace must be 256-B aligned", who);
+    RUN(library_handle(who, m, lib));
+    cone_model_dims d;
+    RUN(cone_model_get_dims(m, &d));
+    const Resident S = resident_of(*lib);
+    LocalizeLayout L;
+    RUN(localize_layout(who, "library", m, d, &S, lib->capacity, q_row0, q_ctx_l, tok_len, nq, K, 0, params, &L, true));
+    CONE_REQUIRE(S.vid_norm && S.vproj && S.adapted, "%s: the library handle misses a region (not one cone_library_open filled)", who);
+    if (ws_bytes < L.total) { set_error("%s: workspace too small (%zu < %zu)", who, ws_bytes, L.total); return CONE_E_WORKSPACE; }
+    return localize(who, m, d, S, lib->capacity, L, q_row0, q_ctx_l, tok, tok_len, nq, cls, K, 0, *params, kept, n_kept, nullptr,
+                    (char*)ws, stream, &lists);
+}

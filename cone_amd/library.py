@@ -9,6 +9,14 @@ of MANY videos in the rows of one arena and answers a list of ``(video, query)``
 session, everything after it is one launch over all windows of all pairs, and every answer equals the localizer's
 ``predict_moment(video_feats, query)`` with ``==``.
 
+``rank_videos`` / ``search`` answer the question that comes before a pair: which of the resident videos shows this, and where.
+One ``cone_library_scan`` (csrc/prefilter.hip) runs the pre-filter over the rows of EVERY video in one pass over the arena --
+windows restart at each video's first row, the window lists are the per-video pre-filter's bit for bit -- and ranks the videos
+by their best window score (a cosine in the adapter's space: comparable across videos); ``search`` then localizes on the
+chosen (video, query) pairs through ``cone_library_localize_ranked``, which takes its window lists from the scan, so the
+moments still equal ``predict_moment``'s with ``==``.  ``scan_table`` lays the videos out for the scan (slots by first row,
+prefix sums of half-blocks).  fp32 libraries only: a ``prefilter_bf16`` library's search is refused by name.
+
 Rows are handed out first-fit from a free list and coalesce when a video is removed.  An open library neither grows nor
 compacts: ``add`` raises when no hole fits, however many clips are free in total -- size it for the working set, or open a
 second one.  Out of scope here: certified window ranking, growing a video in place, capturing the call in a graph.
@@ -102,10 +110,33 @@ def inverse_order(calls, n: int):
     return where
 
 
+def scan_table(videos, S: int):
+    """The table of one ``cone_library_scan``: ``videos`` = ``[(row0, ctx_l), ...]`` in any order, ``S`` = max_v_l // 2 clips
+    per half-block.  Slots are ordered by ``row0`` (the scan walks the arena front to back).  Returns ``(order, v_row0, v_ctx_l,
+    v_hb_off)``: ``order[slot]`` = index into ``videos``; ``v_row0`` int64 / ``v_ctx_l`` int32 per slot; ``v_hb_off`` int64
+    (V + 1) = exclusive prefix sums of ``ceil(ctx_l / S)``, so slot s owns units ``[v_hb_off[s], v_hb_off[s + 1])`` of the flat
+    half-block list and ``v_hb_off[-1]`` is its length.  Pure numpy, no GPU; overlapping ranges are refused."""
+    import numpy as np
+    if S < 1:
+        raise ValueError(f"scan_table: S={S} < 1")
+    videos = [(int(r), int(n)) for r, n in videos]
+    order = sorted(range(len(videos)), key=lambda i: videos[i][0])
+    row0 = np.asarray([videos[i][0] for i in order], dtype=np.int64)
+    ctx = np.asarray([videos[i][1] for i in order], dtype=np.int64)
+    if (ctx < 1).any() or (row0 < 0).any():
+        raise ValueError("scan_table: a video needs row0 >= 0 and at least one clip")
+    if (row0[1:] < row0[:-1] + ctx[:-1]).any():
+        raise ValueError("scan_table: two videos share arena rows")
+    hb_off = np.zeros(len(order) + 1, dtype=np.int64)
+    np.cumsum((ctx + S - 1) // S, out=hb_off[1:])
+    return order, row0, ctx.astype(np.int32), hb_off
+
+
 class VideoLibrary:
     """Many resident videos of a ``CONELocalizator`` (``open_library``).  ``add`` indexes a video into free rows and returns its
     id (never reused); ``predict_moments([(id, (tok, cls)), ...])`` returns, per pair and in the order given, what the
-    localizer's ``predict_moment`` returns for that video and query, ``==``.  No compaction, no growth: see the module text."""
+    localizer's ``predict_moment`` returns for that video and query, ``==``.  ``rank_videos`` / ``search`` answer "which video,
+    and where" without the caller naming one.  No compaction, no growth: see the module text."""
 
     def __init__(self, localizer, capacity_clips: int):
         from .model import Workspace
@@ -126,6 +157,8 @@ class VideoLibrary:
         _lib.check(lib.cone_library_open(h, self._rows.capacity, self._flags, _lib.ptr(self._arena), n_arena, C.byref(self._cl)))
         self._params = _lib.SessionParams(int(a.max_v_l), int(a.max_q_l), float(a.clip_length), NMS_THD, MAX_BEFORE, MAX_AFTER)
         self._ws = Workspace()              # the per-call workspace (grow-only)
+        self._scan_ws = Workspace()         # the scan's planes and ranking scratch (grow-only)
+        self._scan_cache = None             # the device table of ALL resident videos; rebuilt lazily after add / remove
         self._open = True
 
     # ---- lifetime ------------------------------------------------------------------------------
@@ -140,7 +173,7 @@ class VideoLibrary:
 
     def close(self):
         self._open = False              # (the ids stay known: a call on a closed library says "closed", not "unknown id")
-        self._arena = self._cl = self._ws = None
+        self._arena = self._cl = self._ws = self._scan_ws = self._scan_cache = None
 
     def __enter__(self):
         return self
@@ -179,6 +212,7 @@ class VideoLibrary:
         except Exception:
             self._rows.release(row0, n)
             raise
+        self._scan_cache = None
         vid_id, self._next_id = self._next_id, self._next_id + 1
         self._videos[vid_id] = (row0, n, min(int(a.topk_window), ops.num_windows(n, a.max_v_l)))
         return vid_id
@@ -188,6 +222,7 @@ class VideoLibrary:
         overwrites them: one stream).  Its id is never handed out again."""
         row0, n, _ = self._video(vid_id)
         del self._videos[vid_id]
+        self._scan_cache = None
         self._rows.release(row0, n)
 
     def _video(self, vid_id):
@@ -244,3 +279,140 @@ class VideoLibrary:
     def predict_moment(self, vid_id, text_feats):
         """``localizer.predict_moment(video_feats, text_feats)`` for the resident video ``vid_id``."""
         return self.predict_moments([(vid_id, text_feats)])[0]
+
+    # ---- search --------------------------------------------------------------------------------
+    def _search_ids(self, videos):
+        """The ids a search runs over: every resident video, or the caller's (unknown ids and duplicates are refused)."""
+        if videos is None:
+            return None, list(self._videos)
+        ids = list(videos)
+        for v in ids:
+            self._video(v)
+        if len(set(ids)) != len(ids):
+            dup = sorted({v for v in ids if ids.count(v) > 1})
+            raise ValueError(f"VideoLibrary: video id {dup[0]!r} is listed more than once")
+        return ids, ids
+
+    def _table(self, subset, ids):
+        """``scan_table`` of the videos on the device: (ids by slot, device v_row0 / v_ctx_l / v_hb_off, total_hb).  The table of
+        ALL resident videos is kept until the next ``add`` / ``remove``; a subset's is built per call."""
+        if subset is None and self._scan_cache is not None:
+            return self._scan_cache
+        order, row0, ctx, hb_off = scan_table([self._videos[v][:2] for v in ids], int(self._loc.args.max_v_l) // 2)
+        dev = self._loc.device
+        t = ([ids[i] for i in order], torch.from_numpy(row0).to(dev), torch.from_numpy(ctx).to(dev), torch.from_numpy(hb_off).to(dev),
+             int(hb_off[-1]))
+        if subset is None:
+            self._scan_cache = t
+        return t
+
+    def _scan(self, table, queries, n_rank):
+        """One ``cone_library_scan`` of at most MAX_QUERIES queries: (widx, wval, rank) on the device, K = topk_window; rank =
+        (2, nq, n_rank) int32 words: the slots, then the scores' bits (one tensor: one read-back)."""
+        lib, m, dev = _lib.load(), self._loc.localizator, self._loc.device
+        _, row0, ctx, hb_off, total_hb = table
+        V, nq, K = int(ctx.numel()), len(queries), int(self._loc.args.topk_window)
+        cls = torch.stack([c.to(dev, torch.float32).reshape(-1) for _, c in queries]).contiguous()
+        nbytes = lib.cone_library_scan_workspace(C.byref(self._cl), V, total_hb, nq, K, n_rank)
+        if nbytes == 0:
+            raise _lib.ConeHipError(f"libcone_hip error: {lib.cone_last_error().decode()}")
+        ws = self._scan_ws.get(nbytes, dev)
+        widx = torch.empty(nq * V * K, dtype=torch.int32, device=dev)
+        wval = torch.empty(nq * V * K, dtype=torch.float32, device=dev)
+        rank = torch.empty(2, nq, n_rank, dtype=torch.int32, device=dev)
+        _lib.check(lib.cone_library_scan(m._h(), C.byref(self._cl), _lib.ptr(row0), _lib.ptr(ctx), _lib.ptr(hb_off), V, total_hb,
+                                         _lib.ptr(cls, torch.float32), nq, K, n_rank, C.byref(self._params), _lib.ptr(widx),
+                                         _lib.ptr(wval), C.c_void_p(rank[0].data_ptr()), C.c_void_p(rank[1].data_ptr()),
+                                         _lib.ptr(ws), ws.numel(), _lib.stream()))
+        return widx, wval, rank
+
+    def _ranked(self, queries, n_videos, videos):
+        """The scans of one ``rank_videos`` / ``search`` and their ONE read-back: (table, [(first query, queries, widx, wval)],
+        per query [(slot, score), ...]); ``None`` where nothing is to be searched."""
+        queries = list(queries)
+        check_queries([int(q[0].shape[0]) for q in queries], self.max_q_l)
+        subset, ids = self._search_ids(videos)
+        if n_videos is not None and int(n_videos) < 1:
+            raise ValueError(f"VideoLibrary: n_videos={n_videos} < 1")
+        if not queries or not ids:
+            return None, [], [[] for _ in queries]
+        self._check_live()
+        n_rank = len(ids) if n_videos is None else min(int(n_videos), len(ids))
+        table = self._table(subset, ids)
+        scans, ranks = [], []
+        for g in range(0, len(queries), MAX_QUERIES):
+            chunk = queries[g:g + MAX_QUERIES]
+            widx, wval, rank = self._scan(table, chunk, n_rank)
+            scans.append((g, chunk, widx, wval))
+            ranks.append(rank.reshape(2, -1))
+        host = (ranks[0] if len(ranks) == 1 else torch.cat(ranks, dim=1)).cpu()       # the one small read-back
+        slots = host[0].reshape(len(queries), n_rank).tolist()
+        vals = host[1].contiguous().view(torch.float32).reshape(len(queries), n_rank).tolist()
+        return table, scans, [list(zip(s, v)) for s, v in zip(slots, vals)]
+
+    @torch.no_grad()
+    def rank_videos(self, queries, n_videos=None, videos=None):
+        """``[(tok, cls), ...]`` -> per query ``[(video id, score), ...]``: the ``n_videos`` best (all when ``None``) of the
+        resident videos -- or of ``videos``, an iterable of ids -- by their best window score for the query (the pre-filter's
+        cosine in the adapter's space, cone/inference.py:276-299), descending; ties to the video that lies first in the arena.
+        One scan of the arena per 64 queries, one read-back; no window model runs."""
+        table, _, ranked = self._ranked(queries, n_videos, videos)
+        return [[(table[0][s], v) for s, v in row] for row in ranked]
+
+    def _enqueue_ranked(self, K, chunk, scan, V):
+        """One ``cone_library_localize_ranked`` call: ``chunk`` = [((row0, ctx_l), (tok, cls), scan query, slot), ...]."""
+        lib, m, dev = _lib.load(), self._loc.localizator, self._loc.device
+        h, nq = m._h(), len(chunk)
+        _, sq, widx, wval = scan
+        toks = [t.to(dev, torch.float32).contiguous() for _, (t, _), _, _ in chunk]
+        tok_cat = toks[0] if nq == 1 else torch.cat(toks)
+        cls = torch.stack([c.to(dev, torch.float32).reshape(-1) for _, (_, c), _, _ in chunk]).contiguous()
+        i32 = C.c_int32 * nq
+        row0, ctx, lens = i32(*(v[0] for v, _, _, _ in chunk)), i32(*(v[1] for v, _, _, _ in chunk)), i32(*(int(t.shape[0]) for t in toks))
+        pq, ps = i32(*(c[2] for c in chunk)), i32(*(c[3] for c in chunk))
+        nbytes = lib.cone_library_localize_ranked_workspace(h, C.byref(self._cl), row0, ctx, lens, nq, K, C.byref(self._params))
+        if nbytes == 0:
+            raise _lib.ConeHipError(f"libcone_hip error: {lib.cone_last_error().decode()}")
+        ws = self._ws.get(nbytes, dev)
+        R, N = _kept_bytes(nq)
+        buf = torch.empty(R + N, dtype=torch.uint8, device=dev)
+        _lib.check(lib.cone_library_localize_ranked(h, C.byref(self._cl), row0, ctx, _lib.ptr(tok_cat, torch.float32), lens, nq,
+                                                    _lib.ptr(cls, torch.float32), K, C.byref(self._params), pq, ps, _lib.ptr(widx),
+                                                    _lib.ptr(wval), len(sq), V, int(self._loc.args.topk_window),
+                                                    C.c_void_p(buf.data_ptr()), C.c_void_p(buf.data_ptr() + R), _lib.ptr(ws),
+                                                    ws.numel(), _lib.stream()))
+        return buf
+
+    @torch.no_grad()
+    def search(self, queries, n_videos=5, videos=None):
+        """``[(tok, cls), ...]`` -> per query ``[(video id, score, moments), ...]`` for its ``n_videos`` best videos (clamped to
+        the videos searched), in ``rank_videos``' order; ``moments == localizer.predict_moment(video_feats, query)``: the scan's
+        window lists are the per-video pre-filter's, bit for bit, and everything after them is ``predict_moments``' call.  One
+        scan per 64 queries, ONE small read-back (the chosen slots and scores), the ``cone_library_localize_ranked`` calls that
+        ``plan_calls`` lays out (one K per call, pairs sorted by video, at most 64), one read-back of the kept rows."""
+        table, scans, ranked = self._ranked(queries, n_videos, videos)
+        if table is None:
+            return ranked
+        ids, V = table[0], len(table[0])
+        bufs, plans = [], []
+        for scan in scans:
+            g, chunk = scan[0], scan[1]
+            pairs = [(q, slot) for q in range(len(chunk)) for slot, _ in ranked[g + q]]
+            vids = [self._videos[ids[slot]] for _, slot in pairs]
+            calls = plan_calls([v[0] for v in vids], [v[2] for v in vids])
+            where = inverse_order(calls, len(pairs))
+            bufs += [self._enqueue_ranked(K, [(vids[i][:2], chunk[pairs[i][0]], pairs[i][0], pairs[i][1]) for i in idx], scan, V)
+                     for K, idx in calls]
+            plans.append((calls, where))
+        host = (bufs[0] if len(bufs) == 1 else torch.cat(bufs)).cpu()             # the kept rows' one read-back
+        out, at = [], 0
+        for (g, chunk, _, _), (calls, where) in zip(scans, plans):
+            moments = []
+            for _, idx in calls:
+                n = sum(_kept_bytes(len(idx)))
+                moments += VideoSession.read_kept(host[at:at + n].clone() if at else host, len(idx))
+                at += n
+            it = iter(where)
+            for q in range(len(chunk)):
+                out.append([(ids[slot], val, moments[next(it)]) for slot, val in ranked[g + q]])
+        return out

@@ -637,6 +637,56 @@ int cone_library_localize(const cone_model* m, const cone_library* lib, const in
                           const float* tok, const int32_t* tok_len, int nq, const float* cls, int K,
                           const cone_session_params* params, double* kept, int32_t* n_kept, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------ library search (additive in ABI 8)
+ * "Which of my resident videos shows this, and where?"  The coarse stage of the method (cone/inference.py:276-299: a window's
+ * score is the best cosine of its clips with the query in the adapter's space, comparable across videos) over MANY videos of a
+ * library in ONE pass over their arena rows, then the query half on the windows the scan found.  CONTRACT: for every
+ * (query, video) the window list carries the bits of cone_prefilter_scores (the streaming form: launches of at most 4 queries) +
+ * cone_topk_windows_ws on that video's rows alone -- what cone_library_localize's stage A computes per run --, so a search's
+ * moments carry the bits of predict_moment on the videos it chose.  Rows outside the listed videos are never read; a half-block
+ * and a window never cross a video's end.  fp32 libraries only: CONE_SESSION_BF16 and CONE_SESSION_CERTIFIED libraries are
+ * refused by name. */
+
+/* Stage A of run_on_video/cone_localizator.py:121-221 (:83-100; cone/inference.py:276-299) for nq queries against n_videos
+ * videos of the library.  The videos come as a DEVICE table: v_row0 (n_videos) int64 first arena row, v_ctx_l (n_videos) int32
+ * clips, v_hb_off (n_videos + 1) int64 exclusive prefix sums of ceil(v_ctx_l / S), S = max_v_l / 2; total_hb = v_hb_off[n_videos]
+ * (the host knows it: cone_amd/library.py scan_table).  The ranges must be disjoint and inside the arena; a video whose range
+ * leaves [0, capacity) is not read and scores -inf.  cls (nq, v_dim) fp32 on the device.
+ * Outputs (device): widx / wval (nq, n_videos, K): the first K entries of the stable descending order of video v's window
+ * scores for query q (the order, ties and values of cone_topk_windows_ws on that video's score row), padded with -1 / -inf where
+ * the video has fewer than K windows -- a prefix of a stable list is the stable list of a smaller K, so one scan at
+ * K = topk_window serves every video's own K.  rank_slot / rank_val (nq, n_rank): cone_topk_windows_ws over best[q][v] =
+ * wval[q][v][0]: the n_rank best videos as TABLE SLOTS (ties to the lower slot) and their scores.
+ * ws >= cone_library_scan_workspace, 256-B aligned: two planes (nq, total_hb), best (nq, n_videos), the ranking's scratch; no
+ * frame score and no window score is written anywhere.
+ * Refused by name ("library_scan: "), from host values first, before any pointer or the handle is looked at: nq outside [1, 64];
+ * n_videos < 1; total_hb < n_videos or > capacity; K outside [1, 256]; n_rank outside [1, n_videos]; max_v_l < 2; a
+ * CONE_SESSION_CERTIFIED or CONE_SESSION_BF16 library; then null arguments, another handle, a v_dim outside {256, 512, 768, 1024},
+ * a misaligned or short workspace. */
+size_t cone_library_scan_workspace(const cone_library* lib, int64_t n_videos, int64_t total_hb, int nq, int K, int n_rank);
+int cone_library_scan(const cone_model* m, const cone_library* lib, const int64_t* v_row0, const int32_t* v_ctx_l,
+                      const int64_t* v_hb_off, int64_t n_videos, int64_t total_hb, const float* cls, int nq, int K, int n_rank,
+                      const cone_session_params* params, int32_t* widx, float* wval, int32_t* rank_slot, float* rank_val, void* ws,
+                      size_t ws_bytes, void* stream);
+
+/* cone_library_localize (run_on_video/cone_localizator.py:121-221, the query half) with stage A replaced by a gather: pair p's
+ * window list is the first K entries of the scan's list of (query pair_query[p], table slot pair_slot[p]), copied by ONE small
+ * launch; everything from cone_window_table on is cone_library_localize, the same function (cone/inference.py:276-299 has run in
+ * the scan).  pair_query, pair_slot: HOST arrays of nq entries; scan_widx / scan_wval: the DEVICE outputs of a cone_library_scan
+ * with scan_nq queries, scan_n_videos videos and scan_K entries per list; q_row0 / q_ctx_l must name the rows of the video at
+ * that slot (the caller's table: cone_amd/library.py).  cls (nq, v_dim): the PAIRS' cls vectors.  ws >=
+ * cone_library_localize_ranked_workspace (no score rows, no stage-A scratch).
+ * Refused by name ("library_localize_ranked: "): everything cone_library_localize refuses, on the host, the pairs first; then
+ * K > scan_K, a pair_query[p] outside [0, scan_nq), a pair_slot[p] outside [0, scan_n_videos); a CONE_SESSION_BF16 library. */
+size_t cone_library_localize_ranked_workspace(const cone_model* m, const cone_library* lib, const int32_t* q_row0,
+                                              const int32_t* q_ctx_l, const int32_t* tok_len, int nq, int K,
+                                              const cone_session_params* params);
+int cone_library_localize_ranked(const cone_model* m, const cone_library* lib, const int32_t* q_row0, const int32_t* q_ctx_l,
+                                 const float* tok, const int32_t* tok_len, int nq, const float* cls, int K,
+                                 const cone_session_params* params, const int32_t* pair_query, const int32_t* pair_slot,
+                                 const int32_t* scan_widx, const float* scan_wval, int scan_nq, int64_t scan_n_videos, int scan_K,
+                                 double* kept, int32_t* n_kept, void* ws, size_t ws_bytes, void* stream);
+
 /* -------------------------------------------------------------------- metrics on the device
  * Recall@K / IoU counts from the kept rows (layout of cone_fuse_nms: rows (nq, max_after, 5) fp64 [st, ed, ...],
  * n (nq) valid rows) and one target span per query gt (nq, 2) fp64 seconds -- device pointers.  thresholds /
