@@ -224,6 +224,12 @@ _SIGNATURES = {
                                                C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_int, C.POINTER(SessionParams),
                                                C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_int, C.c_int64,
                                                C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # library maintenance (additive in ABI 8): moving resident rows bit for bit (compaction in place, resizing)
+    "cone_library_move_stage_bytes": (C.c_size_t, [C.POINTER(Library), C.c_int64]),
+    # cone_library_move_rows(m, src, dst, mv_src, mv_dst, mv_off (device), n_moves, total_rows, row_begin, row_end, stage,
+    # stage_bytes, stream)
+    "cone_library_move_rows": (C.c_int, [C.c_void_p, C.POINTER(Library), C.POINTER(Library)] + [C.c_void_p] * 3 + [C.c_int64] * 4
+                               + [C.c_void_p, C.c_size_t, C.c_void_p]),
     # cone_test_gemm(A, A2, a2_mod, W, bias, R, ln_g, ln_b, C, C2, ADD, M, N, K, flags, stream)
     "cone_test_gemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,

@@ -17,9 +17,16 @@ chosen (video, query) pairs through ``cone_library_localize_ranked``, which take
 moments still equal ``predict_moment``'s with ``==``.  ``scan_table`` lays the videos out for the scan (slots by first row,
 prefix sums of half-blocks).  fp32 libraries only: a ``prefilter_bf16`` library's search is refused by name.
 
-Rows are handed out first-fit from a free list and coalesce when a video is removed.  An open library neither grows nor
-compacts: ``add`` raises when no hole fits, however many clips are free in total -- size it for the working set, or open a
-second one.  Out of scope here: certified window ranking, growing a video in place, capturing the call in a graph.
+Rows are handed out first-fit from a free list and coalesce when a video is removed, so ``add`` / ``remove`` traffic
+fragments the arena: by default ``add`` raises when no hole fits, however many clips are free in total.  ``compact`` closes the
+holes in place and ``resize`` moves every video into an arena of another size (``add(..., compact=True)`` compacts when that is
+what it takes; ``largest_free`` tells a caller when).  Neither recomputes anything: everything the library holds per clip is a
+row in four or five planes, a row's bits do not depend on where it lives, so ``cone_library_move_rows``
+(csrc/library_move.hip) copies the rows and every answer keeps its bits.  ``compaction_moves`` lays the videos out in arena
+order (ids, rankings and their tie order do not change); ``plan_steps`` cuts the moves into calls that never overwrite a row a
+later call has yet to read -- staged through a buffer where a call's source and destination rows overlap, direct where they
+cannot.  Out of scope here: certified window ranking, growing a video in place, indexing several videos in one launch (a
+row's bits depend on its launch's row count: both would break ``== predict_moment``), capturing the call in a graph.
 """
 from __future__ import annotations
 
@@ -80,6 +87,57 @@ class RowRanges:
             del self.holes[i]
         self.holes.insert(i, (start, n))
 
+    def compacted(self):
+        """After a compaction the owned rows are ``[0, capacity - free)``: one hole at the end (none in a full arena)."""
+        free = self.free
+        self.holes = [(self.capacity - free, free)] if free else []
+
+
+def compaction_moves(videos):
+    """``[(row0, n), ...]`` in any order -> ``[(src, dst, n), ...]`` in ARENA order, ``dst`` = the running sum of the lengths:
+    the videos packed to the front, none overtaking another (``rank_videos`` breaks ties to the video that lies first in the
+    arena: the order must not change).  Videos already in place come out with ``src == dst``.  Pure Python, no GPU;
+    overlapping ranges are refused."""
+    videos = sorted((int(r), int(n)) for r, n in videos)
+    moves, at, end = [], 0, 0
+    for row0, n in videos:
+        if n < 1 or row0 < end:
+            raise ValueError("compaction_moves: a video needs at least one clip and rows of its own")
+        moves.append((row0, at, n))
+        at, end = at + n, row0 + n
+    return moves
+
+
+def plan_steps(moves, stage_rows: int):
+    """The ``cone_library_move_rows`` calls of a compaction: ``moves`` = ``compaction_moves``' list, ``stage_rows`` = rows the
+    staging buffer holds.  Returns ``[(row_begin, row_end, staged), ...]`` over the flat row list of the moves with
+    ``src != dst`` (the table the calls get).  At flat row p let g = src(p) - dst(p), the rows freed below it.  g >= stage_rows:
+    a DIRECT step of min(g, remaining) rows -- the destinations are contiguous, so they end at or below the step's first source
+    row: disjoint.  Otherwise a STAGED step of min(stage_rows, remaining) rows.  g never decreases along the arena, so a plan is
+    a staged prefix and a direct suffix.  Every step's destination rows lie at or below its own source rows and every later
+    step's source rows above them: no step overwrites a row a later step has yet to read."""
+    if stage_rows < 1:
+        raise ValueError(f"plan_steps: stage_rows={stage_rows} < 1")
+    moving = [(int(s), int(d), int(n)) for s, d, n in moves if s != d]
+    at = moving[0][1] if moving else 0
+    gap = 1
+    for s, d, n in moving:
+        if n < 1 or d != at or s - d < gap:
+            raise ValueError("plan_steps: not the moves of a compaction (downward, in arena order, destinations contiguous)")
+        at, gap = d + n, s - d
+    total = sum(n for _, _, n in moving)
+    steps, p, i, first = [], 0, 0, 0            # first = flat row of move i
+    while p < total:
+        while p >= first + moving[i][2]:
+            first += moving[i][2]
+            i += 1
+        g = moving[i][0] - moving[i][1]
+        staged = g < stage_rows
+        n = min(stage_rows if staged else g, total - p)
+        steps.append((p, p + n, staged))
+        p += n
+    return steps
+
 
 def plan_calls(video_of, k_of, limit: int = MAX_QUERIES):
     """The calls of one ``predict_moments``: ``video_of[i]`` / ``k_of[i]`` = video id and window count K of pair i.  Pairs are
@@ -136,7 +194,7 @@ class VideoLibrary:
     """Many resident videos of a ``CONELocalizator`` (``open_library``).  ``add`` indexes a video into free rows and returns its
     id (never reused); ``predict_moments([(id, (tok, cls)), ...])`` returns, per pair and in the order given, what the
     localizer's ``predict_moment`` returns for that video and query, ``==``.  ``rank_videos`` / ``search`` answer "which video,
-    and where" without the caller naming one.  No compaction, no growth: see the module text."""
+    and where" without the caller naming one.  ``compact`` / ``resize`` move the resident rows bit for bit: see the module text."""
 
     def __init__(self, localizer, capacity_clips: int):
         from .model import Workspace
@@ -192,9 +250,10 @@ class VideoLibrary:
 
     # ---- videos --------------------------------------------------------------------------------
     @torch.no_grad()
-    def add(self, video_feats):
+    def add(self, video_feats, compact=False):
         """Index ``video_feats`` (clips, dim) into the first free row range that holds it; returns the video's id.  Raises
-        ``ValueError`` when no hole fits (the message names the clips asked for and the largest free hole)."""
+        ``ValueError`` when no hole fits (the message names the clips asked for and the largest free hole) -- unless
+        ``compact=True`` and the free clips together hold it: then the library compacts first (``compact``)."""
         self._check_live()
         a, m = self._loc.args, self._loc.localizator
         vid = video_feats.to(self._loc.device, torch.float32).contiguous()
@@ -203,6 +262,8 @@ class VideoLibrary:
         m._check_dim(vid, a.v_appear_feat_dim, "appearance clip features")
         m._check_dim(vid, a.v_motion_feat_dim, "motion clip features")
         n = int(vid.shape[0])
+        if compact and self._rows.largest < n <= self._rows.free:
+            self.compact()
         row0 = self._rows.take(n)
         try:
             lib, h = _lib.load(), m._h()
@@ -224,6 +285,93 @@ class VideoLibrary:
         del self._videos[vid_id]
         self._scan_cache = None
         self._rows.release(row0, n)
+
+    # ---- maintenance ---------------------------------------------------------------------------
+    @property
+    def largest_free(self) -> int:
+        """Clips of the largest hole: what one ``add`` can take without a compaction (``free_clips`` is what it can take
+        with one)."""
+        return self._rows.largest if self._open else 0
+
+    def _move(self, src_cl, dst_cl, moves, steps, stage):
+        """Uploads the table of ``moves`` once and enqueues one ``cone_library_move_rows`` per step."""
+        import numpy as np
+        lib, h, n = _lib.load(), self._loc.localizator._h(), len(moves)
+        table = np.zeros(3 * n + 1, dtype=np.int64)                  # mv_src | mv_dst | mv_off: one upload
+        table[:n], table[n:2 * n] = [m[0] for m in moves], [m[1] for m in moves]
+        np.cumsum([m[2] for m in moves], out=table[2 * n + 1:])
+        total = int(table[-1])
+        dev = torch.from_numpy(table).to(self._loc.device)
+        at = lambda k: C.c_void_p(dev.data_ptr() + 8 * k)
+        for begin, end, staged in steps:
+            _lib.check(lib.cone_library_move_rows(h, C.byref(src_cl), C.byref(dst_cl), at(0), at(n), at(2 * n), n, total, begin, end,
+                                                  _lib.ptr(stage) if staged else None, stage.numel() if staged else 0, _lib.stream()))
+        return total
+
+    @torch.no_grad()
+    def compact(self, stage_bytes: int = 256 << 20) -> int:
+        """Closes the holes in place: every video slides down to the end of its predecessor, in arena order; returns the clips
+        moved (0, and nothing is launched, on a compact library).  Ids, answers and rankings do not change -- the rows are
+        copied bit for bit --, the free list becomes one hole at the end, the scan's table is rebuilt on the next search.  The
+        moves run as ``plan_steps`` lays them out, on the library's one stream (queries enqueued earlier have read their
+        rows): steps whose source and destination rows can overlap go through a staging buffer of at most ``stage_bytes``
+        (allocated for the call, released after it; two launches a step), the others are one launch each."""
+        self._check_live()
+        ids = sorted(self._videos, key=lambda v: self._videos[v][0])
+        moves = compaction_moves([self._videos[v][:2] for v in ids])
+        moving = [m for m in moves if m[0] != m[1]]
+        if not moving:
+            self._rows.compacted()              # (already one hole at the end: unchanged)
+            return 0
+        lib = _lib.load()
+        need = lambda rows: lib.cone_library_move_stage_bytes(C.byref(self._cl), rows)
+        cl = self._cl
+        row_bytes = cl.v_dim * (4 + 4 * bool(cl.adapted) + 2 * bool(cl.adapted_bf16)) + cl.hidden_dim * (4 + 12 * bool(cl.qkv_vid))
+        stage_rows = min(sum(m[2] for m in moving), int(stage_bytes) // row_bytes)
+        while stage_rows >= 1 and need(stage_rows) > stage_bytes:     # (every plane of the buffer is rounded up to 256 B)
+            stage_rows -= 1
+        if stage_rows < 1:
+            raise ValueError(f"compact: stage_bytes={stage_bytes} holds no clip (one clip takes {need(1)} bytes)")
+        steps = plan_steps(moving, stage_rows)
+        largest = max((e - b for b, e, staged in steps if staged), default=0)
+        stage = torch.empty(need(largest), dtype=torch.uint8, device=self._loc.device) if largest else None
+        moved = self._move(self._cl, self._cl, moving, steps, stage)
+        for v, (_, dst, _) in zip(ids, moves):
+            self._videos[v] = (dst,) + self._videos[v][1:]
+        self._rows.compacted()
+        self._scan_cache = None
+        return moved
+
+    @torch.no_grad()
+    def resize(self, capacity_clips: int):
+        """Moves the library into a new arena of ``capacity_clips`` clips, larger or smaller, compacting on the way: ONE
+        direct ``cone_library_move_rows`` call copies every video, in arena order, to the front of the new arena; then the
+        arenas are swapped.  Ids and answers do not change.  BOTH arenas live during the call (the old one is released when
+        the copy has run).  Raises ``ValueError`` when ``capacity_clips`` is smaller than the resident clips."""
+        capacity = int(capacity_clips)
+        resident = sum(v[1] for v in self._videos.values())
+        if capacity < resident:
+            raise ValueError(f"resize: capacity_clips={capacity} is smaller than the {resident} resident clips")
+        if capacity < 1:
+            raise ValueError(f"capacity must be at least one clip, got {capacity}")
+        self._check_live()
+        lib, h = _lib.load(), self._loc.localizator._h()
+        n_arena = lib.cone_library_arena_bytes(h, capacity, self._flags)
+        if n_arena == 0:
+            raise _lib.ConeHipError(f"libcone_hip error: {lib.cone_last_error().decode()}")
+        arena, cl = torch.empty(n_arena, dtype=torch.uint8, device=self._loc.device), _lib.Library()
+        _lib.check(lib.cone_library_open(h, capacity, self._flags, _lib.ptr(arena), n_arena, C.byref(cl)))
+        ids = sorted(self._videos, key=lambda v: self._videos[v][0])
+        moves = compaction_moves([self._videos[v][:2] for v in ids])
+        if moves:
+            self._move(self._cl, cl, moves, [(0, resident, False)], None)
+        for v, (_, dst, _) in zip(ids, moves):
+            self._videos[v] = (dst,) + self._videos[v][1:]
+        self._arena, self._cl = arena, cl       # (the old arena goes back to the allocator of this stream: the copy has read it by
+        self._rows = RowRanges(capacity)        #  the time anything enqueued later writes there)
+        if resident:
+            self._rows.take(resident)
+        self._scan_cache = None
 
     def _video(self, vid_id):
         try:

@@ -574,7 +574,7 @@ int cone_session_localize(const cone_model* m, const cone_session* session, cons
  * first-fit free list), the entries only check that a range lies inside the arena.  The rules are the sessions': all memory
  * is the caller's, arena and workspaces 256-B aligned, one stream, nothing allocated, no host read-back, refusals by name on
  * the host before any pointer is read.  Out of scope: CONE_SESSION_CERTIFIED libraries (refused by name), growing a video in
- * place, compaction. */
+ * place, indexing several videos in one launch.  (Compaction and resizing: "library maintenance" below.) */
 
 /* A plain host struct of device pointers into the caller's arena, like cone_session; filled by cone_library_open. */
 typedef struct {
@@ -686,6 +686,38 @@ int cone_library_localize_ranked(const cone_model* m, const cone_library* lib, c
                                  const cone_session_params* params, const int32_t* pair_query, const int32_t* pair_slot,
                                  const int32_t* scan_widx, const float* scan_wval, int scan_nq, int64_t scan_n_videos, int scan_K,
                                  double* kept, int32_t* n_kept, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------ library maintenance (additive in ABI 8)
+ * Compacting a library in place and resizing it into another arena.  run_on_video/cone_localizator.py:121-221 keeps no state
+ * between calls; a library keeps the video half's results, per clip one row in each of four planes (vid_norm, adapted or
+ * adapted_bf16, vproj, and qkv_vid unless the handle is a long-window handle).  A row's bits do not depend on where it lives,
+ * so moving a video is a pure copy.  CONTRACT: the moved rows carry the bits they had -- every (video, query) pair answers
+ * with the bits of predict_moment before and after, once the caller names the video's new rows.  WHO owns which rows stays the
+ * caller's business (cone_amd/library.py plans the moves: compaction_moves, plan_steps).  CONE_SESSION_BF16 libraries and
+ * long-window handles are supported; CONE_SESSION_CERTIFIED libraries are refused by name. */
+
+/* Moves rows of the resident video halves (run_on_video/cone_localizator.py:121-221: nothing of it runs again).  The moves come
+ * as a DEVICE table: move i copies rows [mv_src[i], mv_src[i] + n_i) of every present plane of src to rows [mv_dst[i], ...) of
+ * the same plane of dst, n_i = mv_off[i + 1] - mv_off[i]; mv_off (n_moves + 1) int64 = the exclusive prefix sums, total_rows =
+ * mv_off[n_moves] (the host knows it).  The moves laid end to end are the flat row list; ONE call moves its rows
+ * [row_begin, row_end) and may begin and end inside a move.
+ *   stage == NULL: direct, ONE launch, src rows to dst rows.  The caller guarantees that the call's dst rows and src rows are
+ *     disjoint (another arena, or disjoint sets in the same one).
+ *   stage != NULL: staged, TWO launches of the same kernel body: the call's rows are gathered into stage, packed plane by
+ *     plane, then scattered to dst; stream order is the only synchronisation, so ANY overlap between the call's src and dst
+ *     rows is fine.  stage: 256-B aligned, >= cone_library_move_stage_bytes(lib, row_end - row_begin) = the sum over the present
+ *     planes of row bytes * n_rows, each plane rounded up to 256 B.
+ * Nothing but the listed dst rows (and stage) is written; vacated src rows keep their content.  A move whose src range leaves
+ * [0, src->capacity) or whose dst range leaves [0, dst->capacity) is skipped whole on the device: not read, not written.
+ * Nothing is allocated, nothing read back, no atomics: both forms can be captured in a graph.
+ * Refused by name ("library_move: "), from host values first, before any pointer or the handle is looked at: n_moves < 1;
+ * total_rows < n_moves; row_begin / row_end outside 0 <= begin < end <= total_rows; a CONE_SESSION_CERTIFIED library; then
+ * null arguments, total_rows > src->capacity, src and dst that differ in model, flags, v_dim, hidden_dim or in which planes are
+ * present, another handle than the libraries', a misaligned or short stage. */
+size_t cone_library_move_stage_bytes(const cone_library* lib, int64_t n_rows);
+int cone_library_move_rows(const cone_model* m, const cone_library* src, const cone_library* dst, const int64_t* mv_src,
+                           const int64_t* mv_dst, const int64_t* mv_off, int64_t n_moves, int64_t total_rows, int64_t row_begin,
+                           int64_t row_end, void* stage, size_t stage_bytes, void* stream);
 
 /* -------------------------------------------------------------------- metrics on the device
  * Recall@K / IoU counts from the kept rows (layout of cone_fuse_nms: rows (nq, max_after, 5) fp64 [st, ed, ...],
