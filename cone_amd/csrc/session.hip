@@ -69,7 +69,8 @@ static IndexWs index_ws(const cone_model* m, int64_t n) {
 
 // The video half on n rows: the ONE launcher chain behind cone_session_index (the whole arena, row 0) and cone_library_add
 // (rows [row0, row0 + n) of a library's arena: the caller passes the regions already offset).  Every launcher works row by
-// row, so a row's bits depend on the launch's n alone, never on where the rows live.
+// row: a row's bits depend neither on where the rows live nor on the launch's n (every form launch_gemm picks by the row
+// bound runs the same chains per row; tests/test_library_ingest_gpu.py pins it at the forms' thresholds).
 struct IndexRows { float* vid_norm; float* adapted; uint16_t* adapted_bf16; float* err; float* vproj; float* qkv_vid; };
 static int index_rows(const cone_model* m, const cone_model_dims& d, int flags, const float* raw, int64_t n, const IndexRows& o,
                       char* s, const IndexWs& w, void* stream) {

@@ -25,12 +25,21 @@ row in four or five planes, a row's bits do not depend on where it lives, so ``c
 (csrc/library_move.hip) copies the rows and every answer keeps its bits.  ``compaction_moves`` lays the videos out in arena
 order (ids, rankings and their tie order do not change); ``plan_steps`` cuts the moves into calls that never overwrite a row a
 later call has yet to read -- staged through a buffer where a call's source and destination rows overlap, direct where they
-cannot.  Out of scope here: certified window ranking, growing a video in place, indexing several videos in one launch (a
-row's bits depend on its launch's row count: both would break ``== predict_moment``), capturing the call in a graph.
+cannot.
+
+Ingest.  Every launcher of the video half works row by row and a row's bits do not depend on its launch's row count either
+(every form of the row GEMM runs the same chains per row; tests/test_library_ingest_gpu.py pins it at the forms' thresholds),
+so rows indexed in ANY launch equal the rows of the video's own launch.  ``add_many`` therefore indexes a list of videos with
+one upload and one ``cone_library_add`` per run of adjacent ranges (``plan_runs``) and leaves exactly the state sequential
+``add`` calls leave; ``extend`` appends clips to a resident video -- in place when the rows behind it are free
+(``RowRanges.take_at``), else by moving it into a hole that holds all of it (``plan_extend``) -- indexing only the new rows;
+``trim`` drops a video's oldest clips without a launch.  ``extend`` + ``trim`` are the sliding window of a live recording.
+Out of scope here: certified window ranking, headroom reserved behind a video, capturing the call in a graph.
 """
 from __future__ import annotations
 
 import ctypes as C
+import operator
 
 import torch
 
@@ -69,6 +78,20 @@ class RowRanges:
                 return start
         raise ValueError(f"no free range of {n} clips: the largest free hole has {self.largest} "
                          f"({self.free} of {self.capacity} clips are free; a library does not compact)")
+
+    def take_at(self, start: int, n: int) -> int:
+        """Claims exactly rows ``[start, start + n)`` when they lie inside ONE hole (the hole is split around them); raises
+        ``ValueError`` and changes nothing otherwise."""
+        start, n = int(start), int(n)
+        if n < 1:
+            raise ValueError(f"a range needs at least one row, got {n}")
+        for i, (h0, length) in enumerate(self.holes):
+            if h0 <= start and start + n <= h0 + length:
+                left = [(h0, start - h0)] if start > h0 else []
+                right = [(start + n, h0 + length - start - n)] if start + n < h0 + length else []
+                self.holes[i:i + 1] = left + right
+                return start
+        raise ValueError(f"rows [{start}, {start + n}) do not lie inside one free hole")
 
     def release(self, start: int, n: int):
         i = 0
@@ -137,6 +160,41 @@ def plan_steps(moves, stage_rows: int):
         steps.append((p, p + n, staged))
         p += n
     return steps
+
+
+def plan_runs(placements):
+    """The launches of one ``add_many``: ``placements`` = ``[(row0, n), ...]`` of the call's videos in LIST order.  Consecutive
+    videos whose ranges are adjacent and ascending (``row0`` of the next = the end of the one before) become one run.  Returns
+    ``[(row0, n, first, end), ...]``: videos ``[first, end)`` of the list lie back to back in the ``n`` rows from ``row0``, as
+    their raw rows do in the list's concatenation.  A fresh or compact library yields one run.  Pure Python, no GPU."""
+    runs = []
+    for i, (row0, n) in enumerate(placements):
+        row0, n = int(row0), int(n)
+        if n < 1 or row0 < 0:
+            raise ValueError("plan_runs: a video needs row0 >= 0 and at least one clip")
+        if runs and runs[-1][0] + runs[-1][1] == row0:
+            r = runs[-1]
+            runs[-1] = (r[0], r[1] + n, r[2], i + 1)
+        else:
+            runs.append((row0, n, i, i + 1))
+    return runs
+
+
+def plan_extend(rows: RowRanges, row0: int, n: int, m: int):
+    """Where a resident video ``(row0, n)`` grows by ``m`` clips, decided on the free list alone (``rows`` is not changed):
+    ``("in_place", row0)`` when the ``m`` rows right behind it lie in one hole; else ``("relocate", dst)`` with ``dst`` the first
+    hole that holds ``n + m`` rows (first-fit, as ``take`` would); else ``("no_room", None)``.  Pure Python, no GPU."""
+    row0, n, m = int(row0), int(n), int(m)
+    if n < 1 or m < 1:
+        raise ValueError(f"plan_extend: a video of {n} clips cannot grow by {m}")
+    end = row0 + n
+    for h0, length in rows.holes:
+        if h0 <= end and end + m <= h0 + length:        # (holes never overlap an owned row: h0 == end)
+            return "in_place", row0
+    for h0, length in rows.holes:
+        if length >= n + m:
+            return "relocate", h0
+    return "no_room", None
 
 
 def plan_calls(video_of, k_of, limit: int = MAX_QUERIES):
@@ -285,6 +343,156 @@ class VideoLibrary:
         del self._videos[vid_id]
         self._scan_cache = None
         self._rows.release(row0, n)
+
+    # ---- ingest: many videos a call, growing and trimming resident ones --------------------------
+    def _checked(self, who, feats):
+        """The checks of ``add`` on the tensor as the caller holds it (nothing is uploaded for a refusal); returns its clips."""
+        a, m = self._loc.args, self._loc.localizator
+        try:
+            if not hasattr(feats, "dim") or feats.dim() != 2 or feats.shape[0] < 1:
+                raise ValueError(f"video_feats must be (clips >= 1, dim), got {tuple(getattr(feats, 'shape', ()))}")
+            m._check_dim(feats, a.v_appear_feat_dim, "appearance clip features")
+            m._check_dim(feats, a.v_motion_feat_dim, "motion clip features")
+        except ValueError as e:
+            raise ValueError(f"{who}: {e}") from None
+        return int(feats.shape[0])
+
+    def _k(self, n):
+        a = self._loc.args
+        return min(int(a.topk_window), ops.num_windows(n, a.max_v_l))
+
+    def _index(self, raw, launches):
+        """``launches`` = ``[(arena row, first row of raw, rows), ...]``: one ``cone_library_add`` each, on one workspace sized for
+        the largest (the launches follow each other on one stream)."""
+        lib, h = _lib.load(), self._loc.localizator._h()
+        n_ws = max(lib.cone_library_add_workspace(h, n) for n in {n for _, _, n in launches})
+        ws = torch.empty(max(n_ws, 1), dtype=torch.uint8, device=raw.device)
+        base, row_bytes = _lib.ptr(raw, torch.float32).value, raw.shape[1] * 4
+        for row0, at, n in launches:
+            _lib.check(lib.cone_library_add(h, C.byref(self._cl), row0, C.c_void_p(base + at * row_bytes), n, _lib.ptr(ws), ws.numel(),
+                                            _lib.stream()))
+
+    def _place(self, lens):
+        """Sequential first-fit of the call's videos; on a failure every range taken so far is released again."""
+        taken = []
+        try:
+            for n in lens:
+                taken.append((self._rows.take(n), n))
+        except ValueError as e:
+            for r in reversed(taken):
+                self._rows.release(*r)
+            raise ValueError(f"add_many: video {len(taken)}: {e}") from None
+        return taken
+
+    @torch.no_grad()
+    def add_many(self, videos, compact=False, chunk_clips=262144):
+        """Indexes a list of videos and returns their ids: the library ends in exactly the state ``[lib.add(v) for v in videos]``
+        leaves it in -- consecutive ids, the same first-fit ``(row0, n, K)`` per id, the same holes, the same bits in every
+        plane -- with ONE concatenation and ONE upload of the raw rows and one ``cone_library_add`` per run of ``plan_runs``
+        (one run on a fresh or compact library), cut at ``chunk_clips`` rows so that the workspace stays bounded: a row's bits do
+        not depend on the launch it is indexed in.  Every video is checked before any row is taken and before any GPU work;
+        all or nothing: when some video finds no hole, every range taken for the call is released and the ``ValueError`` names
+        that video's index -- unless ``compact=True`` and ``free_clips`` holds them all: then the library compacts once and places
+        them behind the resident videos.  An empty list returns ``[]`` and launches nothing."""
+        videos = list(videos)
+        lens = [self._checked(f"add_many: video {i}", v) for i, v in enumerate(videos)]
+        if int(chunk_clips) < 1:
+            raise ValueError(f"add_many: chunk_clips={chunk_clips} < 1")
+        if not videos:
+            return []
+        self._check_live()
+        try:
+            placed = self._place(lens)
+        except ValueError:
+            if not (compact and sum(lens) <= self._rows.free):
+                raise
+            self.compact()
+            placed = self._place(lens)              # (one hole at the end that holds them all)
+        try:
+            dev, chunk = self._loc.device, int(chunk_clips)
+            parts = [v.to(torch.float32) for v in videos]
+            if len({p.device for p in parts}) > 1:
+                parts = [p.to(dev) for p in parts]
+            raw = (parts[0] if len(parts) == 1 else torch.cat(parts)).to(dev).contiguous()        # the call's one upload
+            launches, at = [], 0
+            for row0, n, _, _ in plan_runs(placed):
+                launches += [(row0 + c, at + c, min(chunk, n - c)) for c in range(0, n, chunk)]
+                at += n
+            self._index(raw, launches)
+        except Exception:
+            for r in reversed(placed):
+                self._rows.release(*r)
+            raise
+        self._scan_cache = None
+        ids = list(range(self._next_id, self._next_id + len(videos)))
+        self._next_id += len(videos)
+        for vid_id, (row0, n) in zip(ids, placed):
+            self._videos[vid_id] = (row0, n, self._k(n))
+        return ids
+
+    @torch.no_grad()
+    def extend(self, vid_id, more_feats, compact=False) -> int:
+        """Appends the clips ``more_feats`` (clips, dim) to the resident video ``vid_id`` and returns its new clip count; the id
+        stays, and every later answer for it ``==`` ``predict_moment(torch.cat([video, more_feats]), query)``.  ``plan_extend``
+        decides where.  IN PLACE when the rows right behind the video are free: one ``cone_library_add`` of the new rows, nothing
+        else is touched.  Otherwise the video RELOCATES into the first hole that holds all of it: one direct
+        ``cone_library_move_rows`` copies the resident rows (the hole was free: source and destination are disjoint), the new
+        rows are indexed behind them, the old range becomes free.  A relocation changes the arena order and with it the order
+        ``rank_videos`` breaks exact ties in.  ``compact=True`` compacts first when no hole fits but the free clips suffice.
+        Queries enqueued earlier on the stream have read their rows (``remove``'s rule).  Unknown ids, a closed library, a wrong
+        width, no clips and no room are refused before any GPU work, and the free list is then unchanged."""
+        row0, n, _ = self._video(vid_id)
+        m = self._checked("extend", more_feats)
+        self._check_live()
+        where, dst = plan_extend(self._rows, row0, n, m)
+        if where == "no_room":
+            last = row0 == max(v[0] for v in self._videos.values())         # behind the last video a compaction leaves every free clip
+            if compact and self._rows.free >= (m if last else n + m):
+                self.compact()
+                row0 = self._videos[vid_id][0]
+                where, dst = plan_extend(self._rows, row0, n, m)
+            else:
+                try:
+                    self._rows.take(n + m)              # (raises: take's message, the free list unchanged)
+                except ValueError as e:
+                    raise ValueError(f"extend: the {m} rows behind video {vid_id!r} are not free and {e}") from None
+        more = more_feats.to(self._loc.device, torch.float32).contiguous()
+        if where == "in_place":
+            self._rows.take_at(row0 + n, m)
+            try:
+                self._index(more, [(row0 + n, 0, m)])
+            except Exception:
+                self._rows.release(row0 + n, m)
+                raise
+        else:
+            dst = self._rows.take(n + m)                # (first-fit: the hole plan_extend named)
+            try:
+                self._move(self._cl, self._cl, [(row0, dst, n)], [(0, n, False)], None)
+                self._index(more, [(dst + n, 0, m)])
+            except Exception:
+                self._rows.release(dst, n + m)
+                raise
+            self._rows.release(row0, n)
+        self._scan_cache = None
+        self._videos[vid_id] = (dst, n + m, self._k(n + m))
+        return n + m
+
+    def trim(self, vid_id, n_front) -> int:
+        """Drops the video's oldest ``n_front`` clips and returns the clips that remain: their rows become free, nothing is
+        launched (``remove``'s stream rule), and every later answer ``==`` ``predict_moment(video[n_front:], query)`` -- seconds
+        count from the new first clip.  ``0 <= n_front < clips`` (0 changes nothing; dropping every clip is ``remove``)."""
+        row0, n, _ = self._video(vid_id)
+        try:
+            n_front = operator.index(n_front)
+        except TypeError:
+            raise ValueError(f"trim: n_front must be an integer, got {n_front!r}") from None
+        if not 0 <= n_front < n:
+            raise ValueError(f"trim: n_front={n_front} not in [0, {n}) for video {vid_id!r} (remove drops a whole video)")
+        if n_front:
+            self._rows.release(row0, n_front)
+            self._videos[vid_id] = (row0 + n_front, n - n_front, self._k(n - n_front))
+            self._scan_cache = None
+        return n - n_front
 
     # ---- maintenance ---------------------------------------------------------------------------
     @property

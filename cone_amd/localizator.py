@@ -134,8 +134,10 @@ class CONELocalizator:
         (``cone_amd.library.VideoLibrary``).  ``lib.add(video_feats)`` indexes a video into free rows and returns its id,
         ``lib.remove(id)`` frees them; ``lib.predict_moments([(id, text_feats), ...])`` answers pairs on any mix of the videos in
         one C call per 64 pairs (``cone_library_localize``) and one read-back, each answer ``==`` this class's ``predict_moment``
-        on that video and query.  With ``prefilter_bf16`` the library keeps bf16 adapted rows.  No certified ranking, no growth,
-        no compaction."""
+        on that video and query.  With ``prefilter_bf16`` the library keeps bf16 adapted rows.
+        ``lib.add_many([video_feats, ...])`` indexes a list of videos with one upload, ``lib.extend(id, more_feats)`` appends
+        clips to a resident video and ``lib.trim(id, n_front)`` drops its oldest ones; ``lib.compact()`` / ``lib.resize()``
+        close the holes.  No certified ranking."""
         from .library import VideoLibrary
         return VideoLibrary(self, capacity_clips)
 

@@ -601,6 +601,9 @@ int cone_library_open(const cone_model* m, int64_t capacity, int flags, void* ar
  * n_rows rows -- cone_l2_normalize_rows, cone_adapter_norm / cone_adapter_norm_bf16 with renorm == 0, cone_project_tokens of
  * the video side, cone_layer0_project unless the handle is a long-window handle.  Nothing outside those rows is written.
  * raw_clips (n_rows, v_dim) fp32; ws >= cone_library_add_workspace, free again when the call's work is done.
+ * A row's bits depend on its clip alone, not on n_rows or on the row's place in the call (tests/test_library_ingest_gpu.py), so
+ * a caller may index the rows of several adjacent videos, or the new clips behind a resident video, in one call
+ * (cone_amd/library.py: add_many, extend).
  * Refused by name: null arguments, another handle than the library's, row0 < 0, n_rows < 1, row0 + n_rows > capacity, a
  * misaligned or short workspace. */
 size_t cone_library_add_workspace(const cone_model* m, int64_t n_rows);
