@@ -230,6 +230,20 @@ _SIGNATURES = {
     # stage_bytes, stream)
     "cone_library_move_rows": (C.c_int, [C.c_void_p, C.POINTER(Library), C.POINTER(Library)] + [C.c_void_p] * 3 + [C.c_int64] * 4
                                + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    # library window budgets (additive in ABI 8): the W best windows of a query over a scan's lists, a window count per pair
+    "cone_library_budget_workspace": (C.c_size_t, [C.c_int, C.c_int64, C.c_int, C.c_int]),
+    # cone_library_budget(wval (device), nq, n_videos, scan_K, W, n_pairs, pair_slot, pair_k, pair_best (device), ws, ws_bytes, stream)
+    "cone_library_budget": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 4
+                            + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cone_library_localize_ragged_workspace": (C.c_size_t, [C.c_void_p, C.POINTER(Library)] + [C.POINTER(C.c_int32)] * 3
+                                               + [C.c_int, C.POINTER(C.c_int32), C.POINTER(SessionParams), C.c_int]),
+    # cone_library_localize_ragged(<cone_library_localize_ranked's, with pair_k (host) in place of K>): pair_query .. scan_wval all
+    # NULL = the call's own stage A
+    "cone_library_localize_ragged": (C.c_int, [C.c_void_p, C.POINTER(Library), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p,
+                                               C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.POINTER(C.c_int32),
+                                               C.POINTER(SessionParams), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p,
+                                               C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                               C.c_void_p]),
     # cone_test_gemm(A, A2, a2_mod, W, bias, R, ln_g, ln_b, C, C2, ADD, M, N, K, flags, stream)
     "cone_test_gemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,

@@ -1,11 +1,13 @@
 // Video sessions (include/cone_hip.h, "video sessions"): one resident video, indexed once, answering batches of queries.
 // Video libraries ("video libraries"): many videos in the rows of one arena, one call for queries on any mix of them.
 // Library search ("library search"): the query half on the window lists of a cone_library_scan (csrc/prefilter.hip).
+// Library window budgets ("library window budgets"): the query half with a window count per pair (cone_library_localize_ragged;
+// its own layout kernel and a gather of every pair's prefix -- the budget itself is csrc/library_budget.hip).
 //
 // Nothing is computed here.  cone_session_index / cone_library_add and cone_session_localize / cone_library_localize only
 // SEQUENCE the library's own extern "C" launchers -- the calls cone_amd/localizator.py issues one by one through ctypes for
-// run_on_video/cone_localizator.py:121-221 -- and carve their operands out of the caller's arena / workspace.  The two kernels
-// of this file (one body) write a call's index metadata (what the localizer keeps per shape in _const) from lengths, row
+// run_on_video/cone_localizator.py:121-221 -- and carve their operands out of the caller's arena / workspace.  The layout kernels
+// of this file write a call's index metadata (what the localizer keeps per shape in _const) from lengths, row
 // offsets and clip counts that travel as kernel arguments.
 #include "common.h"
 
@@ -154,6 +156,47 @@ __global__ __launch_bounds__(256) void library_layout_kernel(QueryPairs P, int n
                 tok_len, tok_idx, q_ctx_l, q_vid_off, batch_pad, full_w, n_valid);
 }
 
+// The ragged form (cone_library_localize_ragged): pair q brings its own window count k[q] <= Kmax.  What library_layout_kernel
+// writes, except that the window rows are the concatenation of the pairs' k[q] rows: row_q / row_slot / full_w [0, sum k),
+// n_valid[q] = k[q] Nq, cand_off[q] = (rows before pair q) Nq.  One workgroup, one writer per element.
+struct RaggedK { int32_t k[CONE_SESSION_MAX_QUERIES]; };
+__global__ __launch_bounds__(256) void library_ragged_layout_kernel(QueryPairs P, RaggedK R, int nq, int max_q_l, int Kmax, int Nq,
+                                                                    int W, int* __restrict__ tok_off, int* __restrict__ tok_len,
+                                                                    int* __restrict__ tok_idx, int* __restrict__ q_ctx_l,
+                                                                    int* __restrict__ q_vid_off, int* __restrict__ batch_pad,
+                                                                    int* __restrict__ full_w, int* __restrict__ n_valid,
+                                                                    int* __restrict__ row_q, int* __restrict__ row_slot,
+                                                                    int64_t* __restrict__ cand_off) {
+    __shared__ int off[CONE_SESSION_MAX_QUERIES + 1];       // exclusive prefix sums of the token lengths
+    __shared__ int woff[CONE_SESSION_MAX_QUERIES + 1];      // ... of the window counts
+    __shared__ int len[CONE_SESSION_MAX_QUERIES];
+    __shared__ int kq[CONE_SESSION_MAX_QUERIES];
+    const int t = threadIdx.x;
+    if (t == 0) {
+        int a = 0, b = 0;
+        for (int q = 0; q < nq; ++q) {
+            off[q] = a; woff[q] = b; len[q] = P.len[q]; kq[q] = R.k[q];
+            a += P.len[q]; b += R.k[q];
+        }
+        off[nq] = a; woff[nq] = b;
+    }
+    __syncthreads();
+    for (int q = t; q < nq; q += blockDim.x) {
+        tok_off[q] = off[q]; tok_len[q] = len[q];
+        q_ctx_l[q] = P.ctx_l[q]; q_vid_off[q] = P.row0[q]; batch_pad[q] = W;
+        n_valid[q] = kq[q] * Nq; cand_off[q] = (int64_t)woff[q] * Nq;
+    }
+    if (t == 0) tok_off[nq] = off[nq];
+    for (int i = t; i < nq * Kmax; i += blockDim.x) {
+        const int q = i / Kmax, j = i - q * Kmax;
+        if (j < kq[q]) { const int b = woff[q] + j; row_q[b] = q; row_slot[b] = j; full_w[b] = W; }
+    }
+    for (int i = t; i < nq * max_q_l; i += blockDim.x) {
+        const int q = i / max_q_l, j = i - q * max_q_l;
+        if (j < len[q]) tok_idx[off[q] + j] = j;
+    }
+}
+
 static int check_queries(const char* who, const int32_t* tok_len, int nq, int max_q_l, int64_t* total) {
     CONE_REQUIRE(tok_len, "%s: null argument", who);
     CONE_REQUIRE(nq >= 1 && nq <= CONE_SESSION_MAX_QUERIES, "%s: nq=%d not in [1, %d]", who, nq, CONE_SESSION_MAX_QUERIES);
@@ -187,8 +230,22 @@ static int check_pairs(const char* who, const int32_t* q_row0, const int32_t* q_
     return 0;
 }
 
+// The window counts of a ragged call (after check_pairs): pair p has at least pair_k[p] windows.  Kmax = their maximum.
+static int check_ragged(const char* who, const int32_t* pair_k, const int32_t* q_ctx_l, int nq, int max_v_l, int* Kmax) {
+    CONE_REQUIRE(pair_k, "%s: null argument", who);
+    int m = 0;
+    for (int p = 0; p < nq; ++p) {
+        const int64_t nw = cone_num_windows(q_ctx_l[p], max_v_l);
+        CONE_REQUIRE(pair_k[p] >= 1 && pair_k[p] <= nw && pair_k[p] <= 256, "%s: pair_k[%d]=%d not in [1, min(num_window=%lld, 256)]", who, p,
+                     pair_k[p], (long long)nw);
+        m = pair_k[p] > m ? pair_k[p] : m;
+    }
+    *Kmax = m;
+    return 0;
+}
+
 // Consecutive queries of one video: one stage A.  A session is one run.
-struct Run { int q0, n; int64_t row0, ctx_l, nw; size_t score_off; };
+struct Run { int q0, n; int64_t row0, ctx_l, nw; size_t score_off; int k; size_t st_off; };     // (k, st_off: a ragged call's)
 
 // Every buffer and every launcher's scratch of one cone_session_localize / cone_library_localize call: the ONE function
 // behind the workspace-size entries and the entries themselves.  Each take() is a region of its own.
@@ -197,6 +254,7 @@ struct LocalizeLayout {
     int n_runs;
     size_t tok_off, tok_len, tok_idx, q_ctx_l, q_vid_off, batch_pad, full_w, n_valid;      // int32 metadata
     size_t tok_norm, scores, widx, wval, cert, wt, tproj, qkv_txt, txt_pos, txt_pos_qk, logits, spans, match, rows, nms_idx;
+    size_t row_q, row_slot, cand_off, st_idx, st_val;       // a ragged call's: the row maps, the row offsets, the runs' own lists
     size_t pf_ws, pf_bytes, topk_ws, topk_bytes, proj_ws, proj_bytes, l0_ws, l0_bytes, fwd_ws, fwd_bytes, match_ws, match_bytes;
     size_t total;
     int64_t T, nw;
@@ -206,7 +264,8 @@ struct LocalizeLayout {
 // rows: the session's ctx_l, or the library's capacity; q_row0 / q_ctx_l: NULL for a session (one run over all of its rows).
 static int localize_layout(const char* who, const char* what, const cone_model* m, const cone_model_dims& d, const Resident* ses,
                            int64_t rows, const int32_t* q_row0, const int32_t* q_ctx_l, const int32_t* tok_len, int nq, int K,
-                           int n_cand, const cone_session_params* p, LocalizeLayout* out, bool ranked = false) {
+                           int n_cand, const cone_session_params* p, LocalizeLayout* out, bool ranked = false,
+                           const int32_t* pair_k = nullptr) {      // pair_k: a ragged call (K = their maximum, check_ragged's)
     CONE_REQUIRE(m && ses && p, "%s: null argument", who);
     CONE_REQUIRE(ses->model == m, "%s: the %s was indexed with another handle", who, what);
     CONE_REQUIRE(flags_ok(ses->flags), "%s: bad %s flags %d", who, what, ses->flags);
@@ -221,7 +280,7 @@ static int localize_layout(const char* who, const char* what, const cone_model* 
     if (q_row0) {       // (library_precheck has vetted the pairs, K and the capacity)
         for (int q = 0; q < nq; ++q) {
             if (q == 0 || q_row0[q] != q_row0[q - 1] || q_ctx_l[q] != q_ctx_l[q - 1])
-                L.runs[L.n_runs++] = Run{q, 0, q_row0[q], q_ctx_l[q], cone_num_windows(q_ctx_l[q], p->max_v_l), n_scores};
+                L.runs[L.n_runs++] = Run{q, 0, q_row0[q], q_ctx_l[q], cone_num_windows(q_ctx_l[q], p->max_v_l), n_scores, 0, 0};
             Run& r = L.runs[L.n_runs - 1];
             r.n += 1;
             n_scores += (size_t)r.nw;
@@ -230,11 +289,15 @@ static int localize_layout(const char* who, const char* what, const cone_model* 
         CONE_REQUIRE(rows >= 1 && rows < (1ll << 31), "%s: ctx_l=%lld not in [1, 2^31)", who, (long long)rows);
         L.nw = cone_num_windows(rows, p->max_v_l);
         CONE_REQUIRE(K >= 1 && K <= L.nw && K <= 256, "%s: K=%d not in [1, min(num_window=%lld, 256)]", who, K, (long long)L.nw);
-        L.runs[L.n_runs++] = Run{0, nq, 0, rows, L.nw, 0};
+        L.runs[L.n_runs++] = Run{0, nq, 0, rows, L.nw, 0, 0, 0};
         n_scores = (size_t)nq * L.nw;
     }
     CONE_REQUIRE(n_cand >= 0, "%s: n_cand=%d", who, n_cand);
     L.B = nq * K;
+    if (pair_k) {
+        L.B = 0;
+        for (int q = 0; q < nq; ++q) L.B += pair_k[q];
+    }
     const size_t T = (size_t)L.T, B = (size_t)L.B, Nq = (size_t)d.num_queries, dh = (size_t)d.hidden_dim;
     L.use_l0 = ses->qkv_vid != nullptr && !d.long_windows;
     L.use_txt_pos = L.use_l0 && d.txt_pos;
@@ -242,9 +305,21 @@ static int localize_layout(const char* who, const char* what, const cone_model* 
     L.tok_off = r.take((nq + 1) * 4); L.tok_len = r.take(nq * 4); L.tok_idx = r.take(T * 4);
     L.q_ctx_l = r.take(nq * 4); L.q_vid_off = r.take(nq * 4); L.batch_pad = r.take(nq * 4);
     L.full_w = r.take(B * 4); L.n_valid = r.take(nq * 4);
+    if (pair_k) { L.row_q = r.take(B * 4); L.row_slot = r.take(B * 4); L.cand_off = r.take(nq * 8); }
     L.tok_norm = r.take(T * d.t_dim * 4);
     if (!cert && !ranked) L.scores = r.take(n_scores * 4);        // (ranked: the lists come from a scan -- no stage A here)
-    L.widx = r.take(B * 4); L.wval = r.take(B * 4); L.cert = r.take(nq * 4);
+    const size_t n_list = pair_k ? (size_t)nq * K : B;            // the call's (nq, K) window list
+    L.widx = r.take(n_list * 4); L.wval = r.take(n_list * 4); L.cert = r.take(nq * 4);
+    if (pair_k && !ranked) {        // every run ranks its video at the largest count among its pairs; the pairs take prefixes
+        size_t at = 0;
+        for (int i = 0; i < L.n_runs; ++i) {
+            Run& u = L.runs[i];
+            for (int q = u.q0; q < u.q0 + u.n; ++q) u.k = pair_k[q] > u.k ? pair_k[q] : u.k;
+            u.st_off = at;
+            at += (size_t)u.n * u.k;
+        }
+        L.st_idx = r.take(at * 4); L.st_val = r.take(at * 4);
+    }
     L.wt = r.take(7 * align_up(B * 4, SES_ALIGN));
     L.tproj = r.take(T * dh * 4);
     if (L.use_l0) L.qkv_txt = r.take(T * 3 * dh * 4);
@@ -262,7 +337,7 @@ static int localize_layout(const char* who, const char* what, const cone_model* 
             const int n = u.n < 4 ? u.n : 4;
             const size_t pf = ses->flags & CONE_SESSION_BF16 ? cone_prefilter_scores_bf16_workspace(u.ctx_l, n, p->max_v_l)
                                                              : cone_prefilter_scores_workspace(u.ctx_l, n, p->max_v_l);
-            const size_t tk = cone_topk_windows_workspace(u.n, u.nw, K);
+            const size_t tk = cone_topk_windows_workspace(u.n, u.nw, pair_k ? u.k : K);
             L.pf_bytes = pf > L.pf_bytes ? pf : L.pf_bytes;
             L.topk_bytes = tk > L.topk_bytes ? tk : L.topk_bytes;
         }
@@ -386,12 +461,31 @@ __global__ __launch_bounds__(256) void library_gather_lists_kernel(RankedPairs P
     wval[i] = scan_wval[src];
 }
 
+// A ragged call's lists: pair p's first k[p] entries of the list that starts at element off[p] of (src_idx, src_val) -- a scan's
+// lists, or the lists the call's own runs ranked -- -> row p of the call's (nq, Kmax) window list; the rest of the row is
+// (-1, -inf) and never read.  One writer per element, every element written.
+struct RaggedSrc { int64_t off[CONE_SESSION_MAX_QUERIES]; int32_t k[CONE_SESSION_MAX_QUERIES]; };
+__global__ __launch_bounds__(256) void library_gather_ragged_kernel(RaggedSrc R, int nq, int Kmax, const int32_t* __restrict__ src_idx,
+                                                                    const float* __restrict__ src_val, int32_t* __restrict__ widx,
+                                                                    float* __restrict__ wval) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= nq * Kmax) return;
+    const int p = i / Kmax, j = i - p * Kmax;
+    const bool in = j < R.k[p];
+    widx[i] = in ? src_idx[R.off[p] + j] : -1;
+    wval[i] = in ? src_val[R.off[p] + j] : -INFINITY;
+}
+
 // The query half for both kinds of resident rows: q_row0 / q_ctx_l == NULL is a session (one video at row 0, `rows` clips),
 // otherwise a library call (every query names its video's rows inside an arena of `rows`).  Nothing differs after stage A.
+// pair_k != NULL is a ragged library call (K = the largest count): pair q owns pair_k[q] window rows, not K -- its own layout
+// kernel, a gather of every pair's prefix, then the row form of cone_window_table and the offset form of cone_fuse_nms.  The
+// uniform calls run the launches they always ran.
 static int localize(const char* who, const cone_model* m, const cone_model_dims& d, const Resident& S, int64_t rows,
                     const LocalizeLayout& L, const int32_t* q_row0, const int32_t* q_ctx_l, const float* tok, const int32_t* tok_len,
                     int nq, const float* cls, int K, int n_cand, const cone_session_params& P, double* kept, int32_t* n_kept,
-                    int32_t* certified, char* w, void* stream, const RankedLists* lists = nullptr) {
+                    int32_t* certified, char* w, void* stream, const RankedLists* lists = nullptr,
+                    const int32_t* pair_k = nullptr) {
     auto I = [&](size_t at) { return (int32_t*)(w + at); };
     auto F = [&](size_t at) { return (float*)(w + at); };
     auto scratch = [&](size_t at, size_t bytes) { return bytes ? (void*)(w + at) : nullptr; };
@@ -400,7 +494,15 @@ static int localize(const char* who, const cone_model* m, const cone_model_dims&
     int32_t *vid_row0 = I(L.wt), *vid_len = I(L.wt + col), *video_start = I(L.wt + 2 * col), *pad_len = I(L.wt + 3 * col),
             *txt_row0 = I(L.wt + 4 * col), *txt_len = I(L.wt + 5 * col), *cls_row = I(L.wt + 6 * col);
 
-    if (q_row0)
+    if (pair_k) {
+        QueryPairs Q{};
+        RaggedK R{};
+        for (int q = 0; q < nq; ++q) { Q.len[q] = tok_len[q]; Q.row0[q] = q_row0[q]; Q.ctx_l[q] = q_ctx_l[q]; R.k[q] = pair_k[q]; }
+        hipLaunchKernelGGL(library_ragged_layout_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, Q, R, nq, P.max_q_l, K, Nq, W,
+                           I(L.tok_off), I(L.tok_len), I(L.tok_idx), I(L.q_ctx_l), I(L.q_vid_off), I(L.batch_pad), I(L.full_w),
+                           I(L.n_valid), I(L.row_q), I(L.row_slot), (int64_t*)(w + L.cand_off));
+        CONE_LAUNCH_CHECK();
+    } else if (q_row0)
         RUN(cone_library_query_layout(tok_len, q_row0, q_ctx_l, nq, P.max_q_l, K, Nq, W, I(L.tok_off), I(L.tok_len), I(L.tok_idx),
                                       I(L.q_ctx_l), I(L.q_vid_off), I(L.batch_pad), I(L.full_w), I(L.n_valid), stream));
     else
@@ -408,14 +510,14 @@ static int localize(const char* who, const cone_model* m, const cone_model_dims&
                                       I(L.q_vid_off), I(L.batch_pad), I(L.full_w), I(L.n_valid), stream));
     RUN(cone_l2_normalize_rows(tok, L.T, d.t_dim, 1e-5f, 1, F(L.tok_norm), stream));                          // :133
     // stage A (:83-100, stable tie order): the raw cls vectors against the adapted rows
-    if (lists) {        // a scan has ranked the windows (cone_library_scan: the same lists, bit for bit): copy each pair's
+    if (lists && !pair_k) {     // a scan has ranked the windows (cone_library_scan: the same lists, bit for bit): copy each pair's
         hipLaunchKernelGGL(library_gather_lists_kernel, dim3((unsigned)((nq * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                            lists->pairs, nq, K, lists->n_videos, lists->scan_K, lists->widx, lists->wval, I(L.widx), F(L.wval));
         CONE_LAUNCH_CHECK();
     } else if (S.flags & CONE_SESSION_CERTIFIED) {
         RUN(cone_prefilter_topk_certified(S.adapted, S.adapted_bf16, rows, dv, cls, nq, W, Sl, K, n_cand, S.err, I(L.widx),
                                           F(L.wval), certified ? certified : I(L.cert), w + L.pf_ws, L.pf_bytes, stream));
-    } else {
+    } else if (!lists) {
         for (int i = 0; i < L.n_runs; ++i) {        // one video a run, in the form and with the arguments of a session on it
             const Run& u = L.runs[i];
             float* scores = F(L.scores) + u.score_off;
@@ -430,13 +532,31 @@ static int localize(const char* who, const cone_model* m, const cone_model_dims&
                     RUN(cone_prefilter_scores(S.adapted + (size_t)u.row0 * dv, u.ctx_l, dv, c, n, W, Sl, nullptr, sc, w + L.pf_ws,
                                               L.pf_bytes, stream));
             }
-            RUN(cone_topk_windows_ws(scores, u.n, u.nw, K, I(L.widx) + (size_t)u.q0 * K, F(L.wval) + (size_t)u.q0 * K, w + L.topk_ws,
-                                     L.topk_bytes, stream));
+            if (pair_k)     // a ragged call: the run's lists at the largest count among its pairs (a video may have fewer than K windows)
+                RUN(cone_topk_windows_ws(scores, u.n, u.nw, u.k, I(L.st_idx) + u.st_off, F(L.st_val) + u.st_off, w + L.topk_ws,
+                                         L.topk_bytes, stream));
+            else
+                RUN(cone_topk_windows_ws(scores, u.n, u.nw, K, I(L.widx) + (size_t)u.q0 * K, F(L.wval) + (size_t)u.q0 * K, w + L.topk_ws,
+                                         L.topk_bytes, stream));
         }
     }
+    if (pair_k) {       // every pair takes the prefix it asked for: of a scan's list of (query, slot), or of its run's list
+        RaggedSrc R{};
+        for (int q = 0; q < nq; ++q) R.k[q] = pair_k[q];
+        if (lists)
+            for (int q = 0; q < nq; ++q)
+                R.off[q] = ((int64_t)lists->pairs.query[q] * lists->n_videos + lists->pairs.slot[q]) * lists->scan_K;
+        else
+            for (int i = 0; i < L.n_runs; ++i)
+                for (int q = 0; q < L.runs[i].n; ++q)
+                    R.off[L.runs[i].q0 + q] = (int64_t)(L.runs[i].st_off + (size_t)q * L.runs[i].k);
+        hipLaunchKernelGGL(library_gather_ragged_kernel, dim3((unsigned)((nq * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, R, nq,
+                           K, lists ? lists->widx : I(L.st_idx), lists ? lists->wval : F(L.st_val), I(L.widx), F(L.wval));
+        CONE_LAUNCH_CHECK();
+    }
     // every window counts as padded to max_v_l (:150-170): one reference batch per query, its padding max_v_l
-    RUN(cone_window_table(I(L.widx), nq, K, nullptr, nullptr, B, I(L.q_ctx_l), I(L.q_vid_off), I(L.tok_off), I(L.tok_len), 0, 1, W,
-                          I(L.batch_pad), 0, nq, vid_row0, vid_len, video_start, pad_len, txt_row0, txt_len, cls_row, stream));
+    RUN(cone_window_table(I(L.widx), nq, K, pair_k ? I(L.row_q) : nullptr, pair_k ? I(L.row_slot) : nullptr, B, I(L.q_ctx_l),
+                          I(L.q_vid_off), I(L.tok_off), I(L.tok_len), 0, 1, W, I(L.batch_pad), 0, nq, vid_row0, vid_len, video_start, pad_len, txt_row0, txt_len, cls_row, stream));
     RUN(cone_project_tokens(m, 1, F(L.tok_norm), L.T, F(L.tproj), w + L.proj_ws, L.proj_bytes, stream));
     cone_layer0 l0{};
     if (L.use_l0) {
@@ -453,7 +573,7 @@ static int localize(const char* who, const cone_model* m, const cone_model_dims&
                                     w + L.match_ws, L.match_bytes, stream));
     RUN(cone_compose_rows(F(L.logits), F(L.spans), F(L.match), I(L.full_w), video_start, P.clip_length, 0, B, Nq, F(L.rows),
                           stream));                                                                           // :191
-    return cone_fuse_nms(F(L.rows), nullptr, I(L.n_valid), nq, K * Nq, P.nms_thd, P.max_before, P.max_after, kept, n_kept,
+    return cone_fuse_nms(F(L.rows), pair_k ? (const int64_t*)(w + L.cand_off) : nullptr, I(L.n_valid), nq, K * Nq, P.nms_thd, P.max_before, P.max_after, kept, n_kept,
                          I(L.nms_idx), stream);                                                               // :200-219
 }
 
@@ -657,4 +777,75 @@ extern "C" int cone_library_localize_ranked(const cone_model* m, const cone_libr
     if (ws_bytes < L.total) { set_error("%s: workspace too small (%zu < %zu)", who, ws_bytes, L.total); return CONE_E_WORKSPACE; }
     return localize(who, m, d, S, lib->capacity, L, q_row0, q_ctx_l, tok, tok_len, nq, cls, K, 0, *params, kept, n_kept, nullptr,
                     (char*)ws, stream, &lists);
+}
+
+
+// ------------------------------------------------------------------------------ library window budgets: a window count per pair
+namespace cone {
+
+// The refusals of a ragged call from host values alone, in this order: the library call's with K = 1 (every video has a window),
+// then the counts; with lists, then what the ranked entry refuses.  *Kmax = the largest count.
+static int ragged_precheck(const char* who, const cone_library* lib, const int32_t* q_row0, const int32_t* q_ctx_l,
+                           const int32_t* tok_len, int nq, const int32_t* pair_k, const cone_session_params* p, bool ranked, int* Kmax) {
+    RUN(library_precheck(who, lib, q_row0, q_ctx_l, tok_len, nq, 1, p));
+    RUN(check_ragged(who, pair_k, q_ctx_l, nq, p->max_v_l, Kmax));
+    CONE_REQUIRE(!ranked || !(lib->flags & CONE_SESSION_BF16), "%s: CONE_SESSION_BF16 libraries are not supported with a scan's lists", who);
+    return 0;
+}
+
+}  // namespace cone
+
+extern "C" size_t cone_library_localize_ragged_workspace(const cone_model* m, const cone_library* lib, const int32_t* q_row0,
+                                                         const int32_t* q_ctx_l, const int32_t* tok_len, int nq, const int32_t* pair_k,
+                                                         const cone_session_params* params, int ranked) {
+    const char* who = "library_localize_ragged";
+    cone_model_dims d;
+    LocalizeLayout L;
+    int Kmax = 0;
+    if (ragged_precheck(who, lib, q_row0, q_ctx_l, tok_len, nq, pair_k, params, ranked != 0, &Kmax)) return 0;
+    if (library_handle(who, m, lib) || cone_model_get_dims(m, &d)) return 0;
+    const Resident S = resident_of(*lib);
+    if (localize_layout(who, "library", m, d, &S, lib->capacity, q_row0, q_ctx_l, tok_len, nq, Kmax, 0, params, &L, ranked != 0, pair_k))
+        return 0;
+    return L.total;
+}
+
+extern "C" int cone_library_localize_ragged(const cone_model* m, const cone_library* lib, const int32_t* q_row0, const int32_t* q_ctx_l,
+                                            const float* tok, const int32_t* tok_len, int nq, const float* cls, const int32_t* pair_k,
+                                            const cone_session_params* params, const int32_t* pair_query, const int32_t* pair_slot,
+                                            const int32_t* scan_widx, const float* scan_wval, int scan_nq, int64_t scan_n_videos,
+                                            int scan_K, double* kept, int32_t* n_kept, void* ws, size_t ws_bytes, void* stream) {
+    const char* who = "library_localize_ragged";
+    const bool ranked = pair_query || pair_slot || scan_widx || scan_wval;      // the lists come as a block: all of it or none
+    int Kmax = 0;
+    RUN(ragged_precheck(who, lib, q_row0, q_ctx_l, tok_len, nq, pair_k, params, ranked, &Kmax));
+    RankedLists lists{scan_widx, scan_wval, scan_n_videos, scan_K, {}};
+    if (ranked) {
+        CONE_REQUIRE(pair_query && pair_slot, "%s: null argument", who);
+        CONE_REQUIRE(scan_nq >= 1 && scan_n_videos >= 1 && scan_K >= 1 && Kmax <= scan_K,
+                     "%s: max pair_k=%d not in [1, scan_K=%d] (scan_nq=%d, scan_n_videos=%lld)", who, Kmax, scan_K, scan_nq,
+                     (long long)scan_n_videos);
+        for (int q = 0; q < nq; ++q) {
+            CONE_REQUIRE(pair_query[q] >= 0 && pair_query[q] < scan_nq, "%s: pair_query[%d]=%d not in [0, scan_nq=%d)", who, q,
+                         pair_query[q], scan_nq);
+            CONE_REQUIRE(pair_slot[q] >= 0 && pair_slot[q] < scan_n_videos, "%s: pair_slot[%d]=%d not in [0, scan_n_videos=%lld)", who, q,
+                         pair_slot[q], (long long)scan_n_videos);
+            lists.pairs.query[q] = pair_query[q];
+            lists.pairs.slot[q] = pair_slot[q];
+        }
+        CONE_REQUIRE(scan_widx && scan_wval, "%s: null argument", who);
+    }
+    CONE_REQUIRE(m && tok && cls && kept && n_kept && ws, "%s: null argument", who);
+    CONE_REQUIRE(((uintptr_t)ws & (SES_ALIGN - 1)) == 0, "%s: the workspace must be 256-B aligned", who);
+    RUN(library_handle(who, m, lib));
+    cone_model_dims d;
+    RUN(cone_model_get_dims(m, &d));
+    const Resident S = resident_of(*lib);
+    LocalizeLayout L;
+    RUN(localize_layout(who, "library", m, d, &S, lib->capacity, q_row0, q_ctx_l, tok_len, nq, Kmax, 0, params, &L, ranked, pair_k));
+    CONE_REQUIRE(S.vid_norm && S.vproj && (S.flags & CONE_SESSION_BF16 ? S.adapted_bf16 != nullptr : S.adapted != nullptr),
+                 "%s: the library handle misses a region (not one cone_library_open filled)", who);
+    if (ws_bytes < L.total) { set_error("%s: workspace too small (%zu < %zu)", who, ws_bytes, L.total); return CONE_E_WORKSPACE; }
+    return localize(who, m, d, S, lib->capacity, L, q_row0, q_ctx_l, tok, tok_len, nq, cls, Kmax, 0, *params, kept, n_kept, nullptr,
+                    (char*)ws, stream, ranked ? &lists : nullptr, pair_k);
 }

@@ -17,6 +17,13 @@ chosen (video, query) pairs through ``cone_library_localize_ranked``, which take
 moments still equal ``predict_moment``'s with ``==``.  ``scan_table`` lays the videos out for the scan (slots by first row,
 prefix sums of half-blocks).  fp32 libraries only: a ``prefilter_bf16`` library's search is refused by name.
 
+``search_windows`` spends a BUDGET of windows per query instead of K windows on each of n videos: ``cone_library_budget``
+(csrc/library_budget.hip) picks the W best windows over every list of the scan and counts them per video, one small read-back
+brings the (video, count) pairs to the host, and ``cone_library_localize_ragged`` -- the library call with a window count PER
+PAIR -- runs them (``plan_ragged_calls``: sorted by video, cut at 64 pairs, whatever their counts).  The windows chosen from a
+video are a prefix of its stable list, so a video that receives k windows answers with ``predict_moment`` at ``topk_window = k``,
+``==``.  ``predict_moments(..., ragged=True)`` / ``windows=[k, ...]`` reach the same call for a caller's own pairs.
+
 Rows are handed out first-fit from a free list and coalesce when a video is removed, so ``add`` / ``remove`` traffic
 fragments the arena: by default ``add`` raises when no hole fits, however many clips are free in total.  ``compact`` closes the
 holes in place and ``resize`` moves every video into an arena of another size (``add(..., compact=True)`` compacts when that is
@@ -208,6 +215,31 @@ def plan_calls(video_of, k_of, limit: int = MAX_QUERIES):
     for k in sorted(groups):
         idx = sorted(groups[k], key=lambda i: video_of[i])
         calls += [(k, idx[g:g + limit]) for g in range(0, len(idx), limit)]
+    return calls
+
+
+def plan_ragged_calls(video_of, k_of, limit: int = MAX_QUERIES, max_windows: int = 64 * 256):
+    """The calls of a ragged ``predict_moments`` / ``search_windows``: ``cone_library_localize_ragged`` takes a window count per
+    pair, so nothing is grouped by K.  The pairs are sorted by video (stable: a video's pairs become one run, in the caller's
+    order, whatever their k) and cut into calls of at most ``limit`` pairs and ``max_windows`` windows.  Returns
+    ``[[pair index, ...], ...]``; ``inverse_order`` takes it as ``[(None, idx) for idx in calls]``.  Pure Python, no GPU."""
+    limit, max_windows = int(limit), int(max_windows)
+    if limit < 1 or max_windows < 1:
+        raise ValueError(f"plan_ragged_calls: limit={limit} / max_windows={max_windows} < 1")
+    if len(video_of) != len(k_of):
+        raise ValueError(f"plan_ragged_calls: {len(video_of)} videos for {len(k_of)} window counts")
+    calls, cur, windows = [], [], 0
+    for i in sorted(range(len(k_of)), key=lambda i: video_of[i]):
+        k = int(k_of[i])
+        if not 1 <= k <= max_windows:
+            raise ValueError(f"plan_ragged_calls: pair {i} asks for {k} windows, not in [1, max_windows={max_windows}]")
+        if cur and (len(cur) == limit or windows + k > max_windows):
+            calls.append(cur)
+            cur, windows = [], 0
+        cur.append(i)
+        windows += k
+    if cur:
+        calls.append(cur)
     return calls
 
 
@@ -608,19 +640,84 @@ class VideoLibrary:
                                              C.c_void_p(buf.data_ptr() + R), _lib.ptr(ws), ws.numel(), _lib.stream()))
         return buf
 
+    def _enqueue_ragged(self, chunk, ks, scan=None, V=0):
+        """One ``cone_library_localize_ragged`` call: ``chunk`` = [((row0, ctx_l), (tok, cls), scan query, slot), ...] with ``ks``
+        windows each; ``scan`` = the scan whose lists the pairs take their windows from (``None``: the call's own stage A, the
+        last two entries of a pair are ignored)."""
+        lib, m, dev = _lib.load(), self._loc.localizator, self._loc.device
+        h, nq = m._h(), len(chunk)
+        toks = [c[1][0].to(dev, torch.float32).contiguous() for c in chunk]
+        tok_cat = toks[0] if nq == 1 else torch.cat(toks)
+        cls = torch.stack([c[1][1].to(dev, torch.float32).reshape(-1) for c in chunk]).contiguous()
+        i32 = C.c_int32 * nq
+        row0, ctx, lens = i32(*(c[0][0] for c in chunk)), i32(*(c[0][1] for c in chunk)), i32(*(int(t.shape[0]) for t in toks))
+        pk = i32(*ks)
+        if scan is None:
+            lists = (None, None, None, None, 0, 0, 0)
+        else:
+            _, sq, widx, wval = scan
+            lists = (i32(*(c[2] for c in chunk)), i32(*(c[3] for c in chunk)), _lib.ptr(widx), _lib.ptr(wval), len(sq), V,
+                     int(self._loc.args.topk_window))
+        nbytes = lib.cone_library_localize_ragged_workspace(h, C.byref(self._cl), row0, ctx, lens, nq, pk, C.byref(self._params),
+                                                            int(scan is not None))
+        if nbytes == 0:
+            raise _lib.ConeHipError(f"libcone_hip error: {lib.cone_last_error().decode()}")
+        ws = self._ws.get(nbytes, dev)
+        R, N = _kept_bytes(nq)
+        buf = torch.empty(R + N, dtype=torch.uint8, device=dev)
+        _lib.check(lib.cone_library_localize_ragged(h, C.byref(self._cl), row0, ctx, _lib.ptr(tok_cat, torch.float32), lens, nq,
+                                                    _lib.ptr(cls, torch.float32), pk, C.byref(self._params), *lists,
+                                                    C.c_void_p(buf.data_ptr()), C.c_void_p(buf.data_ptr() + R), _lib.ptr(ws),
+                                                    ws.numel(), _lib.stream()))
+        return buf
+
+    @staticmethod
+    def _read_calls(bufs, sizes):
+        """The kept rows of the calls ``bufs`` (``sizes[i]`` pairs each) after ONE read-back, in the calls' order."""
+        host = (bufs[0] if len(bufs) == 1 else torch.cat(bufs)).cpu()
+        out, at = [], 0
+        for nq in sizes:
+            n = sum(_kept_bytes(nq))
+            out += VideoSession.read_kept(host[at:at + n].clone() if at else host, nq)
+            at += n
+        return out
+
     @torch.no_grad()
-    def predict_moments(self, pairs):
+    def predict_moments(self, pairs, ragged=False, windows=None):
         """``[(video id, (text_token_feats, text_cls_feat)), ...]`` for any mix of the library's videos -> a list of moment
         lists in the order given, each ``==`` the localizer's ``predict_moment(video_feats, query)``.  Every pair is checked
         before any GPU work; the pairs are grouped by window count K (long videos all share ``topk_window``: usually one
         group), sorted by video inside a group, cut into calls of at most ``MAX_QUERIES``; every call is enqueued, then ONE
-        read-back."""
+        read-back.
+        ``ragged=True``: the same answers through ``cone_library_localize_ragged``, which takes a window count per pair -- the
+        pairs are only sorted by video and cut at 64 (``plan_ragged_calls``), so videos of different K share a call.
+        ``windows=[k, ...]``, one per pair (implies ragged): pair i runs on its ``k_i`` best windows only and answers with the
+        localizer's ``predict_moment`` at ``topk_window = k_i``; a k outside ``[1, K of the video]`` is refused before any GPU
+        work."""
         pairs = list(pairs)
         videos = [self._video(v) for v, _ in pairs]
         check_queries([int(q[0].shape[0]) for _, q in pairs], self.max_q_l)
+        if windows is not None:
+            windows = list(windows)
+            if len(windows) != len(pairs):
+                raise ValueError(f"VideoLibrary: {len(windows)} window counts for {len(pairs)} pairs")
+            for i, (k, v) in enumerate(zip(windows, videos)):
+                try:
+                    windows[i] = operator.index(k)
+                except TypeError:
+                    raise ValueError(f"VideoLibrary: windows[{i}] must be an integer, got {k!r}") from None
+                if not 1 <= windows[i] <= v[2]:
+                    raise ValueError(f"VideoLibrary: windows[{i}]={k} not in [1, {v[2]}] for video {pairs[i][0]!r}")
         if not pairs:
             return []
         self._check_live()
+        if ragged or windows is not None:
+            ks = windows if windows is not None else [v[2] for v in videos]
+            calls = plan_ragged_calls([v[0] for v in videos], ks)
+            where = inverse_order([(None, idx) for idx in calls], len(pairs))
+            bufs = [self._enqueue_ragged([(videos[i][:2], pairs[i][1], 0, 0) for i in idx], [ks[i] for i in idx]) for idx in calls]
+            out = self._read_calls(bufs, [len(idx) for idx in calls])           # the call's one read-back
+            return [out[w] for w in where]
         calls = plan_calls([v[0] for v in videos], [v[2] for v in videos])        # (a video is its first row: unique while it lives)
         where = inverse_order(calls, len(pairs))
         bufs = [self._enqueue(K, [(videos[i][:2], pairs[i][1]) for i in idx]) for K, idx in calls]
@@ -771,4 +868,82 @@ class VideoLibrary:
             it = iter(where)
             for q in range(len(chunk)):
                 out.append([(ids[slot], val, moments[next(it)]) for slot, val in ranked[g + q]])
+        return out
+
+    # ---- window budgets ------------------------------------------------------------------------
+    def _budget(self, scan, V, W):
+        """``cone_library_budget`` on one scan's lists: (nq, 1 + 3 W) int32 words on the device -- n_pairs, then the slots, the
+        counts and the best scores' bits (one tensor: one read-back)."""
+        lib, dev = _lib.load(), self._loc.device
+        _, chunk, _, wval = scan
+        nq, K = len(chunk), int(self._loc.args.topk_window)
+        nbytes = lib.cone_library_budget_workspace(nq, V, K, W)
+        if nbytes == 0:
+            raise _lib.ConeHipError(f"libcone_hip error: {lib.cone_last_error().decode()}")
+        ws = self._scan_ws.get(nbytes, dev)         # (the scan has run: stream order)
+        out = torch.empty(nq + 3 * nq * W, dtype=torch.int32, device=dev)
+        at = lambda k: C.c_void_p(out.data_ptr() + 4 * (nq + k * nq * W))
+        _lib.check(lib.cone_library_budget(_lib.ptr(wval), nq, V, K, W, C.c_void_p(out.data_ptr()), at(0), at(1), at(2), _lib.ptr(ws),
+                                           ws.numel(), _lib.stream()))
+        return out
+
+    @torch.no_grad()
+    def search_windows(self, queries, n_windows=None, videos=None):
+        """``[(tok, cls), ...]`` -> per query ``[(video id, best score, k, moments), ...]``: a budget of ``n_windows`` windows per
+        query (``None``: ``topk_window``, the price of ONE ``predict_moment``) spent on the best windows of the whole library --
+        or of ``videos`` --, wherever they lie: twelve may go to one video, one each to three more.  The entries are the videos
+        that receive a window, in ``rank_videos``' order, with its score; ``k`` is the video's share and ``moments ==`` a
+        localizer of the same weights with ``topk_window = k``, ``.predict_moment(video_feats, query)`` (the windows chosen from a
+        video are a prefix of its stable list).  A window of score -inf is never chosen: a library with fewer windows than the
+        budget spends it short, every video then at its own K, as in ``search``.
+        One scan and one ``cone_library_budget`` per 64 queries, ONE small read-back (pairs, counts, scores), the
+        ``cone_library_localize_ragged`` calls that ``plan_ragged_calls`` lays out, one read-back of the kept rows.  fp32
+        libraries only (a ``prefilter_bf16`` library is refused by name); ``n_windows`` in [1, 256]."""
+        queries = list(queries)
+        W = int(self._loc.args.topk_window) if n_windows is None else n_windows
+        try:
+            W = operator.index(W)
+        except TypeError:
+            raise ValueError(f"VideoLibrary: n_windows must be an integer, got {n_windows!r}") from None
+        if not 1 <= W <= 256:
+            raise ValueError(f"VideoLibrary: n_windows={W} not in [1, 256]")
+        check_queries([int(q[0].shape[0]) for q in queries], self.max_q_l)
+        subset, ids = self._search_ids(videos)
+        if not queries or not ids:
+            return [[] for _ in queries]
+        self._check_live()
+        if self._flags & _lib.SESSION_BF16:
+            raise _lib.ConeHipError("VideoLibrary: search_windows: CONE_SESSION_BF16 libraries are not supported (prefilter_bf16)")
+        table = self._table(subset, ids)
+        ids, V = table[0], len(table[0])
+        scans, budgets = [], []
+        for g in range(0, len(queries), MAX_QUERIES):
+            chunk = queries[g:g + MAX_QUERIES]
+            widx, wval, _ = self._scan(table, chunk, 1)
+            scans.append((g, chunk, widx, wval))
+            budgets.append(self._budget(scans[-1], V, W))
+        host = (budgets[0] if len(budgets) == 1 else torch.cat(budgets)).cpu()        # the one small read-back
+        bufs, sizes, plans, at = [], [], [], 0
+        for scan in scans:
+            chunk = scan[1]
+            nq = len(chunk)
+            n_pairs = host[at:at + nq].tolist()
+            slots, counts, best = (host[at + nq + k * nq * W:at + nq + (k + 1) * nq * W].reshape(nq, W) for k in range(3))
+            best = best.contiguous().view(torch.float32)
+            at += nq + 3 * nq * W
+            chosen = [(q, int(slots[q, i]), int(counts[q, i]), float(best[q, i])) for q in range(nq) for i in range(n_pairs[q])]
+            vids = [self._videos[ids[slot]] for _, slot, _, _ in chosen]
+            calls = plan_ragged_calls([v[0] for v in vids], [c[2] for c in chosen])
+            bufs += [self._enqueue_ragged([(vids[i][:2], chunk[chosen[i][0]], chosen[i][0], chosen[i][1]) for i in idx],
+                                          [chosen[i][2] for i in idx], scan, V) for idx in calls]
+            sizes += [len(idx) for idx in calls]
+            plans.append((chosen, inverse_order([(None, idx) for idx in calls], len(chosen))))
+        moments = self._read_calls(bufs, sizes) if bufs else []                      # the kept rows' one read-back
+        out, base = [], 0
+        for (g, chunk, _, _), (chosen, where) in zip(scans, plans):
+            rows = [[] for _ in chunk]
+            for i, (q, slot, k, score) in enumerate(chosen):
+                rows[q].append((ids[slot], score, k, moments[base + where[i]]))
+            out += rows
+            base += len(chosen)
         return out

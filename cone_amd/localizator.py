@@ -137,7 +137,10 @@ class CONELocalizator:
         on that video and query.  With ``prefilter_bf16`` the library keeps bf16 adapted rows.
         ``lib.add_many([video_feats, ...])`` indexes a list of videos with one upload, ``lib.extend(id, more_feats)`` appends
         clips to a resident video and ``lib.trim(id, n_front)`` drops its oldest ones; ``lib.compact()`` / ``lib.resize()``
-        close the holes.  No certified ranking."""
+        close the holes.  ``lib.search_windows(queries, n_windows)`` spends a budget of windows per query on the best windows of
+        the whole library -- ``[(id, score, k, moments), ...]``, ``moments ==`` this class's ``predict_moment`` at
+        ``topk_window = k`` --; ``lib.predict_moments(pairs, ragged=True)`` answers videos of different window counts in one
+        call, ``windows=[k, ...]`` gives every pair its own count (``cone_library_localize_ragged``).  No certified ranking."""
         from .library import VideoLibrary
         return VideoLibrary(self, capacity_clips)
 

@@ -722,6 +722,65 @@ int cone_library_move_rows(const cone_model* m, const cone_library* src, const c
                            const int64_t* mv_dst, const int64_t* mv_off, int64_t n_moves, int64_t total_rows, int64_t row_begin,
                            int64_t row_end, void* stage, size_t stage_bytes, void* stream);
 
+/* ------------------------------------------------------------ library window budgets (additive in ABI 8)
+ * A search that spends a fixed budget of W windows per query wherever in the library the evidence is, instead of K windows on
+ * each of n videos: twelve windows may go to one video, five to another, one each to three more.  Two pieces.
+ * cone_library_budget picks, per query, the W best windows over every list of a cone_library_scan and says how many fall to
+ * which video; cone_library_localize_ragged is the query half with a window count PER PAIR.  CONTRACT: a scan's lists are stable
+ * and descending per (query, video), so the chosen windows of a video are a prefix of its list, and a prefix of a stable list is
+ * the stable list of a smaller K: a pair that receives k windows answers with the bits of predict_moment at topk_window = k
+ * (run_on_video/cone_localizator.py:121-221 on the first k windows of cone/inference.py:276-299;
+ * tests/test_library_budget_gpu.py compares with ==).  Planning the pairs stays on the host: one small read-back between the
+ * two.  fp32 libraries for the budget and the lists' form; the ragged call's own stage A serves CONE_SESSION_BF16 libraries. */
+
+/* The W best windows of every query over all the lists of a scan (cone/inference.py:276-299 ranks the windows of ONE video; this
+ * ranks the lists of many against each other -- the scores are cosines in the adapter's space, comparable across videos -- and
+ * run_on_video/cone_localizator.py:121-221 then runs on the chosen ones).  wval (nq, n_videos, scan_K) fp32 on the device: a
+ * cone_library_scan's values (its widx plays no part: padding carries -inf).
+ * Per query: of the n_videos * scan_K entries those > -inf, ordered by value descending, ties to the lower table slot, then to
+ * the lower list position (= the lower flat index slot * scan_K + j; -0.0 ties with +0.0, as in cone_topk_windows_ws, which does
+ * the selection); the first min(W, their count) are chosen.  An entry of -inf is NEVER chosen -- list padding and a window of NaN
+ * frames alike --, so a query with fewer than W finite entries SPENDS ITS BUDGET SHORT.  The lists must be descending per
+ * (query, slot) -- the scan's guarantee --: the chosen entries of a slot are then a prefix of its list.
+ * Outputs (device), every element written: n_pairs (nq); pair_slot / pair_k / pair_best (nq, W): the slots that receive a window
+ * in order of first appearance (best score descending, ties to the lower slot: cone_library_scan's ranking order), the number
+ * chosen from each, the value of its first; rows past n_pairs[q] are -1 / 0 / -inf.  sum of pair_k[q] = min(W, finite entries).
+ * ws >= cone_library_budget_workspace, 256-B aligned: the selected (index, value) lists and the selection's scratch.
+ * Refused by name ("library_budget: "), from host values first, before any pointer is looked at: nq outside [1, 64]; n_videos < 1;
+ * scan_K outside [1, 256]; W outside [1, 256]; n_videos * scan_K >= 2^31 - 1; then null arguments, a misaligned or short
+ * workspace. */
+size_t cone_library_budget_workspace(int nq, int64_t n_videos, int scan_K, int W);
+int cone_library_budget(const float* wval, int nq, int64_t n_videos, int scan_K, int W, int32_t* n_pairs, int32_t* pair_slot,
+                        int32_t* pair_k, float* pair_best, void* ws, size_t ws_bytes, void* stream);
+
+/* cone_library_localize / cone_library_localize_ranked (run_on_video/cone_localizator.py:121-221, the query half) with a HOST
+ * array pair_k (nq) in place of the one K: pair p runs on its first pair_k[p] windows (cone/inference.py:276-299's order), B =
+ * sum of pair_k window rows in all.  ONE one-workgroup launch writes the call's metadata -- what cone_library_query_layout writes,
+ * plus row_q / row_slot / full_w for the B rows, n_valid[p] = pair_k[p] Nq and cand_off[p] = (rows before p) Nq --, stage A leaves
+ * an (nq, Kmax) window list, Kmax = max pair_k, whose row p holds pair p's prefix (the rest is -1 / -inf and never read), and
+ * everything behind it is the uniform call's launch over B windows: cone_window_table in its row_q / row_slot form, the forward,
+ * cone_clip_matching_gathered, cone_compose_rows, cone_fuse_nms with cand_off.
+ * Stage A has two forms, chosen by the lists' block pair_query, pair_slot, scan_widx, scan_wval (all four, or all four NULL):
+ *   lists: as in cone_library_localize_ranked, ONE small launch copies the first pair_k[p] entries of the scan's list of
+ *     (pair_query[p], pair_slot[p]);
+ *   none (scan_nq, scan_n_videos, scan_K are then ignored): cone_library_localize's own stage A per run of consecutive pairs on
+ *     one video -- the pre-filter in launches of at most 4, ONE cone_topk_windows_ws at the largest pair_k of the run -- and the
+ *     same small launch copies every pair's prefix.  CONE_SESSION_BF16 libraries are served in this form.
+ * Pairs of one video with different pair_k may be adjacent: they are one run.  kept / n_kept as in cone_library_localize.
+ * ws >= cone_library_localize_ragged_workspace for the same pairs, counts and form (ranked != 0: the lists' form).
+ * Refused by name ("library_localize_ragged: "): everything cone_library_localize refuses, on the host, the pairs first; then a
+ * pair_k[p] outside [1, min(num_window of pair p, 256)] (the message names p; with nq <= 64 that bounds B by 64 * 256); with
+ * lists: a CONE_SESSION_BF16 library, Kmax > scan_K, a pair_query[p] outside [0, scan_nq), a pair_slot[p] outside
+ * [0, scan_n_videos), a block that is only partly there. */
+size_t cone_library_localize_ragged_workspace(const cone_model* m, const cone_library* lib, const int32_t* q_row0,
+                                              const int32_t* q_ctx_l, const int32_t* tok_len, int nq, const int32_t* pair_k,
+                                              const cone_session_params* params, int ranked);
+int cone_library_localize_ragged(const cone_model* m, const cone_library* lib, const int32_t* q_row0, const int32_t* q_ctx_l,
+                                 const float* tok, const int32_t* tok_len, int nq, const float* cls, const int32_t* pair_k,
+                                 const cone_session_params* params, const int32_t* pair_query, const int32_t* pair_slot,
+                                 const int32_t* scan_widx, const float* scan_wval, int scan_nq, int64_t scan_n_videos, int scan_K,
+                                 double* kept, int32_t* n_kept, void* ws, size_t ws_bytes, void* stream);
+
 /* -------------------------------------------------------------------- metrics on the device
  * Recall@K / IoU counts from the kept rows (layout of cone_fuse_nms: rows (nq, max_after, 5) fp64 [st, ed, ...],
  * n (nq) valid rows) and one target span per query gt (nq, 2) fp64 seconds -- device pointers.  thresholds /
