@@ -244,6 +244,18 @@ _SIGNATURES = {
                                                C.POINTER(SessionParams), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p,
                                                C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                                C.c_void_p]),
+    # library moment search (additive in ABI 8): stage C over one candidate pool per query, the ragged call up to its candidates
+    # cone_corpus_fuse_nms(cand, seg_off, seg_cand, seg_n, seg_tag (device), nq, n_seg, nms_thd, max_before, max_after, out_rows,
+    # out_seg, out_n (device), stream)
+    "cone_corpus_fuse_nms": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_double, C.c_int, C.c_int] + [C.c_void_p] * 4),
+    "cone_library_localize_candidates_workspace": (C.c_size_t, [C.c_void_p, C.POINTER(Library)] + [C.POINTER(C.c_int32)] * 3
+                                                   + [C.c_int, C.POINTER(C.c_int32), C.POINTER(SessionParams), C.c_int]),
+    # cone_library_localize_candidates(<cone_library_localize_ragged's, with cand (device) in place of kept, n_kept>)
+    "cone_library_localize_candidates": (C.c_int, [C.c_void_p, C.POINTER(Library), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                   C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.POINTER(C.c_int32),
+                                                   C.POINTER(SessionParams), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p,
+                                                   C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                   C.c_void_p]),
     # cone_test_gemm(A, A2, a2_mod, W, bias, R, ln_g, ln_b, C, C2, ADD, M, N, K, flags, stream)
     "cone_test_gemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,

@@ -8,56 +8,9 @@
 //     correctly-rounded format + parse produces.
 //   * sum((a, b)) in Python is (0 + a) + b.
 //   * sorted(..., reverse=True) is stable: rank = #{greater} + #{equal with smaller position}.
-#include "common.h"
+#include "stage_c.h"      // round4, pseudo_iou, block_nms: shared with library_corpus.hip
 
 namespace cone {
-
-constexpr int kMaxCand = 1024;
-
-__device__ __forceinline__ double round4(double x) { return rint(x * 1e4) / 1e4; }
-
-__device__ __forceinline__ double pseudo_iou(double s0, double e0, double s1, double e1) {
-    const double lo = fmin(e0, e1) - fmax(s0, s1);
-    const double inter = lo > 0.0 ? lo : 0.0;
-    const double uni = fmax(e0, e1) - fmin(s0, s1);
-    return uni == 0.0 ? 0.0 : inter / uni;
-}
-
-// Greedy NMS over `m` candidates already in score order (sidx[j] = candidate id at sorted position j).
-// Block-cooperative; writes kept sorted positions.
-__device__ void block_nms(const double* st, const double* ed, const int* sidx, int m, double thd,
-                          int max_after, unsigned char* alive, int* kept_pos, int* kept_n_out) {
-    const int tid = threadIdx.x;
-    __shared__ int s_cur;
-    __shared__ int s_kept;
-    for (int j = tid; j < m; j += blockDim.x) alive[j] = 1;
-    if (tid == 0) { s_kept = 0; s_cur = 0; }
-    __syncthreads();
-    if (m == 1) {  // utils/temporal_nms.py:38-39
-        if (tid == 0) { kept_pos[0] = 0; *kept_n_out = 1; }
-        __syncthreads();
-        return;
-    }
-    int start = 0;
-    while (true) {
-        if (tid == 0) {
-            int c = start;
-            while (c < m && !alive[c]) ++c;
-            s_cur = c;
-            if (c < m && s_kept < max_after) kept_pos[s_kept++] = c; else s_cur = m;
-        }
-        __syncthreads();
-        const int cur = s_cur;
-        if (cur >= m) break;
-        const double s0 = st[sidx[cur]], e0 = ed[sidx[cur]];
-        for (int j = cur + 1 + tid; j < m; j += blockDim.x)
-            if (alive[j] && pseudo_iou(s0, e0, st[sidx[j]], ed[sidx[j]]) > thd) alive[j] = 0;
-        start = cur + 1;
-        __syncthreads();
-    }
-    if (tid == 0) *kept_n_out = s_kept;
-    __syncthreads();
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void fuse_nms_kernel(const T* __restrict__ cand, const int64_t* __restrict__ cand_off,
@@ -180,7 +133,7 @@ __global__ __launch_bounds__(256) void fuse_nms_kernel(const T* __restrict__ can
             // positions use the key's first-occurrence candidate for (st, ed)
             for (int j = tid; j < m; j += 256) cidx[j] = u_first[sidx[j]];
             __syncthreads();
-            block_nms(c_st, c_ed, cidx, m, thd, max_after, flag, kept_pos, &s_kept_n);
+            block_nms<false>(c_st, c_ed, nullptr, cidx, m, thd, max_after, flag, kept_pos, &s_kept_n);
             kept = s_kept_n;
         } else {
             kept = min(nu, max_after);
@@ -226,7 +179,7 @@ __global__ __launch_bounds__(256) void temporal_nms_kernel(const double* __restr
         sidx[rank] = i;
     }
     __syncthreads();
-    block_nms(c_st, c_ed, sidx, n, thd, max_after, alive, kept_pos, &s_kept_n);
+    block_nms<false>(c_st, c_ed, nullptr, sidx, n, thd, max_after, alive, kept_pos, &s_kept_n);
     for (int j = tid; j < s_kept_n; j += 256) keep_idx[j] = sidx[kept_pos[j]];
     if (tid == 0) *keep_n = s_kept_n;
 }

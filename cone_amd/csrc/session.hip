@@ -3,6 +3,8 @@
 // Library search ("library search"): the query half on the window lists of a cone_library_scan (csrc/prefilter.hip).
 // Library window budgets ("library window budgets"): the query half with a window count per pair (cone_library_localize_ragged;
 // its own layout kernel and a gather of every pair's prefix -- the budget itself is csrc/library_budget.hip).
+// Library moment search ("library moment search"): the ragged call that ends at its candidate rows
+// (cone_library_localize_candidates; the pooled stage C is csrc/library_corpus.hip).
 //
 // Nothing is computed here.  cone_session_index / cone_library_add and cone_session_localize / cone_library_localize only
 // SEQUENCE the library's own extern "C" launchers -- the calls cone_amd/localizator.py issues one by one through ctypes for
@@ -480,12 +482,13 @@ __global__ __launch_bounds__(256) void library_gather_ragged_kernel(RaggedSrc R,
 // otherwise a library call (every query names its video's rows inside an arena of `rows`).  Nothing differs after stage A.
 // pair_k != NULL is a ragged library call (K = the largest count): pair q owns pair_k[q] window rows, not K -- its own layout
 // kernel, a gather of every pair's prefix, then the row form of cone_window_table and the offset form of cone_fuse_nms.  The
-// uniform calls run the launches they always ran.
+// uniform calls run the launches they always ran.  cand != NULL (cone_library_localize_candidates): the call ends at its
+// candidate rows, composed straight into `cand`; kept / n_kept are not touched.
 static int localize(const char* who, const cone_model* m, const cone_model_dims& d, const Resident& S, int64_t rows,
                     const LocalizeLayout& L, const int32_t* q_row0, const int32_t* q_ctx_l, const float* tok, const int32_t* tok_len,
                     int nq, const float* cls, int K, int n_cand, const cone_session_params& P, double* kept, int32_t* n_kept,
                     int32_t* certified, char* w, void* stream, const RankedLists* lists = nullptr,
-                    const int32_t* pair_k = nullptr) {
+                    const int32_t* pair_k = nullptr, float* cand = nullptr) {
     auto I = [&](size_t at) { return (int32_t*)(w + at); };
     auto F = [&](size_t at) { return (float*)(w + at); };
     auto scratch = [&](size_t at, size_t bytes) { return bytes ? (void*)(w + at) : nullptr; };
@@ -571,8 +574,9 @@ static int localize(const char* who, const cone_model* m, const cone_model_dims&
                             nullptr, nullptr, L.use_l0 ? &l0 : nullptr, w + L.fwd_ws, L.fwd_bytes, stream));
     RUN(cone_clip_matching_gathered(m, cls, cls_row, S.vid_norm, vid_row0, vid_len, pad_len, F(L.spans), B, F(L.match),
                                     w + L.match_ws, L.match_bytes, stream));
-    RUN(cone_compose_rows(F(L.logits), F(L.spans), F(L.match), I(L.full_w), video_start, P.clip_length, 0, B, Nq, F(L.rows),
-                          stream));                                                                           // :191
+    RUN(cone_compose_rows(F(L.logits), F(L.spans), F(L.match), I(L.full_w), video_start, P.clip_length, 0, B, Nq,
+                          cand ? cand : F(L.rows), stream));                                                  // :191
+    if (cand) return 0;     // the caller pools the candidates of many calls (cone_corpus_fuse_nms): the B * Nq rows, no stage C
     return cone_fuse_nms(F(L.rows), pair_k ? (const int64_t*)(w + L.cand_off) : nullptr, I(L.n_valid), nq, K * Nq, P.nms_thd, P.max_before, P.max_after, kept, n_kept,
                          I(L.nms_idx), stream);                                                               // :200-219
 }
@@ -795,10 +799,11 @@ static int ragged_precheck(const char* who, const cone_library* lib, const int32
 
 }  // namespace cone
 
-extern "C" size_t cone_library_localize_ragged_workspace(const cone_model* m, const cone_library* lib, const int32_t* q_row0,
-                                                         const int32_t* q_ctx_l, const int32_t* tok_len, int nq, const int32_t* pair_k,
-                                                         const cone_session_params* params, int ranked) {
-    const char* who = "library_localize_ragged";
+namespace cone {
+
+static size_t ragged_workspace(const char* who, const cone_model* m, const cone_library* lib, const int32_t* q_row0,
+                               const int32_t* q_ctx_l, const int32_t* tok_len, int nq, const int32_t* pair_k,
+                               const cone_session_params* params, int ranked) {
     cone_model_dims d;
     LocalizeLayout L;
     int Kmax = 0;
@@ -810,12 +815,13 @@ extern "C" size_t cone_library_localize_ragged_workspace(const cone_model* m, co
     return L.total;
 }
 
-extern "C" int cone_library_localize_ragged(const cone_model* m, const cone_library* lib, const int32_t* q_row0, const int32_t* q_ctx_l,
-                                            const float* tok, const int32_t* tok_len, int nq, const float* cls, const int32_t* pair_k,
-                                            const cone_session_params* params, const int32_t* pair_query, const int32_t* pair_slot,
-                                            const int32_t* scan_widx, const float* scan_wval, int scan_nq, int64_t scan_n_videos,
-                                            int scan_K, double* kept, int32_t* n_kept, void* ws, size_t ws_bytes, void* stream) {
-    const char* who = "library_localize_ragged";
+// cone_library_localize_ragged (cand == NULL: kept / n_kept are the outputs) and cone_library_localize_candidates (cand is):
+// the same refusals in the same order, the same launches up to cone_compose_rows.
+static int ragged_call(const char* who, const cone_model* m, const cone_library* lib, const int32_t* q_row0, const int32_t* q_ctx_l,
+                       const float* tok, const int32_t* tok_len, int nq, const float* cls, const int32_t* pair_k,
+                       const cone_session_params* params, const int32_t* pair_query, const int32_t* pair_slot,
+                       const int32_t* scan_widx, const float* scan_wval, int scan_nq, int64_t scan_n_videos, int scan_K,
+                       double* kept, int32_t* n_kept, float* cand, bool to_cand, void* ws, size_t ws_bytes, void* stream) {
     const bool ranked = pair_query || pair_slot || scan_widx || scan_wval;      // the lists come as a block: all of it or none
     int Kmax = 0;
     RUN(ragged_precheck(who, lib, q_row0, q_ctx_l, tok_len, nq, pair_k, params, ranked, &Kmax));
@@ -835,7 +841,7 @@ extern "C" int cone_library_localize_ragged(const cone_model* m, const cone_libr
         }
         CONE_REQUIRE(scan_widx && scan_wval, "%s: null argument", who);
     }
-    CONE_REQUIRE(m && tok && cls && kept && n_kept && ws, "%s: null argument", who);
+    CONE_REQUIRE(m && tok && cls && (to_cand ? cand != nullptr : kept && n_kept) && ws, "%s: null argument", who);
     CONE_REQUIRE(((uintptr_t)ws & (SES_ALIGN - 1)) == 0, "%s: the workspace must be 256-B aligned", who);
     RUN(library_handle(who, m, lib));
     cone_model_dims d;
@@ -847,5 +853,41 @@ extern "C" int cone_library_localize_ragged(const cone_model* m, const cone_libr
                  "%s: the library handle misses a region (not one cone_library_open filled)", who);
     if (ws_bytes < L.total) { set_error("%s: workspace too small (%zu < %zu)", who, ws_bytes, L.total); return CONE_E_WORKSPACE; }
     return localize(who, m, d, S, lib->capacity, L, q_row0, q_ctx_l, tok, tok_len, nq, cls, Kmax, 0, *params, kept, n_kept, nullptr,
-                    (char*)ws, stream, ranked ? &lists : nullptr, pair_k);
+                    (char*)ws, stream, ranked ? &lists : nullptr, pair_k, to_cand ? cand : nullptr);
+}
+
+}  // namespace cone
+
+extern "C" size_t cone_library_localize_ragged_workspace(const cone_model* m, const cone_library* lib, const int32_t* q_row0,
+                                                         const int32_t* q_ctx_l, const int32_t* tok_len, int nq, const int32_t* pair_k,
+                                                         const cone_session_params* params, int ranked) {
+    return cone::ragged_workspace("library_localize_ragged", m, lib, q_row0, q_ctx_l, tok_len, nq, pair_k, params, ranked);
+}
+
+extern "C" int cone_library_localize_ragged(const cone_model* m, const cone_library* lib, const int32_t* q_row0, const int32_t* q_ctx_l,
+                                            const float* tok, const int32_t* tok_len, int nq, const float* cls, const int32_t* pair_k,
+                                            const cone_session_params* params, const int32_t* pair_query, const int32_t* pair_slot,
+                                            const int32_t* scan_widx, const float* scan_wval, int scan_nq, int64_t scan_n_videos,
+                                            int scan_K, double* kept, int32_t* n_kept, void* ws, size_t ws_bytes, void* stream) {
+    return cone::ragged_call("library_localize_ragged", m, lib, q_row0, q_ctx_l, tok, tok_len, nq, cls, pair_k, params, pair_query,
+                             pair_slot, scan_widx, scan_wval, scan_nq, scan_n_videos, scan_K, kept, n_kept, nullptr, false, ws, ws_bytes,
+                             stream);
+}
+
+// ------------------------------------------------------------------------------ library moment search: the call that ends at its candidates
+extern "C" size_t cone_library_localize_candidates_workspace(const cone_model* m, const cone_library* lib, const int32_t* q_row0,
+                                                             const int32_t* q_ctx_l, const int32_t* tok_len, int nq,
+                                                             const int32_t* pair_k, const cone_session_params* params, int ranked) {
+    return cone::ragged_workspace("library_localize_candidates", m, lib, q_row0, q_ctx_l, tok_len, nq, pair_k, params, ranked);
+}
+
+extern "C" int cone_library_localize_candidates(const cone_model* m, const cone_library* lib, const int32_t* q_row0,
+                                                const int32_t* q_ctx_l, const float* tok, const int32_t* tok_len, int nq,
+                                                const float* cls, const int32_t* pair_k, const cone_session_params* params,
+                                                const int32_t* pair_query, const int32_t* pair_slot, const int32_t* scan_widx,
+                                                const float* scan_wval, int scan_nq, int64_t scan_n_videos, int scan_K, float* cand,
+                                                void* ws, size_t ws_bytes, void* stream) {
+    return cone::ragged_call("library_localize_candidates", m, lib, q_row0, q_ctx_l, tok, tok_len, nq, cls, pair_k, params, pair_query,
+                             pair_slot, scan_widx, scan_wval, scan_nq, scan_n_videos, scan_K, nullptr, nullptr, cand, true, ws, ws_bytes,
+                             stream);
 }

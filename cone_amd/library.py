@@ -24,6 +24,12 @@ PAIR -- runs them (``plan_ragged_calls``: sorted by video, cut at 64 pairs, what
 video are a prefix of its stable list, so a video that receives k windows answers with ``predict_moment`` at ``topk_window = k``,
 ``==``.  ``predict_moments(..., ragged=True)`` / ``windows=[k, ...]`` reach the same call for a caller's own pairs.
 
+``search_moments`` answers what a library is for: the n best moments for a query in everything it holds.  The lists above are
+each normalised over the candidates of ONE pair (every pair's best proposal becomes 1.0), so they cannot be merged; here the
+budget's pairs run through ``cone_library_localize_candidates`` -- the ragged call stopped before its stage C -- into one
+candidate buffer, and ``cone_corpus_fuse_nms`` (csrc/library_corpus.hip) runs the reference's stage C over the whole pool of a
+query: both score lists normalised over the pool, the dict keyed by (video, st, ed), NMS inside each video only.
+
 Rows are handed out first-fit from a free list and coalesce when a video is removed, so ``add`` / ``remove`` traffic
 fragments the arena: by default ``add`` raises when no hole fits, however many clips are free in total.  ``compact`` closes the
 holes in place and ``resize`` moves every video into an arena of another size (``add(..., compact=True)`` compacts when that is
@@ -52,6 +58,8 @@ import torch
 
 from . import _lib, ops
 from .session import MAX_QUERIES, NMS_THD, MAX_BEFORE, MAX_AFTER, VideoSession, _kept_bytes, check_queries
+
+MAX_POOL = 1024     # candidates of one query in cone_corpus_fuse_nms (csrc/stage_c.h: kMaxCand)
 
 
 class RowRanges:
@@ -640,10 +648,11 @@ class VideoLibrary:
                                              C.c_void_p(buf.data_ptr() + R), _lib.ptr(ws), ws.numel(), _lib.stream()))
         return buf
 
-    def _enqueue_ragged(self, chunk, ks, scan=None, V=0):
+    def _enqueue_ragged(self, chunk, ks, scan=None, V=0, cand=None):
         """One ``cone_library_localize_ragged`` call: ``chunk`` = [((row0, ctx_l), (tok, cls), scan query, slot), ...] with ``ks``
         windows each; ``scan`` = the scan whose lists the pairs take their windows from (``None``: the call's own stage A, the
-        last two entries of a pair are ignored)."""
+        last two entries of a pair are ignored).  ``cand`` (fp32, on the device): ``cone_library_localize_candidates`` instead
+        -- the call's ``sum(ks) * num_queries`` candidate rows are written there, no stage C runs, nothing is returned."""
         lib, m, dev = _lib.load(), self._loc.localizator, self._loc.device
         h, nq = m._h(), len(chunk)
         toks = [c[1][0].to(dev, torch.float32).contiguous() for c in chunk]
@@ -658,11 +667,16 @@ class VideoLibrary:
             _, sq, widx, wval = scan
             lists = (i32(*(c[2] for c in chunk)), i32(*(c[3] for c in chunk)), _lib.ptr(widx), _lib.ptr(wval), len(sq), V,
                      int(self._loc.args.topk_window))
-        nbytes = lib.cone_library_localize_ragged_workspace(h, C.byref(self._cl), row0, ctx, lens, nq, pk, C.byref(self._params),
-                                                            int(scan is not None))
+        size = lib.cone_library_localize_ragged_workspace if cand is None else lib.cone_library_localize_candidates_workspace
+        nbytes = size(h, C.byref(self._cl), row0, ctx, lens, nq, pk, C.byref(self._params), int(scan is not None))
         if nbytes == 0:
             raise _lib.ConeHipError(f"libcone_hip error: {lib.cone_last_error().decode()}")
         ws = self._ws.get(nbytes, dev)
+        if cand is not None:
+            _lib.check(lib.cone_library_localize_candidates(h, C.byref(self._cl), row0, ctx, _lib.ptr(tok_cat, torch.float32), lens, nq,
+                                                            _lib.ptr(cls, torch.float32), pk, C.byref(self._params), *lists,
+                                                            _lib.ptr(cand, torch.float32), _lib.ptr(ws), ws.numel(), _lib.stream()))
+            return None
         R, N = _kept_bytes(nq)
         buf = torch.empty(R + N, dtype=torch.uint8, device=dev)
         _lib.check(lib.cone_library_localize_ragged(h, C.byref(self._cl), row0, ctx, _lib.ptr(tok_cat, torch.float32), lens, nq,
@@ -898,7 +912,9 @@ class VideoLibrary:
         budget spends it short, every video then at its own K, as in ``search``.
         One scan and one ``cone_library_budget`` per 64 queries, ONE small read-back (pairs, counts, scores), the
         ``cone_library_localize_ragged`` calls that ``plan_ragged_calls`` lays out, one read-back of the kept rows.  fp32
-        libraries only (a ``prefilter_bf16`` library is refused by name); ``n_windows`` in [1, 256]."""
+        libraries only (a ``prefilter_bf16`` library is refused by name); ``n_windows`` in [1, 256].
+        The scores inside ``moments`` are normalised per pair and are not comparable across videos: ``search_moments`` is the call
+        that ranks the moments of different videos against each other."""
         queries = list(queries)
         W = int(self._loc.args.topk_window) if n_windows is None else n_windows
         try:
@@ -947,3 +963,113 @@ class VideoLibrary:
             out += rows
             base += len(chosen)
         return out
+
+    # ---- moment search -------------------------------------------------------------------------
+    @torch.no_grad()
+    def search_moments(self, queries, n_windows=None, n_moments=5, videos=None):
+        """``[(tok, cls), ...]`` -> per query ``[(video id, [st, ed, score]), ...]``: the at most ``n_moments`` best moments of
+        the whole library -- or of ``videos`` -- for the query, fused score descending; seconds from each video's first clip,
+        4-decimal doubles like ``predict_moment``'s.  ``search_windows``' budget of ``n_windows`` windows (``None``:
+        ``topk_window``) picks where to look; everything that comes out of those windows is ONE candidate pool per query and
+        run_on_video/cone_localizator.py:187-221 runs on the pool: both score lists are normalised over all of it, so a score
+        means the same in every video, the dict is keyed by (video, st, ed) and a moment suppresses only moments of its own
+        video.  On a one-video library the answer is the localizer's ``predict_moment`` at ``topk_window = `` the video's share.
+        One scan and one ``cone_library_budget`` per 64 queries, ONE small read-back (pairs, counts), the
+        ``cone_library_localize_candidates`` calls that ``plan_ragged_calls`` lays out -- all writing into one candidate buffer
+        --, the segment table built on the host and uploaded once, one ``cone_corpus_fuse_nms`` per 64 queries, ONE read-back.
+        ``n_windows * num_queries`` (the decoder's slots) may not exceed 1 024 candidates; ``n_moments`` in [1, 100]; fp32
+        libraries only."""
+        import numpy as np
+        queries = list(queries)
+        W = int(self._loc.args.topk_window) if n_windows is None else n_windows
+        try:
+            W = operator.index(W)
+        except TypeError:
+            raise ValueError(f"VideoLibrary: n_windows must be an integer, got {n_windows!r}") from None
+        if not 1 <= W <= 256:
+            raise ValueError(f"VideoLibrary: n_windows={W} not in [1, 256]")
+        try:
+            M = operator.index(n_moments)
+        except TypeError:
+            raise ValueError(f"VideoLibrary: n_moments must be an integer, got {n_moments!r}") from None
+        if not 1 <= M <= MAX_BEFORE:
+            raise ValueError(f"VideoLibrary: n_moments={M} not in [1, {MAX_BEFORE}]")
+        Nq = int(self._loc.args.num_queries)
+        if W * Nq > MAX_POOL:
+            raise ValueError(f"VideoLibrary: n_windows={W} x num_queries={Nq} = {W * Nq} candidates > {MAX_POOL} in one pool")
+        check_queries([int(q[0].shape[0]) for q in queries], self.max_q_l)
+        subset, ids = self._search_ids(videos)
+        if not queries or not ids:
+            return [[] for _ in queries]
+        self._check_live()
+        if self._flags & _lib.SESSION_BF16:
+            raise _lib.ConeHipError("VideoLibrary: search_moments: CONE_SESSION_BF16 libraries are not supported (prefilter_bf16)")
+        lib, dev = _lib.load(), self._loc.device
+        table = self._table(subset, ids)
+        ids, V = table[0], len(table[0])
+        scans, budgets = [], []
+        for g in range(0, len(queries), MAX_QUERIES):
+            chunk = queries[g:g + MAX_QUERIES]
+            widx, wval, _ = self._scan(table, chunk, 1)
+            scans.append((g, chunk, widx, wval))
+            budgets.append(self._budget(scans[-1], V, W))
+        host = (budgets[0] if len(budgets) == 1 else torch.cat(budgets)).cpu()        # the one small read-back
+        # the plan of every scan: its pairs in the budget's order (per query: best score descending, ties to the lower slot) and
+        # where each pair's candidates lie in the ONE buffer of the search
+        plans, at, n_rows = [], 0, 0
+        for scan in scans:
+            nq = len(scan[1])
+            n_pairs = host[at:at + nq].tolist()
+            slots, counts = (host[at + nq + k * nq * W:at + nq + (k + 1) * nq * W].reshape(nq, W) for k in range(2))
+            at += nq + 3 * nq * W
+            chosen = [(q, int(slots[q, i]), int(counts[q, i])) for q in range(nq) for i in range(n_pairs[q])]
+            vids = [self._videos[ids[slot]] for _, slot, _ in chosen]
+            calls = plan_ragged_calls([v[0] for v in vids], [c[2] for c in chosen])
+            row_of = [0] * len(chosen)
+            for idx in calls:
+                for i in idx:
+                    row_of[i] = n_rows
+                    n_rows += chosen[i][2] * Nq
+            plans.append((chosen, vids, calls, row_of, n_pairs))
+        cand = torch.empty(max(n_rows, 1), 4, dtype=torch.float32, device=dev)
+        for scan, (chosen, vids, calls, row_of, _) in zip(scans, plans):
+            for idx in calls:
+                self._enqueue_ragged([(vids[i][:2], scan[1][chosen[i][0]], chosen[i][0], chosen[i][1]) for i in idx],
+                                     [chosen[i][2] for i in idx], scan, V, cand=cand[row_of[idx[0]]:])
+        # the segment table of the whole search, one upload: seg_cand (int64) | seg_n | seg_tag | every scan's seg_off (int32)
+        n_seg = sum(len(p[0]) for p in plans)
+        words = np.zeros(2 * n_seg + 2 * n_seg + sum(len(s[1]) + 1 for s in scans) + 1, dtype=np.int32)
+        seg_cand, seg_n, seg_tag = words[:2 * n_seg].view(np.int64), words[2 * n_seg:3 * n_seg], words[3 * n_seg:4 * n_seg]
+        off_at, seg_at, launches = 4 * n_seg, 0, []
+        for scan, (chosen, _, _, row_of, n_pairs) in zip(scans, plans):
+            nq = len(scan[1])
+            seg_cand[seg_at:seg_at + len(chosen)] = row_of
+            seg_n[seg_at:seg_at + len(chosen)] = [c[2] * Nq for c in chosen]
+            seg_tag[seg_at:seg_at + len(chosen)] = [c[1] for c in chosen]
+            words[off_at + 1:off_at + nq + 1] = np.cumsum(n_pairs)
+            launches.append((nq, off_at, seg_at, len(chosen)))
+            off_at += nq + 1
+            seg_at += len(chosen)
+        tab = torch.from_numpy(words).to(dev)
+        # out_rows | out_seg | out_n of every scan in ONE tensor (8-byte words: the rows stay aligned)
+        sizes = [(nq * M * 5, (nq * M + nq + 1) // 2) for nq, _, _, _ in launches]
+        out = torch.empty(sum(a + b for a, b in sizes), dtype=torch.float64, device=dev)
+        o = 0
+        for (nq, off, seg0, ns), (n_r, n_i) in zip(launches, sizes):
+            p = lambda word: C.c_void_p(tab.data_ptr() + 4 * word)
+            _lib.check(lib.cone_corpus_fuse_nms(_lib.ptr(cand), p(off), p(2 * seg0), p(2 * n_seg + seg0), p(3 * n_seg + seg0), nq, ns,
+                                                NMS_THD, MAX_BEFORE, M, C.c_void_p(out.data_ptr() + 8 * o),
+                                                C.c_void_p(out.data_ptr() + 8 * (o + n_r)),
+                                                C.c_void_p(out.data_ptr() + 8 * (o + n_r) + 4 * nq * M), _lib.stream()))
+            o += n_r + n_i
+        host = out.cpu()                                                            # the moments' one read-back
+        res, o = [], 0
+        for (nq, _, _, _), (n_r, n_i), (chosen, _, _, _, n_pairs) in zip(launches, sizes, plans):
+            rows = host[o:o + n_r].view(nq, M, 5).tolist()
+            ints = host[o + n_r:o + n_r + n_i].view(torch.int32)
+            seg, n = ints[:nq * M].view(nq, M).tolist(), ints[nq * M:nq * M + nq].tolist()
+            o += n_r + n_i
+            first = [0] + np.cumsum(n_pairs).tolist()
+            for q in range(nq):
+                res.append([(ids[chosen[first[q] + seg[q][j]][1]], [rows[q][j][0], rows[q][j][1], rows[q][j][4]]) for j in range(n[q])])
+        return res

@@ -781,6 +781,51 @@ int cone_library_localize_ragged(const cone_model* m, const cone_library* lib, c
                                  const int32_t* scan_widx, const float* scan_wval, int scan_nq, int64_t scan_n_videos, int scan_K,
                                  double* kept, int32_t* n_kept, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------ library moment search (additive in ABI 8)
+ * "The n best moments for this query in everything the library holds."  Every per-(video, query) answer above is normalised over
+ * the candidates of that one pair (run_on_video/cone_localizator.py:200-206: each pair's best proposal becomes 1.0, whatever its
+ * logit), so the lists of different videos cannot be merged.  The reference's own rule answers it: everything that came out of the
+ * chosen windows is ONE candidate pool -- in predict_moment the topk_window windows of one video, here the W windows a budget chose
+ * library-wide.  Two pieces: cone_library_localize_candidates is cone_library_localize_ragged stopped before its per-pair stage C;
+ * cone_corpus_fuse_nms is stage C over a pool per query, where a moment belongs to a video. */
+
+/* Stage C (run_on_video/cone_localizator.py:187-221; utils/temporal_nms.py:25-74) over one pool per query, the fused ranking only;
+ * one workgroup per query, fp64, cone_fuse_nms' arithmetic.  cand: fp32 rows [st, ed, prop, match], the flat candidate buffer of
+ * a whole search (device).  The segment table (device): query q owns segments [seg_off[q], seg_off[q + 1]) (seg_off (nq + 1)
+ * int32), segment s is the seg_n[s] (int32) rows from row seg_cand[s] (int64) on, of the video seg_tag[s] (int32; equal tags
+ * inside a query are one video).  The pool of a query = its segments in table order, each one's rows in buffer order:
+ *   1. all four columns rounded to 4 decimals;  2. normalize_score on the pool's proposal column and on its matching column, each
+ *   over the WHOLE pool (mn == mx: the raw values);  3. fused = (0 + a) + b;  4. a dict keyed by (tag, st, ed): the first
+ *   occurrence fixes the position, the last the values;  5. stable descending sort by fused;  6. the first max_before;
+ *   7. greedy temporal NMS in which a kept moment suppresses a later one only where the TAGS ARE EQUAL and pseudo-IoU > nms_thd
+ *   (a list of one is returned untouched; nms_thd == -1 skips the NMS);  8. the first max_after.
+ * Outputs (device), every element written: out_rows (nq, max_after, 5) fp64 [st, ed, prop, match, fused], zeros past the kept
+ * rows; out_seg (nq, max_after) int32 = the kept moment's segment ordinal within its query (of its key's first occurrence), -1
+ * past them; out_n (nq).  A query without segments answers 0.
+ * At most 1 024 candidates per query.  The table is device data: the kernel takes candidates until a query's pool holds 1 024
+ * and truncates the segment that crosses the cap, so a query whose table holds more answers for ITS FIRST 1 024 CANDIDATES;
+ * segment indices are clamped to [0, n_seg), a negative seg_n counts as 0.  No atomics, no allocation, no read-back.
+ * Refused by name ("corpus_fuse_nms: "), from host values first, before any pointer is looked at: nq outside [1, 1024];
+ * n_seg < 0; max_after outside [1, 1024]; max_before < 1; then null arguments (cand and the three per-segment arrays may be NULL
+ * where n_seg == 0). */
+int cone_corpus_fuse_nms(const float* cand, const int32_t* seg_off, const int64_t* seg_cand, const int32_t* seg_n,
+                         const int32_t* seg_tag, int nq, int n_seg, double nms_thd, int max_before, int max_after,
+                         double* out_rows, int32_t* out_seg, int32_t* out_n, void* stream);
+
+/* cone_library_localize_ragged (run_on_video/cone_localizator.py:121-198) with `float* cand` in place of kept / n_kept: the same
+ * launches up to cone_compose_rows, which writes the call's B * Nq rows (B = sum of pair_k, Nq = the decoder's slots) straight
+ * into cand -- pair order, then window order, then decoder slot: pair p's rows start at (window rows before p) * Nq -- and NO
+ * cone_fuse_nms.  Both stage-A forms.  ws >= cone_library_localize_candidates_workspace (same arguments as the ragged size entry).
+ * Refused by name ("library_localize_candidates: "): what cone_library_localize_ragged refuses, in its order. */
+size_t cone_library_localize_candidates_workspace(const cone_model* m, const cone_library* lib, const int32_t* q_row0,
+                                                  const int32_t* q_ctx_l, const int32_t* tok_len, int nq, const int32_t* pair_k,
+                                                  const cone_session_params* params, int ranked);
+int cone_library_localize_candidates(const cone_model* m, const cone_library* lib, const int32_t* q_row0, const int32_t* q_ctx_l,
+                                     const float* tok, const int32_t* tok_len, int nq, const float* cls, const int32_t* pair_k,
+                                     const cone_session_params* params, const int32_t* pair_query, const int32_t* pair_slot,
+                                     const int32_t* scan_widx, const float* scan_wval, int scan_nq, int64_t scan_n_videos, int scan_K,
+                                     float* cand, void* ws, size_t ws_bytes, void* stream);
+
 /* -------------------------------------------------------------------- metrics on the device
  * Recall@K / IoU counts from the kept rows (layout of cone_fuse_nms: rows (nq, max_after, 5) fp64 [st, ed, ...],
  * n (nq) valid rows) and one target span per query gt (nq, 2) fp64 seconds -- device pointers.  thresholds /
