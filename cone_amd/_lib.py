@@ -256,6 +256,12 @@ _SIGNATURES = {
                                                    C.POINTER(SessionParams), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p,
                                                    C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                                    C.c_void_p]),
+    # standing queries (additive in ABI 8): the plan of a poll over the cache of (query, window) candidate rows, and the scatter
+    # cone_watch_plan(widx, wval (device), nq, K, stamp (device), n_win, ctx_l, W, Nq, miss_widx, miss_wval, n_miss, seg_off,
+    # seg_cand, seg_n, seg_tag (device), stream)
+    "cone_watch_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 8),
+    # cone_watch_store(cand, miss_widx, n_miss (device), nq, K, n_win, ctx_l, Nq, cache, stamp (device), stream)
+    "cone_watch_store": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p] * 3),
     # cone_test_gemm(A, A2, a2_mod, W, bias, R, ln_g, ln_b, C, C2, ADD, M, N, K, flags, stream)
     "cone_test_gemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,

@@ -47,17 +47,24 @@ one upload and one ``cone_library_add`` per run of adjacent ranges (``plan_runs`
 ``add`` calls leave; ``extend`` appends clips to a resident video -- in place when the rows behind it are free
 (``RowRanges.take_at``), else by moving it into a hole that holds all of it (``plan_extend``) -- indexing only the new rows;
 ``trim`` drops a video's oldest clips without a launch.  ``extend`` + ``trim`` are the sliding window of a live recording.
+
+``watch`` is what a live recording is for: a fixed set of queries asked again after every few new clips.  A ``VideoWatcher``
+(cone_amd/watch.py) keeps the candidate rows of every (query, window) it has computed; its ``poll`` runs the window model only on
+the listed windows it has not seen, or saw while they were still growing, and stage C on the cache -- the answer is still
+``predict_moment``'s, ``==``.  A ``trim`` resets the video's watchers (``_trimmed``); moves change nothing.
 Out of scope here: certified window ranking, headroom reserved behind a video, capturing the call in a graph.
 """
 from __future__ import annotations
 
 import ctypes as C
 import operator
+import weakref
 
 import torch
 
 from . import _lib, ops
 from .session import MAX_QUERIES, NMS_THD, MAX_BEFORE, MAX_AFTER, VideoSession, _kept_bytes, check_queries
+from .watch import VideoWatcher
 
 MAX_POOL = 1024     # candidates of one query in cone_corpus_fuse_nms (csrc/stage_c.h: kMaxCand)
 
@@ -293,6 +300,8 @@ class VideoLibrary:
     id (never reused); ``predict_moments([(id, (tok, cls)), ...])`` returns, per pair and in the order given, what the
     localizer's ``predict_moment`` returns for that video and query, ``==``.  ``rank_videos`` / ``search`` answer "which video,
     and where" without the caller naming one.  ``compact`` / ``resize`` move the resident rows bit for bit: see the module text."""
+
+    _watchers = None                        # a weak set of the VideoWatchers ``watch`` has handed out (none yet)
 
     def __init__(self, localizer, capacity_clips: int):
         from .model import Workspace
@@ -532,6 +541,8 @@ class VideoLibrary:
             self._rows.release(row0, n_front)
             self._videos[vid_id] = (row0 + n_front, n - n_front, self._k(n - n_front))
             self._scan_cache = None
+            for w in list(self._watchers or ()):        # seconds and window indices shift: what a watcher has cached is stale
+                w._trimmed(vid_id)
         return n - n_front
 
     # ---- maintenance ---------------------------------------------------------------------------
@@ -746,6 +757,33 @@ class VideoLibrary:
     def predict_moment(self, vid_id, text_feats):
         """``localizer.predict_moment(video_feats, text_feats)`` for the resident video ``vid_id``."""
         return self.predict_moments([(vid_id, text_feats)])[0]
+
+    # ---- standing queries ----------------------------------------------------------------------
+    def watch(self, vid_id, queries):
+        """A ``VideoWatcher`` for the standing ``queries`` = ``[(tok, cls), ...]`` (any count >= 1, 64 a call) on the resident
+        video ``vid_id``: ``w.poll()`` returns one moment list per query, each ``==`` ``predict_moment(<the video's current
+        clips>, query)`` after any sequence of ``extend`` / ``trim`` / ``compact`` / ``resize`` and ``add`` / ``remove`` of other
+        videos, and runs the window model only on the listed windows it has not answered from before (``w.windows_run``, of
+        ``w.windows_listed``); a ``trim`` makes the next poll run them all.  ``remove(vid_id)`` makes later polls raise.  The
+        watcher keeps ``num_queries`` rows of 16 B and a 4-B stamp per query and window of the video (``w.nbytes``; 7.7 MB for
+        64 queries on 33 000 clips).  fp32 libraries only; ``topk_window * num_queries`` may not exceed 1 024 candidates."""
+        self._video(vid_id)
+        queries = list(queries)
+        if not queries:
+            raise ValueError("VideoLibrary: watch: an empty query list (a watcher needs at least one standing query)")
+        check_queries([int(q[0].shape[0]) for q in queries], self.max_q_l)
+        K, Nq = int(self._loc.args.topk_window), int(self._loc.args.num_queries)
+        if K * Nq > MAX_POOL:
+            raise ValueError(f"VideoLibrary: topk_window={K} x num_queries={Nq} = {K * Nq} candidates > {MAX_POOL} in one pool")
+        self._check_live()
+        if self._flags & _lib.SESSION_BF16:
+            raise _lib.ConeHipError("watch: CONE_SESSION_BF16 libraries are not supported (prefilter_bf16): the scan that lists a "
+                                    "poll's windows does not serve them")
+        w = VideoWatcher(self, vid_id, queries)
+        if self._watchers is None:
+            self._watchers = weakref.WeakSet()
+        self._watchers.add(w)
+        return w
 
     # ---- search --------------------------------------------------------------------------------
     def _search_ids(self, videos):

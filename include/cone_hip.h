@@ -826,6 +826,47 @@ int cone_library_localize_candidates(const cone_model* m, const cone_library* li
                                      const int32_t* scan_widx, const float* scan_wval, int scan_nq, int64_t scan_n_videos, int scan_K,
                                      float* cand, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------ standing queries (additive in ABI 8)
+ * A fixed set of queries asked again whenever a live video has grown by a few clips.  A window's candidate rows depend on nothing
+ * outside the window: cone_window_table gives window wi the clips [max((wi - 1) S, 0), min((wi - 1) S + W, ctx_l)), S = W / 2,
+ * batch_pad is W for every pair, and a row [st, ed, prop, match] is made from video_start and the window's own outputs
+ * (run_on_video/cone_localizator.py:150-198).  So a watcher (cone_amd/watch.py) keeps the rows of every (query, window) it has
+ * computed and runs cone_library_localize_candidates only on the listed windows it has not seen, or saw while they were still
+ * growing; cone_corpus_fuse_nms then runs on the cache.  The answer carries the bits of predict_moment.
+ *   cache (nq, n_win, Nq, 4) fp32: the Nq candidate rows of window wi for query q at row (q n_win + wi) Nq.
+ *   stamp (nq, n_win) int32: the video's ctx_l when the entry was computed; 0 = never.
+ * VALIDITY at the current ctx_l: entry (q, wi) is valid iff stamp == ctx_l, or stamp > 0 and (wi - 1) S + W <= stamp (the window
+ * was full when it was computed: its clip range then is its clip range now).  A trim moves the first clip: the caller zeroes the
+ * stamps.  Both entries are one small launch, one workgroup per query, plain vector loads and stores: no atomics, no allocation,
+ * no read-back. */
+
+/* The plan of one poll for nq queries.  widx / wval (nq, K): the lists of a cone_library_scan over ONE video (device).  An entry
+ * j is LISTED when 0 <= widx < n_win (a device-side clamp; the padding -1 is not listed) and MISSING when it is listed and not
+ * valid by the rule above.  Outputs (device), every element written:
+ *   miss_widx / miss_wval (nq, K): the missing entries of query q in list order (stable) in [0, n_miss[q]), then -1 / -inf: the
+ *     lists' block of a cone_library_localize_candidates call with pair_query = q, pair_slot = 0, scan_n_videos = 1, scan_K = K,
+ *     pair_k = n_miss[q] (a query with n_miss == 0 is left out of that call);
+ *   n_miss (nq);
+ *   the DENSE segment table of cone_corpus_fuse_nms over the cache: seg_off (nq + 1) = q K; segment q K + j has seg_cand (int64) =
+ *     (q n_win + widx) Nq and seg_n = Nq when entry j is listed, else 0 and 0; seg_tag = 0.  The table does not depend on hit or
+ *     miss: a missing window's rows are in place (cone_watch_store) before stage C runs.
+ * Refused by name ("watch_plan: "), from host values first, in this order, before any pointer is looked at: nq outside [1, 64];
+ * K outside [1, 256]; Nq outside [1, 16]; n_win < 1; ctx_l < 1; W < 2; then null arguments. */
+int cone_watch_plan(const int32_t* widx, const float* wval, int nq, int K, const int32_t* stamp, int n_win, int ctx_l, int W, int Nq,
+                    int32_t* miss_widx, float* miss_wval, int32_t* n_miss, int32_t* seg_off, int64_t* seg_cand,
+                    int32_t* seg_n, int32_t* seg_tag, void* stream);
+
+/* Scatters the rows a cone_library_localize_candidates call wrote for the plan's miss lists into the cache and stamps them.
+ * cand: that call's buffer -- query q's first row is Nq * (sum over q' < q of min(max(n_miss[q'], 0), K)): queries without a miss
+ * contribute nothing, so leaving them out of the call shifts nobody.  For m < min(max(n_miss[q], 0), K) with wi = miss_widx[q][m]
+ * inside [0, n_win): the Nq rows of 16 B go to cache rows (q n_win + wi) Nq .., stamp[q][wi] = ctx_l; an index outside is skipped.
+ * Nothing else is written.  PRECONDITION: the window indices of one query are distinct (a top-k list guarantees it) -- two equal
+ * indices would be two writers of one row.  cand and cache must be 16-B aligned.
+ * Refused by name ("watch_store: "), from host values first, in this order: nq outside [1, 64]; K outside [1, 256]; n_win < 1;
+ * ctx_l < 1; Nq outside [1, 16]; then null arguments, then a misaligned cand or cache. */
+int cone_watch_store(const float* cand, const int32_t* miss_widx, const int32_t* n_miss, int nq, int K, int n_win, int ctx_l, int Nq,
+                     float* cache, int32_t* stamp, void* stream);
+
 /* -------------------------------------------------------------------- metrics on the device
  * Recall@K / IoU counts from the kept rows (layout of cone_fuse_nms: rows (nq, max_after, 5) fp64 [st, ed, ...],
  * n (nq) valid rows) and one target span per query gt (nq, 2) fp64 seconds -- device pointers.  thresholds /
