@@ -380,6 +380,13 @@ def check(rc: int):
         raise ConeHipError(f"libcone_hip error {rc}: {load().cone_last_error().decode()}")
 
 
+def sized(nbytes: int) -> int:
+    """The result of a ``*_workspace`` / ``*_bytes`` entry: a size of 0 means the call was refused."""
+    if nbytes == 0:
+        raise ConeHipError(f"libcone_hip error: {load().cone_last_error().decode()}")
+    return nbytes
+
+
 def ptr(t, dtype=None):
     """Device pointer of a contiguous CUDA(HIP) tensor (None -> NULL)."""
     import torch

@@ -2,15 +2,20 @@
 // Video libraries ("video libraries"): many videos in the rows of one arena, one call for queries on any mix of them.
 // Library search ("library search"): the query half on the window lists of a cone_library_scan (csrc/prefilter.hip).
 // Library window budgets ("library window budgets"): the query half with a window count per pair (cone_library_localize_ragged;
-// its own layout kernel and a gather of every pair's prefix -- the budget itself is csrc/library_budget.hip).
+// the budget itself is csrc/library_budget.hip).
 // Library moment search ("library moment search"): the ragged call that ends at its candidate rows
 // (cone_library_localize_candidates; the pooled stage C is csrc/library_corpus.hip).
 //
-// Nothing is computed here.  cone_session_index / cone_library_add and cone_session_localize / cone_library_localize only
-// SEQUENCE the library's own extern "C" launchers -- the calls cone_amd/localizator.py issues one by one through ctypes for
-// run_on_video/cone_localizator.py:121-221 -- and carve their operands out of the caller's arena / workspace.  The layout kernels
-// of this file write a call's index metadata (what the localizer keeps per shape in _const) from lengths, row
-// offsets and clip counts that travel as kernel arguments.
+// Nothing is computed here.  cone_session_index / cone_library_add and the localize entries only SEQUENCE the library's own
+// extern "C" launchers -- the calls cone_amd/localizator.py issues one by one through ctypes for
+// run_on_video/cone_localizator.py:121-221 -- and carve their operands out of the caller's arena / workspace.
+//
+// The query half is ONE path.  Every size / run entry fills a QueryCall -- the descriptor that names everything such a call can
+// carry -- and walks the same named steps in its own order: a precheck on host values (library_precheck, ranked_precheck,
+// ragged_precheck), check_lists where a scan's lists come along, resolve (handle, dims, localize_layout, "misses a region",
+// "workspace too small"), and for a run entry localize.  A _workspace twin is the same steps stopping after the layout.
+// ONE layout kernel writes a call's index metadata (what the localizer keeps per shape in _const) from each query's
+// (len, row0, ctx_l, k), which travel as kernel arguments: a session is row0 = 0 and one ctx_l, a uniform call is k = K.
 #include "common.h"
 
 namespace cone {
@@ -104,71 +109,34 @@ static Resident resident_of(const cone_library& B) {
     return {B.model, B.flags, B.v_dim, B.hidden_dim, B.vid_norm, B.adapted, B.adapted_bf16, nullptr, B.vproj, B.qkv_vid};
 }
 
-// ------------------------------------------------------------------------------ the query half
-struct QueryLens { int32_t len[CONE_SESSION_MAX_QUERIES]; };
-
-struct QueryPairs { int32_t len[CONE_SESSION_MAX_QUERIES], row0[CONE_SESSION_MAX_QUERIES], ctx_l[CONE_SESSION_MAX_QUERIES]; };
+// ------------------------------------------------------------------------------ the query half: the layout kernel
+// Per query, as kernel arguments: token length, first arena row and clips of its video, window count.
+struct QueryShape {
+    int32_t len[CONE_SESSION_MAX_QUERIES], row0[CONE_SESSION_MAX_QUERIES], ctx_l[CONE_SESSION_MAX_QUERIES], k[CONE_SESSION_MAX_QUERIES];
+};
+// ctx_l: every query's clips where q_ctx_l is NULL (a session); K: every query's windows where pair_k is NULL (a uniform call)
+static QueryShape shape_of(const int32_t* tok_len, const int32_t* q_row0, const int32_t* q_ctx_l, const int32_t* pair_k, int nq,
+                           int64_t ctx_l, int K) {
+    QueryShape P{};
+    for (int q = 0; q < nq; ++q) {
+        P.len[q] = tok_len[q];
+        P.row0[q] = q_row0 ? q_row0[q] : 0;
+        P.ctx_l[q] = q_ctx_l ? q_ctx_l[q] : (int32_t)ctx_l;
+        P.k[q] = pair_k ? pair_k[q] : K;
+    }
+    return P;
+}
+// The arrays the kernel writes.  row_q / row_slot / cand_off: only a ragged call passes them (NULL: not written).
+struct LayoutOut {
+    int32_t *tok_off, *tok_len, *tok_idx, *q_ctx_l, *q_vid_off, *batch_pad, *full_w, *n_valid, *row_q, *row_slot;
+    int64_t* cand_off;
+};
 
 // One workgroup.  Every output element has one writer; nothing outside the documented extents is touched:
-// tok_off [0, nq], the per-query arrays [0, nq), full_w [0, nq K), tok_idx [0, sum of the lengths).
-// in_len: the token lengths (kernel arguments); ctx_of / off_of: query -> clips of its video / first arena row of its video.
-template <class CtxOf, class OffOf>
-__device__ __forceinline__ void layout_body(const int32_t* in_len, CtxOf ctx_of, OffOf off_of, int nq, int max_q_l, int K,
-                                            int n_cand_rows, int W, int* __restrict__ tok_off, int* __restrict__ tok_len,
-                                            int* __restrict__ tok_idx, int* __restrict__ q_ctx_l, int* __restrict__ q_vid_off,
-                                            int* __restrict__ batch_pad, int* __restrict__ full_w, int* __restrict__ n_valid) {
-    __shared__ int off[CONE_SESSION_MAX_QUERIES + 1];
-    __shared__ int len[CONE_SESSION_MAX_QUERIES];
-    const int t = threadIdx.x;
-    if (t == 0) {
-        int a = 0;
-        for (int q = 0; q < nq; ++q) { off[q] = a; len[q] = in_len[q]; a += in_len[q]; }
-        off[nq] = a;
-    }
-    __syncthreads();
-    for (int q = t; q < nq; q += blockDim.x) {
-        tok_off[q] = off[q]; tok_len[q] = len[q];
-        q_ctx_l[q] = ctx_of(q); q_vid_off[q] = off_of(q); batch_pad[q] = W; n_valid[q] = n_cand_rows;
-    }
-    if (t == 0) tok_off[nq] = off[nq];
-    for (int i = t; i < nq * K; i += blockDim.x) full_w[i] = W;
-    for (int i = t; i < nq * max_q_l; i += blockDim.x) {
-        const int q = i / max_q_l, j = i - q * max_q_l;
-        if (j < len[q]) tok_idx[off[q] + j] = j;
-    }
-}
-
-__global__ __launch_bounds__(256) void session_layout_kernel(QueryLens L, int nq, int max_q_l, int ctx_l, int K, int n_cand_rows,
-                                                             int W, int* __restrict__ tok_off, int* __restrict__ tok_len,
-                                                             int* __restrict__ tok_idx, int* __restrict__ q_ctx_l,
-                                                             int* __restrict__ q_vid_off, int* __restrict__ batch_pad,
-                                                             int* __restrict__ full_w, int* __restrict__ n_valid) {
-    layout_body(L.len, [=](int) { return ctx_l; }, [](int) { return 0; }, nq, max_q_l, K, n_cand_rows, W, tok_off, tok_len, tok_idx,
-                q_ctx_l, q_vid_off, batch_pad, full_w, n_valid);
-}
-
-// The library's form: every query brings the clips and the first arena row of ITS video.
-__global__ __launch_bounds__(256) void library_layout_kernel(QueryPairs P, int nq, int max_q_l, int K, int n_cand_rows, int W,
-                                                             int* __restrict__ tok_off, int* __restrict__ tok_len,
-                                                             int* __restrict__ tok_idx, int* __restrict__ q_ctx_l,
-                                                             int* __restrict__ q_vid_off, int* __restrict__ batch_pad,
-                                                             int* __restrict__ full_w, int* __restrict__ n_valid) {
-    const int32_t *ctx = P.ctx_l, *row0 = P.row0;
-    layout_body(P.len, [=](int q) { return ctx[q]; }, [=](int q) { return row0[q]; }, nq, max_q_l, K, n_cand_rows, W, tok_off,
-                tok_len, tok_idx, q_ctx_l, q_vid_off, batch_pad, full_w, n_valid);
-}
-
-// The ragged form (cone_library_localize_ragged): pair q brings its own window count k[q] <= Kmax.  What library_layout_kernel
-// writes, except that the window rows are the concatenation of the pairs' k[q] rows: row_q / row_slot / full_w [0, sum k),
-// n_valid[q] = k[q] Nq, cand_off[q] = (rows before pair q) Nq.  One workgroup, one writer per element.
-struct RaggedK { int32_t k[CONE_SESSION_MAX_QUERIES]; };
-__global__ __launch_bounds__(256) void library_ragged_layout_kernel(QueryPairs P, RaggedK R, int nq, int max_q_l, int Kmax, int Nq,
-                                                                    int W, int* __restrict__ tok_off, int* __restrict__ tok_len,
-                                                                    int* __restrict__ tok_idx, int* __restrict__ q_ctx_l,
-                                                                    int* __restrict__ q_vid_off, int* __restrict__ batch_pad,
-                                                                    int* __restrict__ full_w, int* __restrict__ n_valid,
-                                                                    int* __restrict__ row_q, int* __restrict__ row_slot,
-                                                                    int64_t* __restrict__ cand_off) {
+// tok_off [0, nq], the per-query arrays [0, nq), tok_idx [0, sum of the lengths), and over the window rows -- the concatenation
+// of the queries' k[q] rows, nq K of them in a uniform call -- full_w / row_q / row_slot [0, sum k).
+// n_valid[q] = k[q] Nq, cand_off[q] = (rows before query q) Nq.
+__global__ __launch_bounds__(256) void query_layout_kernel(QueryShape P, int nq, int max_q_l, int Kmax, int Nq, int W, LayoutOut o) {
     __shared__ int off[CONE_SESSION_MAX_QUERIES + 1];       // exclusive prefix sums of the token lengths
     __shared__ int woff[CONE_SESSION_MAX_QUERIES + 1];      // ... of the window counts
     __shared__ int len[CONE_SESSION_MAX_QUERIES];
@@ -177,27 +145,78 @@ __global__ __launch_bounds__(256) void library_ragged_layout_kernel(QueryPairs P
     if (t == 0) {
         int a = 0, b = 0;
         for (int q = 0; q < nq; ++q) {
-            off[q] = a; woff[q] = b; len[q] = P.len[q]; kq[q] = R.k[q];
-            a += P.len[q]; b += R.k[q];
+            off[q] = a; woff[q] = b; len[q] = P.len[q]; kq[q] = P.k[q];
+            a += P.len[q]; b += P.k[q];
         }
         off[nq] = a; woff[nq] = b;
     }
     __syncthreads();
     for (int q = t; q < nq; q += blockDim.x) {
-        tok_off[q] = off[q]; tok_len[q] = len[q];
-        q_ctx_l[q] = P.ctx_l[q]; q_vid_off[q] = P.row0[q]; batch_pad[q] = W;
-        n_valid[q] = kq[q] * Nq; cand_off[q] = (int64_t)woff[q] * Nq;
+        o.tok_off[q] = off[q]; o.tok_len[q] = len[q];
+        o.q_ctx_l[q] = P.ctx_l[q]; o.q_vid_off[q] = P.row0[q]; o.batch_pad[q] = W;
+        o.n_valid[q] = kq[q] * Nq;
+        if (o.cand_off) o.cand_off[q] = (int64_t)woff[q] * Nq;
     }
-    if (t == 0) tok_off[nq] = off[nq];
+    if (t == 0) o.tok_off[nq] = off[nq];
     for (int i = t; i < nq * Kmax; i += blockDim.x) {
         const int q = i / Kmax, j = i - q * Kmax;
-        if (j < kq[q]) { const int b = woff[q] + j; row_q[b] = q; row_slot[b] = j; full_w[b] = W; }
+        if (j < kq[q]) {
+            const int b = woff[q] + j;
+            o.full_w[b] = W;
+            if (o.row_q) { o.row_q[b] = q; o.row_slot[b] = j; }
+        }
     }
     for (int i = t; i < nq * max_q_l; i += blockDim.x) {
         const int q = i / max_q_l, j = i - q * max_q_l;
-        if (j < len[q]) tok_idx[off[q] + j] = j;
+        if (j < len[q]) o.tok_idx[off[q] + j] = j;
     }
 }
+static int launch_layout(const QueryShape& P, int nq, int max_q_l, int Kmax, int Nq, int W, const LayoutOut& o, void* stream) {
+    hipLaunchKernelGGL(query_layout_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, P, nq, max_q_l, Kmax, Nq, W, o);
+    CONE_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------ the query half: the descriptor
+// "The lists are here": the window lists of a cone_library_scan -- (scan_nq, n_videos, scan_K) on the device -- and, per pair of
+// this call, the scan's query index and table slot (host values: kernel arguments, nothing is uploaded).
+struct RankedPairs { int32_t query[CONE_SESSION_MAX_QUERIES], slot[CONE_SESSION_MAX_QUERIES]; };
+struct RankedLists {
+    const int32_t* widx;
+    const float* wval;
+    int64_t n_videos;
+    int scan_K;
+    RankedPairs pairs;
+};
+
+// Everything a query-half call can carry.  An entry fills what it has -- the rest stays zero -- and the steps below read it.
+struct QueryCall {
+    const char *who, *what;                     // the entry's name in its messages; "session" / "library"
+    const cone_model* model;
+    cone_model_dims dims;                       // (resolve fills them)
+    bool resident;                              // the caller passed a session / library: res and rows are its
+    Resident res;
+    int64_t rows;                               // the session's ctx_l, or the library's capacity
+    const int32_t *q_row0, *q_ctx_l;            // per query, its video's first arena row and clips; NULL: a session (one video at row 0)
+    const float* tok;
+    const int32_t* tok_len;
+    int nq;
+    const float* cls;
+    int K, n_cand;                              // windows per query (a ragged call: the largest count, ragged_precheck's)
+    const cone_session_params* params;
+    const int32_t* pair_k;                      // a window count per pair; NULL: a uniform call
+    bool ranked;                                // stage A is a scan's: `lists` (a size entry knows only that much)
+    const int32_t *pair_query, *pair_slot;      // as the caller passed them: check_lists vets them into lists.pairs
+    int scan_nq;
+    RankedLists lists;
+    bool to_cand;                               // the call ends at its candidate rows: `cand` is the output, kept / n_kept are not touched
+    double* kept;
+    int32_t *n_kept, *certified;
+    float* cand;
+    void* ws;
+    size_t ws_bytes;
+    void* stream;
+};
 
 static int check_queries(const char* who, const int32_t* tok_len, int nq, int max_q_l, int64_t* total) {
     CONE_REQUIRE(tok_len, "%s: null argument", who);
@@ -249,8 +268,8 @@ static int check_ragged(const char* who, const int32_t* pair_k, const int32_t* q
 // Consecutive queries of one video: one stage A.  A session is one run.
 struct Run { int q0, n; int64_t row0, ctx_l, nw; size_t score_off; int k; size_t st_off; };     // (k, st_off: a ragged call's)
 
-// Every buffer and every launcher's scratch of one cone_session_localize / cone_library_localize call: the ONE function
-// behind the workspace-size entries and the entries themselves.  Each take() is a region of its own.
+// Every buffer and every launcher's scratch of one call: the ONE function behind the workspace-size entries and the entries
+// themselves.  Each take() is a region of its own.
 struct LocalizeLayout {
     Run runs[CONE_SESSION_MAX_QUERIES];
     int n_runs;
@@ -263,38 +282,41 @@ struct LocalizeLayout {
     int B;
     bool use_l0, use_txt_pos;
 };
-// rows: the session's ctx_l, or the library's capacity; q_row0 / q_ctx_l: NULL for a session (one run over all of its rows).
-static int localize_layout(const char* who, const char* what, const cone_model* m, const cone_model_dims& d, const Resident* ses,
-                           int64_t rows, const int32_t* q_row0, const int32_t* q_ctx_l, const int32_t* tok_len, int nq, int K,
-                           int n_cand, const cone_session_params* p, LocalizeLayout* out, bool ranked = false,
-                           const int32_t* pair_k = nullptr) {      // pair_k: a ragged call (K = their maximum, check_ragged's)
-    CONE_REQUIRE(m && ses && p, "%s: null argument", who);
-    CONE_REQUIRE(ses->model == m, "%s: the %s was indexed with another handle", who, what);
-    CONE_REQUIRE(flags_ok(ses->flags), "%s: bad %s flags %d", who, what, ses->flags);
+static int localize_layout(const QueryCall& c, LocalizeLayout* out) {
+    const char* who = c.who;
+    const cone_model* m = c.model;
+    const cone_model_dims& d = c.dims;
+    const Resident* ses = &c.res;
+    const cone_session_params* p = c.params;
+    const int32_t* pair_k = c.pair_k;
+    const int nq = c.nq, K = c.K;
+    CONE_REQUIRE(m && c.resident && p, "%s: null argument", who);
+    CONE_REQUIRE(ses->model == m, "%s: the %s was indexed with another handle", who, c.what);
+    CONE_REQUIRE(flags_ok(ses->flags), "%s: bad %s flags %d", who, c.what, ses->flags);
     CONE_REQUIRE(ses->v_dim == d.v_dim && ses->hidden_dim == d.hidden_dim, "%s: the %s's row widths %d / %d are not the handle's %d / %d",
-                 who, what, ses->v_dim, ses->hidden_dim, d.v_dim, d.hidden_dim);
+                 who, c.what, ses->v_dim, ses->hidden_dim, d.v_dim, d.hidden_dim);
     CONE_REQUIRE(p->max_v_l >= 2 && p->max_after >= 1 && p->max_before >= 1, "%s: bad params (max_v_l=%d, max_before=%d, max_after=%d)",
                  who, p->max_v_l, p->max_before, p->max_after);
     LocalizeLayout L{};
-    RUN(check_queries(who, tok_len, nq, p->max_q_l, &L.T));
+    RUN(check_queries(who, c.tok_len, nq, p->max_q_l, &L.T));
     const bool cert = (ses->flags & CONE_SESSION_CERTIFIED) != 0;
     size_t n_scores = 0;
-    if (q_row0) {       // (library_precheck has vetted the pairs, K and the capacity)
+    if (c.q_row0) {     // (library_precheck has vetted the pairs, K and the capacity)
         for (int q = 0; q < nq; ++q) {
-            if (q == 0 || q_row0[q] != q_row0[q - 1] || q_ctx_l[q] != q_ctx_l[q - 1])
-                L.runs[L.n_runs++] = Run{q, 0, q_row0[q], q_ctx_l[q], cone_num_windows(q_ctx_l[q], p->max_v_l), n_scores, 0, 0};
+            if (q == 0 || c.q_row0[q] != c.q_row0[q - 1] || c.q_ctx_l[q] != c.q_ctx_l[q - 1])
+                L.runs[L.n_runs++] = Run{q, 0, c.q_row0[q], c.q_ctx_l[q], cone_num_windows(c.q_ctx_l[q], p->max_v_l), n_scores, 0, 0};
             Run& r = L.runs[L.n_runs - 1];
             r.n += 1;
             n_scores += (size_t)r.nw;
         }
     } else {
-        CONE_REQUIRE(rows >= 1 && rows < (1ll << 31), "%s: ctx_l=%lld not in [1, 2^31)", who, (long long)rows);
-        L.nw = cone_num_windows(rows, p->max_v_l);
+        CONE_REQUIRE(c.rows >= 1 && c.rows < (1ll << 31), "%s: ctx_l=%lld not in [1, 2^31)", who, (long long)c.rows);
+        L.nw = cone_num_windows(c.rows, p->max_v_l);
         CONE_REQUIRE(K >= 1 && K <= L.nw && K <= 256, "%s: K=%d not in [1, min(num_window=%lld, 256)]", who, K, (long long)L.nw);
-        L.runs[L.n_runs++] = Run{0, nq, 0, rows, L.nw, 0, 0, 0};
+        L.runs[L.n_runs++] = Run{0, nq, 0, c.rows, L.nw, 0, 0, 0};
         n_scores = (size_t)nq * L.nw;
     }
-    CONE_REQUIRE(n_cand >= 0, "%s: n_cand=%d", who, n_cand);
+    CONE_REQUIRE(c.n_cand >= 0, "%s: n_cand=%d", who, c.n_cand);
     L.B = nq * K;
     if (pair_k) {
         L.B = 0;
@@ -309,10 +331,10 @@ static int localize_layout(const char* who, const char* what, const cone_model* 
     L.full_w = r.take(B * 4); L.n_valid = r.take(nq * 4);
     if (pair_k) { L.row_q = r.take(B * 4); L.row_slot = r.take(B * 4); L.cand_off = r.take(nq * 8); }
     L.tok_norm = r.take(T * d.t_dim * 4);
-    if (!cert && !ranked) L.scores = r.take(n_scores * 4);        // (ranked: the lists come from a scan -- no stage A here)
+    if (!cert && !c.ranked) L.scores = r.take(n_scores * 4);      // (ranked: the lists come from a scan -- no stage A here)
     const size_t n_list = pair_k ? (size_t)nq * K : B;            // the call's (nq, K) window list
     L.widx = r.take(n_list * 4); L.wval = r.take(n_list * 4); L.cert = r.take(nq * 4);
-    if (pair_k && !ranked) {        // every run ranks its video at the largest count among its pairs; the pairs take prefixes
+    if (pair_k && !c.ranked) {      // every run ranks its video at the largest count among its pairs; the pairs take prefixes
         size_t at = 0;
         for (int i = 0; i < L.n_runs; ++i) {
             Run& u = L.runs[i];
@@ -330,10 +352,10 @@ static int localize_layout(const char* who, const char* what, const cone_model* 
     L.match = r.take(B * Nq * 4); L.rows = r.take(B * Nq * 4 * 4);
     L.nms_idx = r.take((size_t)3 * nq * p->max_after * 4);
     if (cert) {
-        L.pf_bytes = cone_prefilter_topk_certified_workspace(rows, nq, p->max_v_l, K, n_cand);
+        L.pf_bytes = cone_prefilter_topk_certified_workspace(c.rows, nq, p->max_v_l, K, c.n_cand);
         CONE_REQUIRE(L.pf_bytes, "%s: n_cand=%d is not a candidate count the certified pre-filter takes for %lld windows and K=%d", who,
-                     n_cand, (long long)L.nw, K);
-    } else if (!ranked) {
+                     c.n_cand, (long long)L.nw, K);
+    } else if (!c.ranked) {
         for (int i = 0; i < L.n_runs; ++i) {        // the runs follow each other on one stream: they share the largest scratch
             const Run& u = L.runs[i];
             const int n = u.n < 4 ? u.n : 4;
@@ -412,12 +434,9 @@ extern "C" int cone_session_query_layout(const int32_t* tok_len, int nq, int max
     CONE_REQUIRE(ctx_l >= 1 && ctx_l < (1ll << 31), "%s: ctx_l=%lld not in [1, 2^31)", who, (long long)ctx_l);
     CONE_REQUIRE(K >= 1 && K <= 256 && Nq >= 1 && Nq <= 16 && max_v_l >= 2 && max_q_l <= 1024, "%s: bad sizes K=%d Nq=%d max_v_l=%d max_q_l=%d",
                  who, K, Nq, max_v_l, max_q_l);
-    QueryLens L{};
-    for (int q = 0; q < nq; ++q) L.len[q] = tok_len[q];
-    hipLaunchKernelGGL(session_layout_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, L, nq, max_q_l, (int)ctx_l, K, K * Nq,
-                       max_v_l, tok_off, tok_len_dev, tok_idx, q_ctx_l, q_vid_off, batch_pad, full_w, n_valid);
-    CONE_LAUNCH_CHECK();
-    return 0;
+    return launch_layout(shape_of(tok_len, nullptr, nullptr, nullptr, nq, ctx_l, K), nq, max_q_l, K, Nq, max_v_l,
+                         LayoutOut{tok_off, tok_len_dev, tok_idx, q_ctx_l, q_vid_off, batch_pad, full_w, n_valid, nullptr, nullptr, nullptr},
+                         stream);
 }
 
 extern "C" int cone_library_query_layout(const int32_t* tok_len, const int32_t* q_row0, const int32_t* q_ctx_l, int nq, int max_q_l,
@@ -430,26 +449,13 @@ extern "C" int cone_library_query_layout(const int32_t* tok_len, const int32_t* 
     RUN(check_pairs(who, q_row0, q_ctx_l, nq, -1, K, max_v_l));
     CONE_REQUIRE(tok_off && tok_len_dev && tok_idx && q_ctx_l_dev && q_vid_off && batch_pad && full_w && n_valid, "%s: null argument", who);
     CONE_REQUIRE(Nq >= 1 && Nq <= 16 && max_q_l <= 1024, "%s: bad sizes Nq=%d max_q_l=%d", who, Nq, max_q_l);
-    QueryPairs P{};
-    for (int q = 0; q < nq; ++q) { P.len[q] = tok_len[q]; P.row0[q] = q_row0[q]; P.ctx_l[q] = q_ctx_l[q]; }
-    hipLaunchKernelGGL(library_layout_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, P, nq, max_q_l, K, K * Nq, max_v_l, tok_off,
-                       tok_len_dev, tok_idx, q_ctx_l_dev, q_vid_off, batch_pad, full_w, n_valid);
-    CONE_LAUNCH_CHECK();
-    return 0;
+    return launch_layout(shape_of(tok_len, q_row0, q_ctx_l, nullptr, nq, 0, K), nq, max_q_l, K, Nq, max_v_l,
+                         LayoutOut{tok_off, tok_len_dev, tok_idx, q_ctx_l_dev, q_vid_off, batch_pad, full_w, n_valid, nullptr, nullptr, nullptr},
+                         stream);
 }
 
 namespace cone {
 
-// "The lists are here": the window lists of a cone_library_scan -- (scan_nq, n_videos, scan_K) on the device -- and, per pair of
-// this call, the scan's query index and table slot (host values: kernel arguments, nothing is uploaded).
-struct RankedPairs { int32_t query[CONE_SESSION_MAX_QUERIES], slot[CONE_SESSION_MAX_QUERIES]; };
-struct RankedLists {
-    const int32_t* widx;
-    const float* wval;
-    int64_t n_videos;
-    int scan_K;
-    RankedPairs pairs;
-};
 // pair p's first K entries of the list of (query[p], slot[p]) -> the call's window list; one writer per element
 __global__ __launch_bounds__(256) void library_gather_lists_kernel(RankedPairs P, int nq, int K, int64_t n_videos, int scan_K,
                                                                    const int32_t* __restrict__ scan_widx,
@@ -478,48 +484,50 @@ __global__ __launch_bounds__(256) void library_gather_ragged_kernel(RaggedSrc R,
     wval[i] = in ? src_val[R.off[p] + j] : -INFINITY;
 }
 
-// The query half for both kinds of resident rows: q_row0 / q_ctx_l == NULL is a session (one video at row 0, `rows` clips),
-// otherwise a library call (every query names its video's rows inside an arena of `rows`).  Nothing differs after stage A.
-// pair_k != NULL is a ragged library call (K = the largest count): pair q owns pair_k[q] window rows, not K -- its own layout
-// kernel, a gather of every pair's prefix, then the row form of cone_window_table and the offset form of cone_fuse_nms.  The
-// uniform calls run the launches they always ran.  cand != NULL (cone_library_localize_candidates): the call ends at its
-// candidate rows, composed straight into `cand`; kept / n_kept are not touched.
-static int localize(const char* who, const cone_model* m, const cone_model_dims& d, const Resident& S, int64_t rows,
-                    const LocalizeLayout& L, const int32_t* q_row0, const int32_t* q_ctx_l, const float* tok, const int32_t* tok_len,
-                    int nq, const float* cls, int K, int n_cand, const cone_session_params& P, double* kept, int32_t* n_kept,
-                    int32_t* certified, char* w, void* stream, const RankedLists* lists = nullptr,
-                    const int32_t* pair_k = nullptr, float* cand = nullptr) {
+// The query half for both kinds of resident rows: c.q_row0 == NULL is a session (one video at row 0, c.rows clips), otherwise a
+// library call (every query names its video's rows inside an arena of c.rows).  Nothing differs after stage A.
+// c.pair_k != NULL is a ragged library call (c.K = the largest count): pair q owns pair_k[q] window rows, not K -- the layout
+// kernel's row maps, a gather of every pair's prefix, then the row form of cone_window_table and the offset form of
+// cone_fuse_nms.  The uniform calls run the launches they always ran.  c.to_cand (cone_library_localize_candidates): the call
+// ends at its candidate rows, composed straight into c.cand; kept / n_kept are not touched.
+static int localize(const QueryCall& c, const LocalizeLayout& L) {
+    const cone_model* m = c.model;
+    const cone_model_dims& d = c.dims;
+    const Resident& S = c.res;
+    const cone_session_params& P = *c.params;
+    const RankedLists* lists = c.ranked ? &c.lists : nullptr;
+    const int32_t* pair_k = c.pair_k;
+    const float* cls = c.cls;
+    void* stream = c.stream;
+    char* w = (char*)c.ws;
     auto I = [&](size_t at) { return (int32_t*)(w + at); };
     auto F = [&](size_t at) { return (float*)(w + at); };
     auto scratch = [&](size_t at, size_t bytes) { return bytes ? (void*)(w + at) : nullptr; };
-    const int W = P.max_v_l, Sl = P.max_v_l / 2, B = L.B, Nq = d.num_queries, dv = d.v_dim;
+    const int nq = c.nq, K = c.K, W = P.max_v_l, Sl = P.max_v_l / 2, B = L.B, Nq = d.num_queries, dv = d.v_dim;
     const size_t col = align_up((size_t)B * 4, SES_ALIGN);
     int32_t *vid_row0 = I(L.wt), *vid_len = I(L.wt + col), *video_start = I(L.wt + 2 * col), *pad_len = I(L.wt + 3 * col),
             *txt_row0 = I(L.wt + 4 * col), *txt_len = I(L.wt + 5 * col), *cls_row = I(L.wt + 6 * col);
 
-    if (pair_k) {
-        QueryPairs Q{};
-        RaggedK R{};
-        for (int q = 0; q < nq; ++q) { Q.len[q] = tok_len[q]; Q.row0[q] = q_row0[q]; Q.ctx_l[q] = q_ctx_l[q]; R.k[q] = pair_k[q]; }
-        hipLaunchKernelGGL(library_ragged_layout_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, Q, R, nq, P.max_q_l, K, Nq, W,
-                           I(L.tok_off), I(L.tok_len), I(L.tok_idx), I(L.q_ctx_l), I(L.q_vid_off), I(L.batch_pad), I(L.full_w),
-                           I(L.n_valid), I(L.row_q), I(L.row_slot), (int64_t*)(w + L.cand_off));
-        CONE_LAUNCH_CHECK();
-    } else if (q_row0)
-        RUN(cone_library_query_layout(tok_len, q_row0, q_ctx_l, nq, P.max_q_l, K, Nq, W, I(L.tok_off), I(L.tok_len), I(L.tok_idx),
+    if (pair_k)
+        RUN(launch_layout(shape_of(c.tok_len, c.q_row0, c.q_ctx_l, pair_k, nq, 0, K), nq, P.max_q_l, K, Nq, W,
+                          LayoutOut{I(L.tok_off), I(L.tok_len), I(L.tok_idx), I(L.q_ctx_l), I(L.q_vid_off), I(L.batch_pad), I(L.full_w),
+                                    I(L.n_valid), I(L.row_q), I(L.row_slot), (int64_t*)(w + L.cand_off)},
+                          stream));
+    else if (c.q_row0)
+        RUN(cone_library_query_layout(c.tok_len, c.q_row0, c.q_ctx_l, nq, P.max_q_l, K, Nq, W, I(L.tok_off), I(L.tok_len), I(L.tok_idx),
                                       I(L.q_ctx_l), I(L.q_vid_off), I(L.batch_pad), I(L.full_w), I(L.n_valid), stream));
     else
-        RUN(cone_session_query_layout(tok_len, nq, P.max_q_l, rows, K, Nq, W, I(L.tok_off), I(L.tok_len), I(L.tok_idx), I(L.q_ctx_l),
+        RUN(cone_session_query_layout(c.tok_len, nq, P.max_q_l, c.rows, K, Nq, W, I(L.tok_off), I(L.tok_len), I(L.tok_idx), I(L.q_ctx_l),
                                       I(L.q_vid_off), I(L.batch_pad), I(L.full_w), I(L.n_valid), stream));
-    RUN(cone_l2_normalize_rows(tok, L.T, d.t_dim, 1e-5f, 1, F(L.tok_norm), stream));                          // :133
+    RUN(cone_l2_normalize_rows(c.tok, L.T, d.t_dim, 1e-5f, 1, F(L.tok_norm), stream));                        // :133
     // stage A (:83-100, stable tie order): the raw cls vectors against the adapted rows
     if (lists && !pair_k) {     // a scan has ranked the windows (cone_library_scan: the same lists, bit for bit): copy each pair's
         hipLaunchKernelGGL(library_gather_lists_kernel, dim3((unsigned)((nq * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                            lists->pairs, nq, K, lists->n_videos, lists->scan_K, lists->widx, lists->wval, I(L.widx), F(L.wval));
         CONE_LAUNCH_CHECK();
     } else if (S.flags & CONE_SESSION_CERTIFIED) {
-        RUN(cone_prefilter_topk_certified(S.adapted, S.adapted_bf16, rows, dv, cls, nq, W, Sl, K, n_cand, S.err, I(L.widx),
-                                          F(L.wval), certified ? certified : I(L.cert), w + L.pf_ws, L.pf_bytes, stream));
+        RUN(cone_prefilter_topk_certified(S.adapted, S.adapted_bf16, c.rows, dv, cls, nq, W, Sl, K, c.n_cand, S.err, I(L.widx),
+                                          F(L.wval), c.certified ? c.certified : I(L.cert), w + L.pf_ws, L.pf_bytes, stream));
     } else if (!lists) {
         for (int i = 0; i < L.n_runs; ++i) {        // one video a run, in the form and with the arguments of a session on it
             const Run& u = L.runs[i];
@@ -527,12 +535,12 @@ static int localize(const char* who, const cone_model* m, const cone_model_dims&
             for (int q0 = 0; q0 < u.n; q0 += 4) {   // at most 4 queries a launch: the streaming form, whatever the run's length
                 const int n = u.n - q0 < 4 ? u.n - q0 : 4;
                 float* sc = scores + (size_t)q0 * u.nw;
-                const float* c = cls + (size_t)(u.q0 + q0) * dv;
+                const float* cq = cls + (size_t)(u.q0 + q0) * dv;
                 if (S.flags & CONE_SESSION_BF16)
-                    RUN(cone_prefilter_scores_bf16(S.adapted_bf16 + (size_t)u.row0 * dv, u.ctx_l, dv, c, n, W, Sl, sc, w + L.pf_ws,
+                    RUN(cone_prefilter_scores_bf16(S.adapted_bf16 + (size_t)u.row0 * dv, u.ctx_l, dv, cq, n, W, Sl, sc, w + L.pf_ws,
                                                    L.pf_bytes, stream));
                 else
-                    RUN(cone_prefilter_scores(S.adapted + (size_t)u.row0 * dv, u.ctx_l, dv, c, n, W, Sl, nullptr, sc, w + L.pf_ws,
+                    RUN(cone_prefilter_scores(S.adapted + (size_t)u.row0 * dv, u.ctx_l, dv, cq, n, W, Sl, nullptr, sc, w + L.pf_ws,
                                               L.pf_bytes, stream));
             }
             if (pair_k)     // a ragged call: the run's lists at the largest count among its pairs (a video may have fewer than K windows)
@@ -559,7 +567,8 @@ static int localize(const char* who, const cone_model* m, const cone_model_dims&
     }
     // every window counts as padded to max_v_l (:150-170): one reference batch per query, its padding max_v_l
     RUN(cone_window_table(I(L.widx), nq, K, pair_k ? I(L.row_q) : nullptr, pair_k ? I(L.row_slot) : nullptr, B, I(L.q_ctx_l),
-                          I(L.q_vid_off), I(L.tok_off), I(L.tok_len), 0, 1, W, I(L.batch_pad), 0, nq, vid_row0, vid_len, video_start, pad_len, txt_row0, txt_len, cls_row, stream));
+                          I(L.q_vid_off), I(L.tok_off), I(L.tok_len), 0, 1, W, I(L.batch_pad), 0, nq, vid_row0, vid_len, video_start,
+                          pad_len, txt_row0, txt_len, cls_row, stream));
     RUN(cone_project_tokens(m, 1, F(L.tok_norm), L.T, F(L.tproj), w + L.proj_ws, L.proj_bytes, stream));
     cone_layer0 l0{};
     if (L.use_l0) {
@@ -575,64 +584,154 @@ static int localize(const char* who, const cone_model* m, const cone_model_dims&
     RUN(cone_clip_matching_gathered(m, cls, cls_row, S.vid_norm, vid_row0, vid_len, pad_len, F(L.spans), B, F(L.match),
                                     w + L.match_ws, L.match_bytes, stream));
     RUN(cone_compose_rows(F(L.logits), F(L.spans), F(L.match), I(L.full_w), video_start, P.clip_length, 0, B, Nq,
-                          cand ? cand : F(L.rows), stream));                                                  // :191
-    if (cand) return 0;     // the caller pools the candidates of many calls (cone_corpus_fuse_nms): the B * Nq rows, no stage C
-    return cone_fuse_nms(F(L.rows), pair_k ? (const int64_t*)(w + L.cand_off) : nullptr, I(L.n_valid), nq, K * Nq, P.nms_thd, P.max_before, P.max_after, kept, n_kept,
-                         I(L.nms_idx), stream);                                                               // :200-219
+                          c.to_cand ? c.cand : F(L.rows), stream));                                           // :191
+    if (c.to_cand) return 0;    // the caller pools the candidates of many calls (cone_corpus_fuse_nms): the B * Nq rows, no stage C
+    return cone_fuse_nms(F(L.rows), pair_k ? (const int64_t*)(w + L.cand_off) : nullptr, I(L.n_valid), nq, K * Nq, P.nms_thd,
+                         P.max_before, P.max_after, c.kept, c.n_kept, I(L.nms_idx), stream);                  // :200-219
+}
+
+// ------------------------------------------------------------------------------ the query half: the steps of an entry
+static bool library_flags_ok(int flags) { return flags == 0 || flags == CONE_SESSION_BF16; }
+
+static int library_handle(const char* who, const cone_model* m, const cone_model* opened_with) {
+    CONE_REQUIRE(m, "%s: null argument", who);
+    CONE_REQUIRE(opened_with == m, "%s: the library was opened with another handle", who);
+    return 0;
+}
+
+// The refusals a library call makes from host values alone, in this order, before the handle is looked at.  K: the window
+// count every pair's video must have.
+static int library_precheck(const QueryCall& c, int K) {
+    CONE_REQUIRE(c.resident && c.q_row0 && c.q_ctx_l && c.tok_len && c.params, "%s: null argument", c.who);
+    CONE_REQUIRE(!(c.res.flags & CONE_SESSION_CERTIFIED), "%s: CONE_SESSION_CERTIFIED libraries are not supported", c.who);
+    CONE_REQUIRE(c.rows >= 1 && c.rows < (1ll << 31), "%s: capacity=%lld not in [1, 2^31)", c.who, (long long)c.rows);
+    int64_t T = 0;
+    RUN(check_queries(c.who, c.tok_len, c.nq, c.params->max_q_l, &T));
+    return check_pairs(c.who, c.q_row0, c.q_ctx_l, c.nq, c.rows, K, c.params->max_v_l);
+}
+static int ranked_precheck(const QueryCall& c) {
+    RUN(library_precheck(c, c.K));
+    CONE_REQUIRE(!(c.res.flags & CONE_SESSION_BF16), "%s: CONE_SESSION_BF16 libraries are not supported", c.who);
+    return 0;
+}
+// A ragged call's: the library call's with K = 1 (every video has a window), then the counts; with lists, then what the ranked
+// entry refuses.  c.K = the largest count.
+static int ragged_precheck(QueryCall& c) {
+    RUN(library_precheck(c, 1));
+    RUN(check_ragged(c.who, c.pair_k, c.q_ctx_l, c.nq, c.params->max_v_l, &c.K));
+    CONE_REQUIRE(!c.ranked || !(c.res.flags & CONE_SESSION_BF16), "%s: CONE_SESSION_BF16 libraries are not supported with a scan's lists",
+                 c.who);
+    return 0;
+}
+
+// The scan's lists of a ranked call, as the caller passed them (after the precheck: c.K is known) -> c.lists.pairs.
+static int check_lists(QueryCall& c) {
+    const char* who = c.who;
+    CONE_REQUIRE(c.pair_query && c.pair_slot, "%s: null argument", who);
+    CONE_REQUIRE(c.scan_nq >= 1 && c.lists.n_videos >= 1 && c.lists.scan_K >= 1 && c.K <= c.lists.scan_K,
+                 "%s: %s=%d not in [1, scan_K=%d] (scan_nq=%d, scan_n_videos=%lld)", who, c.pair_k ? "max pair_k" : "K", c.K,
+                 c.lists.scan_K, c.scan_nq, (long long)c.lists.n_videos);
+    for (int q = 0; q < c.nq; ++q) {
+        CONE_REQUIRE(c.pair_query[q] >= 0 && c.pair_query[q] < c.scan_nq, "%s: pair_query[%d]=%d not in [0, scan_nq=%d)", who, q,
+                     c.pair_query[q], c.scan_nq);
+        CONE_REQUIRE(c.pair_slot[q] >= 0 && c.pair_slot[q] < c.lists.n_videos, "%s: pair_slot[%d]=%d not in [0, scan_n_videos=%lld)", who, q,
+                     c.pair_slot[q], (long long)c.lists.n_videos);
+        c.lists.pairs.query[q] = c.pair_query[q];
+        c.lists.pairs.slot[q] = c.pair_slot[q];
+    }
+    CONE_REQUIRE(c.lists.widx && c.lists.wval, "%s: null argument", who);
+    return 0;
+}
+
+// What only a run entry carries: the device pointers of the call and its workspace.
+static int check_run_pointers(const QueryCall& c) {
+    CONE_REQUIRE(c.model && c.tok && c.cls && (c.to_cand ? c.cand != nullptr : c.kept && c.n_kept) && c.ws, "%s: null argument", c.who);
+    CONE_REQUIRE(((uintptr_t)c.ws & (SES_ALIGN - 1)) == 0, "%s: the workspace must be 256-B aligned", c.who);
+    return 0;
+}
+
+// The handle, its dims and the call's layout; for a run entry (to_run) then the resident regions and the workspace's size.
+static int resolve(QueryCall& c, LocalizeLayout* L, bool to_run) {
+    if (c.q_row0) RUN(library_handle(c.who, c.model, c.res.model));
+    RUN(cone_model_get_dims(c.model, &c.dims));
+    RUN(localize_layout(c, L));
+    if (!to_run) return 0;
+    if (c.q_row0)
+        CONE_REQUIRE(c.res.vid_norm && c.res.vproj && (c.res.flags & CONE_SESSION_BF16 ? c.res.adapted_bf16 != nullptr : c.res.adapted != nullptr),
+                     "%s: the library handle misses a region (not one cone_library_open filled)", c.who);
+    if (c.ws_bytes < L->total) { set_error("%s: workspace too small (%zu < %zu)", c.who, c.ws_bytes, L->total); return CONE_E_WORKSPACE; }
+    return 0;
+}
+
+// What a size entry and its run entry both fill of a library call.
+static QueryCall library_query(const char* who, const cone_model* m, const cone_library* lib, const int32_t* q_row0,
+                               const int32_t* q_ctx_l, const int32_t* tok_len, int nq, const cone_session_params* params) {
+    QueryCall c{};
+    c.who = who; c.what = "library"; c.model = m;
+    if (lib) { c.resident = true; c.res = resident_of(*lib); c.rows = lib->capacity; }
+    c.q_row0 = q_row0; c.q_ctx_l = q_ctx_l; c.tok_len = tok_len; c.nq = nq; c.params = params;
+    return c;
+}
+static QueryCall session_query(const cone_model* m, const cone_session* session, const int32_t* tok_len, int nq, int K, int n_cand,
+                               const cone_session_params* params) {
+    QueryCall c{};
+    c.who = "session_localize"; c.what = "session"; c.model = m;
+    if (session) { c.resident = true; c.res = resident_of(*session); c.rows = session->ctx_l; }
+    c.tok_len = tok_len; c.nq = nq; c.K = K; c.n_cand = n_cand; c.params = params;
+    return c;
+}
+// ... and what only the run entry adds.
+static void run_on(QueryCall& c, const float* tok, const float* cls, void* ws, size_t ws_bytes, void* stream) {
+    c.tok = tok; c.cls = cls; c.ws = ws; c.ws_bytes = ws_bytes; c.stream = stream;
+}
+static void scan_lists(QueryCall& c, const int32_t* pair_query, const int32_t* pair_slot, const int32_t* scan_widx,
+                       const float* scan_wval, int scan_nq, int64_t scan_n_videos, int scan_K) {
+    c.pair_query = pair_query; c.pair_slot = pair_slot; c.scan_nq = scan_nq;
+    c.lists.widx = scan_widx; c.lists.wval = scan_wval; c.lists.n_videos = scan_n_videos; c.lists.scan_K = scan_K;
+}
+static size_t size_of(int rc, const LocalizeLayout& L) { return rc ? 0 : L.total; }
+
+// cone_library_localize_ragged and cone_library_localize_candidates (c.to_cand): the same refusals in the same order, the same
+// launches up to cone_compose_rows.
+static size_t ragged_size(QueryCall& c) {
+    LocalizeLayout L;
+    if (ragged_precheck(c)) return 0;
+    return size_of(resolve(c, &L, false), L);
+}
+static int ragged_run(QueryCall& c) {
+    c.ranked = c.pair_query || c.pair_slot || c.lists.widx || c.lists.wval;     // the lists come as a block: all of it or none
+    RUN(ragged_precheck(c));
+    if (c.ranked) RUN(check_lists(c));
+    RUN(check_run_pointers(c));
+    LocalizeLayout L;
+    RUN(resolve(c, &L, true));
+    return localize(c, L);
 }
 
 }  // namespace cone
 
 extern "C" size_t cone_session_localize_workspace(const cone_model* m, const cone_session* session, const int32_t* tok_len, int nq,
                                                   int K, int n_cand, const cone_session_params* params) {
-    cone_model_dims d;
+    if (!m) return 0;
+    QueryCall c = session_query(m, session, tok_len, nq, K, n_cand, params);
     LocalizeLayout L;
-    if (!m || cone_model_get_dims(m, &d)) return 0;
-    const Resident S = session ? resident_of(*session) : Resident{};
-    if (localize_layout("session_localize", "session", m, d, session ? &S : nullptr, session ? session->ctx_l : 0, nullptr, nullptr,
-                        tok_len, nq, K, n_cand, params, &L))
-        return 0;
-    return L.total;
+    return size_of(resolve(c, &L, false), L);
 }
 
 extern "C" int cone_session_localize(const cone_model* m, const cone_session* session, const float* tok, const int32_t* tok_len,
                                      int nq, const float* cls, int K, int n_cand, const cone_session_params* params, double* kept,
                                      int32_t* n_kept, int32_t* certified, void* ws, size_t ws_bytes, void* stream) {
-    const char* who = "session_localize";
-    CONE_REQUIRE(m && session && tok && tok_len && cls && params && kept && n_kept && ws, "%s: null argument", who);
-    CONE_REQUIRE(((uintptr_t)ws & (SES_ALIGN - 1)) == 0, "%s: the workspace must be 256-B aligned", who);
-    cone_model_dims d;
-    RUN(cone_model_get_dims(m, &d));
-    const Resident S = resident_of(*session);
+    QueryCall c = session_query(m, session, tok_len, nq, K, n_cand, params);
+    run_on(c, tok, cls, ws, ws_bytes, stream);
+    c.kept = kept; c.n_kept = n_kept; c.certified = certified;
+    CONE_REQUIRE(c.resident && tok_len && params, "%s: null argument", c.who);
+    RUN(check_run_pointers(c));
     LocalizeLayout L;
-    RUN(localize_layout(who, "session", m, d, &S, session->ctx_l, nullptr, nullptr, tok_len, nq, K, n_cand, params, &L));
-    if (ws_bytes < L.total) { set_error("%s: workspace too small (%zu < %zu)", who, ws_bytes, L.total); return CONE_E_WORKSPACE; }
-    return localize(who, m, d, S, session->ctx_l, L, nullptr, nullptr, tok, tok_len, nq, cls, K, n_cand, *params, kept, n_kept,
-                    certified, (char*)ws, stream);
+    RUN(resolve(c, &L, true));
+    return localize(c, L);
 }
 
 // ------------------------------------------------------------------------------ video libraries
-namespace cone {
-
-static bool library_flags_ok(int flags) { return flags == 0 || flags == CONE_SESSION_BF16; }
-
-// The refusals a library call makes from host values alone, in this order, before the handle is looked at.
-static int library_precheck(const char* who, const cone_library* lib, const int32_t* q_row0, const int32_t* q_ctx_l,
-                            const int32_t* tok_len, int nq, int K, const cone_session_params* p) {
-    CONE_REQUIRE(lib && q_row0 && q_ctx_l && tok_len && p, "%s: null argument", who);
-    CONE_REQUIRE(!(lib->flags & CONE_SESSION_CERTIFIED), "%s: CONE_SESSION_CERTIFIED libraries are not supported", who);
-    CONE_REQUIRE(lib->capacity >= 1 && lib->capacity < (1ll << 31), "%s: capacity=%lld not in [1, 2^31)", who, (long long)lib->capacity);
-    int64_t T = 0;
-    RUN(check_queries(who, tok_len, nq, p->max_q_l, &T));
-    return check_pairs(who, q_row0, q_ctx_l, nq, lib->capacity, K, p->max_v_l);
-}
-static int library_handle(const char* who, const cone_model* m, const cone_library* lib) {
-    CONE_REQUIRE(m, "%s: null argument", who);
-    CONE_REQUIRE(lib->model == m, "%s: the library was opened with another handle", who);
-    return 0;
-}
-
-}  // namespace cone
 
 extern "C" size_t cone_library_arena_bytes(const cone_model* m, int64_t capacity, int flags) {
     cone_model_dims d;
@@ -670,7 +769,7 @@ extern "C" int cone_library_add(const cone_model* m, const cone_library* lib, in
                                 void* ws, size_t ws_bytes, void* stream) {
     const char* who = "library_add";
     CONE_REQUIRE(m && lib && raw_clips && ws, "%s: null argument", who);
-    RUN(library_handle(who, m, lib));
+    RUN(library_handle(who, m, lib->model));
     CONE_REQUIRE(library_flags_ok(lib->flags), "%s: bad library flags %d", who, lib->flags);
     CONE_REQUIRE(row0 >= 0 && n_rows >= 1 && row0 + n_rows <= lib->capacity, "%s: rows [%lld, %lld + %lld) are not inside [0, capacity=%lld)",
                  who, (long long)row0, (long long)row0, (long long)n_rows, (long long)lib->capacity);
@@ -693,61 +792,37 @@ extern "C" int cone_library_add(const cone_model* m, const cone_library* lib, in
 extern "C" size_t cone_library_localize_workspace(const cone_model* m, const cone_library* lib, const int32_t* q_row0,
                                                   const int32_t* q_ctx_l, const int32_t* tok_len, int nq, int K,
                                                   const cone_session_params* params) {
-    const char* who = "library_localize";
-    cone_model_dims d;
+    QueryCall c = library_query("library_localize", m, lib, q_row0, q_ctx_l, tok_len, nq, params);
+    c.K = K;
     LocalizeLayout L;
-    if (library_precheck(who, lib, q_row0, q_ctx_l, tok_len, nq, K, params)) return 0;
-    if (library_handle(who, m, lib) || cone_model_get_dims(m, &d)) return 0;
-    const Resident S = resident_of(*lib);
-    if (localize_layout(who, "library", m, d, &S, lib->capacity, q_row0, q_ctx_l, tok_len, nq, K, 0, params, &L)) return 0;
-    return L.total;
+    if (library_precheck(c, K)) return 0;
+    return size_of(resolve(c, &L, false), L);
 }
 
 extern "C" int cone_library_localize(const cone_model* m, const cone_library* lib, const int32_t* q_row0, const int32_t* q_ctx_l,
                                      const float* tok, const int32_t* tok_len, int nq, const float* cls, int K,
                                      const cone_session_params* params, double* kept, int32_t* n_kept, void* ws, size_t ws_bytes,
                                      void* stream) {
-    const char* who = "library_localize";
-    CONE_REQUIRE(m && lib && q_row0 && q_ctx_l && tok && tok_len && cls && params && kept && n_kept && ws, "%s: null argument", who);
-    CONE_REQUIRE(((uintptr_t)ws & (SES_ALIGN - 1)) == 0, "%s: the workspace must be 256-B aligned", who);
-    RUN(library_precheck(who, lib, q_row0, q_ctx_l, tok_len, nq, K, params));
-    RUN(library_handle(who, m, lib));
-    cone_model_dims d;
-    RUN(cone_model_get_dims(m, &d));
-    const Resident S = resident_of(*lib);
+    QueryCall c = library_query("library_localize", m, lib, q_row0, q_ctx_l, tok_len, nq, params);
+    run_on(c, tok, cls, ws, ws_bytes, stream);
+    c.K = K; c.kept = kept; c.n_kept = n_kept;
+    CONE_REQUIRE(lib && q_row0 && q_ctx_l && tok_len && params, "%s: null argument", c.who);     // (this entry: pointers first)
+    RUN(check_run_pointers(c));
+    RUN(library_precheck(c, K));
     LocalizeLayout L;
-    RUN(localize_layout(who, "library", m, d, &S, lib->capacity, q_row0, q_ctx_l, tok_len, nq, K, 0, params, &L));
-    CONE_REQUIRE(S.vid_norm && S.vproj && (S.flags & CONE_SESSION_BF16 ? S.adapted_bf16 != nullptr : S.adapted != nullptr),
-                 "%s: the library handle misses a region (not one cone_library_open filled)", who);
-    if (ws_bytes < L.total) { set_error("%s: workspace too small (%zu < %zu)", who, ws_bytes, L.total); return CONE_E_WORKSPACE; }
-    return localize(who, m, d, S, lib->capacity, L, q_row0, q_ctx_l, tok, tok_len, nq, cls, K, 0, *params, kept, n_kept, nullptr,
-                    (char*)ws, stream);
+    RUN(resolve(c, &L, true));
+    return localize(c, L);
 }
-
 
 // ------------------------------------------------------------------------------ library search: the query half on scanned lists
-namespace cone {
-
-static int ranked_precheck(const char* who, const cone_library* lib, const int32_t* q_row0, const int32_t* q_ctx_l,
-                           const int32_t* tok_len, int nq, int K, const cone_session_params* p) {
-    RUN(library_precheck(who, lib, q_row0, q_ctx_l, tok_len, nq, K, p));
-    CONE_REQUIRE(!(lib->flags & CONE_SESSION_BF16), "%s: CONE_SESSION_BF16 libraries are not supported", who);
-    return 0;
-}
-
-}  // namespace cone
-
 extern "C" size_t cone_library_localize_ranked_workspace(const cone_model* m, const cone_library* lib, const int32_t* q_row0,
                                                          const int32_t* q_ctx_l, const int32_t* tok_len, int nq, int K,
                                                          const cone_session_params* params) {
-    const char* who = "library_localize_ranked";
-    cone_model_dims d;
+    QueryCall c = library_query("library_localize_ranked", m, lib, q_row0, q_ctx_l, tok_len, nq, params);
+    c.K = K; c.ranked = true;
     LocalizeLayout L;
-    if (ranked_precheck(who, lib, q_row0, q_ctx_l, tok_len, nq, K, params)) return 0;
-    if (library_handle(who, m, lib) || cone_model_get_dims(m, &d)) return 0;
-    const Resident S = resident_of(*lib);
-    if (localize_layout(who, "library", m, d, &S, lib->capacity, q_row0, q_ctx_l, tok_len, nq, K, 0, params, &L, true)) return 0;
-    return L.total;
+    if (ranked_precheck(c)) return 0;
+    return size_of(resolve(c, &L, false), L);
 }
 
 extern "C" int cone_library_localize_ranked(const cone_model* m, const cone_library* lib, const int32_t* q_row0, const int32_t* q_ctx_l,
@@ -755,113 +830,26 @@ extern "C" int cone_library_localize_ranked(const cone_model* m, const cone_libr
                                             const cone_session_params* params, const int32_t* pair_query, const int32_t* pair_slot,
                                             const int32_t* scan_widx, const float* scan_wval, int scan_nq, int64_t scan_n_videos,
                                             int scan_K, double* kept, int32_t* n_kept, void* ws, size_t ws_bytes, void* stream) {
-    const char* who = "library_localize_ranked";
-    RUN(ranked_precheck(who, lib, q_row0, q_ctx_l, tok_len, nq, K, params));
-    CONE_REQUIRE(pair_query && pair_slot, "%s: null argument", who);
-    CONE_REQUIRE(scan_nq >= 1 && scan_n_videos >= 1 && scan_K >= 1 && K <= scan_K, "%s: K=%d not in [1, scan_K=%d] (scan_nq=%d, scan_n_videos=%lld)",
-                 who, K, scan_K, scan_nq, (long long)scan_n_videos);
-    RankedLists lists{scan_widx, scan_wval, scan_n_videos, scan_K, {}};
-    for (int q = 0; q < nq; ++q) {
-        CONE_REQUIRE(pair_query[q] >= 0 && pair_query[q] < scan_nq, "%s: pair_query[%d]=%d not in [0, scan_nq=%d)", who, q, pair_query[q],
-                     scan_nq);
-        CONE_REQUIRE(pair_slot[q] >= 0 && pair_slot[q] < scan_n_videos, "%s: pair_slot[%d]=%d not in [0, scan_n_videos=%lld)", who, q,
-                     pair_slot[q], (long long)scan_n_videos);
-        lists.pairs.query[q] = pair_query[q];
-        lists.pairs.slot[q] = pair_slot[q];
-    }
-    CONE_REQUIRE(m && tok && cls && scan_widx && scan_wval && kept && n_kept && ws, "%s: null argument", who);
-    CONE_REQUIRE(((uintptr_t)ws & (SES_ALIGN - 1)) == 0, "%s: the workspace must be 256-B aligned", who);
-    RUN(library_handle(who, m, lib));
-    cone_model_dims d;
-    RUN(cone_model_get_dims(m, &d));
-    const Resident S = resident_of(*lib);
+    QueryCall c = library_query("library_localize_ranked", m, lib, q_row0, q_ctx_l, tok_len, nq, params);
+    run_on(c, tok, cls, ws, ws_bytes, stream);
+    c.K = K; c.kept = kept; c.n_kept = n_kept;
+    c.ranked = true;
+    scan_lists(c, pair_query, pair_slot, scan_widx, scan_wval, scan_nq, scan_n_videos, scan_K);
+    RUN(ranked_precheck(c));
+    RUN(check_lists(c));
+    RUN(check_run_pointers(c));
     LocalizeLayout L;
-    RUN(localize_layout(who, "library", m, d, &S, lib->capacity, q_row0, q_ctx_l, tok_len, nq, K, 0, params, &L, true));
-    CONE_REQUIRE(S.vid_norm && S.vproj && S.adapted, "%s: the library handle misses a region (not one cone_library_open filled)", who);
-    if (ws_bytes < L.total) { set_error("%s: workspace too small (%zu < %zu)", who, ws_bytes, L.total); return CONE_E_WORKSPACE; }
-    return localize(who, m, d, S, lib->capacity, L, q_row0, q_ctx_l, tok, tok_len, nq, cls, K, 0, *params, kept, n_kept, nullptr,
-                    (char*)ws, stream, &lists);
+    RUN(resolve(c, &L, true));
+    return localize(c, L);
 }
-
 
 // ------------------------------------------------------------------------------ library window budgets: a window count per pair
-namespace cone {
-
-// The refusals of a ragged call from host values alone, in this order: the library call's with K = 1 (every video has a window),
-// then the counts; with lists, then what the ranked entry refuses.  *Kmax = the largest count.
-static int ragged_precheck(const char* who, const cone_library* lib, const int32_t* q_row0, const int32_t* q_ctx_l,
-                           const int32_t* tok_len, int nq, const int32_t* pair_k, const cone_session_params* p, bool ranked, int* Kmax) {
-    RUN(library_precheck(who, lib, q_row0, q_ctx_l, tok_len, nq, 1, p));
-    RUN(check_ragged(who, pair_k, q_ctx_l, nq, p->max_v_l, Kmax));
-    CONE_REQUIRE(!ranked || !(lib->flags & CONE_SESSION_BF16), "%s: CONE_SESSION_BF16 libraries are not supported with a scan's lists", who);
-    return 0;
-}
-
-}  // namespace cone
-
-namespace cone {
-
-static size_t ragged_workspace(const char* who, const cone_model* m, const cone_library* lib, const int32_t* q_row0,
-                               const int32_t* q_ctx_l, const int32_t* tok_len, int nq, const int32_t* pair_k,
-                               const cone_session_params* params, int ranked) {
-    cone_model_dims d;
-    LocalizeLayout L;
-    int Kmax = 0;
-    if (ragged_precheck(who, lib, q_row0, q_ctx_l, tok_len, nq, pair_k, params, ranked != 0, &Kmax)) return 0;
-    if (library_handle(who, m, lib) || cone_model_get_dims(m, &d)) return 0;
-    const Resident S = resident_of(*lib);
-    if (localize_layout(who, "library", m, d, &S, lib->capacity, q_row0, q_ctx_l, tok_len, nq, Kmax, 0, params, &L, ranked != 0, pair_k))
-        return 0;
-    return L.total;
-}
-
-// cone_library_localize_ragged (cand == NULL: kept / n_kept are the outputs) and cone_library_localize_candidates (cand is):
-// the same refusals in the same order, the same launches up to cone_compose_rows.
-static int ragged_call(const char* who, const cone_model* m, const cone_library* lib, const int32_t* q_row0, const int32_t* q_ctx_l,
-                       const float* tok, const int32_t* tok_len, int nq, const float* cls, const int32_t* pair_k,
-                       const cone_session_params* params, const int32_t* pair_query, const int32_t* pair_slot,
-                       const int32_t* scan_widx, const float* scan_wval, int scan_nq, int64_t scan_n_videos, int scan_K,
-                       double* kept, int32_t* n_kept, float* cand, bool to_cand, void* ws, size_t ws_bytes, void* stream) {
-    const bool ranked = pair_query || pair_slot || scan_widx || scan_wval;      // the lists come as a block: all of it or none
-    int Kmax = 0;
-    RUN(ragged_precheck(who, lib, q_row0, q_ctx_l, tok_len, nq, pair_k, params, ranked, &Kmax));
-    RankedLists lists{scan_widx, scan_wval, scan_n_videos, scan_K, {}};
-    if (ranked) {
-        CONE_REQUIRE(pair_query && pair_slot, "%s: null argument", who);
-        CONE_REQUIRE(scan_nq >= 1 && scan_n_videos >= 1 && scan_K >= 1 && Kmax <= scan_K,
-                     "%s: max pair_k=%d not in [1, scan_K=%d] (scan_nq=%d, scan_n_videos=%lld)", who, Kmax, scan_K, scan_nq,
-                     (long long)scan_n_videos);
-        for (int q = 0; q < nq; ++q) {
-            CONE_REQUIRE(pair_query[q] >= 0 && pair_query[q] < scan_nq, "%s: pair_query[%d]=%d not in [0, scan_nq=%d)", who, q,
-                         pair_query[q], scan_nq);
-            CONE_REQUIRE(pair_slot[q] >= 0 && pair_slot[q] < scan_n_videos, "%s: pair_slot[%d]=%d not in [0, scan_n_videos=%lld)", who, q,
-                         pair_slot[q], (long long)scan_n_videos);
-            lists.pairs.query[q] = pair_query[q];
-            lists.pairs.slot[q] = pair_slot[q];
-        }
-        CONE_REQUIRE(scan_widx && scan_wval, "%s: null argument", who);
-    }
-    CONE_REQUIRE(m && tok && cls && (to_cand ? cand != nullptr : kept && n_kept) && ws, "%s: null argument", who);
-    CONE_REQUIRE(((uintptr_t)ws & (SES_ALIGN - 1)) == 0, "%s: the workspace must be 256-B aligned", who);
-    RUN(library_handle(who, m, lib));
-    cone_model_dims d;
-    RUN(cone_model_get_dims(m, &d));
-    const Resident S = resident_of(*lib);
-    LocalizeLayout L;
-    RUN(localize_layout(who, "library", m, d, &S, lib->capacity, q_row0, q_ctx_l, tok_len, nq, Kmax, 0, params, &L, ranked, pair_k));
-    CONE_REQUIRE(S.vid_norm && S.vproj && (S.flags & CONE_SESSION_BF16 ? S.adapted_bf16 != nullptr : S.adapted != nullptr),
-                 "%s: the library handle misses a region (not one cone_library_open filled)", who);
-    if (ws_bytes < L.total) { set_error("%s: workspace too small (%zu < %zu)", who, ws_bytes, L.total); return CONE_E_WORKSPACE; }
-    return localize(who, m, d, S, lib->capacity, L, q_row0, q_ctx_l, tok, tok_len, nq, cls, Kmax, 0, *params, kept, n_kept, nullptr,
-                    (char*)ws, stream, ranked ? &lists : nullptr, pair_k, to_cand ? cand : nullptr);
-}
-
-}  // namespace cone
-
 extern "C" size_t cone_library_localize_ragged_workspace(const cone_model* m, const cone_library* lib, const int32_t* q_row0,
                                                          const int32_t* q_ctx_l, const int32_t* tok_len, int nq, const int32_t* pair_k,
                                                          const cone_session_params* params, int ranked) {
-    return cone::ragged_workspace("library_localize_ragged", m, lib, q_row0, q_ctx_l, tok_len, nq, pair_k, params, ranked);
+    QueryCall c = library_query("library_localize_ragged", m, lib, q_row0, q_ctx_l, tok_len, nq, params);
+    c.pair_k = pair_k; c.ranked = ranked != 0;
+    return ragged_size(c);
 }
 
 extern "C" int cone_library_localize_ragged(const cone_model* m, const cone_library* lib, const int32_t* q_row0, const int32_t* q_ctx_l,
@@ -869,16 +857,20 @@ extern "C" int cone_library_localize_ragged(const cone_model* m, const cone_libr
                                             const cone_session_params* params, const int32_t* pair_query, const int32_t* pair_slot,
                                             const int32_t* scan_widx, const float* scan_wval, int scan_nq, int64_t scan_n_videos,
                                             int scan_K, double* kept, int32_t* n_kept, void* ws, size_t ws_bytes, void* stream) {
-    return cone::ragged_call("library_localize_ragged", m, lib, q_row0, q_ctx_l, tok, tok_len, nq, cls, pair_k, params, pair_query,
-                             pair_slot, scan_widx, scan_wval, scan_nq, scan_n_videos, scan_K, kept, n_kept, nullptr, false, ws, ws_bytes,
-                             stream);
+    QueryCall c = library_query("library_localize_ragged", m, lib, q_row0, q_ctx_l, tok_len, nq, params);
+    run_on(c, tok, cls, ws, ws_bytes, stream);
+    c.pair_k = pair_k; c.kept = kept; c.n_kept = n_kept;
+    scan_lists(c, pair_query, pair_slot, scan_widx, scan_wval, scan_nq, scan_n_videos, scan_K);
+    return ragged_run(c);
 }
 
 // ------------------------------------------------------------------------------ library moment search: the call that ends at its candidates
 extern "C" size_t cone_library_localize_candidates_workspace(const cone_model* m, const cone_library* lib, const int32_t* q_row0,
                                                              const int32_t* q_ctx_l, const int32_t* tok_len, int nq,
                                                              const int32_t* pair_k, const cone_session_params* params, int ranked) {
-    return cone::ragged_workspace("library_localize_candidates", m, lib, q_row0, q_ctx_l, tok_len, nq, pair_k, params, ranked);
+    QueryCall c = library_query("library_localize_candidates", m, lib, q_row0, q_ctx_l, tok_len, nq, params);
+    c.pair_k = pair_k; c.ranked = ranked != 0;
+    return ragged_size(c);
 }
 
 extern "C" int cone_library_localize_candidates(const cone_model* m, const cone_library* lib, const int32_t* q_row0,
@@ -887,7 +879,9 @@ extern "C" int cone_library_localize_candidates(const cone_model* m, const cone_
                                                 const int32_t* pair_query, const int32_t* pair_slot, const int32_t* scan_widx,
                                                 const float* scan_wval, int scan_nq, int64_t scan_n_videos, int scan_K, float* cand,
                                                 void* ws, size_t ws_bytes, void* stream) {
-    return cone::ragged_call("library_localize_candidates", m, lib, q_row0, q_ctx_l, tok, tok_len, nq, cls, pair_k, params, pair_query,
-                             pair_slot, scan_widx, scan_wval, scan_nq, scan_n_videos, scan_K, nullptr, nullptr, cand, true, ws, ws_bytes,
-                             stream);
+    QueryCall c = library_query("library_localize_candidates", m, lib, q_row0, q_ctx_l, tok_len, nq, params);
+    run_on(c, tok, cls, ws, ws_bytes, stream);
+    c.pair_k = pair_k; c.to_cand = true; c.cand = cand;
+    scan_lists(c, pair_query, pair_slot, scan_widx, scan_wval, scan_nq, scan_n_videos, scan_K);
+    return ragged_run(c);
 }

@@ -63,7 +63,7 @@ import weakref
 import torch
 
 from . import _lib, ops
-from .session import MAX_QUERIES, NMS_THD, MAX_BEFORE, MAX_AFTER, VideoSession, _kept_bytes, check_queries
+from .session import MAX_QUERIES, NMS_THD, MAX_BEFORE, MAX_AFTER, VideoSession, _kept_bytes, _pack_queries, check_queries
 from .watch import VideoWatcher
 
 MAX_POOL = 1024     # candidates of one query in cone_corpus_fuse_nms (csrc/stage_c.h: kMaxCand)
@@ -314,9 +314,7 @@ class VideoLibrary:
         self._handle_obj, self._handle_value = m._handle, m._h().value
         lib, h = _lib.load(), m._h()
         self._flags = _lib.SESSION_BF16 if localizer.prefilter_bf16 else 0
-        n_arena = lib.cone_library_arena_bytes(h, self._rows.capacity, self._flags)
-        if n_arena == 0:
-            raise _lib.ConeHipError(f"libcone_hip error: {lib.cone_last_error().decode()}")
+        n_arena = _lib.sized(lib.cone_library_arena_bytes(h, self._rows.capacity, self._flags))
         self._arena = torch.empty(n_arena, dtype=torch.uint8, device=localizer.device)
         self._cl = _lib.Library()
         _lib.check(lib.cone_library_open(h, self._rows.capacity, self._flags, _lib.ptr(self._arena), n_arena, C.byref(self._cl)))
@@ -615,9 +613,7 @@ class VideoLibrary:
             raise ValueError(f"capacity must be at least one clip, got {capacity}")
         self._check_live()
         lib, h = _lib.load(), self._loc.localizator._h()
-        n_arena = lib.cone_library_arena_bytes(h, capacity, self._flags)
-        if n_arena == 0:
-            raise _lib.ConeHipError(f"libcone_hip error: {lib.cone_last_error().decode()}")
+        n_arena = _lib.sized(lib.cone_library_arena_bytes(h, capacity, self._flags))
         arena, cl = torch.empty(n_arena, dtype=torch.uint8, device=self._loc.device), _lib.Library()
         _lib.check(lib.cone_library_open(h, capacity, self._flags, _lib.ptr(arena), n_arena, C.byref(cl)))
         ids = sorted(self._videos, key=lambda v: self._videos[v][0])
@@ -639,73 +635,47 @@ class VideoLibrary:
             raise ValueError(f"VideoLibrary: unknown or removed video id {vid_id!r}") from None
 
     # ---- queries -------------------------------------------------------------------------------
-    def _enqueue(self, K, chunk):
-        """One ``cone_library_localize`` call: ``chunk`` = [((row0, ctx_l), (tok, cls)), ...], at most MAX_QUERIES."""
-        lib, m, dev = _lib.load(), self._loc.localizator, self._loc.device
-        h, nq = m._h(), len(chunk)
-        toks = [t.to(dev, torch.float32).contiguous() for _, (t, _) in chunk]
-        tok_cat = toks[0] if nq == 1 else torch.cat(toks)
-        cls = torch.stack([c.to(dev, torch.float32).reshape(-1) for _, (_, c) in chunk]).contiguous()
+    def _localize(self, chunk, K=None, ks=None, scan=None, V=0, cand=None):
+        """One C call of the query half: ``chunk`` = [((row0, ctx_l), (tok, cls), scan query, slot), ...], at most MAX_QUERIES
+        (the last two entries of a pair are read only with ``scan``).  ``K``: that many windows for every pair --
+        ``cone_library_localize``, or ``cone_library_localize_ranked`` when ``scan`` = the scan whose lists (of ``V`` videos) the
+        pairs take their windows from.  ``ks``: a window count per pair -- ``cone_library_localize_ragged``; ``scan`` as above
+        (``None``: the call's own stage A).  ``cand`` (fp32, on the device, only with ``ks``):
+        ``cone_library_localize_candidates`` -- the call's ``sum(ks) * num_queries`` candidate rows are written there, no stage C
+        runs, nothing is returned.  Otherwise returns the kept rows and their counts as one byte buffer on the device."""
+        lib, dev = _lib.load(), self._loc.device
+        nq = len(chunk)
+        tok_cat, cls, lens = _pack_queries([c[1] for c in chunk], dev)
         i32 = C.c_int32 * nq
-        row0, ctx, lens = i32(*(v[0] for v, _ in chunk)), i32(*(v[1] for v, _ in chunk)), i32(*(int(t.shape[0]) for t in toks))
-        nbytes = lib.cone_library_localize_workspace(h, C.byref(self._cl), row0, ctx, lens, nq, K, C.byref(self._params))
-        if nbytes == 0:
-            raise _lib.ConeHipError(f"libcone_hip error: {lib.cone_last_error().decode()}")
-        ws = self._ws.get(nbytes, dev)
-        R, N = _kept_bytes(nq)
-        buf = torch.empty(R + N, dtype=torch.uint8, device=dev)
-        _lib.check(lib.cone_library_localize(h, C.byref(self._cl), row0, ctx, _lib.ptr(tok_cat, torch.float32), lens, nq,
-                                             _lib.ptr(cls, torch.float32), K, C.byref(self._params), C.c_void_p(buf.data_ptr()),
-                                             C.c_void_p(buf.data_ptr() + R), _lib.ptr(ws), ws.numel(), _lib.stream()))
-        return buf
-
-    def _enqueue_ragged(self, chunk, ks, scan=None, V=0, cand=None):
-        """One ``cone_library_localize_ragged`` call: ``chunk`` = [((row0, ctx_l), (tok, cls), scan query, slot), ...] with ``ks``
-        windows each; ``scan`` = the scan whose lists the pairs take their windows from (``None``: the call's own stage A, the
-        last two entries of a pair are ignored).  ``cand`` (fp32, on the device): ``cone_library_localize_candidates`` instead
-        -- the call's ``sum(ks) * num_queries`` candidate rows are written there, no stage C runs, nothing is returned."""
-        lib, m, dev = _lib.load(), self._loc.localizator, self._loc.device
-        h, nq = m._h(), len(chunk)
-        toks = [c[1][0].to(dev, torch.float32).contiguous() for c in chunk]
-        tok_cat = toks[0] if nq == 1 else torch.cat(toks)
-        cls = torch.stack([c[1][1].to(dev, torch.float32).reshape(-1) for c in chunk]).contiguous()
-        i32 = C.c_int32 * nq
-        row0, ctx, lens = i32(*(c[0][0] for c in chunk)), i32(*(c[0][1] for c in chunk)), i32(*(int(t.shape[0]) for t in toks))
-        pk = i32(*ks)
-        if scan is None:
-            lists = (None, None, None, None, 0, 0, 0)
-        else:
+        head = (self._loc.localizator._h(), C.byref(self._cl), i32(*(c[0][0] for c in chunk)), i32(*(c[0][1] for c in chunk)))
+        lens, count, params = i32(*lens), K if ks is None else i32(*ks), C.byref(self._params)
+        name = "cone_library_localize" + ("_candidates" if cand is not None else "_ragged" if ks is not None else
+                                          "_ranked" if scan is not None else "")
+        if scan is not None:
             _, sq, widx, wval = scan
             lists = (i32(*(c[2] for c in chunk)), i32(*(c[3] for c in chunk)), _lib.ptr(widx), _lib.ptr(wval), len(sq), V,
                      int(self._loc.args.topk_window))
-        size = lib.cone_library_localize_ragged_workspace if cand is None else lib.cone_library_localize_candidates_workspace
-        nbytes = size(h, C.byref(self._cl), row0, ctx, lens, nq, pk, C.byref(self._params), int(scan is not None))
-        if nbytes == 0:
-            raise _lib.ConeHipError(f"libcone_hip error: {lib.cone_last_error().decode()}")
-        ws = self._ws.get(nbytes, dev)
-        if cand is not None:
-            _lib.check(lib.cone_library_localize_candidates(h, C.byref(self._cl), row0, ctx, _lib.ptr(tok_cat, torch.float32), lens, nq,
-                                                            _lib.ptr(cls, torch.float32), pk, C.byref(self._params), *lists,
-                                                            _lib.ptr(cand, torch.float32), _lib.ptr(ws), ws.numel(), _lib.stream()))
-            return None
-        R, N = _kept_bytes(nq)
-        buf = torch.empty(R + N, dtype=torch.uint8, device=dev)
-        _lib.check(lib.cone_library_localize_ragged(h, C.byref(self._cl), row0, ctx, _lib.ptr(tok_cat, torch.float32), lens, nq,
-                                                    _lib.ptr(cls, torch.float32), pk, C.byref(self._params), *lists,
-                                                    C.c_void_p(buf.data_ptr()), C.c_void_p(buf.data_ptr() + R), _lib.ptr(ws),
-                                                    ws.numel(), _lib.stream()))
+        else:
+            lists = () if ks is None else (None, None, None, None, 0, 0, 0)
+        ranked = () if ks is None else (int(scan is not None),)
+        ws = self._ws.get(_lib.sized(getattr(lib, name + "_workspace")(*head, lens, nq, count, params, *ranked)), dev)
+        if cand is None:
+            R, N = _kept_bytes(nq)
+            buf = torch.empty(R + N, dtype=torch.uint8, device=dev)
+            out = (C.c_void_p(buf.data_ptr()), C.c_void_p(buf.data_ptr() + R))
+        else:
+            buf, out = None, (_lib.ptr(cand, torch.float32),)
+        _lib.check(getattr(lib, name)(*head, _lib.ptr(tok_cat, torch.float32), lens, nq, _lib.ptr(cls, torch.float32), count, params,
+                                      *lists, *out, _lib.ptr(ws), ws.numel(), _lib.stream()))
         return buf
 
-    @staticmethod
-    def _read_calls(bufs, sizes):
-        """The kept rows of the calls ``bufs`` (``sizes[i]`` pairs each) after ONE read-back, in the calls' order."""
-        host = (bufs[0] if len(bufs) == 1 else torch.cat(bufs)).cpu()
-        out, at = [], 0
-        for nq in sizes:
-            n = sum(_kept_bytes(nq))
-            out += VideoSession.read_kept(host[at:at + n].clone() if at else host, nq)
-            at += n
-        return out
+    def _enqueue(self, K, chunk):
+        """One ``cone_library_localize`` call: ``chunk`` = [((row0, ctx_l), (tok, cls)), ...], at most MAX_QUERIES."""
+        return self._localize(chunk, K=K)
+
+    def _enqueue_ragged(self, chunk, ks, scan=None, V=0, cand=None):
+        """One ``cone_library_localize_ragged`` / ``_candidates`` call with ``ks`` windows per pair: ``_localize``'s arguments."""
+        return self._localize(chunk, ks=ks, scan=scan, V=V, cand=cand)
 
     @torch.no_grad()
     def predict_moments(self, pairs, ragged=False, windows=None):
@@ -741,17 +711,12 @@ class VideoLibrary:
             calls = plan_ragged_calls([v[0] for v in videos], ks)
             where = inverse_order([(None, idx) for idx in calls], len(pairs))
             bufs = [self._enqueue_ragged([(videos[i][:2], pairs[i][1], 0, 0) for i in idx], [ks[i] for i in idx]) for idx in calls]
-            out = self._read_calls(bufs, [len(idx) for idx in calls])           # the call's one read-back
+            out = VideoSession._read_calls(bufs, [len(idx) for idx in calls])   # the call's one read-back
             return [out[w] for w in where]
         calls = plan_calls([v[0] for v in videos], [v[2] for v in videos])        # (a video is its first row: unique while it lives)
         where = inverse_order(calls, len(pairs))
         bufs = [self._enqueue(K, [(videos[i][:2], pairs[i][1]) for i in idx]) for K, idx in calls]
-        host = (bufs[0] if len(bufs) == 1 else torch.cat(bufs)).cpu()             # the call's one read-back
-        out, at = [], 0
-        for _, idx in calls:
-            n = sum(_kept_bytes(len(idx)))
-            out += VideoSession.read_kept(host[at:at + n].clone() if at else host, len(idx))
-            at += n
+        out = VideoSession._read_calls(bufs, [len(idx) for _, idx in calls])      # the call's one read-back
         return [out[w] for w in where]
 
     def predict_moment(self, vid_id, text_feats):
@@ -818,10 +783,7 @@ class VideoLibrary:
         _, row0, ctx, hb_off, total_hb = table
         V, nq, K = int(ctx.numel()), len(queries), int(self._loc.args.topk_window)
         cls = torch.stack([c.to(dev, torch.float32).reshape(-1) for _, c in queries]).contiguous()
-        nbytes = lib.cone_library_scan_workspace(C.byref(self._cl), V, total_hb, nq, K, n_rank)
-        if nbytes == 0:
-            raise _lib.ConeHipError(f"libcone_hip error: {lib.cone_last_error().decode()}")
-        ws = self._scan_ws.get(nbytes, dev)
+        ws = self._scan_ws.get(_lib.sized(lib.cone_library_scan_workspace(C.byref(self._cl), V, total_hb, nq, K, n_rank)), dev)
         widx = torch.empty(nq * V * K, dtype=torch.int32, device=dev)
         wval = torch.empty(nq * V * K, dtype=torch.float32, device=dev)
         rank = torch.empty(2, nq, n_rank, dtype=torch.int32, device=dev)
@@ -864,30 +826,6 @@ class VideoLibrary:
         table, _, ranked = self._ranked(queries, n_videos, videos)
         return [[(table[0][s], v) for s, v in row] for row in ranked]
 
-    def _enqueue_ranked(self, K, chunk, scan, V):
-        """One ``cone_library_localize_ranked`` call: ``chunk`` = [((row0, ctx_l), (tok, cls), scan query, slot), ...]."""
-        lib, m, dev = _lib.load(), self._loc.localizator, self._loc.device
-        h, nq = m._h(), len(chunk)
-        _, sq, widx, wval = scan
-        toks = [t.to(dev, torch.float32).contiguous() for _, (t, _), _, _ in chunk]
-        tok_cat = toks[0] if nq == 1 else torch.cat(toks)
-        cls = torch.stack([c.to(dev, torch.float32).reshape(-1) for _, (_, c), _, _ in chunk]).contiguous()
-        i32 = C.c_int32 * nq
-        row0, ctx, lens = i32(*(v[0] for v, _, _, _ in chunk)), i32(*(v[1] for v, _, _, _ in chunk)), i32(*(int(t.shape[0]) for t in toks))
-        pq, ps = i32(*(c[2] for c in chunk)), i32(*(c[3] for c in chunk))
-        nbytes = lib.cone_library_localize_ranked_workspace(h, C.byref(self._cl), row0, ctx, lens, nq, K, C.byref(self._params))
-        if nbytes == 0:
-            raise _lib.ConeHipError(f"libcone_hip error: {lib.cone_last_error().decode()}")
-        ws = self._ws.get(nbytes, dev)
-        R, N = _kept_bytes(nq)
-        buf = torch.empty(R + N, dtype=torch.uint8, device=dev)
-        _lib.check(lib.cone_library_localize_ranked(h, C.byref(self._cl), row0, ctx, _lib.ptr(tok_cat, torch.float32), lens, nq,
-                                                    _lib.ptr(cls, torch.float32), K, C.byref(self._params), pq, ps, _lib.ptr(widx),
-                                                    _lib.ptr(wval), len(sq), V, int(self._loc.args.topk_window),
-                                                    C.c_void_p(buf.data_ptr()), C.c_void_p(buf.data_ptr() + R), _lib.ptr(ws),
-                                                    ws.numel(), _lib.stream()))
-        return buf
-
     @torch.no_grad()
     def search(self, queries, n_videos=5, videos=None):
         """``[(tok, cls), ...]`` -> per query ``[(video id, score, moments), ...]`` for its ``n_videos`` best videos (clamped to
@@ -899,27 +837,24 @@ class VideoLibrary:
         if table is None:
             return ranked
         ids, V = table[0], len(table[0])
-        bufs, plans = [], []
+        bufs, sizes, plans = [], [], []
         for scan in scans:
             g, chunk = scan[0], scan[1]
             pairs = [(q, slot) for q in range(len(chunk)) for slot, _ in ranked[g + q]]
             vids = [self._videos[ids[slot]] for _, slot in pairs]
             calls = plan_calls([v[0] for v in vids], [v[2] for v in vids])
             where = inverse_order(calls, len(pairs))
-            bufs += [self._enqueue_ranked(K, [(vids[i][:2], chunk[pairs[i][0]], pairs[i][0], pairs[i][1]) for i in idx], scan, V)
+            bufs += [self._localize([(vids[i][:2], chunk[pairs[i][0]], pairs[i][0], pairs[i][1]) for i in idx], K=K, scan=scan, V=V)
                      for K, idx in calls]
-            plans.append((calls, where))
-        host = (bufs[0] if len(bufs) == 1 else torch.cat(bufs)).cpu()             # the kept rows' one read-back
-        out, at = [], 0
-        for (g, chunk, _, _), (calls, where) in zip(scans, plans):
-            moments = []
-            for _, idx in calls:
-                n = sum(_kept_bytes(len(idx)))
-                moments += VideoSession.read_kept(host[at:at + n].clone() if at else host, len(idx))
-                at += n
+            sizes += [len(idx) for _, idx in calls]
+            plans.append(where)
+        moments = VideoSession._read_calls(bufs, sizes)                           # the kept rows' one read-back
+        out, base = [], 0
+        for (g, chunk, _, _), where in zip(scans, plans):
             it = iter(where)
             for q in range(len(chunk)):
-                out.append([(ids[slot], val, moments[next(it)]) for slot, val in ranked[g + q]])
+                out.append([(ids[slot], val, moments[base + next(it)]) for slot, val in ranked[g + q]])
+            base += len(where)
         return out
 
     # ---- window budgets ------------------------------------------------------------------------
@@ -929,10 +864,7 @@ class VideoLibrary:
         lib, dev = _lib.load(), self._loc.device
         _, chunk, _, wval = scan
         nq, K = len(chunk), int(self._loc.args.topk_window)
-        nbytes = lib.cone_library_budget_workspace(nq, V, K, W)
-        if nbytes == 0:
-            raise _lib.ConeHipError(f"libcone_hip error: {lib.cone_last_error().decode()}")
-        ws = self._scan_ws.get(nbytes, dev)         # (the scan has run: stream order)
+        ws = self._scan_ws.get(_lib.sized(lib.cone_library_budget_workspace(nq, V, K, W)), dev)     # (the scan has run: stream order)
         out = torch.empty(nq + 3 * nq * W, dtype=torch.int32, device=dev)
         at = lambda k: C.c_void_p(out.data_ptr() + 4 * (nq + k * nq * W))
         _lib.check(lib.cone_library_budget(_lib.ptr(wval), nq, V, K, W, C.c_void_p(out.data_ptr()), at(0), at(1), at(2), _lib.ptr(ws),
@@ -992,7 +924,7 @@ class VideoLibrary:
                                           [chosen[i][2] for i in idx], scan, V) for idx in calls]
             sizes += [len(idx) for idx in calls]
             plans.append((chosen, inverse_order([(None, idx) for idx in calls], len(chosen))))
-        moments = self._read_calls(bufs, sizes) if bufs else []                      # the kept rows' one read-back
+        moments = VideoSession._read_calls(bufs, sizes) if bufs else []              # the kept rows' one read-back
         out, base = [], 0
         for (g, chunk, _, _), (chosen, where) in zip(scans, plans):
             rows = [[] for _ in chunk]

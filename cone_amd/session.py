@@ -65,6 +65,15 @@ def _kept_bytes(nq: int):
     return 3 * nq * MAX_AFTER * 5 * 8, 3 * nq * 4
 
 
+def _pack_queries(queries, dev):
+    """``[(text_token_feats, text_cls_feat), ...]`` -> what one call takes of them, on the device: the token rows back to back
+    (sum of the lengths, t_dim) fp32, ``cls`` (n, v_dim) fp32, and the token lengths."""
+    toks = [t.to(dev, torch.float32).contiguous() for t, _ in queries]
+    tok_cat = toks[0] if len(toks) == 1 else torch.cat(toks)
+    cls = torch.stack([c.to(dev, torch.float32).reshape(-1) for _, c in queries]).contiguous()
+    return tok_cat, cls, [int(t.shape[0]) for t in toks]
+
+
 class VideoSession:
     """One resident video of a ``CONELocalizator`` (``open_video``).  ``predict_moment`` / ``predict_moments`` return what the
     localizer's ``predict_moment`` returns for the same video, ``==``."""
@@ -202,10 +211,8 @@ class VideoSession:
         lib, m = _lib.load(), self._loc.localizator
         h, nq, dev = m._h(), len(lens), tok_cat.device
         arr = (C.c_int32 * nq)(*lens)
-        nbytes = lib.cone_session_localize_workspace(h, C.byref(self._cs), arr, nq, self.K, self.n_cand, C.byref(self._params))
-        if nbytes == 0:
-            raise _lib.ConeHipError(f"libcone_hip error: {lib.cone_last_error().decode()}")
-        ws = self._ws.get(nbytes, dev)
+        ws = self._ws.get(_lib.sized(lib.cone_session_localize_workspace(h, C.byref(self._cs), arr, nq, self.K, self.n_cand,
+                                                                         C.byref(self._params))), dev)
         R, N = _kept_bytes(nq)
         buf = torch.empty(R + N, dtype=torch.uint8, device=dev)
         cert = torch.empty(nq, dtype=torch.int32, device=dev) if self.certified else None
@@ -237,6 +244,18 @@ class VideoSession:
         n = buf_host[R:R + N].view(torch.int32).view(3, nq)[0].tolist()
         return [[[r[0], r[1], r[4]] for r in rows[q][:n[q]]] for q in range(nq)]
 
+    @staticmethod
+    def _read_calls(bufs, sizes):
+        """The moments of the calls ``bufs`` (``enqueue``'s buffers on the device, ``sizes[i]`` queries each) after ONE
+        read-back, in the calls' order."""
+        host = (bufs[0] if len(bufs) == 1 else torch.cat(bufs)).cpu()
+        out, at = [], 0
+        for nq in sizes:
+            n = sum(_kept_bytes(nq))
+            out += VideoSession.read_kept(host[at:at + n].clone() if at else host, nq)      # (a view of another dtype starts aligned)
+            at += n
+        return out
+
     @torch.no_grad()
     def predict_moments(self, queries):
         """``[(text_token_feats, text_cls_feat), ...]`` -> a list of moment lists, each ``==`` the localizer's
@@ -248,22 +267,12 @@ class VideoSession:
         if not queries:
             return []
         self._check_live()
-        dev = self._loc.device
         bufs, counts = [], []
         for g in range(0, len(queries), MAX_QUERIES):
-            chunk = queries[g:g + MAX_QUERIES]
-            toks = [t.to(dev, torch.float32).contiguous() for t, _ in chunk]
-            tok_cat = toks[0] if len(toks) == 1 else torch.cat(toks)
-            cls = torch.stack([c.to(dev, torch.float32).reshape(-1) for _, c in chunk]).contiguous()
-            bufs.append(self.enqueue(tok_cat, [int(t.shape[0]) for t in toks], cls))
-            counts.append(len(chunk))
-        host = (bufs[0] if len(bufs) == 1 else torch.cat(bufs)).cpu()         # the call's one read-back
-        out, at = [], 0
-        for nq in counts:
-            n = sum(_kept_bytes(nq))
-            out += self.read_kept(host[at:at + n].clone() if at else host, nq)      # (a view of another dtype starts aligned)
-            at += n
-        return out
+            tok_cat, cls, lens = _pack_queries(queries[g:g + MAX_QUERIES], self._loc.device)
+            bufs.append(self.enqueue(tok_cat, lens, cls))
+            counts.append(len(lens))
+        return self._read_calls(bufs, counts)                                 # the call's one read-back
 
     def predict_moment(self, text_feats):
         """``localizer.predict_moment(video_feats, text_feats)`` for the resident video."""

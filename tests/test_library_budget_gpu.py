@@ -193,6 +193,38 @@ def test_a_window_count_per_pair_equals_the_uniform_entry_at_that_count(monkeypa
             lib.predict_moments([(ids[0], queries[0])], windows=[3])
 
 
+SMALL_CLIPS = (91, 333)                                     # K = 4, 9
+UNIFORM_WS_BYTES = 12500224                                 # cone_library_localize_workspace of the test's three pairs at K = 2, at d4d17cc
+
+
+def _uniform_ws_bytes(lib, chunk, K):
+    """cone_library_localize_workspace for ``chunk`` = [((row0, ctx_l), (tok, cls)), ...] at K windows a pair."""
+    from cone_amd import _lib
+    i32 = C.c_int32 * len(chunk)
+    return _lib.load().cone_library_localize_workspace(
+        lib._loc.localizator._h(), C.byref(lib._cl), i32(*(v[0] for v, _ in chunk)), i32(*(v[1] for v, _ in chunk)),
+        i32(*(int(q[0].shape[0]) for _, q in chunk)), len(chunk), K, C.byref(lib._params))
+
+
+def test_the_one_layout_kernel_serves_mixed_counts_in_a_run_and_leaves_the_uniform_workspace_as_it_was():
+    """Three pairs on two short videos with counts [1, K, 2]: the second video's run has mixed counts, one pair has k = 1 -- the
+    ragged outputs of the layout kernel (row_q / row_slot / cand_off, n_valid = k Nq) against the uniform entry at each k.  A
+    uniform call passes none of the three: its workspace has the size the parent commit gave it."""
+    loc = _localizer()
+    queries = _queries([7, 20, 3], seed=29)
+    with loc.open_library(sum(SMALL_CLIPS)) as lib:
+        ids = [lib.add(_video(n, seed=9)) for n in SMALL_CLIPS]
+        K = lib._videos[ids[1]][2]
+        assert [lib._videos[i][2] for i in ids] == [4, K] and K == 9
+        pairs, ks = [(ids[0], queries[0]), (ids[1], queries[1]), (ids[1], queries[2])], [1, K, 2]
+        got = lib.predict_moments(pairs, windows=ks)
+        for i, ((vid, q), k) in enumerate(zip(pairs, ks)):
+            assert got[i] == _uniform(lib, vid, q, k), (i, k)
+        n_ws = _uniform_ws_bytes(lib, [(lib._videos[v][:2], q) for v, q in pairs], 2)
+        print("uniform workspace bytes:", n_ws)
+        assert n_ws == UNIFORM_WS_BYTES
+
+
 def test_65_ragged_pairs_cross_the_call_limit_and_a_lowered_window_limit_cuts_the_calls(monkeypatch):
     from cone_amd import library
     loc = _localizer()
