@@ -262,6 +262,13 @@ _SIGNATURES = {
     "cone_watch_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 8),
     # cone_watch_store(cand, miss_widx, n_miss (device), nq, K, n_win, ctx_l, Nq, cache, stamp (device), stream)
     "cone_watch_store": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p] * 3),
+    # standing queries over a library (additive in ABI 8): the plan over the budget's pairs and a cache of one slab per video
+    # cone_watch_pool_plan(widx, wval, n_pairs, pair_slot, pair_k, v_ctx_l, v_win0, v_cap, stamp (device), nq, V, K, Wb, n_win_total,
+    # W, Nq, miss_widx, miss_wval, pair_miss, seg_off, seg_cand, seg_n, seg_tag (device), stream)
+    "cone_watch_pool_plan": (C.c_int, [C.c_void_p] * 9 + [C.c_int] * 7 + [C.c_void_p] * 8),
+    # cone_watch_pool_store(cand, jobs (device), n_jobs, miss_widx, v_ctx_l, v_win0, v_cap (device), nq, V, K, n_win_total, Nq,
+    # cache, stamp (device), stream)
+    "cone_watch_pool_store": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p] * 3),
     # cone_test_gemm(A, A2, a2_mod, W, bias, R, ln_g, ln_b, C, C2, ADD, M, N, K, flags, stream)
     "cone_test_gemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,

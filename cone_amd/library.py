@@ -52,6 +52,9 @@ one upload and one ``cone_library_add`` per run of adjacent ranges (``plan_runs`
 (cone_amd/watch.py) keeps the candidate rows of every (query, window) it has computed; its ``poll`` runs the window model only on
 the listed windows it has not seen, or saw while they were still growing, and stage C on the cache -- the answer is still
 ``predict_moment``'s, ``==``.  A ``trim`` resets the video's watchers (``_trimmed``); moves change nothing.
+``watch_moments`` is the same economy under ``search_moments``' contract: a ``LibraryWatcher`` keeps one slab of cached windows per
+resident video, its ``poll`` answers ``== search_moments`` and runs the window model only on the budget's windows the cache does
+not hold (``cone_watch_pool_plan`` / ``cone_watch_pool_store``, csrc/library_watch_pool.hip).
 Out of scope here: certified window ranking, headroom reserved behind a video, capturing the call in a graph.
 """
 from __future__ import annotations
@@ -64,7 +67,7 @@ import torch
 
 from . import _lib, ops
 from .session import MAX_QUERIES, NMS_THD, MAX_BEFORE, MAX_AFTER, VideoSession, _kept_bytes, _pack_queries, check_queries
-from .watch import VideoWatcher
+from .watch import LibraryWatcher, VideoWatcher
 
 MAX_POOL = 1024     # candidates of one query in cone_corpus_fuse_nms (csrc/stage_c.h: kMaxCand)
 
@@ -131,6 +134,15 @@ class RowRanges:
             n += self.holes[i][1]
             del self.holes[i]
         self.holes.insert(i, (start, n))
+
+    def grow(self, capacity: int):
+        """The range becomes ``[0, capacity)``: the new rows are one hole behind the old ones (coalesced with a hole that ended
+        there).  Owned ranges stay where they are."""
+        capacity = int(capacity)
+        if capacity <= self.capacity:
+            raise ValueError(f"grow: capacity={capacity} is not above the {self.capacity} rows there are")
+        old, self.capacity = self.capacity, capacity
+        self.release(old, capacity - old)
 
     def compacted(self):
         """After a compaction the owned rows are ``[0, capacity - free)``: one hole at the end (none in a full arena)."""
@@ -271,6 +283,14 @@ def inverse_order(calls, n: int):
     if at != n or -1 in where:
         raise ValueError("the plan does not cover every pair")
     return where
+
+
+def pooled_moments(rows, seg, n, seg_video):
+    """One query's answer from a ``cone_corpus_fuse_nms`` launch: ``rows`` = its kept rows ``[st, ed, prop, match, fused]``,
+    ``seg`` = their segment ordinals within the query, ``n`` = how many were kept, ``seg_video[s]`` = the video id behind the
+    query's segment ``s`` (a pair in ``search_moments``, a window in a ``LibraryWatcher``).  Returns
+    ``[(video id, [st, ed, score]), ...]``.  Pure Python, no GPU."""
+    return [(seg_video[seg[j]], [rows[j][0], rows[j][1], rows[j][4]]) for j in range(n)]
 
 
 def scan_table(videos, S: int):
@@ -750,6 +770,47 @@ class VideoLibrary:
         self._watchers.add(w)
         return w
 
+    def watch_moments(self, queries, n_windows=None, n_moments=5, videos=None):
+        """A ``LibraryWatcher`` for the standing ``queries`` = ``[(tok, cls), ...]`` (any count >= 1, 64 a call) over every
+        resident video -- or over ``videos``: ``w.poll() == lib.search_moments(queries, n_windows, n_moments, videos)`` on the
+        library as it is now, after any sequence of ``extend`` / ``trim`` / ``add`` / ``add_many`` / ``remove`` / ``compact`` /
+        ``resize``, and runs the window model only on the budget's windows it has not answered from before (``w.windows_run``,
+        of ``w.windows_listed``, per query).  ``videos=None`` follows the resident set: added videos join at the next poll,
+        removed ones drop out and their cache is freed; with an explicit list a later ``remove`` of a listed video makes
+        ``poll()`` raise what ``search_moments`` raises for that id.  A ``trim`` makes that video's cached windows stale, no
+        other's.  The watcher keeps ``num_queries`` rows of 16 B and a 4-B stamp per query and per window of every watched video
+        plus a quarter of headroom (``w.nbytes``).  fp32 libraries only; the limits are ``search_moments``'."""
+        queries = list(queries)
+        if not queries:
+            raise ValueError("VideoLibrary: watch_moments: an empty query list (a watcher needs at least one standing query)")
+        check_queries([int(q[0].shape[0]) for q in queries], self.max_q_l)
+        W = int(self._loc.args.topk_window) if n_windows is None else n_windows
+        try:
+            W = operator.index(W)
+        except TypeError:
+            raise ValueError(f"VideoLibrary: n_windows must be an integer, got {n_windows!r}") from None
+        if not 1 <= W <= 256:
+            raise ValueError(f"VideoLibrary: n_windows={W} not in [1, 256]")
+        try:
+            M = operator.index(n_moments)
+        except TypeError:
+            raise ValueError(f"VideoLibrary: n_moments must be an integer, got {n_moments!r}") from None
+        if not 1 <= M <= MAX_BEFORE:
+            raise ValueError(f"VideoLibrary: n_moments={M} not in [1, {MAX_BEFORE}]")
+        Nq = int(self._loc.args.num_queries)
+        if W * Nq > MAX_POOL:
+            raise ValueError(f"VideoLibrary: n_windows={W} x num_queries={Nq} = {W * Nq} candidates > {MAX_POOL} in one pool")
+        subset, _ = self._search_ids(videos)
+        self._check_live()
+        if self._flags & _lib.SESSION_BF16:
+            raise _lib.ConeHipError("watch_moments: CONE_SESSION_BF16 libraries are not supported (prefilter_bf16): the scan that "
+                                    "lists a poll's windows does not serve them")
+        w = LibraryWatcher(self, queries, W, M, subset)
+        if self._watchers is None:
+            self._watchers = weakref.WeakSet()
+        self._watchers.add(w)
+        return w
+
     # ---- search --------------------------------------------------------------------------------
     def _search_ids(self, videos):
         """The ids a search runs over: every resident video, or the caller's (unknown ids and duplicates are refused)."""
@@ -1041,5 +1102,5 @@ class VideoLibrary:
             o += n_r + n_i
             first = [0] + np.cumsum(n_pairs).tolist()
             for q in range(nq):
-                res.append([(ids[chosen[first[q] + seg[q][j]][1]], [rows[q][j][0], rows[q][j][1], rows[q][j][4]]) for j in range(n[q])])
+                res.append(pooled_moments(rows[q], seg[q], n[q], [ids[c[1]] for c in chosen[first[q]:first[q + 1]]]))
         return res

@@ -867,6 +867,58 @@ int cone_watch_plan(const int32_t* widx, const float* wval, int nq, int K, const
 int cone_watch_store(const float* cand, const int32_t* miss_widx, const int32_t* n_miss, int nq, int K, int n_win, int ctx_l, int Nq,
                      float* cache, int32_t* stamp, void* stream);
 
+/* ------------------------------------------------------------ standing queries over a library (additive, ABI 8)
+ * The standing queries above, asked of EVERY resident video at once: the library moment search's contract (the budget's windows
+ * are one pool per query) at the watcher's price (the window model runs only on chosen windows the cache does not hold).  One
+ * cache and one stamp plane serve all watched videos (cone_amd/watch.py, LibraryWatcher):
+ *   cache (nq, n_win_total, Nq, 4) fp32, stamp (nq, n_win_total) int32; table slot s of the scan owns the SLAB
+ *   [v_win0[s], v_win0[s] + v_cap[s]) of the window axis: window wi of its video is axis entry v_win0[s] + wi, and its stamps are
+ *   clip counts of that video, judged against v_ctx_l[s] by the rule above.  v_ctx_l / v_win0 / v_cap (V) int32, device.
+ * The caller keeps slabs disjoint and inside the axis and zeroes a slab's stamps when its video is trimmed or the slab changes
+ * hands.  Both entries are one small launch, plain vector loads and stores, every output element with one writer: no atomics, no
+ * allocation, no read-back. */
+
+/* The plan of one poll for nq queries; one workgroup of 256 threads per query.  widx / wval (nq, V, K): a cone_library_scan's
+ * lists; n_pairs (nq), pair_slot / pair_k (nq, Wb): a cone_library_budget's outputs at W = Wb (all device).  The CHOSEN windows of
+ * query q, in POOL ORDER: the pairs in the budget's order, of pair i the list positions 0 .. pair_k - 1 of (q, pair_slot[i]) --
+ * the order in which cone_library_localize_candidates lays a search's pool.  Chosen window t (its ordinal) with list entry wi in
+ * slot s is LISTED when 0 <= wi < v_cap[s] (and v_win0[s] >= 0, v_win0[s] + wi < n_win_total: an entry outside the axis is never
+ * read) and MISSING when it is listed and stamp[q][v_win0[s] + wi] is not valid at v_ctx_l[s].
+ * Device data is clamped, never trusted: n_pairs into [0, Wb]; pair_k into [0, K]; a slot outside [0, V) is an empty pair; chosen
+ * windows past the first Wb are neither planned nor listed (a pair that crosses the cap is cut there).
+ * Outputs (device), every element named here written:
+ *   miss_widx / miss_wval in the scan's (nq, V, K) layout: for every pair with a planned window, row (q, slot) holds the pair's
+ *     missing windows first, in list order (stable), then -1 / -inf up to the pair's planned count: the lists' block of a
+ *     cone_library_localize_candidates call with the pair's own pair_query / pair_slot and pair_k = pair_miss.  Rows of slots
+ *     the budget did not choose, and a row's entries past the planned count, are NOT written;
+ *   pair_miss (nq, Wb): the missing windows of pair i, 0 past n_pairs;
+ *   the DENSE segment table of cone_corpus_fuse_nms over the cache, one segment per chosen window: seg_off (nq + 1) = q Wb;
+ *     segment q Wb + t has seg_cand (int64) = (q n_win_total + v_win0[s] + wi) Nq and seg_n = Nq when listed, else 0 and 0;
+ *     seg_tag = s; t at or past the chosen count: 0, 0, 0.  The table does not depend on hit or miss.
+ * PRECONDITION: the slots of one query's pairs are distinct (the budget guarantees it) -- two pairs on one slot would be two
+ * writers of one miss row.
+ * Refused by name ("watch_pool_plan: "), from host values first, in this order, before any pointer is looked at: nq outside
+ * [1, 64]; V < 1; K outside [1, 256]; Wb outside [1, 256]; Nq outside [1, 16]; n_win_total < 1; W < 2; then null arguments. */
+int cone_watch_pool_plan(const int32_t* widx, const float* wval, const int32_t* n_pairs, const int32_t* pair_slot,
+                         const int32_t* pair_k, const int32_t* v_ctx_l, const int32_t* v_win0, const int32_t* v_cap,
+                         const int32_t* stamp, int nq, int V, int K, int Wb, int n_win_total, int W, int Nq, int32_t* miss_widx,
+                         float* miss_wval, int32_t* pair_miss, int32_t* seg_off, int64_t* seg_cand, int32_t* seg_n,
+                         int32_t* seg_tag, void* stream);
+
+/* Scatters the rows the cone_library_localize_candidates calls wrote for the plan's miss lists into the cache and stamps them;
+ * one workgroup per job.  jobs (n_jobs, 4) int32 on the device, one per pair that missed something, in the order of the host's
+ * planned calls: query, slot, n_miss, the pair's first row in cand (in rows of 16 B).  For m < min(max(n_miss, 0), K) with
+ * wi = miss_widx[(query V + slot) K + m] inside [0, v_cap[slot]) (and inside the axis, as above): the Nq rows of 16 B from
+ * cand row first + m Nq go to cache row (query n_win_total + v_win0[slot] + wi) Nq, and that stamp = v_ctx_l[slot]; an index
+ * outside is skipped, as is a job whose query lies outside [0, nq), whose slot lies outside [0, V) or whose first row is
+ * negative.  Nothing else is written.  PRECONDITION: the (query, slot) of the jobs are distinct and so are the window indices of
+ * one list (a top-k list guarantees it).  cand and cache must be 16-B aligned.
+ * Refused by name ("watch_pool_store: "), from host values first, in this order: nq outside [1, 64]; V < 1; K outside [1, 256];
+ * Nq outside [1, 16]; n_win_total < 1; n_jobs < 1; then null arguments, then a misaligned cand or cache. */
+int cone_watch_pool_store(const float* cand, const int32_t* jobs, int n_jobs, const int32_t* miss_widx, const int32_t* v_ctx_l,
+                          const int32_t* v_win0, const int32_t* v_cap, int nq, int V, int K, int n_win_total, int Nq, float* cache,
+                          int32_t* stamp, void* stream);
+
 /* -------------------------------------------------------------------- metrics on the device
  * Recall@K / IoU counts from the kept rows (layout of cone_fuse_nms: rows (nq, max_after, 5) fp64 [st, ed, ...],
  * n (nq) valid rows) and one target span per query gt (nq, 2) fp64 seconds -- device pointers.  thresholds /
