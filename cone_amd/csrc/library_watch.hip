@@ -7,26 +7,18 @@
 // Both are latency-bound: one workgroup of 256 threads per query, a few hundred bytes each.  The compaction of the missing
 // entries keeps list order: a wave ballot and the count of the lower lanes inside a wave, the four waves' totals through LDS
 // (K <= 256 = one entry per thread).  Every output element has exactly one writer and is written with a plain vector store.
-#include "common.h"
+// The validity rule, the store loop, the constants and the shared refusals are watch_common.h's.
+#include "watch_common.h"
 
 namespace cone {
 
-constexpr int WATCH_MAX_K = 256;        // one thread per list entry
-constexpr int WATCH_MAX_NQ = 16;        // decoder slots per window
-
-// (wi - 1) S + W <= stamp: the window's clip range [max((wi - 1) S, 0), min((wi - 1) S + W, ctx_l)) was not cut by the video's
-// end when the entry was computed, so it is the range of today (a video only grows between two resets of the stamps).
-__device__ __forceinline__ bool watch_valid(int wi, int stamp, int ctx_l, int W, int S) {
-    return stamp == ctx_l || (stamp > 0 && (long long)(wi - 1) * S + W <= (long long)stamp);
-}
-
-__global__ __launch_bounds__(WATCH_MAX_K) void watch_plan_kernel(const int32_t* __restrict__ widx, const float* __restrict__ wval,
+__global__ __launch_bounds__(WATCH_T) void watch_plan_kernel(const int32_t* __restrict__ widx, const float* __restrict__ wval,
                                                                  int nq, int K, const int32_t* __restrict__ stamp, int n_win, int ctx_l,
                                                                  int W, int Nq, int32_t* __restrict__ miss_widx,
                                                                  float* __restrict__ miss_wval, int32_t* __restrict__ n_miss,
                                                                  int32_t* __restrict__ seg_off, int64_t* __restrict__ seg_cand,
                                                                  int32_t* __restrict__ seg_n, int32_t* __restrict__ seg_tag) {
-    __shared__ int s_wave[WATCH_MAX_K / 64];
+    __shared__ int s_wave[WATCH_T / 64];
     const int q = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const size_t row = (size_t)q * K;
     int wi = -1;
@@ -60,7 +52,7 @@ __global__ __launch_bounds__(WATCH_MAX_K) void watch_plan_kernel(const int32_t* 
     }
 }
 
-__global__ __launch_bounds__(256) void watch_store_kernel(const float4* __restrict__ cand, const int32_t* __restrict__ miss_widx,
+__global__ __launch_bounds__(WATCH_T) void watch_store_kernel(const float4* __restrict__ cand, const int32_t* __restrict__ miss_widx,
                                                           const int32_t* __restrict__ n_miss, int K, int n_win, int ctx_l, int Nq,
                                                           float4* __restrict__ cache, int32_t* __restrict__ stamp) {
     __shared__ int s_first;         // window rows of the queries before this one
@@ -73,24 +65,8 @@ __global__ __launch_bounds__(256) void watch_store_kernel(const float4* __restri
     }
     __syncthreads();
     const int n = min(max(n_miss[q], 0), K);
-    const int32_t* list = miss_widx + (size_t)q * K;
-    const float4* src = cand + (size_t)s_first * Nq;
-    for (int i = t; i < n * Nq; i += 256) {
-        const int m = i / Nq, r = i - m * Nq;
-        const int wi = list[m];
-        if (wi >= 0 && wi < n_win) cache[((size_t)q * n_win + wi) * Nq + r] = src[(size_t)m * Nq + r];
-    }
-    for (int m = t; m < n; m += 256) {
-        const int wi = list[m];
-        if (wi >= 0 && wi < n_win) stamp[(size_t)q * n_win + wi] = ctx_l;
-    }
-}
-
-// The refusals from host values alone, in this order, before any pointer is looked at.
-static int watch_precheck(const char* who, int nq, int K) {
-    CONE_REQUIRE(nq >= 1 && nq <= CONE_SESSION_MAX_QUERIES, "%s: nq=%d not in [1, %d]", who, nq, CONE_SESSION_MAX_QUERIES);
-    CONE_REQUIRE(K >= 1 && K <= WATCH_MAX_K, "%s: K=%d not in [1, %d]", who, K, WATCH_MAX_K);
-    return 0;
+    // the one video's slab is the whole axis: windows [0, n_win) of query q
+    watch_store_rows(miss_widx + (size_t)q * K, n, cand + (size_t)s_first * Nq, Nq, (size_t)q * n_win, n_win, n_win, ctx_l, cache, stamp);
 }
 
 }  // namespace cone
@@ -99,15 +75,15 @@ extern "C" int cone_watch_plan(const int32_t* widx, const float* wval, int nq, i
                                int Nq, int32_t* miss_widx, float* miss_wval, int32_t* n_miss, int32_t* seg_off, int64_t* seg_cand,
                                int32_t* seg_n, int32_t* seg_tag, void* stream) {
     using namespace cone;
-    const char* who = "watch_plan";
-    if (int rc = watch_precheck(who, nq, K)) return rc;
-    CONE_REQUIRE(Nq >= 1 && Nq <= WATCH_MAX_NQ, "%s: Nq=%d not in [1, %d]", who, Nq, WATCH_MAX_NQ);
+    const char* who = "watch_plan";     // (the refusals from host values alone, in this order, before any pointer is looked at)
+    if (int rc = watch_precheck(who, nq, 1, K)) return rc;
+    if (int rc = watch_check_slots(who, Nq)) return rc;
     CONE_REQUIRE(n_win >= 1, "%s: n_win=%d < 1", who, n_win);
     CONE_REQUIRE(ctx_l >= 1, "%s: ctx_l=%d < 1", who, ctx_l);
     CONE_REQUIRE(W >= 2, "%s: W=%d < 2", who, W);
     CONE_REQUIRE(widx && wval && stamp && miss_widx && miss_wval && n_miss && seg_off && seg_cand && seg_n && seg_tag,
                  "%s: null argument", who);
-    hipLaunchKernelGGL(watch_plan_kernel, dim3(nq), dim3(WATCH_MAX_K), 0, (hipStream_t)stream, widx, wval, nq, K, stamp, n_win, ctx_l, W,
+    hipLaunchKernelGGL(watch_plan_kernel, dim3(nq), dim3(WATCH_T), 0, (hipStream_t)stream, widx, wval, nq, K, stamp, n_win, ctx_l, W,
                        Nq, miss_widx, miss_wval, n_miss, seg_off, seg_cand, seg_n, seg_tag);
     CONE_LAUNCH_CHECK();
     return 0;
@@ -117,13 +93,13 @@ extern "C" int cone_watch_store(const float* cand, const int32_t* miss_widx, con
                                 int Nq, float* cache, int32_t* stamp, void* stream) {
     using namespace cone;
     const char* who = "watch_store";
-    if (int rc = watch_precheck(who, nq, K)) return rc;
+    if (int rc = watch_precheck(who, nq, 1, K)) return rc;
     CONE_REQUIRE(n_win >= 1, "%s: n_win=%d < 1", who, n_win);
     CONE_REQUIRE(ctx_l >= 1, "%s: ctx_l=%d < 1", who, ctx_l);
-    CONE_REQUIRE(Nq >= 1 && Nq <= WATCH_MAX_NQ, "%s: Nq=%d not in [1, %d]", who, Nq, WATCH_MAX_NQ);
+    if (int rc = watch_check_slots(who, Nq)) return rc;
     CONE_REQUIRE(cand && miss_widx && n_miss && cache && stamp, "%s: null argument", who);
-    CONE_REQUIRE((((uintptr_t)cand | (uintptr_t)cache) & 15) == 0, "%s: cand and cache must be 16-B aligned", who);
-    hipLaunchKernelGGL(watch_store_kernel, dim3(nq), dim3(256), 0, (hipStream_t)stream, (const float4*)cand, miss_widx, n_miss, K,
+    if (int rc = watch_check_rows(who, cand, cache)) return rc;
+    hipLaunchKernelGGL(watch_store_kernel, dim3(nq), dim3(WATCH_T), 0, (hipStream_t)stream, (const float4*)cand, miss_widx, n_miss, K,
                        n_win, ctx_l, Nq, (float4*)cache, stamp);
     CONE_LAUNCH_CHECK();
     return 0;

@@ -10,18 +10,11 @@
 // (which pair owns ordinal t), the missing flags over the ordinals (a wave ballot and the count of the lower lanes); a pair's
 // misses are the difference of the second at the pair's two ends, so the compaction is stable and segmented across wave edges.
 // The store runs one workgroup per job (a pair that missed something).  Every output element has exactly one writer and is written
-// with a plain vector store.
-#include "common.h"
+// with a plain vector store.  A window is missing by watch_common.h's rule (watch_valid) at ITS video's clip count; the store
+// loop, the constants and the shared refusals are that header's too.
+#include "watch_common.h"
 
 namespace cone {
-
-constexpr int POOL_T = 256;             // threads of a workgroup = the most pairs, list entries and chosen windows of a query
-constexpr int POOL_MAX_NQ = 16;         // decoder slots per window
-
-// library_watch.hip's rule: the window was not cut by the video's end when the entry was computed.
-__device__ __forceinline__ bool pool_valid(int wi, int stamp, int ctx_l, int W, int S) {
-    return stamp == ctx_l || (stamp > 0 && (long long)(wi - 1) * S + W <= (long long)stamp);
-}
 
 // Inclusive prefix sum of v over the 256 threads; s_wave holds the four waves' totals afterwards (the caller syncs before it
 // reuses s_wave).
@@ -38,17 +31,17 @@ __device__ __forceinline__ int pool_scan_incl(int v, int* s_wave) {
     return v;
 }
 
-__global__ __launch_bounds__(POOL_T) void watch_pool_plan_kernel(
+__global__ __launch_bounds__(WATCH_T) void watch_pool_plan_kernel(
     const int32_t* __restrict__ widx, const float* __restrict__ wval, const int32_t* __restrict__ n_pairs,
     const int32_t* __restrict__ pair_slot, const int32_t* __restrict__ pair_k, const int32_t* __restrict__ v_ctx_l,
     const int32_t* __restrict__ v_win0, const int32_t* __restrict__ v_cap, const int32_t* __restrict__ stamp, int nq, int V, int K,
     int Wb, int n_win_total, int W, int Nq, int32_t* __restrict__ miss_widx, float* __restrict__ miss_wval,
     int32_t* __restrict__ pair_miss, int32_t* __restrict__ seg_off, int64_t* __restrict__ seg_cand, int32_t* __restrict__ seg_n,
     int32_t* __restrict__ seg_tag) {
-    __shared__ int s_end[POOL_T];           // chosen windows up to and including pair p
-    __shared__ int s_slot[POOL_T];
-    __shared__ int s_before[POOL_T + 1];    // missing windows among the ordinals below t; [256] = all of them
-    __shared__ int s_wave_k[POOL_T / 64], s_wave_m[POOL_T / 64];
+    __shared__ int s_end[WATCH_T];           // chosen windows up to and including pair p
+    __shared__ int s_slot[WATCH_T];
+    __shared__ int s_before[WATCH_T + 1];    // missing windows among the ordinals below t; [256] = all of them
+    __shared__ int s_wave_k[WATCH_T / 64], s_wave_m[WATCH_T / 64];
     const int q = blockIdx.x, t = threadIdx.x, lane = t & 63;
     const size_t prow = (size_t)q * Wb;
     // ---- the pairs: thread t is pair t
@@ -63,7 +56,7 @@ __global__ __launch_bounds__(POOL_T) void watch_pool_plan_kernel(
     s_end[t] = end;
     s_slot[t] = slot;
     __syncthreads();
-    const int total = min(s_end[POOL_T - 1], Wb);      // chosen windows past the first Wb are neither planned nor listed
+    const int total = min(s_end[WATCH_T - 1], Wb);      // chosen windows past the first Wb are neither planned nor listed
     // ---- the chosen windows: thread t is ordinal t
     int p = 0, j = 0, wslot = 0, wi = -1, first = 0;
     float val = -INFINITY;
@@ -71,7 +64,7 @@ __global__ __launch_bounds__(POOL_T) void watch_pool_plan_kernel(
     size_t lrow = 0;
     int64_t cand = 0;
     if (t < total) {
-        int lo = 0, hi = POOL_T - 1;                    // the first pair whose end lies above t (s_end[255] > t)
+        int lo = 0, hi = WATCH_T - 1;                    // the first pair whose end lies above t (s_end[255] > t)
         while (lo < hi) {
             const int mid = (lo + hi) >> 1;
             if (s_end[mid] > t) hi = mid; else lo = mid + 1;
@@ -87,7 +80,7 @@ __global__ __launch_bounds__(POOL_T) void watch_pool_plan_kernel(
         listed = wi >= 0 && wi < v_cap[wslot] && win0 >= 0 && (long long)win0 + wi < (long long)n_win_total;
         if (listed) {
             const size_t at = (size_t)q * n_win_total + win0 + wi;
-            missing = !pool_valid(wi, stamp[at], v_ctx_l[wslot], W, W / 2);
+            missing = !watch_valid(wi, stamp[at], v_ctx_l[wslot], W, W / 2);
             cand = (int64_t)at * Nq;
         }
     }
@@ -104,7 +97,7 @@ __global__ __launch_bounds__(POOL_T) void watch_pool_plan_kernel(
     int before = __popcll(b & ((1ull << lane) - 1ull));
     for (int w = 0; w < (t >> 6); ++w) before += s_wave_m[w];
     s_before[t] = before;
-    if (t == 0) s_before[POOL_T] = s_wave_m[0] + s_wave_m[1] + s_wave_m[2] + s_wave_m[3];
+    if (t == 0) s_before[WATCH_T] = s_wave_m[0] + s_wave_m[1] + s_wave_m[2] + s_wave_m[3];
     __syncthreads();
     if (t < total) {        // ordinal t is entry j of pair p: the pair's misses first, in list order, then the padding
         const int last = min(s_end[p], total);
@@ -130,36 +123,17 @@ __global__ __launch_bounds__(POOL_T) void watch_pool_plan_kernel(
     }
 }
 
-__global__ __launch_bounds__(POOL_T) void watch_pool_store_kernel(
+__global__ __launch_bounds__(WATCH_T) void watch_pool_store_kernel(
     const float4* __restrict__ cand, const int32_t* __restrict__ jobs, const int32_t* __restrict__ miss_widx,
     const int32_t* __restrict__ v_ctx_l, const int32_t* __restrict__ v_win0, const int32_t* __restrict__ v_cap, int nq, int V, int K,
     int n_win_total, int Nq, float4* __restrict__ cache, int32_t* __restrict__ stamp) {
-    const int t = threadIdx.x;
     const int32_t* job = jobs + (size_t)blockIdx.x * 4;
     const int q = job[0], slot = job[1], n = min(max(job[2], 0), K), first = job[3];
     if (q < 0 || q >= nq || slot < 0 || slot >= V || first < 0) return;        // (uniform over the workgroup)
     const int win0 = v_win0[slot], cap = v_cap[slot], ctx_l = v_ctx_l[slot];
     if (win0 < 0) return;
-    const int32_t* list = miss_widx + ((size_t)q * V + slot) * K;
-    const float4* src = cand + (size_t)first;
-    const size_t base = (size_t)q * n_win_total + win0;
-    for (int i = t; i < n * Nq; i += POOL_T) {
-        const int m = i / Nq, r = i - m * Nq;
-        const int wi = list[m];
-        if (wi >= 0 && wi < cap && (long long)win0 + wi < (long long)n_win_total) cache[(base + wi) * Nq + r] = src[(size_t)m * Nq + r];
-    }
-    for (int m = t; m < n; m += POOL_T) {
-        const int wi = list[m];
-        if (wi >= 0 && wi < cap && (long long)win0 + wi < (long long)n_win_total) stamp[base + wi] = ctx_l;
-    }
-}
-
-// The refusals from host values alone, in this order, before any pointer is looked at.
-static int watch_pool_precheck(const char* who, int nq, int V, int K) {
-    CONE_REQUIRE(nq >= 1 && nq <= CONE_SESSION_MAX_QUERIES, "%s: nq=%d not in [1, %d]", who, nq, CONE_SESSION_MAX_QUERIES);
-    CONE_REQUIRE(V >= 1, "%s: V=%d < 1", who, V);
-    CONE_REQUIRE(K >= 1 && K <= POOL_T, "%s: K=%d not in [1, %d]", who, K, POOL_T);
-    return 0;
+    watch_store_rows(miss_widx + ((size_t)q * V + slot) * K, n, cand + (size_t)first, Nq, (size_t)q * n_win_total + win0, cap,
+                     (long long)n_win_total - win0, ctx_l, cache, stamp);
 }
 
 }  // namespace cone
@@ -170,16 +144,16 @@ extern "C" int cone_watch_pool_plan(const int32_t* widx, const float* wval, cons
                                     int32_t* miss_widx, float* miss_wval, int32_t* pair_miss, int32_t* seg_off, int64_t* seg_cand,
                                     int32_t* seg_n, int32_t* seg_tag, void* stream) {
     using namespace cone;
-    const char* who = "watch_pool_plan";
-    if (int rc = watch_pool_precheck(who, nq, V, K)) return rc;
-    CONE_REQUIRE(Wb >= 1 && Wb <= POOL_T, "%s: Wb=%d not in [1, %d]", who, Wb, POOL_T);
-    CONE_REQUIRE(Nq >= 1 && Nq <= POOL_MAX_NQ, "%s: Nq=%d not in [1, %d]", who, Nq, POOL_MAX_NQ);
+    const char* who = "watch_pool_plan";    // (the refusals from host values alone, in this order, before any pointer is looked at)
+    if (int rc = watch_precheck(who, nq, V, K)) return rc;
+    CONE_REQUIRE(Wb >= 1 && Wb <= WATCH_T, "%s: Wb=%d not in [1, %d]", who, Wb, WATCH_T);
+    if (int rc = watch_check_slots(who, Nq)) return rc;
     CONE_REQUIRE(n_win_total >= 1, "%s: n_win_total=%d < 1", who, n_win_total);
     CONE_REQUIRE(W >= 2, "%s: W=%d < 2", who, W);
     CONE_REQUIRE(widx && wval && n_pairs && pair_slot && pair_k && v_ctx_l && v_win0 && v_cap && stamp && miss_widx && miss_wval &&
                      pair_miss && seg_off && seg_cand && seg_n && seg_tag,
                  "%s: null argument", who);
-    hipLaunchKernelGGL(watch_pool_plan_kernel, dim3(nq), dim3(POOL_T), 0, (hipStream_t)stream, widx, wval, n_pairs, pair_slot, pair_k,
+    hipLaunchKernelGGL(watch_pool_plan_kernel, dim3(nq), dim3(WATCH_T), 0, (hipStream_t)stream, widx, wval, n_pairs, pair_slot, pair_k,
                        v_ctx_l, v_win0, v_cap, stamp, nq, V, K, Wb, n_win_total, W, Nq, miss_widx, miss_wval, pair_miss, seg_off,
                        seg_cand, seg_n, seg_tag);
     CONE_LAUNCH_CHECK();
@@ -191,13 +165,13 @@ extern "C" int cone_watch_pool_store(const float* cand, const int32_t* jobs, int
                                      int n_win_total, int Nq, float* cache, int32_t* stamp, void* stream) {
     using namespace cone;
     const char* who = "watch_pool_store";
-    if (int rc = watch_pool_precheck(who, nq, V, K)) return rc;
-    CONE_REQUIRE(Nq >= 1 && Nq <= POOL_MAX_NQ, "%s: Nq=%d not in [1, %d]", who, Nq, POOL_MAX_NQ);
+    if (int rc = watch_precheck(who, nq, V, K)) return rc;
+    if (int rc = watch_check_slots(who, Nq)) return rc;
     CONE_REQUIRE(n_win_total >= 1, "%s: n_win_total=%d < 1", who, n_win_total);
     CONE_REQUIRE(n_jobs >= 1, "%s: n_jobs=%d < 1", who, n_jobs);
     CONE_REQUIRE(cand && jobs && miss_widx && v_ctx_l && v_win0 && v_cap && cache && stamp, "%s: null argument", who);
-    CONE_REQUIRE((((uintptr_t)cand | (uintptr_t)cache) & 15) == 0, "%s: cand and cache must be 16-B aligned", who);
-    hipLaunchKernelGGL(watch_pool_store_kernel, dim3(n_jobs), dim3(POOL_T), 0, (hipStream_t)stream, (const float4*)cand, jobs, miss_widx,
+    if (int rc = watch_check_rows(who, cand, cache)) return rc;
+    hipLaunchKernelGGL(watch_pool_store_kernel, dim3(n_jobs), dim3(WATCH_T), 0, (hipStream_t)stream, (const float4*)cand, jobs, miss_widx,
                        v_ctx_l, v_win0, v_cap, nq, V, K, n_win_total, Nq, (float4*)cache, stamp);
     CONE_LAUNCH_CHECK();
     return 0;

@@ -29,6 +29,9 @@ each normalised over the candidates of ONE pair (every pair's best proposal beco
 budget's pairs run through ``cone_library_localize_candidates`` -- the ragged call stopped before its stage C -- into one
 candidate buffer, and ``cone_corpus_fuse_nms`` (csrc/library_corpus.hip) runs the reference's stage C over the whole pool of a
 query: both score lists normalised over the pool, the dict keyed by (video, st, ed), NMS inside each video only.
+Every budgeted call is built from the same pieces: ``_budget_args`` (the refusals), ``_scan_budget`` (scan + budget per 64
+queries), ``decode_budget`` (the read-back's words), ``place_calls`` (the calls' rows in the one candidate buffer) and ``FuseOut``
+(stage C's output layout, its launch and its read-back).
 
 Rows are handed out first-fit from a free list and coalesce when a video is removed, so ``add`` / ``remove`` traffic
 fragments the arena: by default ``add`` raises when no hole fits, however many clips are free in total.  ``compact`` closes the
@@ -61,6 +64,7 @@ from __future__ import annotations
 
 import ctypes as C
 import operator
+import struct
 import weakref
 
 import torch
@@ -291,6 +295,83 @@ def pooled_moments(rows, seg, n, seg_video):
     query's segment ``s`` (a pair in ``search_moments``, a window in a ``LibraryWatcher``).  Returns
     ``[(video id, [st, ed, score]), ...]``.  Pure Python, no GPU."""
     return [(seg_video[seg[j]], [rows[j][0], rows[j][1], rows[j][4]]) for j in range(n)]
+
+
+def _as_int(value, refusal):
+    try:
+        return operator.index(value)
+    except TypeError:
+        raise ValueError(refusal) from None
+
+
+def _chunked(queries):
+    return [queries[g:g + MAX_QUERIES] for g in range(0, len(queries), MAX_QUERIES)]
+
+
+def decode_budget(words, at, nq, W, best=False, miss_at=None):
+    """One chunk of the budget's read-back, ``words`` = the int32 words as a flat list, ``at`` = the chunk's first word: ``n_pairs
+    (nq) | pair_slot | pair_k | pair_best (nq x W each)``.  Returns ``(pairs, the next chunk's first word)``; ``pairs[q]`` = the
+    query's pairs in the budget's order, ``(slot, k)`` each -- ``(slot, k, best score)`` with ``best``, the score decoded from its
+    float32 bits; ``(slot, k, miss)`` with ``miss_at`` = the first word of the chunk's ``pair_miss`` plane ``(nq, W)`` that a
+    ``LibraryWatcher`` appends to the read-back.  Pure Python, no GPU."""
+    pairs = []
+    for q in range(nq):
+        n, row = words[at + q], at + nq + q * W
+        if not 0 <= n <= W:
+            raise IndexError(f"decode_budget: query {q} of the chunk has n_pairs={n}, not in [0, {W}]")
+        cols = [words[row:row + n], words[row + nq * W:row + nq * W + n]]
+        if best:
+            bits = words[row + 2 * nq * W:row + 2 * nq * W + n]
+            cols.append(struct.unpack(f"{n}f", struct.pack(f"{n}i", *bits)))
+        if miss_at is not None:
+            cols.append(words[miss_at + q * W:miss_at + q * W + n])
+        pairs.append(list(zip(*cols)))
+    return pairs, at + nq + 3 * nq * W
+
+
+def place_calls(calls, counts, Nq: int, first: int = 0):
+    """Where the candidate rows of ragged calls lie in ONE buffer: ``calls`` = ``plan_ragged_calls``' index lists over pairs of
+    ``counts[i]`` windows, ``Nq`` rows a window.  The calls follow each other from row ``first``, inside a call the pairs lie in
+    the call's order (a call writes from its first pair's row).  Returns ``(row_of, end)``: pair i's first row, and the row behind
+    the last.  Pure Python, no GPU."""
+    row_of, at = [0] * len(counts), first
+    for idx in calls:
+        for i in idx:
+            row_of[i] = at
+            at += counts[i] * Nq
+    return row_of, at
+
+
+class FuseOut:
+    """The outputs of the ``cone_corpus_fuse_nms`` launches of one call in ONE float64 tensor, one read-back: per chunk of ``nq``
+    queries ``out_rows (nq, M, 5) float64 | out_seg (nq, M) int32 | out_n (nq) int32``, the int32 words padded to a whole 8-byte
+    word so that the next chunk's rows stay aligned.  ``regions[i]`` = chunk i's three outputs, ``(byte offset, bytes)`` each.
+    A watcher keeps one for its life: the sizes never change, and a poll has read the buffer back before the next writes it."""
+
+    def __init__(self, nqs, M, device):
+        self.nqs, self.M, self.regions = list(nqs), int(M), []
+        at = 0
+        for nq in self.nqs:
+            seg = at + 8 * nq * M * 5
+            self.regions.append(((at, seg - at), (seg, 4 * nq * M), (seg + 4 * nq * M, 4 * nq)))
+            at += 8 * (nq * M * 5 + (nq * M + nq + 1) // 2)
+        self.buf = torch.empty(at // 8, dtype=torch.float64, device=device)
+
+    def launch(self, i, cand, seg_off, seg_cand, seg_n, seg_tag, n_seg):
+        """Stage C of chunk i over the candidate rows at ``cand`` and a table of ``n_seg`` segments (five device pointers)."""
+        out = [C.c_void_p(self.buf.data_ptr() + off) for off, _ in self.regions[i]]
+        _lib.check(_lib.load().cone_corpus_fuse_nms(cand, seg_off, seg_cand, seg_n, seg_tag, self.nqs[i], n_seg, NMS_THD, MAX_BEFORE,
+                                                    self.M, *out, _lib.stream()))
+
+    def read(self, seg=True):
+        """The one read-back: per chunk ``(rows, seg, kept)`` as lists -- per query ``M`` rows ``[st, ed, prop, match, fused]``,
+        their ``M`` segment ordinals (``None`` without ``seg``: a caller with one video does not ask), and how many were kept."""
+        host, M, out = self.buf.cpu(), self.M, []
+        for nq, ((r, n_r), (s, _), (k, n_k)) in zip(self.nqs, self.regions):
+            ints = host[s // 8:(k + n_k + 7) // 8].view(torch.int32).tolist()
+            out.append((host[r // 8:s // 8].view(nq, M, 5).tolist(), [ints[q * M:(q + 1) * M] for q in range(nq)] if seg else None,
+                        ints[nq * M:nq * M + nq]))
+        return out
 
 
 def scan_table(videos, S: int):
@@ -549,10 +630,7 @@ class VideoLibrary:
         launched (``remove``'s stream rule), and every later answer ``==`` ``predict_moment(video[n_front:], query)`` -- seconds
         count from the new first clip.  ``0 <= n_front < clips`` (0 changes nothing; dropping every clip is ``remove``)."""
         row0, n, _ = self._video(vid_id)
-        try:
-            n_front = operator.index(n_front)
-        except TypeError:
-            raise ValueError(f"trim: n_front must be an integer, got {n_front!r}") from None
+        n_front = _as_int(n_front, f"trim: n_front must be an integer, got {n_front!r}")
         if not 0 <= n_front < n:
             raise ValueError(f"trim: n_front={n_front} not in [0, {n}) for video {vid_id!r} (remove drops a whole video)")
         if n_front:
@@ -717,10 +795,7 @@ class VideoLibrary:
             if len(windows) != len(pairs):
                 raise ValueError(f"VideoLibrary: {len(windows)} window counts for {len(pairs)} pairs")
             for i, (k, v) in enumerate(zip(windows, videos)):
-                try:
-                    windows[i] = operator.index(k)
-                except TypeError:
-                    raise ValueError(f"VideoLibrary: windows[{i}] must be an integer, got {k!r}") from None
+                windows[i] = _as_int(k, f"VideoLibrary: windows[{i}] must be an integer, got {k!r}")
                 if not 1 <= windows[i] <= v[2]:
                     raise ValueError(f"VideoLibrary: windows[{i}]={k} not in [1, {v[2]}] for video {pairs[i][0]!r}")
         if not pairs:
@@ -757,14 +832,16 @@ class VideoLibrary:
         if not queries:
             raise ValueError("VideoLibrary: watch: an empty query list (a watcher needs at least one standing query)")
         check_queries([int(q[0].shape[0]) for q in queries], self.max_q_l)
-        K, Nq = int(self._loc.args.topk_window), int(self._loc.args.num_queries)
-        if K * Nq > MAX_POOL:
-            raise ValueError(f"VideoLibrary: topk_window={K} x num_queries={Nq} = {K * Nq} candidates > {MAX_POOL} in one pool")
+        self._check_pool("topk_window", int(self._loc.args.topk_window))
+        return self._watcher("watch", VideoWatcher, vid_id, queries)
+
+    def _watcher(self, call, cls, *args):
+        """The tail of ``watch`` / ``watch_moments``: a live fp32 library, the watcher built and registered for ``trim``'s word."""
         self._check_live()
         if self._flags & _lib.SESSION_BF16:
-            raise _lib.ConeHipError("watch: CONE_SESSION_BF16 libraries are not supported (prefilter_bf16): the scan that lists a "
+            raise _lib.ConeHipError(f"{call}: CONE_SESSION_BF16 libraries are not supported (prefilter_bf16): the scan that lists a "
                                     "poll's windows does not serve them")
-        w = VideoWatcher(self, vid_id, queries)
+        w = cls(self, *args)
         if self._watchers is None:
             self._watchers = weakref.WeakSet()
         self._watchers.add(w)
@@ -784,32 +861,9 @@ class VideoLibrary:
         if not queries:
             raise ValueError("VideoLibrary: watch_moments: an empty query list (a watcher needs at least one standing query)")
         check_queries([int(q[0].shape[0]) for q in queries], self.max_q_l)
-        W = int(self._loc.args.topk_window) if n_windows is None else n_windows
-        try:
-            W = operator.index(W)
-        except TypeError:
-            raise ValueError(f"VideoLibrary: n_windows must be an integer, got {n_windows!r}") from None
-        if not 1 <= W <= 256:
-            raise ValueError(f"VideoLibrary: n_windows={W} not in [1, 256]")
-        try:
-            M = operator.index(n_moments)
-        except TypeError:
-            raise ValueError(f"VideoLibrary: n_moments must be an integer, got {n_moments!r}") from None
-        if not 1 <= M <= MAX_BEFORE:
-            raise ValueError(f"VideoLibrary: n_moments={M} not in [1, {MAX_BEFORE}]")
-        Nq = int(self._loc.args.num_queries)
-        if W * Nq > MAX_POOL:
-            raise ValueError(f"VideoLibrary: n_windows={W} x num_queries={Nq} = {W * Nq} candidates > {MAX_POOL} in one pool")
+        W, M = self._budget_args(n_windows, n_moments)
         subset, _ = self._search_ids(videos)
-        self._check_live()
-        if self._flags & _lib.SESSION_BF16:
-            raise _lib.ConeHipError("watch_moments: CONE_SESSION_BF16 libraries are not supported (prefilter_bf16): the scan that "
-                                    "lists a poll's windows does not serve them")
-        w = LibraryWatcher(self, queries, W, M, subset)
-        if self._watchers is None:
-            self._watchers = weakref.WeakSet()
-        self._watchers.add(w)
-        return w
+        return self._watcher("watch_moments", LibraryWatcher, queries, W, M, subset)
 
     # ---- search --------------------------------------------------------------------------------
     def _search_ids(self, videos):
@@ -868,10 +922,9 @@ class VideoLibrary:
         n_rank = len(ids) if n_videos is None else min(int(n_videos), len(ids))
         table = self._table(subset, ids)
         scans, ranks = [], []
-        for g in range(0, len(queries), MAX_QUERIES):
-            chunk = queries[g:g + MAX_QUERIES]
+        for chunk in _chunked(queries):
             widx, wval, rank = self._scan(table, chunk, n_rank)
-            scans.append((g, chunk, widx, wval))
+            scans.append((MAX_QUERIES * len(scans), chunk, widx, wval))
             ranks.append(rank.reshape(2, -1))
         host = (ranks[0] if len(ranks) == 1 else torch.cat(ranks, dim=1)).cpu()       # the one small read-back
         slots = host[0].reshape(len(queries), n_rank).tolist()
@@ -932,6 +985,55 @@ class VideoLibrary:
                                            ws.numel(), _lib.stream()))
         return out
 
+    def _budget_args(self, n_windows, n_moments, pool=True):
+        """``(W, M)`` of a budgeted call, or its refusal: ``n_windows`` (``None``: ``topk_window``) an integer in [1, 256], then
+        -- with ``pool``; ``search_windows`` has none and gets ``(W, None)`` -- ``n_moments`` an integer in [1, 100] and at most
+        ``MAX_POOL`` candidates in a query's pool."""
+        a = self._loc.args
+        W = _as_int(int(a.topk_window) if n_windows is None else n_windows,
+                    f"VideoLibrary: n_windows must be an integer, got {n_windows!r}")
+        if not 1 <= W <= 256:
+            raise ValueError(f"VideoLibrary: n_windows={W} not in [1, 256]")
+        if not pool:
+            return W, None
+        M = _as_int(n_moments, f"VideoLibrary: n_moments must be an integer, got {n_moments!r}")
+        if not 1 <= M <= MAX_BEFORE:
+            raise ValueError(f"VideoLibrary: n_moments={M} not in [1, {MAX_BEFORE}]")
+        self._check_pool("n_windows", W)
+        return W, M
+
+    def _check_pool(self, name, n):
+        """``n`` windows of ``num_queries`` candidates each must fit the pool of one ``cone_corpus_fuse_nms`` query."""
+        Nq = int(self._loc.args.num_queries)
+        if n * Nq > MAX_POOL:
+            raise ValueError(f"VideoLibrary: {name}={n} x num_queries={Nq} = {n * Nq} candidates > {MAX_POOL} in one pool")
+
+    def _scan_budget(self, table, chunks, W):
+        """One ``_scan`` and one ``_budget`` of ``W`` windows per chunk of at most MAX_QUERIES queries (a watcher's chunks are on the
+        device already and stay there).  Yields, chunk by chunk, ``((first query, chunk, widx, wval), the budget's words)``, all on
+        the device -- a watcher plans a chunk before the next is scanned --; the caller reads the words back in one copy."""
+        V, g = len(table[0]), 0
+        for chunk in chunks:
+            widx, wval, _ = self._scan(table, chunk, 1)
+            scan = (g, chunk, widx, wval)
+            yield scan, self._budget(scan, V, W)
+            g += len(chunk)
+
+    def _budgeted(self, call, queries, videos, W):
+        """What ``search_windows`` / ``search_moments`` do between their budget's refusals and their plans: the queries' and the
+        videos' refusals, then -- on a live fp32 library -- the scans and budgets of ``W`` windows and their ONE read-back.
+        Returns ``(ids by table slot, scans, the budgets' words as a flat list)``; no scans where nothing is to be searched."""
+        check_queries([int(q[0].shape[0]) for q in queries], self.max_q_l)
+        subset, ids = self._search_ids(videos)
+        if not queries or not ids:
+            return ids, [], []
+        self._check_live()
+        if self._flags & _lib.SESSION_BF16:
+            raise _lib.ConeHipError(f"VideoLibrary: {call}: CONE_SESSION_BF16 libraries are not supported (prefilter_bf16)")
+        table = self._table(subset, ids)
+        scans, budgets = zip(*self._scan_budget(table, _chunked(queries), W))
+        return table[0], scans, (budgets[0] if len(budgets) == 1 else torch.cat(budgets)).cpu().tolist()
+
     @torch.no_grad()
     def search_windows(self, queries, n_windows=None, videos=None):
         """``[(tok, cls), ...]`` -> per query ``[(video id, best score, k, moments), ...]``: a budget of ``n_windows`` windows per
@@ -947,38 +1049,16 @@ class VideoLibrary:
         The scores inside ``moments`` are normalised per pair and are not comparable across videos: ``search_moments`` is the call
         that ranks the moments of different videos against each other."""
         queries = list(queries)
-        W = int(self._loc.args.topk_window) if n_windows is None else n_windows
-        try:
-            W = operator.index(W)
-        except TypeError:
-            raise ValueError(f"VideoLibrary: n_windows must be an integer, got {n_windows!r}") from None
-        if not 1 <= W <= 256:
-            raise ValueError(f"VideoLibrary: n_windows={W} not in [1, 256]")
-        check_queries([int(q[0].shape[0]) for q in queries], self.max_q_l)
-        subset, ids = self._search_ids(videos)
-        if not queries or not ids:
+        W, _ = self._budget_args(n_windows, None, pool=False)
+        ids, scans, host = self._budgeted("search_windows", queries, videos, W)                 # the one small read-back
+        if not scans:
             return [[] for _ in queries]
-        self._check_live()
-        if self._flags & _lib.SESSION_BF16:
-            raise _lib.ConeHipError("VideoLibrary: search_windows: CONE_SESSION_BF16 libraries are not supported (prefilter_bf16)")
-        table = self._table(subset, ids)
-        ids, V = table[0], len(table[0])
-        scans, budgets = [], []
-        for g in range(0, len(queries), MAX_QUERIES):
-            chunk = queries[g:g + MAX_QUERIES]
-            widx, wval, _ = self._scan(table, chunk, 1)
-            scans.append((g, chunk, widx, wval))
-            budgets.append(self._budget(scans[-1], V, W))
-        host = (budgets[0] if len(budgets) == 1 else torch.cat(budgets)).cpu()        # the one small read-back
+        V = len(ids)
         bufs, sizes, plans, at = [], [], [], 0
         for scan in scans:
             chunk = scan[1]
-            nq = len(chunk)
-            n_pairs = host[at:at + nq].tolist()
-            slots, counts, best = (host[at + nq + k * nq * W:at + nq + (k + 1) * nq * W].reshape(nq, W) for k in range(3))
-            best = best.contiguous().view(torch.float32)
-            at += nq + 3 * nq * W
-            chosen = [(q, int(slots[q, i]), int(counts[q, i]), float(best[q, i])) for q in range(nq) for i in range(n_pairs[q])]
+            pairs, at = decode_budget(host, at, len(chunk), W, best=True)
+            chosen = [(q, slot, k, score) for q in range(len(chunk)) for slot, k, score in pairs[q]]
             vids = [self._videos[ids[slot]] for _, slot, _, _ in chosen]
             calls = plan_ragged_calls([v[0] for v in vids], [c[2] for c in chosen])
             bufs += [self._enqueue_ragged([(vids[i][:2], chunk[chosen[i][0]], chosen[i][0], chosen[i][1]) for i in idx],
@@ -1012,56 +1092,21 @@ class VideoLibrary:
         libraries only."""
         import numpy as np
         queries = list(queries)
-        W = int(self._loc.args.topk_window) if n_windows is None else n_windows
-        try:
-            W = operator.index(W)
-        except TypeError:
-            raise ValueError(f"VideoLibrary: n_windows must be an integer, got {n_windows!r}") from None
-        if not 1 <= W <= 256:
-            raise ValueError(f"VideoLibrary: n_windows={W} not in [1, 256]")
-        try:
-            M = operator.index(n_moments)
-        except TypeError:
-            raise ValueError(f"VideoLibrary: n_moments must be an integer, got {n_moments!r}") from None
-        if not 1 <= M <= MAX_BEFORE:
-            raise ValueError(f"VideoLibrary: n_moments={M} not in [1, {MAX_BEFORE}]")
-        Nq = int(self._loc.args.num_queries)
-        if W * Nq > MAX_POOL:
-            raise ValueError(f"VideoLibrary: n_windows={W} x num_queries={Nq} = {W * Nq} candidates > {MAX_POOL} in one pool")
-        check_queries([int(q[0].shape[0]) for q in queries], self.max_q_l)
-        subset, ids = self._search_ids(videos)
-        if not queries or not ids:
+        W, M = self._budget_args(n_windows, n_moments)
+        ids, scans, host = self._budgeted("search_moments", queries, videos, W)                 # the one small read-back
+        if not scans:
             return [[] for _ in queries]
-        self._check_live()
-        if self._flags & _lib.SESSION_BF16:
-            raise _lib.ConeHipError("VideoLibrary: search_moments: CONE_SESSION_BF16 libraries are not supported (prefilter_bf16)")
-        lib, dev = _lib.load(), self._loc.device
-        table = self._table(subset, ids)
-        ids, V = table[0], len(table[0])
-        scans, budgets = [], []
-        for g in range(0, len(queries), MAX_QUERIES):
-            chunk = queries[g:g + MAX_QUERIES]
-            widx, wval, _ = self._scan(table, chunk, 1)
-            scans.append((g, chunk, widx, wval))
-            budgets.append(self._budget(scans[-1], V, W))
-        host = (budgets[0] if len(budgets) == 1 else torch.cat(budgets)).cpu()        # the one small read-back
+        V, Nq, dev = len(ids), int(self._loc.args.num_queries), self._loc.device
         # the plan of every scan: its pairs in the budget's order (per query: best score descending, ties to the lower slot) and
         # where each pair's candidates lie in the ONE buffer of the search
         plans, at, n_rows = [], 0, 0
         for scan in scans:
-            nq = len(scan[1])
-            n_pairs = host[at:at + nq].tolist()
-            slots, counts = (host[at + nq + k * nq * W:at + nq + (k + 1) * nq * W].reshape(nq, W) for k in range(2))
-            at += nq + 3 * nq * W
-            chosen = [(q, int(slots[q, i]), int(counts[q, i])) for q in range(nq) for i in range(n_pairs[q])]
+            pairs, at = decode_budget(host, at, len(scan[1]), W)
+            chosen = [(q, slot, k) for q, row in enumerate(pairs) for slot, k in row]
             vids = [self._videos[ids[slot]] for _, slot, _ in chosen]
             calls = plan_ragged_calls([v[0] for v in vids], [c[2] for c in chosen])
-            row_of = [0] * len(chosen)
-            for idx in calls:
-                for i in idx:
-                    row_of[i] = n_rows
-                    n_rows += chosen[i][2] * Nq
-            plans.append((chosen, vids, calls, row_of, n_pairs))
+            row_of, n_rows = place_calls(calls, [c[2] for c in chosen], Nq, n_rows)
+            plans.append((chosen, vids, calls, row_of, pairs))
         cand = torch.empty(max(n_rows, 1), 4, dtype=torch.float32, device=dev)
         for scan, (chosen, vids, calls, row_of, _) in zip(scans, plans):
             for idx in calls:
@@ -1072,35 +1117,21 @@ class VideoLibrary:
         words = np.zeros(2 * n_seg + 2 * n_seg + sum(len(s[1]) + 1 for s in scans) + 1, dtype=np.int32)
         seg_cand, seg_n, seg_tag = words[:2 * n_seg].view(np.int64), words[2 * n_seg:3 * n_seg], words[3 * n_seg:4 * n_seg]
         off_at, seg_at, launches = 4 * n_seg, 0, []
-        for scan, (chosen, _, _, row_of, n_pairs) in zip(scans, plans):
+        for scan, (chosen, _, _, row_of, pairs) in zip(scans, plans):
             nq = len(scan[1])
             seg_cand[seg_at:seg_at + len(chosen)] = row_of
             seg_n[seg_at:seg_at + len(chosen)] = [c[2] * Nq for c in chosen]
             seg_tag[seg_at:seg_at + len(chosen)] = [c[1] for c in chosen]
-            words[off_at + 1:off_at + nq + 1] = np.cumsum(n_pairs)
+            words[off_at + 1:off_at + nq + 1] = np.cumsum([len(row) for row in pairs])
             launches.append((nq, off_at, seg_at, len(chosen)))
             off_at += nq + 1
             seg_at += len(chosen)
         tab = torch.from_numpy(words).to(dev)
-        # out_rows | out_seg | out_n of every scan in ONE tensor (8-byte words: the rows stay aligned)
-        sizes = [(nq * M * 5, (nq * M + nq + 1) // 2) for nq, _, _, _ in launches]
-        out = torch.empty(sum(a + b for a, b in sizes), dtype=torch.float64, device=dev)
-        o = 0
-        for (nq, off, seg0, ns), (n_r, n_i) in zip(launches, sizes):
-            p = lambda word: C.c_void_p(tab.data_ptr() + 4 * word)
-            _lib.check(lib.cone_corpus_fuse_nms(_lib.ptr(cand), p(off), p(2 * seg0), p(2 * n_seg + seg0), p(3 * n_seg + seg0), nq, ns,
-                                                NMS_THD, MAX_BEFORE, M, C.c_void_p(out.data_ptr() + 8 * o),
-                                                C.c_void_p(out.data_ptr() + 8 * (o + n_r)),
-                                                C.c_void_p(out.data_ptr() + 8 * (o + n_r) + 4 * nq * M), _lib.stream()))
-            o += n_r + n_i
-        host = out.cpu()                                                            # the moments' one read-back
-        res, o = [], 0
-        for (nq, _, _, _), (n_r, n_i), (chosen, _, _, _, n_pairs) in zip(launches, sizes, plans):
-            rows = host[o:o + n_r].view(nq, M, 5).tolist()
-            ints = host[o + n_r:o + n_r + n_i].view(torch.int32)
-            seg, n = ints[:nq * M].view(nq, M).tolist(), ints[nq * M:nq * M + nq].tolist()
-            o += n_r + n_i
-            first = [0] + np.cumsum(n_pairs).tolist()
-            for q in range(nq):
-                res.append(pooled_moments(rows[q], seg[q], n[q], [ids[c[1]] for c in chosen[first[q]:first[q + 1]]]))
+        out = FuseOut([nq for nq, _, _, _ in launches], M, dev)
+        p = lambda word: C.c_void_p(tab.data_ptr() + 4 * word)
+        for i, (nq, off, seg0, ns) in enumerate(launches):
+            out.launch(i, _lib.ptr(cand), p(off), p(2 * seg0), p(2 * n_seg + seg0), p(3 * n_seg + seg0), ns)
+        res = []
+        for (*_, pairs), (rows, seg, kept) in zip(plans, out.read()):                         # the moments' one read-back
+            res += [pooled_moments(rows[q], seg[q], kept[q], [ids[slot] for slot, _ in pairs[q]]) for q in range(len(kept))]
         return res

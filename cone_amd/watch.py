@@ -34,6 +34,13 @@ the segment table has one segment per chosen window --; ONE small read-back (the
 ``cone_library_localize_candidates`` calls over the pairs that miss something; ``cone_watch_pool_store`` (a job per such pair);
 ``cone_corpus_fuse_nms`` on the cache; one read-back of the kept rows.  A ``trim`` zeroes that video's slab of stamps only.
 
+Shared.  Both watchers are a ``_Watcher``: the standing queries uploaded once in chunks of one call, the cache and stamp planes
+and their widening along the window axis, the lifetime; both polls write stage C's output through a ``FuseOut``
+(cone_amd/library.py), the one owner of that layout, which the watcher keeps for its life.  The polls plan differently -- K
+listed windows of one video; a budget over the slab axis -- and stay apart; ``LibraryWatcher.poll`` takes its budget through the
+pieces ``search_moments`` uses: ``_scan_budget``, ``decode_budget`` and ``place_calls``.  On the device csrc/watch_common.h holds
+the validity rule and the store loop of both store kernels.
+
 Not supported: ``prefilter_bf16`` and certified libraries, pools above 1 024 candidates, planning on the device (the miss counts
 are read back), shifting cached rows through a ``trim``, sharing cache between different queries, capturing a poll in a graph,
 more than one GPU.
@@ -45,53 +52,49 @@ import ctypes as C
 import torch
 
 from . import _lib, ops
-from .session import MAX_QUERIES, NMS_THD, MAX_BEFORE, MAX_AFTER
+from .session import MAX_QUERIES, MAX_AFTER
 
 
-class VideoWatcher:
-    """``lib.watch(vid_id, queries)``.  ``poll()`` returns one moment list per query, each ``==`` the localizer's
-    ``predict_moment(<the video's current clips>, query)``; ``windows_run`` / ``windows_listed`` describe the last poll."""
+class _Watcher:
+    """What the two watchers share: the standing queries on the device, the cache ``(nq, windows, Nq, 4)`` with its stamp plane
+    ``(nq, windows)``, and the lifetime.  A subclass names in ``_held`` what else ``close`` lets go of."""
 
-    def __init__(self, library, vid_id, queries):
-        self._lib, self._vid = library, vid_id
-        loc = library._loc
-        a, dev = loc.args, loc.device
+    _held = ()
+
+    def _upload(self, library, queries):
+        """The queries live on the device for the watcher's life, in chunks of one call each."""
+        self._lib = library
+        a, dev = library._loc.args, library._loc.device
         self._K, self._Nq, self._W = int(a.topk_window), int(a.num_queries), int(a.max_v_l)
-        # the queries live on the device for the watcher's life, in chunks of one call each
-        self._chunks = []
-        for g in range(0, len(queries), MAX_QUERIES):
-            self._chunks.append([(t.to(dev, torch.float32).contiguous(), c.to(dev, torch.float32).reshape(-1).contiguous())
-                                 for t, c in queries[g:g + MAX_QUERIES]])
+        self._chunks = [[(t.to(dev, torch.float32).contiguous(), c.to(dev, torch.float32).reshape(-1).contiguous())
+                         for t, c in queries[g:g + MAX_QUERIES]] for g in range(0, len(queries), MAX_QUERIES)]
         self._nq = len(queries)
-        K = self._K
-        # the plan's outputs, per chunk (their sizes never change); the miss counts of ALL chunks are one tensor: one read-back
-        self._n_miss = torch.zeros(self._nq, dtype=torch.int32, device=dev)
-        self._plans = []
-        for chunk in self._chunks:
-            n = len(chunk)
-            self._plans.append(dict(miss_widx=torch.empty(n * K, dtype=torch.int32, device=dev),
-                                    miss_wval=torch.empty(n * K, dtype=torch.float32, device=dev),
-                                    seg_cand=torch.empty(n * K, dtype=torch.int64, device=dev),
-                                    seg=torch.empty(2 * n * K + n + 1, dtype=torch.int32, device=dev)))     # seg_n | seg_tag | seg_off
-        _, ctx_l, _ = library._video(vid_id)
-        self._n_win = ops.num_windows(ctx_l, self._W)
-        self._cache = torch.empty(self._nq, self._n_win, self._Nq, 4, dtype=torch.float32, device=dev)
-        self._stamp = torch.zeros(self._nq, self._n_win, dtype=torch.int32, device=dev)
-        self._reset = False
-        self._table = None                  # ((row0, ctx_l), the one-video scan table)
         self.windows_run = [0] * self._nq
         self.windows_listed = [0] * self._nq
-        self._open = True
+        return dev
 
-    # ---- lifetime ------------------------------------------------------------------------------
+    def _planes(self, n_win, dev):
+        """The cache rows and the stamps (0: never computed) of ``n_win`` windows per query."""
+        self._cache = torch.empty(self._nq, n_win, self._Nq, 4, dtype=torch.float32, device=dev)
+        self._stamp = torch.zeros(self._nq, n_win, dtype=torch.int32, device=dev)
+
+    def _widen(self, n_win):
+        """The window axis becomes ``n_win`` long: new planes and stamps, the old ones copied to their front."""
+        old_cache, old_stamp = self._cache, self._stamp
+        self._planes(n_win, old_cache.device)
+        self._cache[:, :old_cache.shape[1]] = old_cache
+        self._stamp[:, :old_stamp.shape[1]] = old_stamp
+
     @property
     def nbytes(self) -> int:
-        """Bytes that stay resident for the watcher's cache: the candidate rows and the stamps."""
+        """Bytes that stay resident for the watcher's cache: the candidate rows and the stamps of the whole window axis (not
+        counted: the queries, the plan's tables and stage C's output buffer, a few hundred bytes per query)."""
         return int(self._cache.numel() * 4 + self._stamp.numel() * 4) if self._open else 0
 
     def close(self):
         self._open = False
-        self._cache = self._stamp = self._plans = self._chunks = self._n_miss = self._table = None
+        for name in ("_cache", "_stamp", "_plans", "_chunks", "_table", "_out") + self._held:
+            setattr(self, name, None)
 
     def __enter__(self):
         return self
@@ -100,6 +103,36 @@ class VideoWatcher:
         self.close()
         return False
 
+    def _check_open(self):
+        if not self._open:
+            raise RuntimeError(f"{type(self).__name__}: the watcher is closed")
+
+
+class VideoWatcher(_Watcher):
+    """``lib.watch(vid_id, queries)``.  ``poll()`` returns one moment list per query, each ``==`` the localizer's
+    ``predict_moment(<the video's current clips>, query)``; ``windows_run`` / ``windows_listed`` describe the last poll."""
+
+    _held = ("_n_miss",)
+
+    def __init__(self, library, vid_id, queries):
+        from .library import FuseOut
+        dev = self._upload(library, queries)
+        self._vid, K = vid_id, self._K
+        # the plan's outputs, per chunk (their sizes never change); the miss counts of ALL chunks are one tensor: one read-back
+        self._n_miss = torch.zeros(self._nq, dtype=torch.int32, device=dev)
+        self._plans = [dict(miss_widx=torch.empty(n * K, dtype=torch.int32, device=dev),
+                            miss_wval=torch.empty(n * K, dtype=torch.float32, device=dev),
+                            seg_cand=torch.empty(n * K, dtype=torch.int64, device=dev),
+                            seg=torch.empty(2 * n * K + n + 1, dtype=torch.int32, device=dev))              # seg_n | seg_tag | seg_off
+                       for n in map(len, self._chunks)]
+        _, ctx_l, _ = library._video(vid_id)
+        self._n_win = ops.num_windows(ctx_l, self._W)
+        self._reset = False
+        self._table = None                  # ((row0, ctx_l), the one-video scan table)
+        self._planes(self._n_win, dev)
+        self._out = FuseOut([len(c) for c in self._chunks], MAX_AFTER, dev)      # stage C's outputs, every poll's
+        self._open = True
+
     def _trimmed(self, vid_id):
         """The library's word that ``vid_id`` lost clips at its front: every entry of the cache is stale (nothing is launched
         here; the next poll zeroes the stamps)."""
@@ -107,22 +140,16 @@ class VideoWatcher:
             self._reset = True
 
     def _grow(self, n_win):
-        """The video has more windows than the cache has planes: a quarter more than it needs, the planes and stamps copied."""
-        dev, old = self._cache.device, self._n_win
-        new = max(n_win, old + old // 4 + 1)
-        cache = torch.empty(self._nq, new, self._Nq, 4, dtype=torch.float32, device=dev)
-        stamp = torch.zeros(self._nq, new, dtype=torch.int32, device=dev)
-        cache[:, :old] = self._cache
-        stamp[:, :old] = self._stamp
-        self._cache, self._stamp, self._n_win = cache, stamp, new
+        """The video has more windows than the cache has planes: a quarter more than it needs."""
+        self._n_win = max(n_win, self._n_win + self._n_win // 4 + 1)
+        self._widen(self._n_win)
 
     # ---- the poll ------------------------------------------------------------------------------
     @torch.no_grad()
     def poll(self):
         """One moment list per query, ``==`` ``predict_moment`` on the video as it is now.  The window model runs only on the
         listed windows the cache does not hold (``windows_run``); two read-backs."""
-        if not self._open:
-            raise RuntimeError("VideoWatcher: the watcher is closed")
+        self._check_open()
         L = self._lib
         L._check_live()
         row0, ctx_l, _ = L._video(self._vid)
@@ -150,10 +177,8 @@ class VideoWatcher:
             g += n
         n_miss = self._n_miss.cpu().tolist()                                    # the one small read-back
         # 4-6. the query half on the missing windows, the scatter, stage C on the cache
-        sizes = [(len(c) * MAX_AFTER * 5, (len(c) * MAX_AFTER + len(c) + 1) // 2) for c in self._chunks]
-        out = torch.empty(sum(a + b for a, b in sizes), dtype=torch.float64, device=dev)
-        g = o = 0
-        for chunk, P, (n_r, n_i) in zip(self._chunks, self._plans, sizes):
+        out, g = self._out, 0
+        for i, (chunk, P) in enumerate(zip(self._chunks, self._plans)):
             n = len(chunk)
             cache = p32(self._cache, g * self._n_win * Nq * 4)
             miss = [q for q in range(n) if n_miss[g + q] > 0]
@@ -164,43 +189,28 @@ class VideoWatcher:
                                   cand=cand)
                 _lib.check(lib.cone_watch_store(_lib.ptr(cand), _lib.ptr(P["miss_widx"]), p32(self._n_miss, g), n, K, self._n_win,
                                                 ctx_l, Nq, cache, p32(self._stamp, g * self._n_win), _lib.stream()))
-            _lib.check(lib.cone_corpus_fuse_nms(cache, p32(P["seg"], 2 * n * K), _lib.ptr(P["seg_cand"]), p32(P["seg"]),
-                                                p32(P["seg"], n * K), n, n * K, NMS_THD, MAX_BEFORE, MAX_AFTER,
-                                                C.c_void_p(out.data_ptr() + 8 * o), C.c_void_p(out.data_ptr() + 8 * (o + n_r)),
-                                                C.c_void_p(out.data_ptr() + 8 * (o + n_r) + 4 * n * MAX_AFTER), _lib.stream()))
+            out.launch(i, cache, p32(P["seg"], 2 * n * K), _lib.ptr(P["seg_cand"]), p32(P["seg"]), p32(P["seg"], n * K), n * K)
             g += n
-            o += n_r + n_i
-        host = out.cpu()                                                        # the moments' one read-back
-        res, o = [], 0
-        for chunk, (n_r, n_i) in zip(self._chunks, sizes):
-            n = len(chunk)
-            rows = host[o:o + n_r].view(n, MAX_AFTER, 5).tolist()
-            kept = host[o + n_r:o + n_r + n_i].view(torch.int32)[n * MAX_AFTER:n * MAX_AFTER + n].tolist()
-            o += n_r + n_i
-            res += [[[r[0], r[1], r[4]] for r in rows[q][:kept[q]]] for q in range(n)]
+        res = []
+        for rows, _, kept in out.read(seg=False):                               # the moments' one read-back
+            res += [[[r[0], r[1], r[4]] for r in rows[q][:kept[q]]] for q in range(len(kept))]
         self.windows_run = n_miss
         self.windows_listed = [min(K, n_win)] * self._nq
         return res
 
 
-class LibraryWatcher:
+class LibraryWatcher(_Watcher):
     """``lib.watch_moments(queries, n_windows, n_moments, videos)``.  ``poll()`` returns one list per query, ``==``
     ``lib.search_moments(queries, n_windows, n_moments, videos)`` on the library as it is now; ``windows_listed`` /
     ``windows_run`` count, per query and for the last poll, the windows the budget chose and those the window model ran."""
 
+    _held = ("_pair_miss", "_vtab", "_slabs", "_axis")
+
     def __init__(self, library, queries, n_windows, n_moments, videos):
-        from .library import RowRanges
-        self._lib = library
-        loc = library._loc
-        a, dev = loc.args, loc.device
-        self._K, self._Nq, self._W = int(a.topk_window), int(a.num_queries), int(a.max_v_l)
+        from .library import FuseOut, RowRanges
+        dev = self._upload(library, queries)
         self._Wb, self._M = int(n_windows), int(n_moments)
         self._ids = None if videos is None else list(videos)
-        self._chunks = []
-        for g in range(0, len(queries), MAX_QUERIES):
-            self._chunks.append([(t.to(dev, torch.float32).contiguous(), c.to(dev, torch.float32).reshape(-1).contiguous())
-                                 for t, c in queries[g:g + MAX_QUERIES]])
-        self._nq = len(queries)
         Wb = self._Wb
         # the plan's outputs: the miss counts of ALL chunks are one tensor (they ride the poll's one small read-back); the segment
         # tables never change size, the miss lists follow the table's slot count
@@ -213,32 +223,12 @@ class LibraryWatcher:
         n_tot = max(sum(self._cap(ops.num_windows(library._videos[v][1], self._W)) for v in watched), 1)
         self._axis = RowRanges(n_tot)
         self._slabs = {}                    # id -> (win0, cap)
-        self._cache = torch.empty(self._nq, n_tot, self._Nq, 4, dtype=torch.float32, device=dev)
-        self._stamp = torch.zeros(self._nq, n_tot, dtype=torch.int32, device=dev)
         self._stale = set()                 # ids trimmed since the last poll
         self._table = None                  # (key, scan table) of an explicit video list
         self._vtab = (None, None)           # (host v_win0 + v_cap by slot, their device copy)
-        self.windows_run = [0] * self._nq
-        self.windows_listed = [0] * self._nq
+        self._planes(n_tot, dev)
+        self._out = FuseOut([len(c) for c in self._chunks], self._M, dev)       # stage C's outputs, every poll's
         self._open = True
-
-    # ---- lifetime ------------------------------------------------------------------------------
-    @property
-    def nbytes(self) -> int:
-        """Bytes that stay resident for the watcher's cache: the candidate rows and the stamps of the whole window axis."""
-        return int(self._cache.numel() * 4 + self._stamp.numel() * 4) if self._open else 0
-
-    def close(self):
-        self._open = False
-        self._cache = self._stamp = self._plans = self._chunks = self._pair_miss = self._table = self._vtab = None
-        self._slabs = self._axis = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
 
     def _trimmed(self, vid_id):
         """The library's word that ``vid_id`` lost clips at its front: its slab is stale for every query (nothing is launched
@@ -252,18 +242,13 @@ class LibraryWatcher:
         return n_win + (n_win + 3) // 4
 
     def _take(self, n):
-        """First-fit on the axis; when no range fits the axis grows by a quarter (at least by ``n``) and is copied."""
+        """First-fit on the axis; when no range fits the axis grows by a quarter (at least by ``n``)."""
         try:
             return self._axis.take(n)
         except ValueError:
             pass
-        dev, old = self._cache.device, self._axis.capacity
-        new = old + max(old // 4 + 1, n)
-        cache = torch.empty(self._nq, new, self._Nq, 4, dtype=torch.float32, device=dev)
-        stamp = torch.zeros(self._nq, new, dtype=torch.int32, device=dev)
-        cache[:, :old] = self._cache
-        stamp[:, :old] = self._stamp
-        self._cache, self._stamp = cache, stamp
+        new = self._axis.capacity + max(self._axis.capacity // 4 + 1, n)
+        self._widen(new)
         self._axis.grow(new)
         return self._axis.take(n)
 
@@ -301,9 +286,8 @@ class LibraryWatcher:
     def poll(self):
         """Per query ``[(video id, [st, ed, score]), ...]``, ``==`` ``search_moments`` on the library as it is now.  The window
         model runs only on the chosen windows the cache does not hold (``windows_run``, of ``windows_listed``); two read-backs."""
-        from .library import plan_ragged_calls, pooled_moments
-        if not self._open:
-            raise RuntimeError("LibraryWatcher: the watcher is closed")
+        self._check_open()
+        from .library import decode_budget, place_calls, plan_ragged_calls, pooled_moments
         L = self._lib
         L._check_live()
         subset, ids = L._search_ids(self._ids)
@@ -329,11 +313,11 @@ class LibraryWatcher:
         v_ctx_l, v_tab = table[2], self._vtab[1]
         p32 = lambda t, word=0: C.c_void_p(t.data_ptr() + 4 * word)
         # 1-3. the lists, the budget and the plan of every chunk
-        budgets, g = [], 0
-        for chunk, P in zip(self._chunks, self._plans):
-            n = len(chunk)
-            widx, wval, _ = L._scan(table, chunk, 1)
-            b = L._budget((g, chunk, widx, wval), V, Wb)                        # n_pairs | pair_slot | pair_k | pair_best
+        scans, budgets = [], []
+        for ((g, chunk, widx, wval), b), P in zip(L._scan_budget(table, self._chunks, Wb), self._plans):
+            n = len(chunk)                                                      # b = n_pairs | pair_slot | pair_k | pair_best
+            scans.append((g, chunk))
+            budgets.append(b)
             if P["miss"] is None or P["miss"].numel() < 2 * n * V * K:
                 P["miss"] = torch.empty(2 * n * V * K, dtype=torch.int32, device=dev)          # miss_widx | miss_wval
             _lib.check(lib.cone_watch_pool_plan(_lib.ptr(widx), _lib.ptr(wval), p32(b), p32(b, n), p32(b, n + n * Wb), _lib.ptr(v_ctx_l),
@@ -341,67 +325,43 @@ class LibraryWatcher:
                                                 p32(P["miss"]), p32(P["miss"], n * V * K), p32(self._pair_miss, g * Wb),
                                                 p32(P["seg"], 2 * n * Wb), _lib.ptr(P["seg_cand"]), p32(P["seg"]),
                                                 p32(P["seg"], n * Wb), _lib.stream()))
-            budgets.append(b)
-            g += n
         host = torch.cat(budgets + [self._pair_miss]).cpu().tolist()            # the one small read-back
         # the host's plan: every query's pairs in the budget's order, the calls over the pairs that miss something, their jobs
         miss_at = sum(b.numel() for b in budgets)
-        plans, jobs, n_rows, at, g = [], [], 0, 0, 0
+        plans, jobs, n_rows, at = [], [], 0, 0
         run, listed = [], []
-        for chunk in self._chunks:
+        for g, chunk in scans:
             n = len(chunk)
-            pairs = []                                                          # per query [(slot, k, miss), ...]
-            for q in range(n):
-                np_q = host[at + q]
-                row = at + n + q * Wb
-                pairs.append([(host[row + i], host[row + n * Wb + i], host[miss_at + (g + q) * Wb + i]) for i in range(np_q)])
-                listed.append(sum(p[1] for p in pairs[-1]))
-                run.append(sum(p[2] for p in pairs[-1]))
-            at += n + 3 * n * Wb
+            pairs, at = decode_budget(host, at, n, Wb, miss_at=miss_at + g * Wb)            # per query [(slot, k, miss), ...]
+            listed += [sum(p[1] for p in row) for row in pairs]
+            run += [sum(p[2] for p in row) for row in pairs]
             missing = [(q, slot, m) for q in range(n) for slot, _, m in pairs[q] if m > 0]
             vids = [L._videos[ids[slot]] for _, slot, _ in missing]
             calls = plan_ragged_calls([v[0] for v in vids], [m[2] for m in missing]) if missing else []
-            first_job, rows_of = len(jobs), []
-            for idx in calls:
-                rows_of.append(n_rows)
-                for i in idx:
-                    jobs.append((missing[i][0], missing[i][1], missing[i][2], n_rows))
-                    n_rows += missing[i][2] * Nq
-            plans.append((pairs, missing, vids, calls, rows_of, first_job, len(jobs) - first_job))
-            g += n
+            row_of, n_rows = place_calls(calls, [m[2] for m in missing], Nq, n_rows)
+            first_job = len(jobs)
+            jobs += [missing[i] + (row_of[i],) for idx in calls for i in idx]
+            plans.append((pairs, missing, vids, calls, row_of, first_job, len(jobs) - first_job))
         if jobs:
             cand = torch.empty(n_rows, 4, dtype=torch.float32, device=dev)
             job_tab = torch.tensor(jobs, dtype=torch.int32).to(dev)             # the poll's one small upload
         # 5-7. the query half on the missing windows, the scatter, stage C on the cache
-        sizes = [(len(c) * M * 5, (len(c) * M + len(c) + 1) // 2) for c in self._chunks]
-        out = torch.empty(sum(a + b for a, b in sizes), dtype=torch.float64, device=dev)
-        g = o = 0
-        for chunk, P, (pairs, missing, vids, calls, rows_of, job0, n_jobs), (n_r, n_i) in zip(self._chunks, self._plans, plans, sizes):
+        out = self._out
+        for i, ((g, chunk), P, (pairs, missing, vids, calls, row_of, job0, n_jobs)) in enumerate(zip(scans, self._plans, plans)):
             n = len(chunk)
             cache = p32(self._cache, g * n_tot * Nq * 4)
             miss_widx, miss_wval = P["miss"][:n * V * K], P["miss"][n * V * K:2 * n * V * K].view(torch.float32)
-            for idx, row in zip(calls, rows_of):
+            for idx in calls:
                 L._enqueue_ragged([(vids[i][:2], chunk[missing[i][0]], missing[i][0], missing[i][1]) for i in idx],
-                                  [missing[i][2] for i in idx], (g, chunk, miss_widx, miss_wval), V, cand=cand[row:])
+                                  [missing[i][2] for i in idx], (g, chunk, miss_widx, miss_wval), V, cand=cand[row_of[idx[0]]:])
             if n_jobs:
                 _lib.check(lib.cone_watch_pool_store(_lib.ptr(cand), p32(job_tab, 4 * job0), n_jobs, p32(miss_widx), _lib.ptr(v_ctx_l),
                                                      p32(v_tab), p32(v_tab, V), n, V, K, n_tot, Nq, cache, p32(self._stamp, g * n_tot),
                                                      _lib.stream()))
-            _lib.check(lib.cone_corpus_fuse_nms(cache, p32(P["seg"], 2 * n * Wb), _lib.ptr(P["seg_cand"]), p32(P["seg"]),
-                                                p32(P["seg"], n * Wb), n, n * Wb, NMS_THD, MAX_BEFORE, M,
-                                                C.c_void_p(out.data_ptr() + 8 * o), C.c_void_p(out.data_ptr() + 8 * (o + n_r)),
-                                                C.c_void_p(out.data_ptr() + 8 * (o + n_r) + 4 * n * M), _lib.stream()))
-            g += n
-            o += n_r + n_i
-        host = out.cpu()                                                        # the moments' one read-back
-        res, o = [], 0
-        for chunk, (pairs, *_), (n_r, n_i) in zip(self._chunks, plans, sizes):
-            n = len(chunk)
-            rows = host[o:o + n_r].view(n, M, 5).tolist()
-            ints = host[o + n_r:o + n_r + n_i].view(torch.int32)
-            seg, kept = ints[:n * M].view(n, M).tolist(), ints[n * M:n * M + n].tolist()
-            o += n_r + n_i
-            for q in range(n):      # a segment is a chosen window here: window t of the pool belongs to the pair that owns ordinal t
+            out.launch(i, cache, p32(P["seg"], 2 * n * Wb), _lib.ptr(P["seg_cand"]), p32(P["seg"]), p32(P["seg"], n * Wb), n * Wb)
+        res = []
+        for (pairs, *_), (rows, seg, kept) in zip(plans, out.read()):           # the moments' one read-back
+            for q in range(len(kept)):      # a segment is a chosen window here: window t of the pool belongs to the pair that owns ordinal t
                 seg_video = [ids[slot] for slot, k, _ in pairs[q] for _ in range(k)]
                 res.append(pooled_moments(rows[q], seg[q], kept[q], seg_video))
         self.windows_run, self.windows_listed = run, listed

@@ -273,6 +273,10 @@ def test_search_moments_refuses_and_answers_empty_before_any_gpu_work(monkeypatc
             lib.search_moments([_q(5)], n_moments=bad)
     with pytest.raises(ValueError, match="n_moments must be an integer, got 1.5"):
         lib.search_moments([_q(5)], n_moments=1.5)
+    with pytest.raises(ValueError, match="n_moments must be an integer, got None"):     # (None is n_windows' default, not this one's)
+        lib.search_moments([_q(5)], n_moments=None)
+    with pytest.raises(ValueError, match="n_moments must be an integer, got None"):     # ... before the empty answers too
+        lib.search_moments([], n_moments=None)
     with pytest.raises(ValueError, match=r"n_windows=205 x num_queries=5 = 1025 candidates > 1024"):
         lib.search_moments([_q(5)], n_windows=205)
     with pytest.raises(ValueError, match=r"n_windows=103 x num_queries=10 = 1030 candidates > 1024"):

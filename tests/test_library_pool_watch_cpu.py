@@ -362,6 +362,8 @@ def test_watch_moments_refuses_before_any_gpu_work(monkeypatch):
             lib.watch_moments([_q(5)], n_windows=bad, n_moments=0)
     with pytest.raises(ValueError, match="n_windows must be an integer"):
         lib.watch_moments([_q(5)], n_windows=2.5)
+    with pytest.raises(ValueError, match="n_moments must be an integer, got None"):
+        lib.watch_moments([_q(5)], n_moments=None, videos=[7])
     for bad in (0, 101):
         with pytest.raises(ValueError, match=r"n_moments=%d not in \[1, 100\]" % bad):
             lib.watch_moments([_q(5)], n_windows=205, n_moments=bad)
@@ -412,3 +414,95 @@ def test_search_moments_and_the_watcher_share_the_helper_that_names_a_segments_v
     assert "pooled_moments(" in inspect.getsource(library.VideoLibrary.search_moments)
     from cone_amd import watch
     assert "pooled_moments(" in inspect.getsource(watch.LibraryWatcher.poll)
+
+
+# ------------------------------------------------------------------------------------------------ the shared host helpers
+def _bits(x):
+    return int(np.asarray(x, np.float32).view(np.int32))
+
+
+@pytest.mark.parametrize("W", (1, 3))
+@pytest.mark.parametrize("tail", (False, True))
+def test_the_budget_decoder_against_a_plain_loop_over_hand_written_words(W, tail):
+    """Two chunks of 2 and 3 queries; per query ``n_pairs`` runs 0, W, 1, 0, W (clamped to W); the slots, counts, score bits and
+    miss counts of every (query, column) are distinct, so a word taken from the wrong place shows."""
+    from cone_amd.library import decode_budget
+    nqs, n_pairs = (2, 3), [[0, W], [1, 0, W]]
+    scores = [[[0.5 - 0.01 * (10 * q + i) - c for i in range(W)] for q in range(nq)] for c, nq in enumerate(nqs)]
+    words = []
+    for c, nq in enumerate(nqs):
+        words += n_pairs[c]
+        words += [100 * c + 10 * q + i for q in range(nq) for i in range(W)]                   # pair_slot
+        words += [1000 + 100 * c + 10 * q + i for q in range(nq) for i in range(W)]            # pair_k
+        words += [_bits(scores[c][q][i]) for q in range(nq) for i in range(W)]                 # pair_best
+    miss_at = len(words)
+    if tail:
+        words += [5000 + 10 * g + i for g in range(sum(nqs)) for i in range(W)]                # pair_miss of ALL queries
+    at = g = 0
+    for c, nq in enumerate(nqs):
+        want_plain, want_best, want_miss = [], [], []
+        for q in range(nq):                                                                    # the layout, word by word
+            row_p, row_b, row_m = [], [], []
+            for i in range(n_pairs[c][q]):
+                slot, k = words[at + nq + q * W + i], words[at + nq + nq * W + q * W + i]
+                row_p.append((slot, k))
+                row_b.append((slot, k, float(np.float32(scores[c][q][i]))))
+                if tail:
+                    row_m.append((slot, k, words[miss_at + (g + q) * W + i]))
+            want_plain.append(row_p), want_best.append(row_b), want_miss.append(row_m)
+        assert decode_budget(words, at, nq, W) == (want_plain, at + nq + 3 * nq * W)
+        assert decode_budget(words, at, nq, W, best=True)[0] == want_best
+        if tail:
+            assert decode_budget(words, at, nq, W, miss_at=miss_at + g * W)[0] == want_miss
+            assert want_miss[-1] == [] or want_miss[-1][-1][2] == 5000 + 10 * (g + nq - 1) + W - 1
+        assert want_plain[0 if c == 0 else 1] == [] and len(want_plain[-1]) == W
+        at, g = at + nq + 3 * nq * W, g + nq
+    assert at == miss_at
+    for bad in (W + 1, -1):                                                                    # a count the budget cannot have written
+        with pytest.raises(IndexError, match="n_pairs=%d" % bad):
+            decode_budget([bad] + [0] * (3 * W), 0, 1, W)
+
+
+def test_ragged_calls_are_placed_in_call_order_whatever_the_pair_order():
+    from cone_amd.library import place_calls, plan_ragged_calls
+    Nq = 3
+    assert place_calls([], [], Nq) == ([], 0) and place_calls([], [], Nq, 7) == ([], 7)
+    # pairs 0 .. 3 with 2, 1, 4, 3 windows; the first call holds pairs 3 and 2, the second pairs 1 and 0
+    row_of, end = place_calls([[3, 2], [1, 0]], [2, 1, 4, 3], Nq)
+    assert row_of == [(3 + 4 + 1) * Nq, (3 + 4) * Nq, 3 * Nq, 0] and end == 10 * Nq
+    assert place_calls([[3, 2], [1, 0]], [2, 1, 4, 3], Nq, 5) == ([r + 5 for r in row_of], 10 * Nq + 5)
+    # as plan_ragged_calls cuts them: sorted by video, so the pairs of the video that lies first come first
+    counts, video_of = [2, 1, 4, 3], [30, 20, 10, 0]
+    calls = plan_ragged_calls(video_of, counts, limit=2)
+    assert calls == [[3, 2], [1, 0]] and place_calls(calls, counts, Nq) == (row_of, end)
+
+
+@pytest.mark.parametrize("M", (1, 5))
+def test_the_stage_c_output_buffer_is_three_disjoint_regions_a_chunk_in_order(M):
+    """Chunks of 1, 64 and 3 queries: ``nq * M + nq`` is even for every ``nq`` at M = 1 and at M = 5, so chunks of 2 queries at
+    M = 2 (6 words) and of 1 and 3 at M = 2 (3 and 9 words) add the odd parity."""
+    from cone_amd.library import FuseOut
+    for nqs, m in (((1, 64, 3), M), ((1, 2, 3), 2 * M)):
+        out = FuseOut(nqs, m, "cpu")
+        assert out.buf.dtype == torch.float64 and out.buf.device.type == "cpu"
+        raw, at, parities = out.buf.view(torch.uint8), 0, set()
+        raw.fill_(0xEE)
+        written = []
+        for i, nq in enumerate(nqs):
+            (r, n_r), (s, n_s), (k, n_k) = out.regions[i]
+            assert r == at and r % 8 == 0 and s == r + n_r and k == s + n_s                     # in order, back to back, disjoint
+            assert (n_r, n_s, n_k) == (8 * nq * m * 5, 4 * nq * m, 4 * nq)
+            pad = 4 * ((nq * m + nq) % 2)                                                       # the int32 words fill 8-byte words
+            parities.add(pad)
+            at = k + n_k + pad
+            rows = torch.arange(nq * m * 5, dtype=torch.float64) + 1000.0 * i
+            seg = torch.arange(nq * m, dtype=torch.int32) + 100 * i
+            kept = torch.arange(nq, dtype=torch.int32) + 7 * i
+            raw[r:r + n_r] = rows.view(torch.uint8)
+            raw[s:s + n_s] = seg.view(torch.uint8)
+            raw[k:k + n_k] = kept.view(torch.uint8)
+            written.append((rows.view(nq, m, 5).tolist(), seg.view(nq, m).tolist(), kept.tolist()))
+        assert at == raw.numel()                                                                # nothing else in the buffer
+        assert out.read() == written
+        assert out.read(seg=False) == [(rows, None, kept) for rows, _, kept in written]
+        assert parities == ({0} if nqs == (1, 64, 3) and m in (1, 5) else {0, 4})

@@ -151,6 +151,24 @@ def test_the_store_clamps_hostile_jobs_and_skips_indices_outside_the_slab():
     assert (got[1][4, d["v_win0"][1] + np.asarray([2, 3])] == d["v_ctx_l"][1]).all()
 
 
+def test_the_store_stops_at_the_end_of_the_axis_when_a_slab_overhangs_it():
+    """Slot 1 owns windows [4, 8) of an axis of 6: windows 1, 2, 3 of the slab are inside ``v_cap`` and only window 1 (axis
+    entry 5) is inside the axis.  The axis bound is the one predicate the one-video store does not have."""
+    Nq, K = 3, 3
+    d = dict(nq=1, V=2, K=K, n_tot=6, v_ctx_l=np.asarray([100, 200], np.int32), v_win0=np.asarray([0, 4], np.int32),
+             v_cap=np.asarray([4, 4], np.int32))
+    miss = np.full((1, 2, K), -1, np.int32)
+    miss[0, 1] = [1, 2, 3]
+    jobs = np.asarray([[0, 1, 3, 0]], np.int32)
+    cand = R.cand_rows(3 * Nq)
+    cache, stamp = _poisoned_cache(1, 6, Nq), np.full((1, 6), 7, np.int32)
+    want = R.store_ref(cand, jobs, miss, d["v_ctx_l"], d["v_win0"], d["v_cap"], Nq, cache, stamp)
+    got = _store(d, Nq, cand, jobs, miss, cache, stamp)                          # (checks the guards around every buffer)
+    assert np.array_equal(_words(got[0]), _words(want[0])) and np.array_equal(got[1], want[1])
+    assert got[1].tolist() == [[7, 7, 7, 7, 7, 200]]
+    assert np.array_equal(got[0][0, 5], cand[:Nq]) and (_words(got[0][0, :5]) == POISON).all()
+
+
 # ------------------------------------------------------------------------------------------------ end to end
 class _Mirror:
     """The host's mirror of a library watcher's stamps: per (query, video id) the clip count each window was run at.  ``poll``
