@@ -94,6 +94,11 @@ class Library(C.Structure):
                 ("vproj", C.c_void_p), ("qkv_vid", C.c_void_p)]
 
 
+# certified library budgets (additive in ABI 8): cone_library_shadow
+class LibraryShadow(C.Structure):
+    _fields_ = [("model", C.c_void_p), ("capacity", C.c_int64), ("v_dim", C.c_int32), ("rows_bf16", C.c_void_p), ("err", C.c_void_p)]
+
+
 _SIGNATURES = {
     "cone_last_error": (C.c_char_p, []),
     "cone_abi_version": (C.c_int, []),
@@ -269,6 +274,18 @@ _SIGNATURES = {
     # cone_watch_pool_store(cand, jobs (device), n_jobs, miss_widx, v_ctx_l, v_win0, v_cap (device), nq, V, K, n_win_total, Nq,
     # cache, stamp (device), stream)
     "cone_watch_pool_store": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p] * 3),
+    # certified library budgets (additive in ABI 8): a bf16 shadow of the adapted rows, the scan's lists for a budget from it
+    "cone_library_shadow_bytes": (C.c_size_t, [C.POINTER(Library)]),
+    "cone_library_shadow_open": (C.c_int, [C.POINTER(Library), C.c_void_p, C.c_size_t, C.POINTER(LibraryShadow)]),
+    # cone_library_shadow_index(m, lib, shadow, row0, n_rows, stream)
+    "cone_library_shadow_index": (C.c_int, [C.c_void_p, C.POINTER(Library), C.POINTER(LibraryShadow), C.c_int64, C.c_int64, C.c_void_p]),
+    # cone_library_scan_certified_workspace(lib, n_videos, total_hb, total_win, nq, K, W, n_cand)
+    "cone_library_scan_certified_workspace": (C.c_size_t, [C.POINTER(Library), C.c_int64, C.c_int64, C.c_int64] + [C.c_int] * 4),
+    # cone_library_scan_certified(m, lib, shadow, v_row0, v_ctx_l, v_hb_off, v_win_off (device), n_videos, total_hb, total_win, cls,
+    # nq, K, W, n_cand, params, widx, wval, certified (device), ws, ws_bytes, stream)
+    "cone_library_scan_certified": (C.c_int, [C.c_void_p, C.POINTER(Library), C.POINTER(LibraryShadow)] + [C.c_void_p] * 4
+                                    + [C.c_int64] * 3 + [C.c_void_p] + [C.c_int] * 4 + [C.POINTER(SessionParams)] + [C.c_void_p] * 3
+                                    + [C.c_void_p, C.c_size_t, C.c_void_p]),
     # cone_test_gemm(A, A2, a2_mod, W, bias, R, ln_g, ln_b, C, C2, ADD, M, N, K, flags, stream)
     "cone_test_gemm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,

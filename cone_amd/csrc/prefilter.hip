@@ -2174,8 +2174,8 @@ static ScanLayout scan_layout(int64_t n_videos, int64_t total_hb, int nq, int n_
 }
 
 // The refusals a scan makes from host values alone, in this order, before any pointer or the handle is looked at.
-static int scan_precheck(const cone_library* lib, int64_t n_videos, int64_t total_hb, int nq, int K, int n_rank, int max_v_l) {
-    const char* who = "library_scan";
+static int scan_precheck(const cone_library* lib, int64_t n_videos, int64_t total_hb, int nq, int K, int n_rank, int max_v_l,
+                         const char* who = "library_scan") {
     CONE_REQUIRE(lib, "%s: null argument", who);
     CONE_REQUIRE(nq >= 1 && nq <= CONE_SESSION_MAX_QUERIES, "%s: nq=%d not in [1, %d]", who, nq, CONE_SESSION_MAX_QUERIES);
     CONE_REQUIRE(n_videos >= 1, "%s: n_videos=%lld < 1", who, (long long)n_videos);
@@ -2244,4 +2244,545 @@ extern "C" int cone_library_scan(const cone_model* m, const cone_library* lib, c
     CONE_LAUNCH_CHECK();
     // the videos' order: the existing stable top-k on best (nq, V) -- slots, ties to the lower one
     return cone_topk_windows_ws(best, nq, n_videos, n_rank, rank_slot, rank_val, L.rank_bytes ? w + L.rank_ws : nullptr, L.rank_bytes, stream);
+}
+
+// ---- certified library budgets (include/cone_hip.h, "certified library budgets") ---------------------------------
+// cone_library_scan's lists for a budget of W windows at half the scan's bytes: the library scan's skeleton over a bf16 shadow of
+// the adapted rows, the n_cand best coarse windows of the WHOLE table as one set per query, their exact scores in the scan's own
+// fp32 arithmetic, and the proof of 3d per query.  Every device function below is the one the per-video certified path uses.
+namespace cone {
+
+// One wave per row: pf_index_kernel's arithmetic for that row (the same lane-strided float4 chains, wave_sum, sqrtf, inflation),
+// the two measures stored per row instead of maximised over the grid.  max over rows of these = that kernel's err, bit for bit:
+// x -> x * PF_CERT_INFLATE + PF_INDEX_TINY is monotone in fp32, and a NaN is the same positive quiet NaN.
+__global__ __launch_bounds__(256) void lib_shadow_index_kernel(const float* __restrict__ x, int64_t row0, int64_t n_rows, int dim,
+                                                               uint16_t* __restrict__ out, float* __restrict__ err) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave_id = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (int64_t)gridDim.x * 4;
+    const int n4 = dim >> 2;
+    for (int64_t i = wave_id; i < n_rows; i += n_waves) {
+        const int64_t row = row0 + i;
+        const float4* src = reinterpret_cast<const float4*>(x + row * dim);
+        uint2* dst = reinterpret_cast<uint2*>(out + row * dim);
+        float sr = 0.f, sx = 0.f, sh = 0.f;
+        for (int c = lane; c < n4; c += 64) {
+            const float4 v = src[c];
+            const unsigned lo = pf_pk(v.x, v.y), hi = pf_pk(v.z, v.w);
+            dst[c] = make_uint2(lo, hi);
+            const float h[4] = {__uint_as_float(lo << 16), __uint_as_float(lo & 0xffff0000u), __uint_as_float(hi << 16),
+                                __uint_as_float(hi & 0xffff0000u)};
+            const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float d = e[j] - h[j];
+                sr = __builtin_fmaf(d, d, sr);
+                sx = __builtin_fmaf(e[j], e[j], sx);
+                sh = __builtin_fmaf(h[j], h[j], sh);
+            }
+        }
+        sr = wave_sum(sr); sx = wave_sum(sx); sh = wave_sum(sh);
+        const float r = sqrtf(sr), n = sqrtf(fmaxf(sx, sh));
+        const float mr = (r != r) ? NAN : fmaxf(0.f, r);
+        const float mn = (sx != sx || sh != sh) ? NAN : fmaxf(0.f, n);
+        if (lane == 0) {
+            const float R = mr * PF_CERT_INFLATE + PF_INDEX_TINY, N = mn * PF_CERT_INFLATE + PF_INDEX_TINY;
+            reinterpret_cast<float2*>(err)[row] = make_float2(R == R ? R : __int_as_float(0x7fc00000), N == N ? N : __int_as_float(0x7fc00000));
+        }
+    }
+}
+
+// a measure's bits on the order atomicMax keeps: non-negative floats order like their bits, a NaN above +inf (pf_index_kernel)
+__device__ __forceinline__ int lib_measure_bits(float x) { return x == x ? __float_as_int(x) : 0x7fc00000; }
+
+// library_scan_kernel over the shadow: the same flat list of half-block units, owner search, restart at every video's first
+// row and -inf for a video outside the arena; the rows through pf16_half_block / pf16_load_query (frame_score_bf16_kernel's
+// bits for that video).  The pass of the first queries (blockIdx.y == 0) also takes the maxima of the per-row measures over
+// exactly the rows it scores -- 8 bytes a row beside a 2 dv-byte stream -- into rn_bits[0..1] (zeroed by the host).
+template <int VPL /* 16-B loads per lane and row: dv <= 512 VPL */, int QG, int RPW, int WPH>
+__global__ __launch_bounds__(256) void library_scan_bf16_kernel(const uint16_t* __restrict__ arena, const float* __restrict__ err,
+                                                                int64_t capacity, int dv, const int64_t* __restrict__ v_row0,
+                                                                const int32_t* __restrict__ v_ctx_l, const int64_t* __restrict__ v_hb_off,
+                                                                int n_videos, int64_t total_hb, int S, const float* __restrict__ txt,
+                                                                int nq, float* __restrict__ hm, float* __restrict__ fr,
+                                                                int* __restrict__ rn_bits) {
+    constexpr int UPB = 4 / WPH;
+    __shared__ float red[4][QG];
+    const int q0 = QG * (int)blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), sub = wave % WPH;
+    PF_LANE_SLOT(RPW, QG, lane);
+    float q[QG][VPL][8];
+#pragma unroll
+    for (int g = 0; g < QG; ++g) pf16_load_query<VPL>(txt + (size_t)min(q0 + g, nq - 1) * dv, dv, lane, q[g]);
+    const bool measure = blockIdx.y == 0 && sub == 0;
+    int br = 0, bn = 0;
+    for (int64_t g = (int64_t)blockIdx.x * UPB + wave / WPH; g < total_hb; g += (int64_t)gridDim.x * UPB) {
+        int lo = 0, hi = n_videos - 1;                                   // the last video whose first unit is at or before g
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (v_hb_off[mid] <= g) lo = mid; else hi = mid - 1;
+        }
+        const int64_t h = g - v_hb_off[lo], row0 = v_row0[lo], ctx_l = v_ctx_l[lo], r_lo = h * S;
+        int n = (int)max(min((int64_t)S, ctx_l - r_lo), (int64_t)0);     // frames of this half-block
+        if (h < 0 || row0 < 0 || ctx_l > capacity - row0) n = 0;         // a video outside the arena is not read: -inf
+        float first = -INFINITY;
+        const float m = pf16_half_block<VPL, QG, RPW, CONE_PF_NT != 0>(arena + (row0 + r_lo) * dv, n, dv, q, lane, sub, WPH, first);
+        if (out_lane && sub == 0 && q0 + my_g < nq) fr[(size_t)(q0 + my_g) * total_hb + g] = first;
+        pf_store_half_max<QG, WPH>(m, my_g, out_lane, lane, wave, red, q0, nq, total_hb, g, hm);
+        if (measure)
+            for (int j = lane; j < n; j += 64) {
+                const float2 e = reinterpret_cast<const float2*>(err)[row0 + r_lo + j];
+                br = max(br, lib_measure_bits(e.x));
+                bn = max(bn, lib_measure_bits(e.y));
+            }
+    }
+    if (measure) {
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) { br = max(br, __shfl_xor(br, o, 64)); bn = max(bn, __shfl_xor(bn, o, 64)); }
+        // (a maximum only grows: a wave whose value is not above what it reads -- however stale -- has nothing to add; without the
+        // test every wave of the grid queues on one address, 0.1 - 0.2 ms of a 0.26 ms scan at 1 M clips)
+        if (lane == 0) {
+            if (br > __atomic_load_n(rn_bits, __ATOMIC_RELAXED)) atomicMax(rn_bits, br);
+            if (bn > __atomic_load_n(rn_bits + 1, __ATOMIC_RELAXED)) atomicMax(rn_bits + 1, bn);
+        }
+    }
+}
+
+// the slot that owns flat window t: the last v with v_win_off[v] <= t
+__device__ __forceinline__ int lib_window_owner(const int64_t* __restrict__ v_win_off, int n_videos, int64_t t) {
+    int lo = 0, hi = n_videos - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (v_win_off[mid] <= t) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// The coarse window row (nq, total_win): window j of slot v at v_win_off[v] + j = pf_window_of_halves over that video's OWN
+// half-blocks (library_topk_kernel's rule: the odd-W term exists only inside the video).  A table whose two prefix sums disagree
+// scores -inf there and reads nothing outside the planes.
+__global__ __launch_bounds__(256) void lib_window_row_kernel(const float* __restrict__ hm, const float* __restrict__ fr,
+                                                             const int64_t* __restrict__ v_hb_off, const int64_t* __restrict__ v_win_off,
+                                                             int n_videos, int64_t total_hb, int64_t total_win, int odd,
+                                                             float* __restrict__ win) {
+    const int q = blockIdx.y;
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total_win) return;
+    const int v = lib_window_owner(v_win_off, n_videos, t);
+    const int64_t i = t - v_win_off[v], off = v_hb_off[v], nh = v_hb_off[v + 1] - off;
+    float x = -INFINITY;
+    if (i >= 0 && i <= nh && nh >= 1 && off >= 0 && off + nh <= total_hb)
+        x = pf_window_of_halves(hm + (size_t)q * total_hb + off, fr + (size_t)q * total_hb + off, nh, odd, i);
+    win[(size_t)q * total_win + t] = x;
+}
+
+// One level of the candidate sets' merge: group g of a query takes up to `group` consecutive sets of k pairs (group * k <= 256 PT
+// values in registers) to one set of k -- pf_cand_merge_kernel's selection, repeated until one set is left: a library's row is
+// past one merge workgroup's pairs.  The last level (one group) writes the query's candidates (index -1: none).
+template <int PT>
+__global__ __launch_bounds__(256) void lib_cand_merge_kernel(const float* __restrict__ cv_in, const int* __restrict__ ci_in,
+                                                             int n_lists, int k, int group, float* __restrict__ cv_out,
+                                                             int* __restrict__ ci_out, int32_t* __restrict__ cand,
+                                                             float* __restrict__ coarse) {
+    const int q = blockIdx.y, g = blockIdx.x, n_groups = gridDim.x;
+    const int l0 = g * group, m = (min(l0 + group, n_lists) - l0) * k;
+    const float* cv = cv_in + ((size_t)q * n_lists + l0) * k;
+    const int* ci = ci_in + ((size_t)q * n_lists + l0) * k;
+    float v[PT];
+    int ix[PT];
+#pragma unroll
+    for (int u = 0; u < PT; ++u) {
+        const int j = u * 256 + threadIdx.x;
+        v[u] = j < m ? cv[j] : -INFINITY;
+        ix[u] = j < m ? ci[j] : 0x7fffffff;
+    }
+    const bool last = n_groups == 1;
+    pf_block_select_set<PT>(v, ix, k, last ? coarse + (size_t)q * k : cv_out + ((size_t)q * n_groups + g) * k,
+                            last ? cand + (size_t)q * k : ci_out + ((size_t)q * n_groups + g) * k, last ? -1 : 0x7fffffff);
+}
+
+// pf_rescore_kernel for a flat window index: slot v = its owner, window i = the remainder, frames [max((i-1)S, 0), min((i-1)S
+// + W, ctx_l_v)) of the video's rows, every frame by pf_lane_dot + wave_sum_multi<1> -- frame_score_kernel's bits, hence
+// library_scan_kernel's --, the max by fmaxf (a window of NaN frames scores -inf).  Also leaves (slot, window) per candidate for
+// the walk.  A video outside the arena is not read.
+template <int VPL>
+__global__ __launch_bounds__(PF_RS_NT) void lib_rescore_kernel(const float* __restrict__ arena, int64_t capacity,
+                                                               const int64_t* __restrict__ v_row0, const int32_t* __restrict__ v_ctx_l,
+                                                               const int64_t* __restrict__ v_win_off, int n_videos, int64_t total_win,
+                                                               int W, int S, const float* __restrict__ txt,
+                                                               const int32_t* __restrict__ cand, int n_cand, float* __restrict__ exact,
+                                                               int32_t* __restrict__ c_slot, int32_t* __restrict__ c_win) {
+    constexpr int DV = 256 * VPL, RPW = 4;
+    constexpr int NW = PF_RS_NT / 64;
+    __shared__ float red[NW];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int q = blockIdx.y, slot = blockIdx.x;
+    const int32_t t = cand[(size_t)q * n_cand + slot];
+    float m = -INFINITY;
+    int v = -1, i = -1;
+    if (t >= 0 && t < total_win) {                                  // (uniform over the workgroup)
+        v = lib_window_owner(v_win_off, n_videos, t);
+        i = (int)(t - v_win_off[v]);
+        const int64_t row0 = v_row0[v], ctx_l = v_ctx_l[v];
+        int64_t lo = max(((int64_t)i - 1) * S, (int64_t)0), hi = min(((int64_t)i - 1) * S + W, ctx_l);
+        if (i < 0 || row0 < 0 || ctx_l > capacity - row0) hi = lo;
+        const float* vid = arena + row0 * DV;
+        float4 qv[1][VPL];
+#pragma unroll
+        for (int c = 0; c < VPL; ++c) qv[0][c] = reinterpret_cast<const float4*>(txt + (size_t)q * DV)[lane + 64 * c];
+        for (int64_t f0 = lo + wave * RPW; f0 < hi; f0 += NW * RPW) {
+            float4 x[RPW][VPL];
+#pragma unroll
+            for (int r = 0; r < RPW; ++r) {
+                const int64_t row = min(f0 + r, hi - 1);
+#pragma unroll
+                for (int c = 0; c < VPL; ++c) x[r][c] = reinterpret_cast<const float4*>(vid + row * DV)[lane + 64 * c];
+            }
+#pragma unroll
+            for (int r = 0; r < RPW; ++r) {
+                const float part[1] = {pf_lane_dot<VPL>(x[r], qv[0])};
+                const float s = wave_sum_multi<1>(part, lane);
+                if (f0 + r < hi) m = fmaxf(m, s);
+            }
+        }
+    }
+    if (lane == 0) red[wave] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float best = red[0];
+#pragma unroll
+        for (int w2 = 1; w2 < NW; ++w2) best = fmaxf(best, red[w2]);
+        exact[(size_t)q * n_cand + slot] = best;
+        c_slot[(size_t)q * n_cand + slot] = v;
+        c_win[(size_t)q * n_cand + slot] = i;
+    }
+}
+
+__global__ __launch_bounds__(256) void lib_fill_lists_kernel(int32_t* __restrict__ widx, float* __restrict__ wval, size_t n) {
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) { widx[e] = -1; wval[e] = -INFINITY; }
+}
+
+// One workgroup per query: the walk and the proof.  The candidates (n_cand <= LIB_CERT_MAX_CAND, in LDS) are ranked by (exact
+// score desc, flat index asc) by counting: rs = a candidate's rank among those of its own slot, eligible iff rs < cap = min(K, its
+// video's windows) -- the walk skips exactly the others --, pos = its rank among the eligible, taken iff pos < W.  A taken
+// candidate's list position is rs (every candidate of its slot ahead of it is taken too).  t = the exact score at pos W - 1,
+// c_last = the smallest coarse score of the set; E as in pf_certify_kernel, from the measures of the scan.  The lists were
+// filled with -1 / -inf by lib_fill_lists_kernel; a taken candidate's element has this one writer.
+constexpr int LIB_CERT_MAX_CAND = 4096;
+__global__ __launch_bounds__(256) void lib_certify_kernel(const float* __restrict__ txt, int dv, const float* __restrict__ rn,
+                                                          const int32_t* __restrict__ cand, const float* __restrict__ coarse,
+                                                          const float* __restrict__ exact, const int32_t* __restrict__ c_slot,
+                                                          const int32_t* __restrict__ c_win, const int64_t* __restrict__ v_win_off,
+                                                          int n_cand, int64_t total_win, int n_videos, int K, int W,
+                                                          int32_t* __restrict__ widx, float* __restrict__ wval,
+                                                          int32_t* __restrict__ certified) {
+    __shared__ float s_ex[LIB_CERT_MAX_CAND];
+    __shared__ int s_flat[LIB_CERT_MAX_CAND];
+    __shared__ int s_slot[LIB_CERT_MAX_CAND];           // -1: not eligible (after the first pass: an empty or capped candidate)
+    __shared__ double nrm[4][3];
+    __shared__ float c_min[4];
+    __shared__ float s_t;
+    __shared__ int s_taken[4];
+    constexpr int PT = LIB_CERT_MAX_CAND / 256;
+    const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    double s_q = 0., s_h = 0., s_d = 0.;                            // |q|^2, |qh|^2, |qh - q|^2 (pf_certify_kernel)
+    if (tid * 4 < dv) {
+        const float4 a = reinterpret_cast<const float4*>(txt + (size_t)q * dv)[tid];
+        const float e[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double x = e[j], h = pf16_rne(e[j]);
+            s_q += x * x; s_h += h * h; s_d += (h - x) * (h - x);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        s_q += __shfl_xor(s_q, o, 64); s_h += __shfl_xor(s_h, o, 64); s_d += __shfl_xor(s_d, o, 64);
+    }
+    if (lane == 0) { nrm[wave][0] = s_q; nrm[wave][1] = s_h; nrm[wave][2] = s_d; }
+    float cm = INFINITY;
+    int cap[PT];
+    for (int j = tid; j < n_cand; j += 256) {
+        const size_t at = (size_t)q * n_cand + j;
+        const int flat = cand[at], v = c_slot[at];
+        const bool ok = flat >= 0 && v >= 0 && v < n_videos;
+        const float x = ok ? exact[at] : -INFINITY;
+        s_ex[j] = x == x ? x : -INFINITY;
+        s_flat[j] = ok ? flat : 0x7fffffff;
+        s_slot[j] = ok ? v : -1;
+        cm = fminf(cm, flat >= 0 ? coarse[at] : -INFINITY);
+    }
+#pragma unroll
+    for (int u = 0; u < PT; ++u) {
+        const int j = u * 256 + tid;
+        cap[u] = 0;
+        if (j < n_cand) {
+            const int v = c_slot[(size_t)q * n_cand + j];
+            if (v >= 0 && v < n_videos) cap[u] = (int)min((int64_t)K, v_win_off[v + 1] - v_win_off[v]);
+        }
+    }
+    cm = -wave_max(-cm);
+    if (lane == 0) c_min[wave] = cm;
+    __syncthreads();
+    int rs[PT];
+#pragma unroll
+    for (int u = 0; u < PT; ++u) {                                   // rank inside the slot
+        const int j = u * 256 + tid;
+        rs[u] = 0;
+        if (j < n_cand && s_slot[j] >= 0) {
+            const float x = s_ex[j];
+            const int f = s_flat[j], v = s_slot[j];
+            int r = 0;
+            for (int i = 0; i < n_cand; ++i) {
+                const float y = s_ex[i];
+                r += (s_slot[i] == v) & ((y > x) | ((y == x) & (s_flat[i] < f)));
+            }
+            rs[u] = r;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < PT; ++u) {
+        const int j = u * 256 + tid;
+        if (j < n_cand && s_slot[j] >= 0 && rs[u] >= cap[u]) s_slot[j] = -1;
+    }
+    __syncthreads();
+    int mine = 0;
+    float t_mine = 0.f;
+    bool have_t = false;
+#pragma unroll
+    for (int u = 0; u < PT; ++u) {                                   // rank among the eligible
+        const int j = u * 256 + tid;
+        if (j < n_cand && s_slot[j] >= 0) {
+            const float x = s_ex[j];
+            const int f = s_flat[j];
+            int pos = 0;
+            for (int i = 0; i < n_cand; ++i) {
+                const float y = s_ex[i];
+                pos += (s_slot[i] >= 0) & ((y > x) | ((y == x) & (s_flat[i] < f)));
+            }
+            if (pos < W) {
+                const size_t o = ((size_t)q * n_videos + s_slot[j]) * K + rs[u];
+                widx[o] = c_win[(size_t)q * n_cand + j];
+                wval[o] = x;
+                ++mine;
+                if (pos == W - 1) { t_mine = x; have_t = true; }
+            }
+        }
+    }
+    if (have_t) s_t = t_mine;                                        // (one candidate holds rank W - 1)
+    mine = (int)wave_sum((float)mine);                               // (<= 256: exact in fp32)
+    if (lane == 0) s_taken[wave] = mine;
+    __syncthreads();
+    if (tid != 0) return;
+    const int taken = s_taken[0] + s_taken[1] + s_taken[2] + s_taken[3];
+    const double n_q = sqrt(nrm[0][0] + nrm[1][0] + nrm[2][0] + nrm[3][0]), n_h = sqrt(nrm[0][1] + nrm[1][1] + nrm[2][1] + nrm[3][1]),
+                 n_d = sqrt(nrm[0][2] + nrm[1][2] + nrm[2][2] + nrm[3][2]);
+    const double R = rn[0], N = rn[1];
+    const double du = (dv + 1) * 0x1p-24, gam = du / (1. - du);
+    const double E = (R * n_h + N * n_d + 2. * gam * N * fmax(n_q, n_h)) * (1. + 0x1p-10) + PF_CERT_TINY * (1. + n_h + N);
+    bool ok = total_win <= n_cand;
+    if (!ok && taken == W) {
+        const double t = s_t, c_last = fminf(fminf(c_min[0], c_min[1]), fminf(c_min[2], c_min[3]));
+        ok = isfinite(E) && isfinite(t) && isfinite(c_last) && t - c_last > E;
+    }
+    certified[q] = ok ? 1 : 0;
+}
+
+struct LibCertLayout {
+    int n_cand, n_chunks, group, pt;
+    size_t hm, fr, win, lists_a, lists_b, cand, coarse, exact, c_slot, c_win, rn, total;
+};
+static LibCertLayout lib_cert_layout(int64_t total_hb, int64_t total_win, int nq, int W, int n_cand) {
+    LibCertLayout L{};
+    if (n_cand == 0) {
+        const int64_t d = 4 * (int64_t)W > 128 ? 4 * (int64_t)W : 128;
+        n_cand = (int)(d < total_win ? d : total_win);
+    }
+    L.n_cand = n_cand;
+    L.n_chunks = (int)((total_win + TK_CH - 1) / TK_CH);
+    L.pt = 2 * n_cand <= 256 * TK_PT ? TK_PT : 2 * TK_PT;           // a merge of two sets always fits: 2 n_cand <= 8192
+    L.group = 256 * L.pt / n_cand;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o += align_up(bytes, 256); return at; };
+    L.hm = take((size_t)nq * total_hb * 4);
+    L.fr = take((size_t)nq * total_hb * 4);
+    L.win = take((size_t)nq * total_win * 4);
+    L.lists_a = take((size_t)nq * L.n_chunks * n_cand * 8);         // values, then indices
+    L.lists_b = take((size_t)nq * ((L.n_chunks + L.group - 1) / L.group) * n_cand * 8);
+    L.cand = take((size_t)nq * n_cand * 4);
+    L.coarse = take((size_t)nq * n_cand * 4);
+    L.exact = take((size_t)nq * n_cand * 4);
+    L.c_slot = take((size_t)nq * n_cand * 4);
+    L.c_win = take((size_t)nq * n_cand * 4);
+    L.rn = take(8);
+    L.total = o;
+    return L;
+}
+
+// The refusals from host values alone, in this order, before any pointer or the handles are looked at.
+static int scan_certified_precheck(const cone_library* lib, int64_t n_videos, int64_t total_hb, int64_t total_win, int nq, int K, int W,
+                                   int n_cand, int max_v_l) {
+    const char* who = "library_scan_certified";
+    if (int rc = scan_precheck(lib, n_videos, total_hb, nq, K, 1, max_v_l, who)) return rc;
+    CONE_REQUIRE(W >= 1 && W <= 256, "%s: W=%d not in [1, 256]", who, W);
+    CONE_REQUIRE(total_win == total_hb + n_videos && total_win < 0x7fffffff,
+                 "%s: total_win=%lld is not total_hb=%lld + n_videos=%lld (a video of nh half-blocks has nh + 1 windows) or does not fit an int32 index",
+                 who, (long long)total_win, (long long)total_hb, (long long)n_videos);
+    if (n_cand != 0) {
+        const int64_t lo = W < total_win ? W : total_win, hi = total_win < LIB_CERT_MAX_CAND ? total_win : LIB_CERT_MAX_CAND;
+        CONE_REQUIRE(n_cand >= lo && n_cand <= hi, "%s: n_cand=%d must lie in [min(W, total_win)=%lld, min(total_win, %d)=%lld]", who,
+                     n_cand, (long long)lo, LIB_CERT_MAX_CAND, (long long)hi);
+    }
+    return 0;
+}
+
+static int shadow_precheck(const cone_library* lib) {
+    const char* who = "library_shadow";
+    CONE_REQUIRE(lib, "%s: null argument", who);
+    CONE_REQUIRE(lib->flags == 0, "%s: flags=%d: the shadow belongs to a plain fp32 library (flags 0)", who, lib->flags);
+    CONE_REQUIRE(lib->capacity >= 1 && lib->capacity < (1ll << 31), "%s: capacity=%lld not in [1, 2^31)", who, (long long)lib->capacity);
+    CONE_PF_REQUIRE_DIM("library_shadow", lib->v_dim);
+    return 0;
+}
+
+static bool shadow_matches(const cone_library* lib, const cone_library_shadow* sh) {
+    return sh->model == lib->model && sh->capacity == lib->capacity && sh->v_dim == lib->v_dim && sh->rows_bf16 && sh->err;
+}
+
+}  // namespace cone
+
+extern "C" size_t cone_library_shadow_bytes(const cone_library* lib) {
+    if (cone::shadow_precheck(lib)) return 0;
+    return cone::align_up((size_t)lib->capacity * lib->v_dim * 2, 256) + cone::align_up((size_t)lib->capacity * 8, 256);
+}
+
+extern "C" int cone_library_shadow_open(const cone_library* lib, void* arena, size_t arena_bytes, cone_library_shadow* out) {
+    const char* who = "library_shadow";
+    if (int rc = cone::shadow_precheck(lib)) return rc;
+    CONE_REQUIRE(arena && out, "%s: null argument", who);
+    CONE_REQUIRE(((uintptr_t)arena & 255) == 0, "%s: the arena must be 256-B aligned", who);
+    const size_t need = cone_library_shadow_bytes(lib);
+    CONE_REQUIRE(arena_bytes >= need, "%s: arena too small (%zu < %zu)", who, arena_bytes, need);
+    out->model = lib->model;
+    out->capacity = lib->capacity;
+    out->v_dim = lib->v_dim;
+    out->rows_bf16 = (uint16_t*)arena;
+    out->err = (float*)((char*)arena + cone::align_up((size_t)lib->capacity * lib->v_dim * 2, 256));
+    return 0;
+}
+
+extern "C" int cone_library_shadow_index(const cone_model* m, const cone_library* lib, const cone_library_shadow* shadow, int64_t row0,
+                                         int64_t n_rows, void* stream) {
+    const char* who = "library_shadow";
+    if (int rc = cone::shadow_precheck(lib)) return rc;
+    CONE_REQUIRE(row0 >= 0 && n_rows >= 1 && n_rows <= lib->capacity && row0 <= lib->capacity - n_rows,
+                 "%s: rows [%lld, %lld + %lld) leave the arena of %lld", who, (long long)row0, (long long)row0, (long long)n_rows,
+                 (long long)lib->capacity);
+    CONE_REQUIRE(m && shadow, "%s: null argument", who);
+    CONE_REQUIRE(lib->model == m, "%s: the library was opened with another handle", who);
+    CONE_REQUIRE(cone::shadow_matches(lib, shadow), "%s: the shadow belongs to another library (handle, capacity or v_dim)", who);
+    CONE_REQUIRE(lib->adapted, "%s: the library handle misses a region (not one cone_library_open filled)", who);
+    int64_t blocks = (n_rows + 3) / 4;                                      // a wave per row, grid-stride past 64 workgroups per CU
+    if (blocks > 256 * 64) blocks = 256 * 64;
+    hipLaunchKernelGGL(cone::lib_shadow_index_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, lib->adapted, row0, n_rows,
+                       lib->v_dim, shadow->rows_bf16, shadow->err);
+    CONE_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t cone_library_scan_certified_workspace(const cone_library* lib, int64_t n_videos, int64_t total_hb, int64_t total_win,
+                                                        int nq, int K, int W, int n_cand) {
+    if (cone::scan_certified_precheck(lib, n_videos, total_hb, total_win, nq, K, W, n_cand, 2)) return 0;
+    return cone::lib_cert_layout(total_hb, total_win, nq, W, n_cand).total;
+}
+
+extern "C" int cone_library_scan_certified(const cone_model* m, const cone_library* lib, const cone_library_shadow* shadow,
+                                           const int64_t* v_row0, const int32_t* v_ctx_l, const int64_t* v_hb_off,
+                                           const int64_t* v_win_off, int64_t n_videos, int64_t total_hb, int64_t total_win,
+                                           const float* cls, int nq, int K, int W, int n_cand, const cone_session_params* params,
+                                           int32_t* widx, float* wval, int32_t* certified, void* ws, size_t ws_bytes, void* stream) {
+    using namespace cone;
+    const char* who = "library_scan_certified";
+    CONE_REQUIRE(lib && params, "%s: null argument", who);
+    if (int rc = scan_certified_precheck(lib, n_videos, total_hb, total_win, nq, K, W, n_cand, params->max_v_l)) return rc;
+    CONE_REQUIRE(m && shadow && v_row0 && v_ctx_l && v_hb_off && v_win_off && cls && widx && wval && certified && ws, "%s: null argument", who);
+    CONE_REQUIRE(lib->model == m, "%s: the library was opened with another handle", who);
+    CONE_REQUIRE(shadow_matches(lib, shadow), "%s: the shadow belongs to another library (handle, capacity or v_dim)", who);
+    CONE_PF_REQUIRE_DIM("library_scan_certified", lib->v_dim);
+    CONE_REQUIRE(lib->adapted, "%s: the library handle misses a region (not one cone_library_open filled)", who);
+    CONE_REQUIRE(((uintptr_t)ws & 255) == 0, "%s: the workspace must be 256-B aligned", who);
+    const LibCertLayout L = lib_cert_layout(total_hb, total_win, nq, W, n_cand);
+    if (ws_bytes < L.total) { set_error("%s: workspace too small (%zu < %zu)", who, ws_bytes, L.total); return CONE_E_WORKSPACE; }
+    hipStream_t s = (hipStream_t)stream;
+    char* w = (char*)ws;
+    float *hm = (float*)(w + L.hm), *fr = (float*)(w + L.fr), *win = (float*)(w + L.win);
+    int32_t *cand = (int32_t*)(w + L.cand), *c_slot = (int32_t*)(w + L.c_slot), *c_win = (int32_t*)(w + L.c_win);
+    float *coarse = (float*)(w + L.coarse), *exact = (float*)(w + L.exact);
+    int* rn = (int*)(w + L.rn);
+    const int Wl = params->max_v_l, S = Wl / 2, V = (int)n_videos, dv = lib->v_dim;
+    // (1) + (2) the coarse scan and the measures of the rows it scores
+    CONE_CHECK_HIP(hipMemsetAsync(rn, 0, 8, s));                            // +0.0f: the maxima's neutral element
+    {
+        const PfStreamGrid g(total_hb);
+        const int qg = nq >= 3 ? 4 : nq;                                    // 3 queries ride a 4-query pass, as in pf_stream_passes
+        ProfScope ps(PK_FRAME_SCORE, total_hb * S, dv, qg, nullptr, s);
+        const dim3 grid(g.blocks, (unsigned)((nq + qg - 1) / qg));
+#define CONE_SCAN16_LAUNCH(VPL, QG, WPH)                                                                                         \
+    hipLaunchKernelGGL((library_scan_bf16_kernel<VPL, QG, CONE_PF_RPW, WPH>), grid, dim3(256), 0, s, shadow->rows_bf16, shadow->err, \
+                       lib->capacity, dv, v_row0, v_ctx_l, v_hb_off, V, total_hb, S, cls, nq, hm, fr, rn)
+#define CONE_SCAN16_FORMS(VPL)                                                                                                   \
+    if (g.wide) { if (qg == 4) CONE_SCAN16_LAUNCH(VPL, 4, 4); else if (qg == 2) CONE_SCAN16_LAUNCH(VPL, 2, 4); else CONE_SCAN16_LAUNCH(VPL, 1, 4); } \
+    else { if (qg == 4) CONE_SCAN16_LAUNCH(VPL, 4, 1); else if (qg == 2) CONE_SCAN16_LAUNCH(VPL, 2, 1); else CONE_SCAN16_LAUNCH(VPL, 1, 1); }
+        if (dv <= 512) { CONE_SCAN16_FORMS(1) } else { CONE_SCAN16_FORMS(2) }
+#undef CONE_SCAN16_FORMS
+#undef CONE_SCAN16_LAUNCH
+        CONE_LAUNCH_CHECK();
+    }
+    // (3) the coarse window row, (4) its n_cand best as a set: chunk sets, then merges until one set is left
+    hipLaunchKernelGGL(lib_window_row_kernel, dim3((unsigned)((total_win + 255) / 256), (unsigned)nq), dim3(256), 0, s, hm, fr, v_hb_off,
+                       v_win_off, V, total_hb, total_win, Wl & 1, win);
+    CONE_LAUNCH_CHECK();
+    {
+        float* cv = (float*)(w + L.lists_a);
+        int* ci = (int*)(cv + (size_t)nq * L.n_chunks * L.n_cand);
+        hipLaunchKernelGGL(pf_cand_chunk_kernel, dim3((unsigned)L.n_chunks, (unsigned)nq), dim3(256), 0, s, win, total_win, L.n_cand, cv, ci,
+                           L.n_chunks);
+        CONE_LAUNCH_CHECK();
+        char *in_buf = w + L.lists_a, *out_buf = w + L.lists_b;
+        for (int n_lists = L.n_chunks;;) {
+            const int n_groups = (n_lists + L.group - 1) / L.group;
+            float* cv_in = (float*)in_buf;
+            int* ci_in = (int*)(cv_in + (size_t)nq * n_lists * L.n_cand);
+            float* cv_out = (float*)out_buf;
+            int* ci_out = (int*)(cv_out + (size_t)nq * n_groups * L.n_cand);
+            if (L.pt == TK_PT)
+                hipLaunchKernelGGL(lib_cand_merge_kernel<TK_PT>, dim3((unsigned)n_groups, (unsigned)nq), dim3(256), 0, s, cv_in, ci_in, n_lists,
+                                   L.n_cand, L.group, cv_out, ci_out, cand, coarse);
+            else
+                hipLaunchKernelGGL(lib_cand_merge_kernel<2 * TK_PT>, dim3((unsigned)n_groups, (unsigned)nq), dim3(256), 0, s, cv_in, ci_in,
+                                   n_lists, L.n_cand, L.group, cv_out, ci_out, cand, coarse);
+            CONE_LAUNCH_CHECK();
+            if (n_groups == 1) break;
+            n_lists = n_groups;                                 // (the lists shrink: each buffer holds every later level too)
+            char* t = in_buf; in_buf = out_buf; out_buf = t;
+        }
+    }
+    // (5) the candidates' exact scores
+    pf_with_vpl(dv, [&](auto VPL) {
+        hipLaunchKernelGGL(lib_rescore_kernel<decltype(VPL)::value>, dim3((unsigned)L.n_cand, (unsigned)nq), dim3(PF_RS_NT), 0, s, lib->adapted,
+                           lib->capacity, v_row0, v_ctx_l, v_win_off, V, total_win, Wl, S, cls, cand, L.n_cand, exact, c_slot, c_win);
+        return 0;
+    });
+    CONE_LAUNCH_CHECK();
+    // (6) the lists' padding everywhere, then the walk and the proof
+    {
+        const size_t n = (size_t)nq * V * K;
+        const size_t blocks = (n + 255) / 256;
+        hipLaunchKernelGGL(lib_fill_lists_kernel, dim3((unsigned)(blocks > 256 * 8 ? 256 * 8 : blocks)), dim3(256), 0, s, widx, wval, n);
+        CONE_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(lib_certify_kernel, dim3(nq), dim3(256), 0, s, cls, dv, (const float*)rn, cand, coarse, exact, c_slot, c_win, v_win_off,
+                       L.n_cand, total_win, V, K, W, widx, wval, certified);
+    CONE_LAUNCH_CHECK();
+    return 0;
 }

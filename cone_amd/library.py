@@ -58,7 +58,19 @@ the listed windows it has not seen, or saw while they were still growing, and st
 ``watch_moments`` is the same economy under ``search_moments``' contract: a ``LibraryWatcher`` keeps one slab of cached windows per
 resident video, its ``poll`` answers ``== search_moments`` and runs the window model only on the budget's windows the cache does
 not hold (``cone_watch_pool_plan`` / ``cone_watch_pool_store``, csrc/library_watch_pool.hip).
-Out of scope here: certified window ranking, headroom reserved behind a video, capturing the call in a graph.
+
+Certified budgets (``open_library(..., certified=True)``).  The scan is the one part of a budgeted search that grows with the
+library; a certified library keeps, beside its fp32 arena, a bf16 SHADOW of the adapted rows and two fp32 measures per row
+(``cone_library_shadow_index``: a pure function of the adapted rows, so whoever writes or moves rows re-indexes them -- ``add``,
+``add_many``, ``extend``, ``compact``, ``resize``; ``remove`` / ``trim`` do nothing).  ``_budgeted`` then takes the lists of
+``search_windows`` / ``search_moments`` from ``cone_library_scan_certified`` (csrc/prefilter.hip): the shadow scanned at half
+the bytes, the ``n_cand`` best coarse windows of the whole table rescored in fp32 with the scan's own bits, and a proof per
+query that the budget's choice is the fp32 scan's.  The flags ride in the budget's read-back; a chunk with an uncertified query
+runs the fp32 scan again, so the answers ``==`` a plain library's whatever ``last_certified`` says.  ``certified_table`` adds the
+windows' prefix sums to ``scan_table``'s arrays.  Everything else -- ``predict_moments``, ``rank_videos``, ``search``, the
+watchers -- runs its fp32 path unchanged.
+Out of scope here: certified ``rank_videos`` / ``search`` / watcher polls, headroom reserved behind a video, capturing the call
+in a graph.
 """
 from __future__ import annotations
 
@@ -70,7 +82,8 @@ import weakref
 import torch
 
 from . import _lib, ops
-from .session import MAX_QUERIES, NMS_THD, MAX_BEFORE, MAX_AFTER, VideoSession, _kept_bytes, _pack_queries, check_queries
+from .session import (CERTIFIED_WITH_BF16, MAX_QUERIES, NMS_THD, MAX_BEFORE, MAX_AFTER, VideoSession, _kept_bytes, _pack_queries,
+                      check_queries)
 from .watch import LibraryWatcher, VideoWatcher
 
 MAX_POOL = 1024     # candidates of one query in cone_corpus_fuse_nms (csrc/stage_c.h: kMaxCand)
@@ -329,6 +342,36 @@ def decode_budget(words, at, nq, W, best=False, miss_at=None):
     return pairs, at + nq + 3 * nq * W
 
 
+def merge_ranges(ranges):
+    """``[(row0, n), ...]`` -> the same rows as sorted ranges with adjacent and overlapping ones merged: the destinations of a
+    compaction, or the launches of one ``add_many`` run, become one ``cone_library_shadow_index`` launch.  Pure Python, no GPU."""
+    out = []
+    for row0, n in sorted((int(r), int(n)) for r, n in ranges):
+        if n < 1:
+            raise ValueError(f"merge_ranges: a range needs at least one row, got {n}")
+        if out and row0 <= out[-1][0] + out[-1][1]:
+            out[-1] = (out[-1][0], max(out[-1][1], row0 + n - out[-1][0]))
+        else:
+            out.append((row0, n))
+    return out
+
+
+def splice_budgets(host, nqs, W, redo, words):
+    """``host`` = the budgets' words of chunks of ``nqs[i]`` queries back to back (``decode_budget``'s layout: ``nq + 3 nq W`` words
+    a chunk); ``words`` = the budgets of the chunks ``redo`` (ascending indices) run again, back to back.  Overwrites those chunks'
+    words in ``host``, in place.  Pure Python, no GPU."""
+    first = [0]
+    for nq in nqs:
+        first.append(first[-1] + nq * (1 + 3 * W))
+    at = 0
+    for i in redo:
+        n = first[i + 1] - first[i]
+        host[first[i]:first[i + 1]] = words[at:at + n]
+        at += n
+    if at != len(words) or first[-1] != len(host):
+        raise ValueError("splice_budgets: the words do not match the chunks")
+
+
 def place_calls(calls, counts, Nq: int, first: int = 0):
     """Where the candidate rows of ragged calls lie in ONE buffer: ``calls`` = ``plan_ragged_calls``' index lists over pairs of
     ``counts[i]`` windows, ``Nq`` rows a window.  The calls follow each other from row ``first``, inside a call the pairs lie in
@@ -396,6 +439,20 @@ def scan_table(videos, S: int):
     return order, row0, ctx.astype(np.int32), hb_off
 
 
+def certified_table(videos, S: int, max_v_l: int):
+    """The table of one ``cone_library_scan_certified``: ``scan_table``'s ``(order, v_row0, v_ctx_l, v_hb_off)`` plus ``v_win_off``
+    int64 (V + 1) = exclusive prefix sums of ``cone_num_windows(ctx_l, max_v_l)`` = ``ceil(ctx_l / S) + 1``, so window j of slot
+    s is entry ``v_win_off[s] + j`` of the flat window row and ``v_win_off[-1]`` is its length.  ``S`` must be ``max_v_l // 2``.
+    Pure numpy, no GPU."""
+    import numpy as np
+    if int(S) != int(max_v_l) // 2:
+        raise ValueError(f"certified_table: S={S} is not max_v_l // 2 = {int(max_v_l) // 2}")
+    order, row0, ctx, hb_off = scan_table(videos, S)
+    win_off = np.zeros(len(order) + 1, dtype=np.int64)
+    np.cumsum((ctx.astype(np.int64) + S - 1) // S + 1, out=win_off[1:])
+    return order, row0, ctx, hb_off, win_off
+
+
 class VideoLibrary:
     """Many resident videos of a ``CONELocalizator`` (``open_library``).  ``add`` indexes a video into free rows and returns its
     id (never reused); ``predict_moments([(id, (tok, cls)), ...])`` returns, per pair and in the order given, what the
@@ -403,8 +460,12 @@ class VideoLibrary:
     and where" without the caller naming one.  ``compact`` / ``resize`` move the resident rows bit for bit: see the module text."""
 
     _watchers = None                        # a weak set of the VideoWatchers ``watch`` has handed out (none yet)
+    certified, n_cand, last_certified = False, 0, None      # a plain library: no shadow, no certified scans
+    _shadow = _sh = _cert_cache = None
 
-    def __init__(self, localizer, capacity_clips: int):
+    def __init__(self, localizer, capacity_clips: int, certified: bool = False, n_cand=None):
+        if certified and localizer.prefilter_bf16:
+            raise ValueError(CERTIFIED_WITH_BF16)
         from .model import Workspace
         self._loc = localizer
         a, m = localizer.args, localizer.localizator
@@ -423,13 +484,36 @@ class VideoLibrary:
         self._ws = Workspace()              # the per-call workspace (grow-only)
         self._scan_ws = Workspace()         # the scan's planes and ranking scratch (grow-only)
         self._scan_cache = None             # the device table of ALL resident videos; rebuilt lazily after add / remove
+        self.certified, self.n_cand = bool(certified), int(n_cand or 0)
+        self.last_certified = None          # the flags of the last budgeted call on a certified library, one per query
+        self._cert_cache = None             # (the scan table it belongs to, device v_win_off, total_win)
+        self._shadow, self._sh = self._open_shadow(self._cl) if self.certified else (None, None)
         self._open = True
+
+    # ---- the certified shadow --------------------------------------------------------------------
+    def _open_shadow(self, cl):
+        """A shadow arena for the library handle ``cl`` and its layout: (tensor, ``cone_library_shadow``)."""
+        lib = _lib.load()
+        n = _lib.sized(lib.cone_library_shadow_bytes(C.byref(cl)))
+        arena, sh = torch.empty(n, dtype=torch.uint8, device=self._loc.device), _lib.LibraryShadow()
+        _lib.check(lib.cone_library_shadow_open(C.byref(cl), _lib.ptr(arena), n, C.byref(sh)))
+        return arena, sh
+
+    def _shadow_index(self, ranges, cl=None, sh=None):
+        """Re-indexes the shadow rows of ``ranges`` = ``[(row0, n), ...]`` from the adapted rows there (the stream's order: after
+        the launches that wrote them); nothing on a plain library."""
+        if not self.certified:
+            return
+        lib, h = _lib.load(), self._loc.localizator._h()
+        cl, sh = (self._cl, self._sh) if cl is None else (cl, sh)
+        for row0, n in merge_ranges(ranges):
+            _lib.check(lib.cone_library_shadow_index(h, C.byref(cl), C.byref(sh), int(row0), int(n), _lib.stream()))
 
     # ---- lifetime ------------------------------------------------------------------------------
     @property
     def nbytes(self) -> int:
-        """Bytes that stay resident for the library (its arena, whatever it holds)."""
-        return int(self._arena.numel()) if self._open else 0
+        """Bytes that stay resident for the library (its arena, whatever it holds; a certified library's shadow too)."""
+        return int(self._arena.numel()) + (int(self._shadow.numel()) if self.certified else 0) if self._open else 0
 
     @property
     def free_clips(self) -> int:
@@ -437,7 +521,7 @@ class VideoLibrary:
 
     def close(self):
         self._open = False              # (the ids stay known: a call on a closed library says "closed", not "unknown id")
-        self._arena = self._cl = self._ws = self._scan_ws = self._scan_cache = None
+        self._arena = self._cl = self._ws = self._scan_ws = self._scan_cache = self._shadow = self._sh = self._cert_cache = None
 
     def __enter__(self):
         return self
@@ -476,6 +560,7 @@ class VideoLibrary:
             n_ws = lib.cone_library_add_workspace(h, n)
             ws = torch.empty(max(n_ws, 1), dtype=torch.uint8, device=vid.device)
             _lib.check(lib.cone_library_add(h, C.byref(self._cl), row0, _lib.ptr(vid), n, _lib.ptr(ws), n_ws, _lib.stream()))
+            self._shadow_index([(row0, n)])
         except Exception:
             self._rows.release(row0, n)
             raise
@@ -519,6 +604,7 @@ class VideoLibrary:
         for row0, at, n in launches:
             _lib.check(lib.cone_library_add(h, C.byref(self._cl), row0, C.c_void_p(base + at * row_bytes), n, _lib.ptr(ws), ws.numel(),
                                             _lib.stream()))
+        self._shadow_index([(row0, n) for row0, _, n in launches])
 
     def _place(self, lens):
         """Sequential first-fit of the call's videos; on a failure every range taken so far is released again."""
@@ -616,6 +702,7 @@ class VideoLibrary:
             dst = self._rows.take(n + m)                # (first-fit: the hole plan_extend named)
             try:
                 self._move(self._cl, self._cl, [(row0, dst, n)], [(0, n, False)], None)
+                self._shadow_index([(dst, n)])
                 self._index(more, [(dst + n, 0, m)])
             except Exception:
                 self._rows.release(dst, n + m)
@@ -691,6 +778,7 @@ class VideoLibrary:
         largest = max((e - b for b, e, staged in steps if staged), default=0)
         stage = torch.empty(need(largest), dtype=torch.uint8, device=self._loc.device) if largest else None
         moved = self._move(self._cl, self._cl, moving, steps, stage)
+        self._shadow_index([(dst, n) for _, dst, n in moving])
         for v, (_, dst, _) in zip(ids, moves):
             self._videos[v] = (dst,) + self._videos[v][1:]
         self._rows.compacted()
@@ -716,10 +804,13 @@ class VideoLibrary:
         _lib.check(lib.cone_library_open(h, capacity, self._flags, _lib.ptr(arena), n_arena, C.byref(cl)))
         ids = sorted(self._videos, key=lambda v: self._videos[v][0])
         moves = compaction_moves([self._videos[v][:2] for v in ids])
+        shadow, sh = self._open_shadow(cl) if self.certified else (None, None)
         if moves:
             self._move(self._cl, cl, moves, [(0, resident, False)], None)
+            self._shadow_index([(0, resident)], cl, sh)             # (the videos lie packed at the front of the new arena)
         for v, (_, dst, _) in zip(ids, moves):
             self._videos[v] = (dst,) + self._videos[v][1:]
+        self._shadow, self._sh = shadow, sh
         self._arena, self._cl = arena, cl       # (the old arena goes back to the allocator of this stream: the copy has read it by
         self._rows = RowRanges(capacity)        #  the time anything enqueued later writes there)
         if resident:
@@ -1019,18 +1110,79 @@ class VideoLibrary:
             yield scan, self._budget(scan, V, W)
             g += len(chunk)
 
+    def _cert_table(self, table):
+        """``certified_table``'s ``v_win_off`` for a ``_table``: (device int64 (V + 1), total_win); the one of ALL resident videos is
+        kept as long as its scan table is."""
+        if self._cert_cache is not None and self._cert_cache[0] is table:
+            return self._cert_cache[1:]
+        W = int(self._loc.args.max_v_l)
+        win_off = certified_table([self._videos[v][:2] for v in table[0]], W // 2, W)[4]
+        t = (table, torch.from_numpy(win_off).to(self._loc.device), int(win_off[-1]))
+        if table is self._scan_cache:
+            self._cert_cache = t
+        return t[1:]
+
+    def _scan_certified(self, table, queries, W):
+        """One ``cone_library_scan_certified`` of at most MAX_QUERIES queries for a budget of ``W`` windows: (widx, wval,
+        certified) on the device, ``_scan``'s lists where a query's flag is 1."""
+        lib, m, dev = _lib.load(), self._loc.localizator, self._loc.device
+        _, row0, ctx, hb_off, total_hb = table
+        win_off, total_win = self._cert_table(table)
+        V, nq, K = int(ctx.numel()), len(queries), int(self._loc.args.topk_window)
+        n_cand = min(max(self.n_cand, min(W, total_win)), total_win, 4096) if self.n_cand else 0
+        cls = torch.stack([c.to(dev, torch.float32).reshape(-1) for _, c in queries]).contiguous()
+        ws = self._scan_ws.get(_lib.sized(lib.cone_library_scan_certified_workspace(C.byref(self._cl), V, total_hb, total_win, nq, K, W,
+                                                                                    n_cand)), dev)
+        widx = torch.empty(nq * V * K, dtype=torch.int32, device=dev)
+        wval = torch.empty(nq * V * K, dtype=torch.float32, device=dev)
+        cert = torch.empty(nq, dtype=torch.int32, device=dev)
+        _lib.check(lib.cone_library_scan_certified(m._h(), C.byref(self._cl), C.byref(self._sh), _lib.ptr(row0), _lib.ptr(ctx),
+                                                   _lib.ptr(hb_off), _lib.ptr(win_off), V, total_hb, total_win,
+                                                   _lib.ptr(cls, torch.float32), nq, K, W, n_cand, C.byref(self._params), _lib.ptr(widx),
+                                                   _lib.ptr(wval), _lib.ptr(cert), _lib.ptr(ws), ws.numel(), _lib.stream()))
+        return widx, wval, cert
+
+    def _budgeted_certified(self, table, chunks, W):
+        """``_budgeted``'s scans and budgets on a certified library: ``cone_library_scan_certified`` + ``cone_library_budget`` per
+        chunk, the flags behind the budgets' words in the ONE read-back; a chunk with an uncertified query is run again, whole,
+        through ``_scan`` + ``_budget`` and those budgets are read back in a second copy (in that case only)."""
+        V, scans, budgets, flags, g = len(table[0]), [], [], [], 0
+        for chunk in chunks:
+            widx, wval, cert = self._scan_certified(table, chunk, W)
+            scans.append((g, chunk, widx, wval))
+            budgets.append(self._budget(scans[-1], V, W))
+            flags.append(cert)
+            g += len(chunk)
+        host = torch.cat(budgets + flags).cpu().tolist()                # the one small read-back
+        host, self.last_certified = host[:-g], host[-g:]
+        redo = [i for i, s in enumerate(scans) if not all(self.last_certified[s[0]:s[0] + len(s[1])])]
+        if redo:
+            again = []
+            for i in redo:
+                widx, wval, _ = self._scan(table, scans[i][1], 1)
+                scans[i] = scans[i][:2] + (widx, wval)
+                again.append(self._budget(scans[i], V, W))
+            splice_budgets(host, [len(s[1]) for s in scans], W, redo, torch.cat(again).cpu().tolist())     # the fallback's read-back
+        return scans, host
+
     def _budgeted(self, call, queries, videos, W):
         """What ``search_windows`` / ``search_moments`` do between their budget's refusals and their plans: the queries' and the
-        videos' refusals, then -- on a live fp32 library -- the scans and budgets of ``W`` windows and their ONE read-back.
+        videos' refusals, then -- on a live fp32 library -- the scans and budgets of ``W`` windows and their ONE read-back (a
+        certified library: ``_budgeted_certified``).
         Returns ``(ids by table slot, scans, the budgets' words as a flat list)``; no scans where nothing is to be searched."""
         check_queries([int(q[0].shape[0]) for q in queries], self.max_q_l)
         subset, ids = self._search_ids(videos)
+        if self.certified:
+            self.last_certified = []                # (nothing searched: no flags; a search that runs fills them in)
         if not queries or not ids:
             return ids, [], []
         self._check_live()
         if self._flags & _lib.SESSION_BF16:
             raise _lib.ConeHipError(f"VideoLibrary: {call}: CONE_SESSION_BF16 libraries are not supported (prefilter_bf16)")
         table = self._table(subset, ids)
+        if self.certified:
+            scans, host = self._budgeted_certified(table, _chunked(queries), W)
+            return table[0], scans, host
         scans, budgets = zip(*self._scan_budget(table, _chunked(queries), W))
         return table[0], scans, (budgets[0] if len(budgets) == 1 else torch.cat(budgets)).cpu().tolist()
 

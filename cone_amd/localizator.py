@@ -129,7 +129,7 @@ class CONELocalizator:
         from .session import VideoSession
         return VideoSession(self, video_feats, certified=certified, n_cand=n_cand, step=step)
 
-    def open_library(self, capacity_clips):
+    def open_library(self, capacity_clips, certified=False, n_cand=None):
         """cone_amd extension: one arena for ``capacity_clips`` clip rows that holds many indexed videos
         (``cone_amd.library.VideoLibrary``).  ``lib.add(video_feats)`` indexes a video into free rows and returns its id,
         ``lib.remove(id)`` frees them; ``lib.predict_moments([(id, text_feats), ...])`` answers pairs on any mix of the videos in
@@ -140,9 +140,15 @@ class CONELocalizator:
         close the holes.  ``lib.search_windows(queries, n_windows)`` spends a budget of windows per query on the best windows of
         the whole library -- ``[(id, score, k, moments), ...]``, ``moments ==`` this class's ``predict_moment`` at
         ``topk_window = k`` --; ``lib.predict_moments(pairs, ragged=True)`` answers videos of different window counts in one
-        call, ``windows=[k, ...]`` gives every pair its own count (``cone_library_localize_ragged``).  No certified ranking."""
+        call, ``windows=[k, ...]`` gives every pair its own count (``cone_library_localize_ragged``).
+        ``certified=True`` (not with ``prefilter_bf16``: ``open_video``'s refusal): the library also keeps a bf16 shadow of its
+        adapted rows (2 v_dim + 8 bytes per clip of capacity on top of ``lib.nbytes``) and ``search_windows`` /
+        ``search_moments`` take their window lists from ``cone_library_scan_certified`` -- the shadow scanned at half the bytes,
+        ``n_cand`` candidates per query (``None``: max(4 n_windows, 128)) rescored in fp32, the budget's choice proved unchanged
+        on the device; a chunk with a query the proof does not cover runs the fp32 scan again, so both calls ``==`` the plain
+        library's whatever ``lib.last_certified`` says.  Every other call runs its fp32 path unchanged."""
         from .library import VideoLibrary
-        return VideoLibrary(self, capacity_clips)
+        return VideoLibrary(self, capacity_clips, certified=certified, n_cand=n_cand)
 
     @torch.no_grad()
     def predict_moment(self, video_feats, text_feats):

@@ -74,14 +74,18 @@ def _pack_queries(queries, dev):
     return tok_cat, cls, [int(t.shape[0]) for t in toks]
 
 
+# what ``open_video`` and ``open_library`` answer to certified=True on a prefilter_bf16 localizer
+CERTIFIED_WITH_BF16 = ("open_video: certified=True and prefilter_bf16=True exclude each other -- the certified index "
+                       "returns the exact-fp32 ranking, the bf16 pre-filter ranks on bf16 rows")
+
+
 class VideoSession:
     """One resident video of a ``CONELocalizator`` (``open_video``).  ``predict_moment`` / ``predict_moments`` return what the
     localizer's ``predict_moment`` returns for the same video, ``==``."""
 
     def __init__(self, localizer, video_feats, certified: bool = False, n_cand=None, step: str = "python"):
         if certified and localizer.prefilter_bf16:
-            raise ValueError("open_video: certified=True and prefilter_bf16=True exclude each other -- the certified index "
-                             "returns the exact-fp32 ranking, the bf16 pre-filter ranks on bf16 rows")
+            raise ValueError(CERTIFIED_WITH_BF16)
         if step not in ("python", "c"):
             raise ValueError(f"open_video: step must be 'python' or 'c', got {step!r}")
         from .model import Workspace

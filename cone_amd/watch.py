@@ -41,7 +41,10 @@ listed windows of one video; a budget over the slab axis -- and stay apart; ``Li
 pieces ``search_moments`` uses: ``_scan_budget``, ``decode_budget`` and ``place_calls``.  On the device csrc/watch_common.h holds
 the validity rule and the store loop of both store kernels.
 
-Not supported: ``prefilter_bf16`` and certified libraries, pools above 1 024 candidates, planning on the device (the miss counts
+On a certified library (``open_library(..., certified=True)``) both watchers run this fp32 path unchanged -- ``_scan_budget``, not
+the certified scan: a poll plans chunk by chunk before a read-back, where a certificate's flags would have to be known.
+
+Not supported: ``prefilter_bf16`` libraries, certified polls, pools above 1 024 candidates, planning on the device (the miss counts
 are read back), shifting cached rows through a ``trim``, sharing cache between different queries, capturing a poll in a graph,
 more than one GPU.
 """

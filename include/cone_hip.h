@@ -919,6 +919,75 @@ int cone_watch_pool_store(const float* cand, const int32_t* jobs, int n_jobs, co
                           const int32_t* v_win0, const int32_t* v_cap, int nq, int V, int K, int n_win_total, int Nq, float* cache,
                           int32_t* stamp, void* stream);
 
+/* ------------------------------------------------------------ certified library budgets (additive, ABI 8)
+ * cone_library_scan reads every listed row in fp32: the one part of a search that grows with the library.  A budgeted search
+ * (cone_library_budget) wants the W <= 256 best windows of the WHOLE table per query, so the certified pre-filter's three steps fit
+ * it: scan a bf16 SHADOW of the adapted rows at half the bytes, rescore a small candidate set in fp32 with the scan's own bits,
+ * prove on the device that the budget's choice is unchanged (cone/inference.py:276-299 is the score,
+ * run_on_video/cone_localizator.py:83-100 the stage it serves).  The library stays a plain fp32 library (flags 0: a CONE_SESSION_CERTIFIED
+ * library is still refused everywhere) and every other entry runs on it unchanged; the shadow lives BESIDE it in its own
+ * caller-owned arena and is a pure function of the adapted rows, row by row -- whoever writes or moves adapted rows re-indexes
+ * those rows (cone_library_shadow_index), nothing teaches cone_library_move_rows a new plane.
+ * CONTRACT: for a query with certified[q] == 1, cone_library_budget on the emitted wval produces bit for bit the outputs it
+ * produces on cone_library_scan's lists at the same K, and the prefixes widx / wval[q, slot, :pair_k] of the chosen slots are the
+ * fp32 scan's, bit for bit.  For certified[q] == 0 row q is well-formed (descending, padded) and the caller must not use it.
+ * The rules are the libraries': all memory is the caller's, 256-B aligned, one stream, nothing allocated, no host read-back,
+ * refusals by name from host values first, before any pointer is read. */
+
+/* A plain host struct of device pointers into the caller's shadow arena; filled by cone_library_shadow_open. */
+typedef struct {
+    const cone_model* model;        /* the library's handle */
+    int64_t capacity;               /* the library's capacity: row r of the shadow belongs to row r of lib->adapted */
+    int32_t v_dim;
+    uint16_t* rows_bf16;            /* (capacity, v_dim) round-to-nearest-even bf16 of lib->adapted */
+    float* err;                     /* (capacity, 2) per row (r, n): r >= |v - bf16(v)|_2, n >= max(|v|_2, |bf16(v)|_2) */
+} cone_library_shadow;
+
+/* Bytes of a shadow arena for `lib` (2 v_dim + 8 per row, each plane rounded up to 256 B; 0 and cone_last_error on a refusal)
+ * and its layout: launches nothing, writes nothing (run_on_video/cone_localizator.py:121-221 keeps no state).
+ * Refused by name ("library_shadow: "): null arguments, a library that is not fp32 (flags != 0), capacity outside [1, 2^31), a
+ * v_dim outside {256, 512, 768, 1024}, a misaligned or short arena. */
+size_t cone_library_shadow_bytes(const cone_library* lib);
+int cone_library_shadow_open(const cone_library* lib, void* arena, size_t arena_bytes, cone_library_shadow* out);
+
+/* For rows [row0, row0 + n_rows): rows_bf16 = the round-to-nearest-even bf16 of lib->adapted (cone_prefilter_index_bf16's
+ * bits, which are cone_rows_to_bf16's) and err[row] = (r, n) by that entry's arithmetic for ONE row -- the same fma chains,
+ * butterfly, inflation and absolute term --, stored per row where that entry takes a maximum over the grid; a row with a
+ * non-finite sum stores a NaN.  One wave per row, 16-B loads; nothing outside those rows is written (cone/inference.py:276-299:
+ * the rows the coarse scores are taken from).
+ * Refused by name ("library_shadow: "): null arguments, row0 < 0, n_rows < 1, row0 + n_rows > capacity, a shadow of another
+ * library (capacity / v_dim / handle), another handle than the library's. */
+int cone_library_shadow_index(const cone_model* m, const cone_library* lib, const cone_library_shadow* shadow, int64_t row0,
+                              int64_t n_rows, void* stream);
+
+/* cone_library_scan's window lists for a budget of W windows, from the shadow (run_on_video/cone_localizator.py:83-100;
+ * cone/inference.py:276-299).  The table is cone_library_scan's plus v_win_off (n_videos + 1) int64: the exclusive prefix sums
+ * of cone_num_windows(v_ctx_l, max_v_l); total_win = its last entry = total_hb + n_videos (the host knows it).
+ * Stages, one stream: (1) the library scan's skeleton over rows_bf16 (bf16 operands, fp32 sums: cone_prefilter_scores_bf16's
+ * streaming form, passes of at most 4 queries) into two planes (nq, total_hb); a table entry leaving [0, capacity) scores -inf;
+ * rows outside the table are never addressed; (2) R = max r, N = max n over exactly the table's rows, a NaN sticks; (3) the
+ * coarse window row (nq, total_win), window j of slot v at v_win_off[v] + j, from that video's own half-blocks; (4) the n_cand
+ * best coarse entries as an unordered set (score descending, ties to the lower flat index), merged level by level; (5) the
+ * candidates' exact fp32 scores off lib->adapted with cone_library_scan's bits; (6) per query: the candidates ordered by (exact
+ * score descending, flat index ascending) are walked, skipping a candidate whose slot has already given min(K, its windows),
+ * until W are taken; t = the last taken score, c_last = the smallest coarse score of the set; certified[q] = 1 iff every window
+ * of the table is a candidate, or W were taken and t - c_last > E(q) strictly with every quantity finite (E: the certified
+ * pre-filter's bound with the R, N of stage 2, in fp64).
+ * Outputs (device): widx / wval (nq, n_videos, K) in the scan's layout, EVERY element written: -1 / -inf, then per slot its
+ * taken candidates at positions 0.. in walk order (window index within the video, exact score); certified (nq) int32.  There
+ * is no ranking output.  n_cand = 0: min(total_win, max(4 W, 128)); ws >= cone_library_scan_certified_workspace, 256-B aligned.
+ * Refused by name ("library_scan_certified: "), from host values first: cone_library_scan's own (nq, n_videos, total_hb, K,
+ * max_v_l, a CONE_SESSION_CERTIFIED or CONE_SESSION_BF16 library); W outside [1, 256]; total_win != total_hb + n_videos or
+ * >= 2^31; n_cand outside [min(W, total_win), min(total_win, 4096)]; then null arguments, another handle, a shadow of another
+ * library, a v_dim outside {256, 512, 768, 1024}, a misaligned or short workspace. */
+size_t cone_library_scan_certified_workspace(const cone_library* lib, int64_t n_videos, int64_t total_hb, int64_t total_win, int nq,
+                                             int K, int W, int n_cand);
+int cone_library_scan_certified(const cone_model* m, const cone_library* lib, const cone_library_shadow* shadow,
+                                const int64_t* v_row0, const int32_t* v_ctx_l, const int64_t* v_hb_off, const int64_t* v_win_off,
+                                int64_t n_videos, int64_t total_hb, int64_t total_win, const float* cls, int nq, int K, int W,
+                                int n_cand, const cone_session_params* params, int32_t* widx, float* wval, int32_t* certified,
+                                void* ws, size_t ws_bytes, void* stream);
+
 /* -------------------------------------------------------------------- metrics on the device
  * Recall@K / IoU counts from the kept rows (layout of cone_fuse_nms: rows (nq, max_after, 5) fp64 [st, ed, ...],
  * n (nq) valid rows) and one target span per query gt (nq, 2) fp64 seconds -- device pointers.  thresholds /
