@@ -294,6 +294,19 @@ _SIGNATURES = {
     "cone_test_gemm_tall": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                       C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    # the packed fp32 weight streams (tail_pack.hip) and the two weight-ring kernels on them
+    "cone_test_f32_pack_tail_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    # cone_test_f32_pack_tail(Wo | None, W1, W2, ff, Wq | None, n_qkv, img, stream)
+    "cone_test_f32_pack_tail": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "cone_test_f32_pack_rows_bytes": (C.c_size_t, [C.c_int]),
+    "cone_test_f32_packed_launches": (C.c_long, [C.c_int]),
+    "cone_test_f32_pack_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    # cone_test_gemm_tall_packed(A, W, bias, R, C, M, N, flags, M_dev, n_cu, img | None, stream)
+    "cone_test_gemm_tall_packed": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    # cone_test_tail_packed(A | None, Wo, bo, R, pg, pb, W1, b1, W2, b2, ln_g, ln_b, OUT, M, ff, pre, OUT2, Wq, qb, QKV, n_qkv,
+    #                       nw, n_cu, img | None, stream)
+    "cone_test_tail_packed": (C.c_int, [C.c_void_p] * 13 + [C.c_int] * 3 + [C.c_void_p] * 4 + [C.c_int] * 3
+                              + [C.c_void_p, C.c_void_p]),
     # cone_test_gemm_bf16(<cone_test_gemm's up to flags>, img, ldc, r_mod, M_dev, stream): the row GEMM of option general_bf16
     "cone_test_gemm_bf16_image_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "cone_test_gemm_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,

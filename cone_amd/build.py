@@ -17,7 +17,7 @@ LIB = os.path.join(HERE, "libcone_hip.so")
 PYLISTS = os.path.join(HERE, "_cone_pylists.so")      # host helper (CPython C API): kept rows -> submission lists
 SOURCES = ["api.hip", "gemm.hip", "rowops.hip", "attention.hip", "window_ops.hip", "prefilter.hip",
            "postproc.hip", "prof.hip", "dec_cross.hip", "metrics.hip", "ffn.hip", "criterion.hip", "dec_cross_mfma.hip", "ffn_split.hip", "ffn_wide.hip",
-           "general.hip", "ffn_bf16.hip", "gemm_bf16.hip", "gemm_tall.hip", "session.hip", "library_move.hip",
+           "general.hip", "ffn_bf16.hip", "gemm_bf16.hip", "gemm_tall.hip", "tail_pack.hip", "session.hip", "library_move.hip",
            "library_budget.hip", "library_corpus.hip", "library_watch.hip", "library_watch_pool.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # Files whose scalar arithmetic must round operation by operation like the reference's torch / Python

@@ -103,6 +103,26 @@ struct cone_model {
     // attention launches carry this value as their key capacity (the streaming core of general.hip) -- a window's bits
     // depend neither on the batch it rides in nor on the entry it came through
     int opt_max_tokens = CONE_MAX_WINDOW_TOKENS;
+    // derived (256 / 8 handles with an ff the fused tail takes): the packed fp32 weight streams of the two weight-ring kernels
+    // (tail_pack.hip), freed with the handle: f32_img, built with the weights, per layer tail [Wo | W1 W2 | the riding layer's
+    // q | k | v] (TailWeights::pk); f32_tall_img, built at the first gemm_tall_packed = 1 (the tall GEMM's default stream is
+    // the row-major one), the N = 768 in-projections the tall row GEMM runs (encoder layers, decoder self-attention), found by
+    // the weight's address (tall_image).  The options pick the stream form per kernel; the bits do not depend on them.
+    char* f32_img = nullptr; char* f32_tall_img = nullptr;
+    struct TallImage { const float* W; int N; const char* img; };
+    std::vector<TallImage> tall_images;
+    int opt_tail_packed = CONE_TAIL_PACKED_DEFAULT;         // the layer tail's row kernel streams its packed image
+    int opt_gemm_tall_packed = CONE_GEMM_TALL_PACKED_DEFAULT;   // the tall row GEMM streams W's packed image where W has one
+    // the image of the N rows at W: W may start at any multiple of 32 rows inside a packed matrix
+    const void* tall_image(const float* W, int N) const {
+        for (const TallImage& t : tall_images) {
+            const uintptr_t w = (uintptr_t)W, base = (uintptr_t)t.W;        // (W may lie in another allocation: no pointer difference)
+            if (w < base || (w - base) % (32 * 256 * sizeof(float)) != 0) continue;
+            const size_t off = (w - base) / sizeof(float);
+            if (off / 256 + (size_t)N <= (size_t)t.N) return t.img + (size_t)(off / (32 * 256)) * cone::F32_PACK_CHUNK_BYTES;
+        }
+        return nullptr;
+    }
     bool long_windows() const { return opt_max_tokens > CONE_MAX_WINDOW_TOKENS; }
     bool general() const { return gen_native || opt_general || long_windows(); }
 };
@@ -129,6 +149,8 @@ static void free_model(cone_model* m) {
     if (m->split_img) (void)hipFree(m->split_img);
     if (m->bf16_img) (void)hipFree(m->bf16_img);
     if (m->gen_bf16_img) (void)hipFree(m->gen_bf16_img);
+    if (m->f32_img) (void)hipFree(m->f32_img);
+    if (m->f32_tall_img) (void)hipFree(m->f32_tall_img);
     if (m->tab_arena) (void)hipFree(m->tab_arena);
     delete m;
 }
@@ -154,6 +176,53 @@ static int build_tail_images(cone_model* m, int mode, char** img) {
         if (int rc = k.pack(t.W1, t.W2, m->ff, ip + k.proj_image_bytes(), nullptr)) return rc;
         t.img[mode].wo = ip; t.img[mode].ffn = ip + k.proj_image_bytes();
     }
+    return 0;
+}
+
+// The packed fp32 streams of the layer tails (cone_model::f32_img): 2.25 MB per tail at ff = 1024 (+ 0.75 MB where the next
+// encoder layer's q | k | v projection can ride) -- 9.75 MB for the shipped two-plus-two layers.
+static int build_f32_images(cone_model* m) {
+    const int ff = m->ff, nl = m->n_enc + m->n_dec;
+    size_t total = 0;
+    for (int i = 0; i < nl; ++i) total += f32_pack_tail_bytes(ff, true, i + 1 < m->n_enc ? 768 : 0);
+    if (hipMalloc((void**)&m->f32_img, total) != hipSuccess) {
+        set_error("model_create: hipMalloc of %zu bytes of packed fp32 weight streams failed", total);
+        return CONE_E_HIP;
+    }
+    char* ip = m->f32_img;
+    for (int i = 0; i < nl; ++i) {
+        TailWeights& t = i < m->n_enc ? m->enc_tail[i] : m->dec_tail[i - m->n_enc];
+        const float* Wq = i + 1 < m->n_enc ? m->enc_tail[i + 1].Wq : nullptr;
+        if (int rc = launch_f32_pack_tail(t.Wo, t.W1, t.W2, ff, Wq, 768, ip, nullptr)) return rc;
+        t.pk = ip; t.pk_nq = Wq ? 768 : 0;
+        ip += f32_pack_tail_bytes(ff, true, t.pk_nq);
+    }
+    return 0;
+}
+// The tall row GEMM's images (cone_model::f32_tall_img; 0.75 MB per N = 768 in-projection: encoder layers, decoder
+// self-attention).  The tall GEMM's default stream is the row-major one (profiles/tail_packed_measured.txt), so these are
+// built only where the packed one is asked for: at the first gemm_tall_packed = 1 (synchronously), kept until the handle goes.
+static int build_tall_images(cone_model* m) {
+    if (m->f32_tall_img) return 0;
+    const int nl = m->n_enc + m->n_dec;
+    if (hipMalloc((void**)&m->f32_tall_img, (size_t)nl * f32_pack_rows_bytes(768)) != hipSuccess) {
+        set_error("gemm_tall_packed: hipMalloc of %zu bytes of packed fp32 weight streams failed", (size_t)nl * f32_pack_rows_bytes(768));
+        return CONE_E_HIP;
+    }
+    char* ip = m->f32_tall_img;
+    std::vector<cone_model::TallImage> images;
+    int rc = 0;
+    for (int i = 0; i < nl && rc == 0; ++i, ip += f32_pack_rows_bytes(768)) {
+        const float* W = i < m->n_enc ? m->enc[i].sa.in_w : m->dec[i - m->n_enc].sa.in_w;
+        rc = launch_f32_pack_rows(W, 768, ip, nullptr);
+        images.push_back({W, 768, ip});
+    }
+    if (rc == 0 && hipDeviceSynchronize() != hipSuccess) {
+        set_error("gemm_tall_packed: building the weight images failed");
+        rc = CONE_E_HIP;
+    }
+    if (rc) { (void)hipFree(m->f32_tall_img); m->f32_tall_img = nullptr; return rc; }
+    m->tall_images.swap(images);
     return 0;
 }
 
@@ -338,6 +407,12 @@ static int build_model(const cone_weights* w, cone_model** out) {
             return CONE_E_HIP;
         }
     }
+    if (!m->gen_native && ffn_fused_supported(m->ff)) {
+        if (build_f32_images(m) != 0 || hipDeviceSynchronize() != hipSuccess || (m->opt_gemm_tall_packed && build_tall_images(m) != 0)) {
+            free_model(m);
+            return CONE_E_HIP;
+        }
+    }
     if (dec0_constants(m, nullptr) != 0 || hipDeviceSynchronize() != hipSuccess) {
         free_model(m);
         return CONE_E_HIP;
@@ -381,6 +456,7 @@ static GemmArgs G(const cone_model* m, const float* A, int lda, const float* W, 
     g.M = M; g.M_dev = M_dev; g.N = N; g.K = K; g.flags = flags;
     g.variant = m ? m->opt_gemm | ((m->opt_gemm_tall_min + 1) << GEMM_TALL_MIN_SHIFT) : GEMM_AUTO;
     if (m && !m->opt_spread) g.flags |= GEMM_NO_SPREAD;        // option ffn_spread = 0: no spread forms anywhere
+    if (m && m->opt_gemm_tall_packed && K == 256 && ldw == 256) g.Wimg = m->tall_image(W, N);   // (only the tall form reads it)
     return g;
 }
 
@@ -850,6 +926,7 @@ static int launch_layer_tail(const cone_model* m, const FwdBuffers& f, TailArgs 
     const bool spread = m->opt_spread && f.SPR && ffn_spread_supported(t.M, ff);
     t.next = nullptr;
     t.scratch = f.SPR;
+    t.packed = m->opt_tail_packed != 0;
     *rode = false;
     if (t.pre) {
         if (bf16) return TAIL_MODES[TAIL_IMG_BF16]->proj_ffn_prenorm(t, s);
@@ -1582,6 +1659,8 @@ static const OptionRow OPTION_ROWS[] = {
     {"rows_chain", &cone_model::opt_chain, 0, 1, true},
     {"ffn_spread", &cone_model::opt_spread, 0, 1, true},
     {"gemm_tall_min_rows", &cone_model::opt_gemm_tall_min, -1, GEMM_TALL_MIN_MAX, false},
+    // the weight stream of the two ring kernels: 1 = from the handle's packed images, 0 = gathered from the row-major matrices
+    {"tail_packed", &cone_model::opt_tail_packed, 0, 1, true},
 };
 extern "C" int cone_model_set_option(cone_model* m, const char* name, int value) {
     CONE_REQUIRE(m && name, "set_option: null argument");
@@ -1630,6 +1709,13 @@ extern "C" int cone_model_set_option(cone_model* m, const char* name, int value)
         m->opt_general_bf16 = 1;
         return 0;
     }
+    // the tall GEMM's packed stream: its images are built at the first 1 (a handle of another shape than 256 / 8 has none: inert)
+    if (!strcmp(name, "gemm_tall_packed")) {
+        if (value != 0 && !m->gen_native)
+            if (int rc = build_tall_images(m)) return rc;
+        m->opt_gemm_tall_packed = value != 0;
+        return 0;
+    }
     if (!strcmp(name, "gemm")) {
         CONE_REQUIRE(value >= GEMM_AUTO && value <= GEMM_TALL, "set_option: gemm tile family %d not in [0, 4]", value);
         m->opt_gemm = value;
@@ -1673,6 +1759,25 @@ extern "C" int cone_test_gemm_tall(const float* A, const float* A2, int a2_mod, 
     g.C2 = C2; g.ADD = ADD;
     CONE_REQUIRE(n_cu >= 0, "gemm tall hook: negative CU count");
     return n_cu > 0 ? launch_gemm_tall(g, n_cu, (hipStream_t)stream) : launch_gemm(g, (hipStream_t)stream);
+}
+// The packed fp32 weight streams (tail_pack.hip) and the two ring kernels on them.
+extern "C" size_t cone_test_f32_pack_tail_bytes(int ff, int proj, int n_qkv) { return f32_pack_tail_bytes(ff, proj != 0, n_qkv); }
+extern "C" int cone_test_f32_pack_tail(const float* Wo, const float* W1, const float* W2, int ff, const float* Wq, int n_qkv,
+                                       void* img, void* stream) {
+    return launch_f32_pack_tail(Wo, W1, W2, ff, Wq, n_qkv, img, (hipStream_t)stream);
+}
+extern "C" long cone_test_f32_packed_launches(int which) { return f32_packed_launches(which); }
+extern "C" size_t cone_test_f32_pack_rows_bytes(int N) { return f32_pack_rows_bytes(N); }
+extern "C" int cone_test_f32_pack_rows(const float* W, int N, void* img, void* stream) {
+    return launch_f32_pack_rows(W, N, img, (hipStream_t)stream);
+}
+// cone_test_gemm_tall on contiguous operands with W's packed image (null: the row-major stream): always the tall form itself
+extern "C" int cone_test_gemm_tall_packed(const float* A, const float* W, const float* bias, const float* R, float* C, int M,
+                                          int N, int flags, const int32_t* M_dev, int n_cu, const void* img, void* stream) {
+    GemmArgs g = G(nullptr, A, 256, W, 256, bias, C, N, M, M_dev, N, 256, flags & (EPI_RELU | EPI_RESIDUAL));
+    g.variant = GEMM_TALL; g.R = R; g.ldr = N; g.Wimg = img;
+    CONE_REQUIRE(n_cu >= 0, "gemm tall hook: negative CU count");
+    return launch_gemm_tall(g, n_cu, (hipStream_t)stream);
 }
 extern "C" size_t cone_test_gemm_bf16_image_bytes(int N, int K) { return gemm_bf16_image_bytes(N, K); }
 // cone_test_gemm's arguments, then: img (cone_test_gemm_bf16_image_bytes(N, K) bytes: W is packed into it first), ldc (0: N),
@@ -1724,6 +1829,20 @@ extern "C" int cone_test_tail_form(const float* A, const float* Wo, const float*
     TailArgs t = test_tail(&w, A, Wo, bo, R, pg, pb, W1, b1, W2, b2, ln_g, ln_b, OUT, M, ff);
     t.r_idx = r_idx; t.R2 = R2; t.M_dev = M_dev; t.pre = pre != 0; t.OUT2 = OUT2; t.ldo2 = 256; t.scratch = (float*)scratch;
     return launch_tail_f32_form(t, form, n_cu, (hipStream_t)stream);
+}
+// The row kernel of the exact-fp32 tail on the packed stream img (null: the row-major one); A == null: the block alone on R;
+// Wq != null: with the q | k | v ride (qb, QKV (M, n_qkv)); pre: the pre-norm form (OUT2 may be null); nw: 8 | 4 waves; n_cu > 0:
+// a persistent grid sized for that many CUs
+extern "C" int cone_test_tail_packed(const float* A, const float* Wo, const float* bo, const float* R, const float* pg,
+                                     const float* pb, const float* W1, const float* b1, const float* W2, const float* b2,
+                                     const float* ln_g, const float* ln_b, float* OUT, int M, int ff, int pre, float* OUT2,
+                                     const float* Wq, const float* qb, float* QKV, int n_qkv, int nw, int n_cu, const void* img,
+                                     void* stream) {
+    TailWeights w, nx{};
+    TailArgs t = test_tail(&w, A, Wo, bo, R, pg, pb, W1, b1, W2, b2, ln_g, ln_b, OUT, M, ff);
+    t.pre = pre != 0; t.OUT2 = OUT2; t.ldo2 = 256;
+    if (Wq) { nx.Wq = Wq; nx.qb = qb; t.next = &nx; t.QKV = QKV; t.ldq = n_qkv; t.n_qkv = n_qkv; }
+    return launch_tail_f32_rows_hook(t, img, nw, n_cu, (hipStream_t)stream);
 }
 // pack: CONE_TEST_SINGLE_PIECE selects the single-piece form (ffn_bf16.hip), which packs only with CONE_TEST_PACK; the split
 // form packs with any non-zero value

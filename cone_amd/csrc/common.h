@@ -122,6 +122,7 @@ struct GemmArgs {
     int N, K;
     int flags;
     int variant;                          // tile family: 0 automatic (GEMM_ROWS8 where the shape allows), else forced
+    const void* Wimg;                     // null, or W's packed slab image (launch_f32_pack_rows): only the tall form reads it
 };
 // GEMM_SQUARE: register-staged 128x128 / 64x256 tiles; GEMM_ROWS4 / GEMM_ROWS8: the 128x256 row-owning LDS-DMA tile
 // with 4 waves x 32 rows (32x32x2) / 8 waves x 16 rows (16x16x4).  The family is a function of the shape and of
@@ -153,6 +154,9 @@ struct TailWeights {
     const float *Wq, *qb;                 // encoder layers: the layer's OWN q | k | v projection (768, 256) -- what the tail of
                                           // the layer before it computes when the projection rides
     TailImages img[TAIL_IMG_MODES];
+    // the exact-fp32 row kernel's packed weight stream (tail_pack.hip: [Wo chunks | feed-forward chunks | q | k | v chunks of the
+    // layer that rides]; null: none) and the q | k | v width it was built with (0: no ride chunks)
+    const void* pk; int pk_nq;
 };
 // TailArgs: one launch.  Every launcher of a projecting tail takes it, checks what its form needs and fills its kernel's struct.
 struct TailArgs {
@@ -170,6 +174,7 @@ struct TailArgs {
     int m_off;                            // wide form: the rows are rows m_off .. m_off + M of a larger job whose count is *M_dev
     float* X1; float* H;                  // the unfused forms' rows (api.hip, launch_layer_tail): LN_in's output (M, 256), hidden (M, ff)
     float* C2; const float* ADD;          // != null: a second output C2 = OUT + ADD, which only the unfused GEMM epilogue writes
+    bool packed;                          // the exact-fp32 row kernel streams w->pk (where it has one that fits the launch)
 };
 
 // ---------------------------------------------------------------- the exact-fp32 layer tail (ffn.hip, ffn_wide.hip)
@@ -203,6 +208,37 @@ bool ffn_spread_supported(int M, int ff);
 int launch_proj_ffn_spread(const TailArgs& t, hipStream_t s);      // post-norm and pre-norm (t.pre)
 // test hook (cone_test_tail_form): the projecting tail in the forced form CONE_TAIL_FORM_*
 int launch_tail_f32_form(const TailArgs& t, int form, int n_cu, hipStream_t s);
+
+// ---------------------------------------------------------------- packed fp32 weight streams (tail_pack.hip)
+// The weight ring of ffn.hip / gemm_tall.hip consumes 32-KiB chunks of 32 slabs x 64 lanes x 16 B.  These images hold the
+// chunks in the order a tile walks them, every 16 B where the ring's LDS-DMA piece puts it (gather and chunk swizzle resolved
+// once): a piece's source is image + chunk * 32 KiB + slab * 1 KiB + lane * 16.
+constexpr size_t F32_PACK_CHUNK_BYTES = 32 * 1024;
+// What a handle streams when no option says otherwise (options "tail_packed" / "gemm_tall_packed"), per kernel: set by the A/B
+// of profiles/tail_packed_measured.txt, both stream forms with the lane offset pinned next to the load -- the packed stream is
+// the default only where it wins by more than the row-major form's own spread at the headline shape.  The layer tail does
+// (-2.2 %: the image removes the per-piece select between two lane offsets and 40 % of the scalar work); the tall GEMM does
+// not (-0.3 %, inside the spread: its row-major address was already one base + one lane offset).
+#ifndef CONE_TAIL_PACKED_DEFAULT
+#define CONE_TAIL_PACKED_DEFAULT 1
+#endif
+#ifndef CONE_GEMM_TALL_PACKED_DEFAULT
+#define CONE_GEMM_TALL_PACKED_DEFAULT 0
+#endif
+// [Wo != null: 8 chunks of Wo | ff / 16 feed-forward chunks (W1 slabs 0-15, W2 slabs 16-31) | Wq != null: n_qkv / 32 chunks]
+size_t f32_pack_tail_bytes(int ff, bool proj, int n_qkv);
+int launch_f32_pack_tail(const float* Wo, const float* W1, const float* W2, int ff, const float* Wq, int n_qkv, void* img,
+                         hipStream_t s);
+// N / 32 chunks of W (N, 256), contiguous rows, in the projection's slab format
+size_t f32_pack_rows_bytes(int N);
+int launch_f32_pack_rows(const float* W, int N, void* img, hipStream_t s);
+// launches that streamed a packed image since the library was loaded (which 0: the layer tail's row kernel, 1: the tall row
+// GEMM): what lets a test see that a handle's images are actually attached to its launches
+void f32_packed_note(int which);
+long f32_packed_launches(int which);
+// test hooks: the row kernel of ffn.hip on filled operands (A == null: the block alone on R as its input; nw 8 | 4; n_cu > 0
+// sizes the persistent grid; img: the packed stream or null)
+int launch_tail_f32_rows_hook(const TailArgs& t, const void* img, int nw, int n_cu, hipStream_t s);
 
 // ---------------------------------------------------------------- the same on the bf16 matrix cores
 // Two numeric modes, one interface each (TAIL_MODES[TAIL_IMG_*] in api.hip; the code of both: tail_bf16_common.h):

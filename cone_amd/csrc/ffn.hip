@@ -30,6 +30,8 @@
 // ring (128 KiB): chunk c+2 streams in while chunk c is multiplied, one counted s_waitcnt vmcnt + raw s_barrier per
 // chunk (128 MFMAs per wave).  b1 is copied to LDS once so that no ordinary global load sits inside the loop (hipcc
 // would drain the DMA queue for it, cdna_hip_programming.md section 5 "Three .s-level traps" (b)).
+// Where the handle has the layer's packed image (tail_pack.hip: the chunks of a tile in walking order, gather and swizzle
+// resolved once) the PK instantiations stream the same bytes from it: scalar base + (chunk, slab) + lane * 16.
 //
 // One PERSISTENT 8-wave workgroup per CU (132 KiB of LDS, <= 256 VGPRs) walks the 128-row tiles: two waves per SIMD
 // keep the matrix pipe fed; GEMM1 of chunk i and GEMM2 of chunk i-1 share the units of one iteration (software
@@ -54,7 +56,9 @@ constexpr int FFN_NST = 4;                        // ring depth: a stage is refi
 // NW = 4 (64-row tiles, ONE wave per SIMD) is the small-M form: a wave runs the very same instruction sequence on its 16
 // rows (bit-identical results), but has its SIMD's matrix pipe to itself -- a tile takes half the time -- and the tile
 // grid is twice as fine; chosen by the launcher when the 128-row tiles would leave at least half of the CUs idle.
-template <bool PROJ, bool QKV, int NW, bool PRE = false>
+// PK: the weight pieces stream from the packed image p.Wimg (tail_pack.hip) instead of being gathered from the row-major
+// matrices: the same bytes at the same LDS addresses, so nothing else in the kernel knows of it.
+template <bool PROJ, bool QKV, int NW, bool PRE = false, bool PK = false>
 __global__ __launch_bounds__(64 * NW, NW / 4) void ffn_fused_kernel(FfnArgs p) {
     static_assert(!PRE || (PROJ && !QKV), "the pre-norm form is the layer tail");
     constexpr int FFN_ROWS = 16 * NW, FFN_NPIECE = 32 / NW, NT = 64 * NW, HW = NW / 2;
@@ -130,11 +134,25 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ffn_fused_kernel(FfnArgs p) {
     // first chunks of the NEXT tile this workgroup will run -- the same weights, so the ring simply runs on (after
     // the last tile they land in stages nobody reads again).  sb = (chunks consumed before this tile) % FFN_NST.
     int sb = 0;
+    unsigned pkvo = (unsigned)(lane * 16);        // PK: the lane's offset inside every piece
+    unsigned poff4 = (unsigned)(poff * 4), foff4 = (unsigned)(foff * 4);      // row-major: the lane's byte offsets
     auto stream_piece = [&](int g, int i) {
         float* dstp = smem + ((sb + g) % FFN_NST) * FFN_STAGE + (wave * FFN_NPIECE + i) * 256;
         const int gg = g < G ? g : g - G;
-        // wave-uniform pointer + zero-extended 32-bit lane offset: the saddr + voffset form of global_load_lds (one
-        // address VGPR for all pieces instead of a hoisted 64-bit VGPR pair per piece)
+        if (PK) {
+            // the image holds a tile's chunks in walking order, every lane's 16 B in place: scalar base + one 32-bit offset of
+            // (chunk, slab), and lane * 16 -- no select, no swizzle, no per-side stride (the pin: as below)
+            const char* ub = reinterpret_cast<const char*>(p.Wimg) + (((unsigned)gg << 15) + (unsigned)(wave * FFN_NPIECE + i) * 1024u);
+            asm volatile("" : "+s"(ub));
+            // the lane offset is pinned HERE too: hoisted, its zero-extension lands in another block than the load, and the
+            // load then takes a 64-bit VGPR address (one v_lshl_add_u64 per piece in the MFMA stream) instead of saddr + voffset
+            // (in place, on ONE variable that lives across the kernel: a pinned copy would cost a v_mov per piece)
+            asm volatile("" : "+v"(pkvo));
+            TF_GLDS16(ub + pkvo, dstp);
+            return;
+        }
+        // wave-uniform pointer + zero-extended 32-bit lane offset: the saddr + voffset form of global_load_lds -- which the
+        // load takes only with BOTH pins below (the base's and the lane offsets')
         // ONE scalar base (selected, not branched on) + ONE 32-bit lane offset; the empty asm pins the base in SGPRs at
         // this point: hoisted out of the tile loop, base + lane offset becomes a 64-bit VGPR pair per piece, spilled,
         // and every reload drains the DMA queue with a vmcnt(0)
@@ -143,8 +161,12 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ffn_fused_kernel(FfnArgs p) {
         const char* ub = reinterpret_cast<const char*>(
             qk ? p.Wq + ((size_t)(gg - NP - nc) * (32 * 256) + 16 * i)
                : (pj ? p.Wo + ((size_t)gg * (32 * 256) + 16 * i) : fbase + ((size_t)(gg - NP) * fchunk + (size_t)i * fpiece)));
-        const unsigned vo = (unsigned)((pj ? poff : foff) * 4);
         asm volatile("" : "+s"(ub));
+        // the lane offsets are pinned next to the load as well (in place, on the two variables that live across the kernel):
+        // hoisted, the zero-extension of the offset lands in another block than the load, and the load then takes a 64-bit
+        // VGPR address -- one v_lshl_add_u64 per piece in the MFMA stream -- instead of saddr + voffset
+        asm volatile("" : "+v"(poff4), "+v"(foff4));
+        const unsigned vo = pj ? poff4 : foff4;
         TF_GLDS16(ub + vo, dstp);
     };
 
@@ -487,7 +509,7 @@ static int ffn_cu_count(int* n_cu) {
 }
 
 // n_cu: the CU count that sizes the grid (0: the device's)
-template <bool PROJ, bool QKV, int NW, bool PRE = false>
+template <bool PROJ, bool QKV, int NW, bool PRE = false, bool PK = false>
 static int launch_ffn_nw(const TailF32Args& a, int n_cu, hipStream_t s) {
     const size_t lds = (size_t)(FFN_NST * FFN_STAGE + a.ff + 6 * 256 + (QKV ? a.n_qkv : 0)) * sizeof(float);
     CONE_REQUIRE(lds <= 160 * 1024, "fused layer tail: %zu bytes of LDS (ff %d, q|k|v %d) exceed 160 KiB", lds, a.ff, a.n_qkv);
@@ -496,7 +518,7 @@ static int launch_ffn_nw(const TailF32Args& a, int n_cu, hipStream_t s) {
     static DeviceOnce once;
     int dev_cu = 0;
     CONE_CHECK_HIP(device_once(once, [] {
-        return hipFuncSetAttribute((const void*)ffn_fused_kernel<PROJ, QKV, NW, PRE>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        return hipFuncSetAttribute((const void*)ffn_fused_kernel<PROJ, QKV, NW, PRE, PK>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    160 * 1024);
     }, &dev_cu));
     if (!n_cu) n_cu = dev_cu;
@@ -508,18 +530,24 @@ static int launch_ffn_nw(const TailF32Args& a, int n_cu, hipStream_t s) {
                  a.ff + (QKV ? a.n_qkv / 2 : 0), 256, a.M_dev, s);
     FfnArgs k;
     static_cast<TailF32Args&>(k) = a;
-    hipLaunchKernelGGL((ffn_fused_kernel<PROJ, QKV, NW, PRE>), dim3((unsigned)grid), dim3(64 * NW), lds, s, k);
+    hipLaunchKernelGGL((ffn_fused_kernel<PROJ, QKV, NW, PRE, PK>), dim3((unsigned)grid), dim3(64 * NW), lds, s, k);
     CONE_LAUNCH_CHECK();
+    if (PK) f32_packed_note(0);
     return 0;
 }
 
 // The row kernel on filled arguments: nw = 8 (128-row tiles) or 4 (64-row tiles); the ride (a.Wq) and the pre-norm form exist
 // on 8 waves only.
+template <bool PK>
+static int launch_ffn_rows_pk(const TailF32Args& a, bool proj, bool pre, int nw, int n_cu, hipStream_t s) {
+    if (pre) return launch_ffn_nw<true, false, 8, true, PK>(a, n_cu, s);
+    if (a.Wq) return launch_ffn_nw<true, true, 8, false, PK>(a, n_cu, s);
+    if (nw == 4) return proj ? launch_ffn_nw<true, false, 4, false, PK>(a, n_cu, s) : launch_ffn_nw<false, false, 4, false, PK>(a, n_cu, s);
+    return proj ? launch_ffn_nw<true, false, 8, false, PK>(a, n_cu, s) : launch_ffn_nw<false, false, 8, false, PK>(a, n_cu, s);
+}
+// a.Wimg (the packed stream, from its Wo chunks when it has them) picks the stream form; the block alone starts behind them
 static int launch_ffn_rows(const TailF32Args& a, bool proj, bool pre, int nw, int n_cu, hipStream_t s) {
-    if (pre) return launch_ffn_nw<true, false, 8, true>(a, n_cu, s);
-    if (a.Wq) return launch_ffn_nw<true, true, 8>(a, n_cu, s);
-    if (nw == 4) return proj ? launch_ffn_nw<true, false, 4>(a, n_cu, s) : launch_ffn_nw<false, false, 4>(a, n_cu, s);
-    return proj ? launch_ffn_nw<true, false, 8>(a, n_cu, s) : launch_ffn_nw<false, false, 8>(a, n_cu, s);
+    return a.Wimg ? launch_ffn_rows_pk<true>(a, proj, pre, nw, n_cu, s) : launch_ffn_rows_pk<false>(a, proj, pre, nw, n_cu, s);
 }
 
 // Rows past the last FULL round of the persistent grid (n_cu tiles of 128 rows) cost the row forms a partial round -- half
@@ -605,5 +633,31 @@ int launch_tail_f32_form(const TailArgs& t, int form, int n_cu, hipStream_t s) {
     if (form == CONE_TAIL_FORM_WIDE) return launch_tail_f32_wide(a, true, t.pre, s);
     if (form == CONE_TAIL_FORM_LADDER) return launch_ffn_ladder(a, true, n_cu, 0, s);
     return launch_ffn_rows(a, true, t.pre, form == CONE_TAIL_FORM_ROWS64 ? 4 : 8, 0, s);
+}
+
+// Test hook (cone_test_tail_packed): the row kernel itself -- t.A == null: the block alone on t.R as its input -- on nw waves
+// (8 | 4), a persistent grid sized for n_cu CUs (0: the device's), streaming the packed image img (null: the row-major
+// matrices).  img is what launch_f32_pack_tail built from these weights: with the Wo chunks exactly when t.A is given.
+int launch_tail_f32_rows_hook(const TailArgs& t, const void* img, int nw, int n_cu, hipStream_t s) {
+    CONE_REQUIRE(nw == 8 || nw == 4, "tail rows hook: %d waves", nw);
+    CONE_REQUIRE(n_cu >= 0, "tail rows hook: negative CU count");
+    const bool proj = t.A != nullptr;
+    CONE_REQUIRE(proj || (!t.pre && !t.next), "tail rows hook: the block alone has no pre-norm form and no ride");
+    CONE_REQUIRE(nw == 8 || (!t.pre && !t.next), "tail rows hook: the ride and the pre-norm form run on 8 waves");
+    TailF32Args a;
+    if (proj) {
+        if (int rc = tail_f32_check(t, TF_FORM_ROWS, "tail rows hook")) return rc;
+        a = tail_f32_args(t);
+    } else {
+        const TailWeights& w = *t.w;
+        CONE_REQUIRE(ffn_fused_supported(t.ff) && t.R && w.W1 && w.b1 && w.W2 && w.b2 && w.out_g && w.out_b && t.OUT,
+                     "tail rows hook: bad block arguments");
+        a = TailF32Args{};
+        a.X = t.R; a.ldx = t.ldr; a.W1 = w.W1; a.b1 = w.b1; a.W2 = w.W2; a.b2 = w.b2; a.ln_g = w.out_g; a.ln_b = w.out_b;
+        a.OUT = t.OUT; a.ldo = t.ldo; a.M = t.M; a.M_dev = t.M_dev; a.ff = t.ff;
+    }
+    a.Wimg = img;
+    if (t.M <= 0) return 0;
+    return launch_ffn_rows(a, proj, t.pre, nw, n_cu, s);
 }
 }  // namespace cone

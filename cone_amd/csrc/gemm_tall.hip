@@ -30,6 +30,9 @@
 // (a wave with rows past M issues the same count; an idle wave issues pieces only): the pieces of chunk g + 1, issued a chunk
 // earlier, have landed, and so have the stores of chunk g - 1 and the row loads, which had a whole chunk (3.7 us) to do so.
 // The stores of chunk g are issued BEHIND the barrier, so no wait ever covers a store younger than a chunk.
+//
+// Weight stream.  gemm_tall_kernel<RES, false> gathers a piece's 16 row segments from the row-major W; <RES, true> reads the
+// same bytes from W's packed image (tail_pack.hip, a.Wimg), where every lane's 16 B already sits in place.
 #include "gemm_tall.h"
 #include "tail_f32_common.h"
 
@@ -42,7 +45,9 @@ constexpr int GT_NPIECE = 4;                      // 1-KiB LDS-DMA pieces per wa
 static_assert(GT_NPIECE * 8 * 256 == GT_STAGE, "8 waves x GT_NPIECE pieces of 256 floats fill a stage");
 static_assert(GT_NST == 4, "the stage index is advanced with & 3, and chunk c + 2 must not land in a stage still being read");
 
-template <bool RES>
+// PK: the weight pieces stream from W's packed image p.Wimg (tail_pack.hip: the chunks in walking order, every lane's 16 B in
+// place) instead of being gathered from the row-major matrix -- the same bytes at the same LDS addresses.
+template <bool RES, bool PK = false>
 __global__ __launch_bounds__(512, 2) void gemm_tall_kernel(GemmArgs p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* bs = smem + GT_NST * GT_STAGE;         // bias (N floats; zeros without one)
@@ -64,15 +69,22 @@ __global__ __launch_bounds__(512, 2) void gemm_tall_kernel(GemmArgs p) {
     // chunk XOR-swizzled.  A piece's source = a wave-uniform base (SGPRs) + ONE 32-bit lane offset.
     const int drow = lane >> 2;
     const int dch = (lane & 3) ^ tf_swz16(drow);
-    const unsigned vo = (unsigned)(((16 * (wave >> 2) + drow) * 256 + 16 * GT_NPIECE * (wave & 3) + 4 * dch) * 4);
+    unsigned vo = PK ? (unsigned)(lane * 16)
+                           : (unsigned)(((16 * (wave >> 2) + drow) * 256 + 16 * GT_NPIECE * (wave & 3) + 4 * dch) * 4);
     int stg = 0;                                  // ring stage of the chunk being multiplied
     int ws = 0;                                   // weight chunk (< NC) that streams next
     auto stream_piece = [&](int stage, int wchunk, int i) {
         float* dstp = smem + stage * GT_STAGE + (wave * GT_NPIECE + i) * 256;
         // the empty asm pins the base in SGPRs at this point: hoisted out of the loops, base + lane offset becomes a 64-bit
         // VGPR pair per piece
-        const char* ub = reinterpret_cast<const char*>(p.W + ((size_t)wchunk * (32 * 256) + 16 * i));
+        // (PK: one 32-bit offset of (chunk, slab); an image is far below 4 GiB)
+        const char* ub = PK ? reinterpret_cast<const char*>(p.Wimg) + (((unsigned)wchunk << 15) + (unsigned)(wave * GT_NPIECE + i) * 1024u)
+                            : reinterpret_cast<const char*>(p.W + ((size_t)wchunk * (32 * 256) + 16 * i));
         asm volatile("" : "+s"(ub));
+        // the lane offset is pinned here too -- hoisted, its zero-extension lands in another block than the load, which then
+        // takes a 64-bit VGPR address (one v_lshl_add_u64 per piece in the MFMA stream) instead of saddr + voffset
+        // (in place, on the one variable: a pinned copy would cost a v_mov per piece)
+        asm volatile("" : "+v"(vo));
         TF_GLDS16(ub + vo, dstp);
     };
     auto next_chunk = [&]() { ws = ws + 1 < NC ? ws + 1 : 0; stg = (stg + 1) & 3; };
@@ -247,9 +259,11 @@ int launch_gemm_tall(const GemmArgs& a, int n_cu, hipStream_t s) {
     static DeviceOnce once;
     int dev_cu = 0;
     CONE_CHECK_HIP(device_once(once, [] {
-        hipError_t rc = hipFuncSetAttribute((const void*)gemm_tall_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (rc == hipSuccess)
-            rc = hipFuncSetAttribute((const void*)gemm_tall_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        const void* const kernels[4] = {(const void*)gemm_tall_kernel<false, false>, (const void*)gemm_tall_kernel<true, false>,
+                                        (const void*)gemm_tall_kernel<false, true>, (const void*)gemm_tall_kernel<true, true>};
+        hipError_t rc = hipSuccess;
+        for (int i = 0; i < 4 && rc == hipSuccess; ++i)
+            rc = hipFuncSetAttribute(kernels[i], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         return rc;
     }, &dev_cu));
     if (n_cu <= 0) n_cu = dev_cu;
@@ -257,11 +271,13 @@ int launch_gemm_tall(const GemmArgs& a, int n_cu, hipStream_t s) {
     const int grid = tiles < n_cu ? tiles : n_cu;
     // booked as the 8-wave row tile's kind: the same computation, and the FLOP accounting by shape stays complete
     ProfScope ps(PK_GEMM_ROWS16, a.M, a.N, a.K, a.M_dev, s);
-    if (a.flags & EPI_RESIDUAL)
-        hipLaunchKernelGGL(gemm_tall_kernel<true>, dim3((unsigned)grid), dim3(512), gt_lds_bytes(a.N), s, a);
-    else
-        hipLaunchKernelGGL(gemm_tall_kernel<false>, dim3((unsigned)grid), dim3(512), gt_lds_bytes(a.N), s, a);
+    // a.Wimg (W's packed image) picks the stream form
+    const bool res = (a.flags & EPI_RESIDUAL) != 0;
+    auto* const kernel = a.Wimg ? (res ? gemm_tall_kernel<true, true> : gemm_tall_kernel<false, true>)
+                                : (res ? gemm_tall_kernel<true, false> : gemm_tall_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(512), gt_lds_bytes(a.N), s, a);
     CONE_LAUNCH_CHECK();
+    if (a.Wimg) f32_packed_note(1);
     return 0;
 }
 

@@ -105,6 +105,9 @@ struct TailF32Args {
     float* OUT2; int ldo2;
     // wide and spread forms: the rows are rows m_off .. m_off + M of a larger job whose device-side count is *M_dev
     int m_off;
+    // row kernels of ffn.hip: the packed weight stream (tail_pack.hip), starting at the first chunk the kernel walks; null:
+    // the pieces are gathered from the row-major matrices
+    const void* Wimg;
 };
 struct FfnArgs : TailF32Args {};
 struct FfnWideArgs : TailF32Args {};
@@ -131,6 +134,8 @@ static inline TailF32Args tail_f32_args(const TailArgs& t) {
     a.OUT = t.OUT; a.ldo = t.ldo; a.M = t.M; a.M_dev = t.M_dev; a.ff = t.ff; a.m_off = t.m_off;
     if (t.pre) { a.OUT2 = t.OUT2; a.ldo2 = t.ldo2; }
     if (tail_f32_rides(t)) { a.Wq = t.next->Wq; a.qb = t.next->qb; a.QKV = t.QKV; a.ldq = t.ldq; a.n_qkv = t.n_qkv; }
+    // an image with ride chunks serves a launch without a ride (they are never reached); a ride needs its own chunks
+    if (t.packed && w.pk && (!a.Wq || w.pk_nq == a.n_qkv)) a.Wimg = w.pk;
     return a;
 }
 

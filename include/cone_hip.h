@@ -1101,7 +1101,14 @@ int64_t cone_prof_collect(double* out, int64_t max_rec);
  *   (gemm_tall.hip: K = 256, N % 32 == 0, no addend / second output / LayerNorm epilogue / periodic residual; the bits of 3),
  *   a launch it cannot run is refused by name.
  * "gemm_tall_min_rows" (default -1 = the built-in threshold): automatic launches of at least this many rows (host bound) that
- *   the tall form can run take it; 0 = never.  The bits do not depend on it. */
+ *   the tall form can run take it; 0 = never.  The bits do not depend on it.
+ * "tail_packed" (additive, ABI 8; switch, default 1): the weight stream of the persistent row kernel of the exact-fp32 layer
+ *   tail: 1 = from the handle's packed slab images (built at cone_model_create from the weights, freed with the handle: the
+ *   ring's chunks in walking order, gather and swizzle resolved once), 0 = gathered from the row-major matrices.
+ * "gemm_tall_packed" (additive, ABI 8; switch, default 0): the same for the tall row GEMM; its images (the N = 768
+ *   in-projections) are built at the first 1, synchronously, and kept until cone_model_destroy; a tall launch whose weight has
+ *   no image streams row-major.  Measured inside the noise against the row-major stream, hence off.
+ *   The LDS contents are the same bytes in either form, so the bits depend on neither option. */
 int cone_model_set_option(cone_model* m, const char* name, int value);
 /* C = epi((A [+ A2]) W^T + bias); flags: 1 relu, 2 add residual R, 4 LayerNorm(g,b) (N must be 256), 8 = keep a launch of a few
  * row groups on the workgroup-per-16-rows form (else: one wave per 16 x 16 output tile, same bits);
@@ -1118,6 +1125,31 @@ int cone_test_gemm_tall(const float* A, const float* A2, int a2_mod, const float
                         const float* R, const float* ln_g, const float* ln_b, float* C, float* C2,
                         const float* ADD, int M, int N, int K, int flags, int lda, int ldc, const int32_t* M_dev,
                         int n_cu, void* stream);
+/* ---- packed fp32 weight streams (additive, ABI 8; tests and benchmarks only).  An image is a sequence of 32-KiB chunks
+ * [slab 0..31][lane 0..63][4 floats]; with row = lane / 4, ch = (lane % 4) ^ ((0x1230 >> (4 * ((row / 4) % 4))) & 3):
+ *   projection format, chunk c of W (N, 256):  slab s = W[32 c + 16 (s / 16) + row][16 (s % 16) + 4 ch ..]
+ *   feed-forward format, chunk c:              slab s < 16 = W1[16 c + row][16 s + 4 ch ..], slab 16 + t = W2[16 t + row][16 c + 4 ch ..]
+ * cone_test_f32_pack_tail: [Wo != NULL: its 8 chunks | ff / 16 feed-forward chunks | Wq != NULL: n_qkv / 32 chunks of Wq];
+ * cone_test_f32_pack_rows: the N / 32 chunks of W.  The *_bytes entries return the image size (0: unsupported). */
+size_t cone_test_f32_pack_tail_bytes(int ff, int proj, int n_qkv);
+int cone_test_f32_pack_tail(const float* Wo, const float* W1, const float* W2, int ff, const float* Wq, int n_qkv, void* img,
+                            void* stream);
+size_t cone_test_f32_pack_rows_bytes(int N);
+/* launches that streamed a packed image since the library was loaded: which 0 = the layer tail's row kernel, 1 = the tall GEMM */
+long cone_test_f32_packed_launches(int which);
+int cone_test_f32_pack_rows(const float* W, int N, void* img, void* stream);
+/* The tall form itself (K = 256, contiguous operands; flags 1 relu, 2 residual R) streaming W's packed image img (NULL: the
+ * row-major matrix); n_cu > 0 sizes the persistent grid. */
+int cone_test_gemm_tall_packed(const float* A, const float* W, const float* bias, const float* R, float* C, int M, int N,
+                               int flags, const int32_t* M_dev, int n_cu, const void* img, void* stream);
+/* The persistent row kernel of the exact-fp32 tail (cone_test_proj_ffn's operands) streaming the packed image img (NULL: the
+ * row-major matrices).  A == NULL: the feed-forward block alone on R as its input (an image without Wo chunks); Wq != NULL: with
+ * the q | k | v ride, QKV (M, n_qkv) = OUT Wq^T + qb (an image with the Wq chunks); pre: the pre-norm form (OUT2 may be NULL);
+ * nw = 8 (128-row tiles) | 4 (64-row tiles; no ride, no pre-norm form); n_cu > 0 sizes the persistent grid. */
+int cone_test_tail_packed(const float* A, const float* Wo, const float* bo, const float* R, const float* pg, const float* pb,
+                          const float* W1, const float* b1, const float* W2, const float* b2, const float* ln_g,
+                          const float* ln_b, float* OUT, int M, int ff, int pre, float* OUT2, const float* Wq, const float* qb,
+                          float* QKV, int n_qkv, int nw, int n_cu, const void* img, void* stream);
 /* The row GEMM of option "general_bf16" (gemm_bf16.hip): cone_test_gemm's arguments and
  *   C[m][n] = sum_k bf16(A[m][k] (+ A2[a2_mod ? m % a2_mod : m][k], added in fp32 first)) * bf16(W[n][k])   (fp32 accumulation)
  *             + bias[n],  then ReLU (flag 1),  then + R[r_mod ? m % r_mod : m][n] (flag 2; the residual is never rounded)
