@@ -324,6 +324,13 @@ _SIGNATURES = {
     "cone_test_rows_split": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "cone_test_proj_split_image_bytes": (C.c_size_t, []),
     "cone_test_proj_ffn_split": (C.c_int, [C.c_void_p] * 13 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    # cone_test_tail_mc(A | None, Wo, bo, R, pg, pb, W1, b1, W2, b2, ln_g, ln_b, OUT, M, ff, r_idx, R2, M_dev, pre, OUT2, Wq, qb, QKV,
+    #                   n_qkv, lda, ldr, ldo, ldo2, ldq, n_cu, img, wo_img, q_img, pack, stream)
+    "cone_test_tail_mc": (C.c_int, [C.c_void_p] * 13 + [C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 4
+                          + [C.c_int] * 7 + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]),
+    # cone_test_rows_mc(X, W, bias, C, M, N, img, pack, ldx, ldc, M_dev, n_cu, stream)
+    "cone_test_rows_mc": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p, C.c_int,
+                                                                                                        C.c_void_p]),
     "cone_test_enc_attn": (C.c_int, [C.c_int] + [C.c_void_p] * 9 + [C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "cone_test_dec_cross": (C.c_int, [C.c_void_p] * 9 + [C.c_int] * 4 + [C.c_void_p, C.c_void_p]),
     "cone_test_dec_cross_slab_floats": (C.c_size_t, []),

@@ -530,7 +530,7 @@ static int encoder_qkv(const cone_model* m, int l, const float* X, float* QKV, i
     const int mode = m->opt_bf16 && m->bf16_img && !m->general()               ? TAIL_IMG_BF16
                      : split_ok && l > 0 && m->opt_split_bf16 && m->split_img ? TAIL_IMG_SPLIT
                                                                                : -1;
-    if (mode >= 0) return TAIL_MODES[mode]->rows256(X, 256, t.img[mode].qkv, t.qb, QKV, 768, M, M_dev, 768, s);
+    if (mode >= 0) return TAIL_MODES[mode]->rows256(X, 256, t.img[mode].qkv, t.qb, QKV, 768, M, M_dev, 768, s, 0);
     return launch_gemm(G(m, X, d, t.Wq, d, t.qb, QKV, 3 * d, M, M_dev, 3 * d, d), s);
 }
 
@@ -1864,7 +1864,7 @@ extern "C" int cone_test_ffn_split(const float* X, const float* W1, const float*
         const int rc = k.pack(W1, W2, ff, img, (hipStream_t)stream);
         if (rc) return rc;
     }
-    return k.ffn(X, 256, img, b1, b2, ln_g, ln_b, OUT, 256, M, nullptr, ff, (hipStream_t)stream);
+    return k.ffn(X, 256, img, b1, b2, ln_g, ln_b, OUT, 256, M, nullptr, ff, (hipStream_t)stream, 0);
 }
 extern "C" size_t cone_test_rows_split_image_bytes(int N) {
     const TailMode& k = *TAIL_MODES[TAIL_IMG_SPLIT];
@@ -1878,7 +1878,7 @@ extern "C" int cone_test_rows_split(const float* X, const float* W, const float*
         const int rc = k.pack(W, nullptr, N, img, (hipStream_t)stream);
         if (rc) return rc;
     }
-    return k.rows256(X, 256, img, bias, C, N, M, nullptr, N, (hipStream_t)stream);
+    return k.rows256(X, 256, img, bias, C, N, M, nullptr, N, (hipStream_t)stream, 0);
 }
 extern "C" size_t cone_test_proj_split_image_bytes(void) { return TAIL_MODES[TAIL_IMG_SPLIT]->proj_image_bytes(); }
 extern "C" int cone_test_proj_ffn_split(const float* A, const float* Wo, const float* bo, const float* R, const float* pg,
@@ -1898,6 +1898,56 @@ extern "C" int cone_test_proj_ffn_split(const float* A, const float* Wo, const f
     const TailArgs t = test_tail(&w, A, Wo, bo, R, pg, pb, W1, b1, W2, b2, ln_g, ln_b, OUT, M, ff);
     w.img[mode] = TailImages{wo_img, img, nullptr};
     return k.proj_ffn(t, (hipStream_t)stream);
+}
+// The matrix-core tails in every form their launchers have, as cone_test_tail_packed is for the exact-fp32 one: A == null: the
+// block alone on R as its input (no gather, ride or pre-norm form); Wq != null: the q | k | v ride; pre: the pre-norm form (the
+// single-piece mode only; OUT2 may be null); r_idx / R2: the gathered residual; M_dev; row strides (0 = dense); n_cu > 0: a
+// persistent grid sized for that many CUs.  The images are packed first where `pack` says so (test_tail_mode).
+extern "C" int cone_test_tail_mc(const float* A, const float* Wo, const float* bo, const float* R, const float* pg,
+                                 const float* pb, const float* W1, const float* b1, const float* W2, const float* b2,
+                                 const float* ln_g, const float* ln_b, float* OUT, int M, int ff, const int32_t* r_idx,
+                                 const float* R2, const int32_t* M_dev, int pre, float* OUT2, const float* Wq, const float* qb,
+                                 float* QKV, int n_qkv, int lda, int ldr, int ldo, int ldo2, int ldq, int n_cu, void* img,
+                                 void* wo_img, void* q_img, int pack, void* stream) {
+    bool do_pack;
+    const int mode = test_tail_mode(pack, &do_pack);
+    const TailMode& k = *TAIL_MODES[mode];
+    hipStream_t s = (hipStream_t)stream;
+    CONE_REQUIRE(!pre || k.proj_ffn_prenorm, "tail hook: the three-piece split tail has no pre-norm form");
+    CONE_REQUIRE(!pre || !Wq, "tail hook: the pre-norm form has no q|k|v ride");
+    CONE_REQUIRE(A || (!pre && !Wq && !r_idx), "tail hook: the block alone has no pre-norm, ride or gather form");
+    CONE_REQUIRE(!Wq || q_img, "tail hook: the ride needs its image buffer");
+    if (do_pack) {
+        if (int rc = k.pack(W1, W2, ff, img, s)) return rc;
+        if (A)
+            if (int rc = k.pack(Wo, nullptr, 256, wo_img, s)) return rc;
+        if (Wq)
+            if (int rc = k.pack(Wq, nullptr, n_qkv, q_img, s)) return rc;
+    }
+    if (!A) return k.ffn(R, ldr ? ldr : 256, img, b1, b2, ln_g, ln_b, OUT, ldo ? ldo : 256, M, M_dev, ff, s, n_cu);
+    TailWeights w, nx{};
+    TailArgs t = test_tail(&w, A, Wo, bo, R, pg, pb, W1, b1, W2, b2, ln_g, ln_b, OUT, M, ff);
+    w.img[mode] = TailImages{wo_img, img, nullptr};
+    if (lda) t.lda = lda;
+    if (ldr) t.ldr = ldr;
+    if (ldo) t.ldo = ldo;
+    t.r_idx = r_idx; t.R2 = R2; t.M_dev = M_dev; t.pre = pre != 0; t.OUT2 = OUT2; t.ldo2 = ldo2 ? ldo2 : 256; t.n_cu = n_cu;
+    if (Wq) {
+        nx.Wq = Wq; nx.qb = qb; nx.img[mode] = TailImages{nullptr, nullptr, q_img};
+        t.next = &nx; t.QKV = QKV; t.n_qkv = n_qkv; t.ldq = ldq ? ldq : n_qkv;
+    }
+    return pre ? k.proj_ffn_prenorm(t, s) : k.proj_ffn(t, s);
+}
+// cone_test_rows_split with row strides (0 = dense), a device-side row count and a CU count for the persistent grid
+extern "C" int cone_test_rows_mc(const float* X, const float* W, const float* bias, float* C, int M, int N, void* img, int pack,
+                                 int ldx, int ldc, const int32_t* M_dev, int n_cu, void* stream) {
+    bool do_pack;
+    const TailMode& k = *TAIL_MODES[test_tail_mode(pack, &do_pack)];
+    if (do_pack) {
+        const int rc = k.pack(W, nullptr, N, img, (hipStream_t)stream);
+        if (rc) return rc;
+    }
+    return k.rows256(X, ldx ? ldx : 256, img, bias, C, ldc ? ldc : N, M, M_dev, N, (hipStream_t)stream, n_cu);
 }
 extern "C" int cone_test_enc_attn(int mode, const float* QKV, const float* qkv_vid, const float* qkv_txt,
                                   const float* pos_qk, const int32_t* vrow0, const int32_t* vlen, const int32_t* trow0,

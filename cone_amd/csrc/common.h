@@ -175,6 +175,8 @@ struct TailArgs {
     float* X1; float* H;                  // the unfused forms' rows (api.hip, launch_layer_tail): LN_in's output (M, 256), hidden (M, ff)
     float* C2; const float* ADD;          // != null: a second output C2 = OUT + ADD, which only the unfused GEMM epilogue writes
     bool packed;                          // the exact-fp32 row kernel streams w->pk (where it has one that fits the launch)
+    int n_cu;                             // matrix-core tails: the CU count that sizes the persistent grid (0 = the device's:
+                                          //   what every production launch passes; > 0: cone_test_tail_mc)
 };
 
 // ---------------------------------------------------------------- the exact-fp32 layer tail (ffn.hip, ffn_wide.hip)
@@ -252,14 +254,15 @@ struct TailMode {
     size_t (*ffn_image_bytes)(int ff);
     // the layer's W1 / W2 (W2 == null: any (N = ff, 256) weight of a 256-channel product) laid out once for the kernels
     int (*pack)(const float* W1, const float* W2, int ff, void* img, hipStream_t s);
-    // launch_ffn_fused's computation; Wimg = pack(W1, W2, ff) (ffn_image_bytes(ff) bytes)
+    // launch_ffn_fused's computation; Wimg = pack(W1, W2, ff) (ffn_image_bytes(ff) bytes).  n_cu, here and in rows256: the CU
+    // count that sizes the persistent grid (0 = the device's: every production launch; > 0: the test hooks; < 0 is refused)
     int (*ffn)(const float* X, int ldx, const void* Wimg, const float* b1, const float* b2, const float* ln_g, const float* ln_b,
-               float* OUT, int ldo, int M, const int* M_dev, int ff, hipStream_t s);
+               float* OUT, int ldo, int M, const int* M_dev, int ff, hipStream_t s, int n_cu);
     // C (M, N) = X (M, 256) W^T + bias on the same operands; Wimg = pack(W, nullptr, N) (rows_image_bytes(N) bytes)
     bool (*rows_supported)(int N);
     size_t (*rows_image_bytes)(int N);
     int (*rows256)(const float* X, int ldx, const void* Wimg, const float* bias, float* C, int ldc, int M, const int* M_dev, int N,
-                   hipStream_t s);
+                   hipStream_t s, int n_cu);
     // launch_proj_ffn_fused's computation on t.w->img[mode]: wo = pack(Wo, nullptr, 256) (proj_image_bytes()), ffn as
     // above, the ride's qkv = pack(Wq, nullptr, n_qkv)
     size_t (*proj_image_bytes)();

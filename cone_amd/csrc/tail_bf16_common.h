@@ -224,17 +224,21 @@ template <class Mode> static bool tail_qkv_fits(int ff, int n_qkv) {
 static bool tail_rows_supported(int N) { return N >= 32 && N % 32 == 0 && N <= 3072; }
 template <class Mode> static size_t tail_rows_image_bytes(int N) { return (size_t)(N / 32) * Mode::SLOT; }
 
+// n_cu, in every launcher below: the CU count that sizes the persistent grid; 0 = the device's, which is what every production
+// caller passes; > 0 (the test hooks) makes a workgroup walk several tiles at a few hundred rows
 template <class Mode, bool PROJ, bool QKV, bool PRE = false>
-static int tail_launch_kernel(const typename Mode::FfnArgs& a, hipStream_t s) {
+static int tail_launch_kernel(const typename Mode::FfnArgs& a, int n_cu, hipStream_t s) {
+    CONE_REQUIRE(n_cu >= 0, "%s fused layer tail: negative CU count", Mode::NAME);
     const size_t lds = tail_lds<Mode>(a.ff, QKV ? a.n_qkv : 0);
     CONE_REQUIRE(lds <= (size_t)TB_LDS_MAX, "%s fused layer tail: %zu bytes of LDS (ff %d, q|k|v %d) exceed 160 KiB", Mode::NAME, lds,
                  a.ff, a.n_qkv);
     constexpr auto kernel = Mode::template ffn_kernel<PROJ, QKV, PRE>();
     static DeviceOnce once;
-    int n_cu = 0;
+    int dev_cu = 0;
     CONE_CHECK_HIP(device_once(once, [] {
         return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TB_LDS_MAX);
-    }, &n_cu));
+    }, &dev_cu));
+    if (!n_cu) n_cu = dev_cu;
     const int tiles = (a.M + TB_ROWS - 1) / TB_ROWS;
     const int grid = tiles < n_cu ? tiles : n_cu;
     // FLOPs of a record = 4 M ff 256 (+ 2 M 256 256 with the projection); the fused q | k | v projection adds
@@ -247,7 +251,7 @@ static int tail_launch_kernel(const typename Mode::FfnArgs& a, hipStream_t s) {
 
 template <class Mode>
 static int tail_launch_ffn(const float* X, int ldx, const void* Wimg, const float* b1, const float* b2, const float* ln_g,
-                           const float* ln_b, float* OUT, int ldo, int M, const int* M_dev, int ff, hipStream_t s) {
+                           const float* ln_b, float* OUT, int ldo, int M, const int* M_dev, int ff, hipStream_t s, int n_cu) {
     CONE_REQUIRE(tail_ffn_supported(ff), "%s fused FFN: dim_feedforward=%d unsupported", Mode::NAME, ff);
     CONE_REQUIRE(X && Wimg && b1 && b2 && ln_g && ln_b && OUT, "%s fused FFN: null argument", Mode::NAME);
     CONE_REQUIRE(ldx % 4 == 0 && ldo % 4 == 0, "%s fused FFN: row strides must be multiples of 4", Mode::NAME);
@@ -255,7 +259,7 @@ static int tail_launch_ffn(const float* X, int ldx, const void* Wimg, const floa
     typename Mode::FfnArgs a{};
     a.X = X; a.ldx = ldx; a.Wimg = Wimg; a.b1 = b1; a.b2 = b2; a.ln_g = ln_g; a.ln_b = ln_b;
     a.OUT = OUT; a.ldo = ldo; a.M = M; a.M_dev = M_dev; a.ff = ff;
-    return tail_launch_kernel<Mode, false, false>(a, s);
+    return tail_launch_kernel<Mode, false, false>(a, n_cu, s);
 }
 
 // the projecting tail: post-norm (with the ride where t.next is set), and PRE = the --pre_norm form where the mode has one
@@ -283,30 +287,32 @@ static int tail_launch_proj_ffn(const TailArgs& t, hipStream_t s) {
     a.OUT = t.OUT; a.ldo = t.ldo; a.M = t.M; a.M_dev = t.M_dev; a.ff = t.ff;
     if constexpr (PRE) {
         a.OUT2 = t.OUT2; a.ldo2 = t.ldo2;
-        return tail_launch_kernel<Mode, true, false, true>(a, s);
+        return tail_launch_kernel<Mode, true, false, true>(a, t.n_cu, s);
     } else {
         if (Qimg) {
             CONE_REQUIRE(t.next->qb && t.QKV && t.n_qkv >= 32 && t.n_qkv % 32 == 0 && t.ldq % 4 == 0,
                          "%s fused layer tail: bad q|k|v arguments", Mode::NAME);
             a.Qimg = Qimg; a.qb = t.next->qb; a.QKV = t.QKV; a.ldq = t.ldq; a.n_qkv = t.n_qkv;
-            return tail_launch_kernel<Mode, true, true>(a, s);
+            return tail_launch_kernel<Mode, true, true>(a, t.n_cu, s);
         }
-        return tail_launch_kernel<Mode, true, false>(a, s);
+        return tail_launch_kernel<Mode, true, false>(a, t.n_cu, s);
     }
 }
 
 template <class Mode>
 static int tail_launch_rows256(const float* X, int ldx, const void* Wimg, const float* bias, float* C, int ldc, int M,
-                               const int* M_dev, int N, hipStream_t s) {
+                               const int* M_dev, int N, hipStream_t s, int n_cu) {
     CONE_REQUIRE(tail_rows_supported(N), "%s row GEMM: N=%d unsupported", Mode::NAME, N);
+    CONE_REQUIRE(n_cu >= 0, "%s row GEMM: negative CU count", Mode::NAME);
     CONE_REQUIRE(X && Wimg && C && ldx % 4 == 0 && ldc % 4 == 0, "%s row GEMM: bad argument", Mode::NAME);
     if (M <= 0) return 0;
     static DeviceOnce once;
-    int n_cu = 0;
+    int dev_cu = 0;
     CONE_CHECK_HIP(device_once(once, [] {
         return hipFuncSetAttribute((const void*)Mode::rows_kernel(), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    Mode::NSLOT * Mode::SLOT + 3072 * (int)sizeof(float));
-    }, &n_cu));
+    }, &dev_cu));
+    if (!n_cu) n_cu = dev_cu;
     typename Mode::RowsArgs a{{X, ldx, Wimg, bias, C, ldc, M, M_dev, N}};
     const int tiles = (M + TB_ROWS - 1) / TB_ROWS;
     const int grid = tiles < n_cu ? tiles : n_cu;

@@ -1210,6 +1210,31 @@ int cone_test_proj_ffn_split(const float* A, const float* Wo, const float* bo, c
                              const float* pb, const float* W1, const float* b1, const float* W2, const float* b2,
                              const float* ln_g, const float* ln_b, float* OUT, int M, int ff, void* img, void* wo_img,
                              int pack, void* stream);
+/* ---- every form of the matrix-core layer tails and their row GEMM (additive, ABI 8; tests only: no option or production path
+ * reads these).  pack selects the mode and whether the images are built first, as in the three entries above.
+ * cone_test_tail_mc: cone_test_proj_ffn_split's operands, then
+ *   A == NULL       the feed-forward block alone on R as its input (cone_test_ffn_split's computation; no r_idx, pre or Wq);
+ *   r_idx / R2      the gathered residual: row i = R[r_idx[i]] where r_idx[i] >= 0, else R2[~r_idx[i]] (both with stride ldr);
+ *                   r_idx without R2 is refused by name;
+ *   M_dev           optional device-side row count: rows past min(M, *M_dev) are neither computed nor stored;
+ *   pre, OUT2       the pre-norm form, single-piece mode only (the split mode refuses it by name): OUT = the un-normalised
+ *                   stream, OUT2 (may be NULL: then nothing but OUT is written) = its LayerNorm;
+ *   Wq, qb, QKV     Wq != NULL: the q | k | v ride, QKV (M, n_qkv) = OUT Wq^T + qb from the registers that hold OUT (post-norm
+ *                   only; n_qkv % 32 == 0; a ride whose ring, parameter rows and bias exceed the 160 KiB of LDS is refused by name);
+ *   lda, ldr, ldo, ldo2, ldq   row strides in floats of A, R / R2, OUT, OUT2, QKV: 0 = dense (256, n_qkv), else a multiple of 4;
+ *   n_cu            > 0: the persistent grid is sized for that many CUs, so that a few hundred rows make a workgroup walk
+ *                   several 128-row tiles; 0: the device's count (what every production launch uses); < 0 is refused by name;
+ *   img, wo_img, q_img   scratch of cone_test_ffn_split_image_bytes(ff), cone_test_proj_split_image_bytes() (A != NULL) and
+ *                   cone_test_rows_split_image_bytes(n_qkv) (Wq != NULL) bytes.
+ * cone_test_rows_mc: cone_test_rows_split with row strides ldx / ldc (0 = 256 / N), M_dev and n_cu as above. */
+int cone_test_tail_mc(const float* A, const float* Wo, const float* bo, const float* R, const float* pg, const float* pb,
+                      const float* W1, const float* b1, const float* W2, const float* b2, const float* ln_g,
+                      const float* ln_b, float* OUT, int M, int ff, const int32_t* r_idx, const float* R2,
+                      const int32_t* M_dev, int pre, float* OUT2, const float* Wq, const float* qb, float* QKV, int n_qkv,
+                      int lda, int ldr, int ldo, int ldo2, int ldq, int n_cu, void* img, void* wo_img, void* q_img, int pack,
+                      void* stream);
+int cone_test_rows_mc(const float* X, const float* W, const float* bias, float* C, int M, int N, void* img, int pack, int ldx,
+                      int ldc, const int32_t* M_dev, int n_cu, void* stream);
 /* Encoder self-attention core (cone/transformer.py:239, 8 heads x 32) over windows of packed tokens off[b] .. off[b+1]:
  * mode 0: QKV (M, 768) = q | k | v rows that already carry the position term; mode 2: the same without it, the kernel adds
  * pos_qk[(vlen[b], p)] (R, 512) to q | k of clip token p; mode 1: q | k | v gathered from per-clip rows qkv_vid[vrow0[b] + p]

@@ -1,7 +1,8 @@
 """Hostile value distributions, float64 references and DERIVED elementwise bounds for the row kernels: the fp32 GEMM family
 (gemm.hip), the fused layer tails (ffn.hip / ffn_wide.hip, ffn_split.hip, ffn_bf16.hip), gemm_bf16.hip and the row LayerNorm /
 L2 normalisation (rowops.hip).  Used by tests/test_row_kernels_cpu.py (the bounds hold for a plain evaluation and every
-planted error leaves them) and tests/test_row_kernels_gpu.py (the kernels stay inside them).
+planted error leaves them), tests/test_row_kernels_gpu.py (the kernels stay inside them) and tests/test_tail_mc_forms_gpu.py
+(the matrix-core tails' ride, pre-norm, gather and walk forms: tail_mc_case, the ride's bound in tail_ref_bound, mc_runs).
 
 Nothing here is measured on a kernel.  U = 2^-24 is the unit roundoff of fp32.
 
@@ -247,6 +248,42 @@ def tail_case(family, M, ff):
     return c
 
 
+def gather_rows(c, fault=None):
+    """The residual rows as the kernels gather them: row i = Rg[r_idx[i]] where r_idx[i] >= 0, else R2[~r_idx[i]]
+    (TB_ADD_RESIDUAL in tail_bf16_common.h).  fault: "gather_sign" reads Rg for the negative indices too, "gather_identity"
+    ignores r_idx (row i = Rg[i])."""
+    if fault == "gather_identity":
+        return c.Rg[:c.M]
+    ix = c.r_idx.long()
+    neg = ix < 0
+    pos_ix = torch.where(neg, ~ix, ix)
+    second = c.Rg if fault == "gather_sign" else c.R2
+    return torch.where(neg[:, None], second[pos_ix], c.Rg[pos_ix])
+
+
+@functools.lru_cache(maxsize=None)
+def tail_mc_case(family, M, ff, n_qkv):
+    """tail_case plus what the matrix-core tails' ride and gather forms read: the NEXT layer's q | k | v projection Wq (n_qkv,
+    256) / qb, and the residual R scattered over two (M, 256) source matrices Rg / R2 with the index row r_idx (int32; every
+    third row lives in R2 and carries ~position, the others in Rg; positions are a seeded permutation, so no row sits at its own
+    index once M > 2): gather_rows(c) == c.R bit for bit, which is why the gathered forms share the references of the plain
+    ones.  The rows of Rg / R2 that no index names hold OTHER rows of the same family (decoys a wrong gather would read)."""
+    base = tail_case(family, M, ff)
+    c = SimpleNamespace(**{k: v for k, v in vars(base).items() if not k.startswith("_")})
+    g = torch.Generator().manual_seed(_seed(family + "/mc", M, ff, n_qkv))
+    c.n_qkv = n_qkv
+    c.Wq = torch.randn(n_qkv, 256, generator=g) / 16
+    c.qb = torch.randn(n_qkv, generator=g) * 0.2
+    pos = torch.randperm(M, generator=g)
+    in2 = torch.arange(M) % 3 == 1
+    c.Rg = c.R[(torch.arange(M) + 1) % M].clone()
+    c.R2 = c.R.flip(0).roll(2, 0).clone()
+    c.Rg[pos[~in2]] = c.R[~in2]
+    c.R2[pos[in2]] = c.R[in2]
+    c.r_idx = torch.where(in2, ~pos, pos).to(torch.int32)
+    return c
+
+
 @functools.lru_cache(maxsize=None)
 def ln_case(family, M, dim):
     g = torch.Generator().manual_seed(_seed(family, M, dim))
@@ -352,6 +389,9 @@ def ln_plain(y, g, b, eps=1e-5, fault=None):
 LN_FAULTS = ("one_pass", "eps6", "div255", "gb_swap")
 EPI_FAULTS = ("relu_after_res", "bias_last32", "k_swap", "res_row_m1")
 SPLIT_FAULTS = ("drop_mm", "drop_l")
+RIDE_FAULTS = ("qkv_row_m1", "qkv_from_prenorm", "qkv_bias_last32")
+GATHER_FAULTS = ("gather_sign", "gather_identity")
+PRE_FAULTS = ("pre_out_normalised", "pre_res_normalised")
 
 
 def _a_in(c, dt):
@@ -387,19 +427,22 @@ def eval_gemm(c, flags, mm, dt, fault=None):
     return y
 
 
-def eval_tail(c, mm, dt, proj=True, pre=False, fault=None):
+def eval_tail(c, mm, dt, proj=True, pre=False, fault=None, ride=False, gather=False):
     """The layer tail in dtype dt.  proj: x0 = R + A Wo^T + bo, x1 = LN(x0; pg, pb); post-norm: OUT = LN(x1 + ffn(x1));
-    pre-norm: OUT = x0 + ffn(x1), OUT2 = LN(OUT).  Without proj the block input is R.  -> (OUT, OUT2 or None)."""
+    pre-norm: OUT = x0 + ffn(x1), OUT2 = LN(OUT).  Without proj the block input is R.  gather (a tail_mc_case): the residual
+    rows are gathered through r_idx from Rg / R2.  ride (post-norm, a tail_mc_case): QKV = OUT Wq^T + qb.
+    -> (OUT, OUT2 or None), with ride (OUT, OUT2, QKV)."""
+    assert not ride or (proj and not pre), "the ride belongs to the projecting post-norm tail"
     lnf = fault if fault in LN_FAULTS else None
     W1 = _swap_k(c.W1) if fault == "k_swap" else c.W1
     b2 = c.b2.to(dt).clone()
     if fault == "bias_last32":
         b2[-32:] = 0
-    R = c.R.to(dt)
+    R = (gather_rows(c, fault) if gather else c.R).to(dt)
     if proj:
         x0 = R + mm(c.A.to(dt), c.Wo).to(dt) + c.bo.to(dt)
         x1 = ln_plain(x0, c.pg, c.pb, fault=lnf)
-        res = x0 if pre else x1
+        res = x0 if pre and fault != "pre_res_normalised" else x1
     else:
         x1 = res = R
     if fault == "res_row_m1":
@@ -408,9 +451,16 @@ def eval_tail(c, mm, dt, proj=True, pre=False, fault=None):
     y = res + mm(h, c.W2).to(dt) + b2
     if fault == "relu_after_res":
         y = y.clamp(min=0)
+    o = ln_plain(y, c.lg, c.lb, fault=lnf)
     if pre:
-        return y, ln_plain(y, c.lg, c.lb, fault=lnf)
-    return ln_plain(y, c.lg, c.lb, fault=lnf), None
+        return (o if fault == "pre_out_normalised" else y), o
+    if not ride:
+        return o, None
+    src = y if fault == "qkv_from_prenorm" else o.roll(1, 0) if fault == "qkv_row_m1" else o
+    qb = c.qb.to(dt).clone()
+    if fault == "qkv_bias_last32":
+        qb[-32:] = 0
+    return o, None, mm(src, c.Wq).to(dt) + qb
 
 
 def eval_ln(c, dt, fault=None):
@@ -507,10 +557,19 @@ def gemm_ref_bound(c, flags, mode="f32"):
     return y, d, NO_LN
 
 
-def tail_ref_bound(c, mode="f32", proj=True, pre=False):
-    """-> dict(OUT=(ref, bound), OUT2=(ref, bound) or None, valid=the worst domain figures over the LayerNorms).
-    A hidden unit whose pre-activation stays below zero under its own bound (p + dh < 0) is exactly 0 in the kernel too: it
-    carries no error into the second GEMM (this is what makes `dead` sharp: nothing of the hidden path may leak)."""
+def tail_ref_bound(c, mode="f32", proj=True, pre=False, ride=False):
+    """-> dict(OUT=(ref, bound), OUT2=(ref, bound) or None, QKV=(ref, bound) with ride, valid=the worst domain figures over
+    the LayerNorms).  A hidden unit whose pre-activation stays below zero under its own bound (p + dh < 0) is exactly 0 in the
+    kernel too: it carries no error into the second GEMM (this is what makes `dead` sharp: nothing of the hidden path may leak).
+    pre: the fp32 and the single-piece tails have the form (Mode::HAS_PRE); the three-piece split has none and is refused.
+    ride (a tail_mc_case; post-norm with proj): QKV = rd(OUT) rd(Wq)^T + qb; the kernel projects its own OUT, which lies within
+    OUT's bound of the reference's, so that bound is carried into the GEMM as `da` exactly as dha is into the second GEMM:
+    as it is in mode "split", through the one rounding (`flip`) in mode "bf16".  A gathered residual changes nothing here: the
+    gathered rows ARE c.R (tail_mc_case)."""
+    if pre and mode == "split":
+        raise ValueError("the three-piece split tail has no pre-norm form")
+    if ride and (pre or not proj):
+        raise ValueError("the ride belongs to the projecting post-norm tail")
     rd = _rd(mode)
     valid = NO_LN
     R = c.R.double()
@@ -537,7 +596,13 @@ def tail_ref_bound(c, mode="f32", proj=True, pre=False):
     valid = _worse(valid, v)
     if pre:
         return dict(OUT=(y, dy), OUT2=(o, bo_), valid=valid)
-    return dict(OUT=(o, bo_), OUT2=None, valid=valid)
+    rb = dict(OUT=(o, bo_), OUT2=None, valid=valid)
+    if ride:
+        oa, doa = (bf(o), flip(o, bo_)) if mode == "bf16" else (o, bo_)
+        Wq = rd(c.Wq)
+        q = oa @ Wq.t() + c.qb.double()
+        rb["QKV"] = (q, gemm_delta(oa, Wq, c.qb.double().abs().expand_as(q), mode, da=doa))
+    return rb
 
 
 def ln_kernel_ref_bound(c):
@@ -591,6 +656,45 @@ ROWS_SPLIT_NS = (64, 768)
 GEMM_BF16_SHAPES = ((256, 256), (128, 96))
 L2_DIMS = (256, 512, 1024)
 L2_FAMILIES = ("benign", "spike", "zero", "huge", "minute")
+
+
+# the ride, pre-norm and gather forms of the matrix-core tails (tests/test_tail_mc_forms_gpu.py): 130 rows = two tiles on two
+# workgroups (un-walked), 677 = 5 * 128 + 37 rows on a grid sized for 2 CUs = three tiles per workgroup, the last one partial
+# with five idle waves.  The walked launches run at the ff where the ring phase moves from tile to tile in every form (slots per
+# tile G = 8 + ff / 16 + n_qkv / 32 against a ring of 8 (single piece) or 3 (split) slots: MC_WALK_FF).  MC_EDGE: the shipped
+# layout (ff, n_qkv), where the split mode's ride fills 157 of the 160 KiB of LDS.
+MC_MS = (130, 677)
+MC_NQKV = (96, 768)
+MC_WALK_FF = {"split": 128, "bf16": 64}
+MC_EDGE = (1024, 768)
+# At ff = 1024 the worst-case chain through |W1| |W2| leaves benign and cancel rows without a LayerNorm bound (ds / s = 0.98 /
+# 1.14 split, 0.74 / 0.87 single piece), so the edge runs the two families whose bound is finite there in both modes and that
+# pin the two halves of the launch: `dead` (nothing of the hidden path may leak: bounds of 4e-5 on OUT, 2e-3 on QKV) and `alive`
+# (every hidden unit passes; a coarse bound).  Its sharp checks are the bit identities of the GPU suite.
+MC_EDGE_FAMILIES = ("dead", "alive")
+# FAMILIES_TAIL left out of the matrix-core form tests, by name: `cancel` in mode "split" -- at ff = 128 and 677 rows one row of
+# its projecting tail has ds / s = 0.53 > LN_RIG_VALID under the split's worst-case chain, i.e. NO bound, and no case may carry
+# such a row.  Nothing is left out in mode "bf16": the ride's bound is finite wherever OUT's is.
+MC_LEFT_OUT = {"split": ("cancel",), "bf16": ()}
+
+
+def mc_families(mode, M):
+    return [f for f in tail_families(M) if f not in MC_LEFT_OUT[mode]]
+
+
+def mc_forms(mode):
+    """The forms of the matrix-core tails beyond the plain ones: (name, pre, ride, gather).  The split has no pre-norm kernel."""
+    forms = (("ride", False, True, False), ("gather", False, False, True), ("gather ride", False, True, True))
+    return forms + ((("pre", True, False, False),) if mode == "bf16" else ())
+
+
+def mc_runs(mode):
+    """(M, ff, n_qkv) of the float64 checks: every ff and ride width un-walked, the walking ff walked."""
+    for ff in TAIL_FFS[mode]:
+        for nq in MC_NQKV:
+            yield MC_MS[0], ff, nq
+    for nq in MC_NQKV:
+        yield MC_MS[1], MC_WALK_FF[mode], nq
 
 
 def gemm_families(M, K, flags):

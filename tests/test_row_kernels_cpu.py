@@ -4,7 +4,8 @@ tests/test_row_kernels_gpu.py holds the kernels to them):
   * a plain fp32 evaluation (matmul + epilogue; for the split and single-piece kernels their torch emulation) stays inside the
     bound of the float64 reference on every family and every shape the GPU suite runs, and every LayerNorm row of every case
     has a bound (first-order domain max(delta) / s <= 0.05, or the non-linearised bound's ds <= s / 2);
-  * every planted wrong version is put at least 10 bounds away by at least one family of its kernel class;
+  * every planted wrong version is put at least 10 bounds away by at least one family of its kernel class -- those of the
+    matrix-core tails' ride, gather and pre-norm forms included (one table per mode);
   * the pow2 scales are exact: nothing overflows or goes subnormal for the chosen s.
 
 Run with -s to see the tables (worst err / bound per family, the family that catches each planted error)."""
@@ -27,8 +28,9 @@ def _tail_runs(mode):
 
 
 def _tail_forms(mode):
-    """(proj, pre) of the hooks: the fp32 tail has all three, the matrix-core tails no pre-norm entry."""
-    return ((True, False), (True, True), (False, False)) if mode == "f32" else ((True, False), (False, False))
+    """(proj, pre) of the hooks: the fp32 and the single-piece tail have all three (cone_test_tail_form / cone_test_tail_mc);
+    the three-piece split has no pre-norm kernel.  The ride and gather forms of the matrix-core tails: row_refs.mc_forms."""
+    return ((True, False), (False, False)) if mode == "split" else ((True, False), (True, True), (False, False))
 
 
 MM = {"f32": R.mm32, "split": R.mm_split, "bf16": R.mm32_bf}
@@ -107,6 +109,62 @@ def test_tail_reference_stays_inside_every_bound(mode):
             _note(dom, key, rb["valid"]["first"])
     _table(f"layer tail, mode {mode}: its torch emulation vs float64", worst)
     _table("  worst max(delta) / s over the LayerNorms (beyond 0.05: the non-linearised bound)", dom)
+    assert max(worst.values()) <= 1.0
+
+
+def test_split_tail_reference_refuses_the_pre_norm_form():
+    with pytest.raises(ValueError, match="no pre-norm form"):
+        R.tail_ref_bound(R.tail_case("benign", 17, 64), "split", True, True)
+
+
+def test_gathered_rows_are_the_residual_rows():
+    """tail_mc_case: the two source matrices and the index row reproduce R bit for bit, both signs occur, no row sits at its
+    own index (M > 2), and what a wrong gather would read differs from R."""
+    for M in (1, 17) + R.MC_MS:
+        c = R.tail_mc_case("benign", M, 64, 96)
+        assert c.r_idx.dtype == torch.int32 and c.Rg.shape == c.R2.shape == (M, 256)
+        assert torch.equal(R.gather_rows(c), c.R)
+        if M > 2:
+            assert bool((c.r_idx < 0).any()) and bool((c.r_idx >= 0).any())
+            for fault in R.GATHER_FAULTS:
+                assert not torch.equal(R.gather_rows(c, fault), c.R), fault
+
+
+def _mc_cases(mode):
+    for M, ff, nq in R.mc_runs(mode):
+        for fam in R.mc_families(mode, M):
+            yield fam, M, ff, nq
+    for fam in R.MC_EDGE_FAMILIES:
+        yield fam, R.MC_MS[0], *R.MC_EDGE
+
+
+@pytest.mark.parametrize("mode", ["split", "bf16"])
+def test_mc_tail_forms_reference_stays_inside_every_bound(mode):
+    """The ride, gather and pre-norm forms on every case tests/test_tail_mc_forms_gpu.py runs.  Two conditions per case: every
+    element of OUT, OUT2 and QKV has a FINITE bound (every LayerNorm row inside LN_RIG_VALID), and the mode's plain torch
+    emulation in fp32 stays inside every bound.  Left out by name (row_refs.MC_LEFT_OUT): `cancel` in mode "split", one row of
+    which has no LayerNorm bound at ff = 128 and 677 rows (ds / s = 0.53).  Nothing is left out in mode "bf16": the ride's bound
+    carries OUT's bound through |Wq| and through the one rounding (`flip` adds 1.5 spacings where a rounding boundary lies
+    within OUT's bound), which is finite wherever OUT's is, and the emulation meets it on every family.  The ff = 1024 edge
+    runs row_refs.MC_EDGE_FAMILIES (benign and cancel have no bound there)."""
+    worst = {}
+    for fam, M, ff, nq in _mc_cases(mode):
+        c = R.tail_mc_case(fam, M, ff, nq)
+        what = (mode, fam, M, ff, nq)
+        rb = R.tail_ref_bound(c, mode, True, False, ride=True)
+        _domain_ok(rb["valid"], what)
+        assert bool(torch.isfinite(rb["OUT"][1]).all()) and bool(torch.isfinite(rb["QKV"][1]).all()), what
+        out, _, qkv = R.eval_tail(c, MM[mode], F32, True, False, ride=True, gather=True)
+        assert bool(torch.isfinite(out).all()) and bool(torch.isfinite(qkv).all()), what
+        _note(worst, f"{fam}/ride OUT", R.worst_ratio(out, *rb["OUT"]))
+        _note(worst, f"{fam}/ride QKV {nq}", R.worst_ratio(qkv, *rb["QKV"]))
+        if mode == "bf16" and nq == R.MC_NQKV[0]:
+            rb = R.tail_ref_bound(c, mode, True, True)
+            _domain_ok(rb["valid"], what + ("pre",))
+            assert bool(torch.isfinite(rb["OUT"][1]).all()) and bool(torch.isfinite(rb["OUT2"][1]).all()), what
+            out, out2 = R.eval_tail(c, MM[mode], F32, True, True, gather=True)
+            _note(worst, f"{fam}/pre", max(R.worst_ratio(out, *rb["OUT"]), R.worst_ratio(out2, *rb["OUT2"])))
+    _table(f"matrix-core tail forms, mode {mode}: its torch emulation vs float64", worst)
     assert max(worst.values()) <= 1.0
 
 
@@ -215,6 +273,36 @@ def test_every_planted_error_is_caught_tail_class(proj, pre):
                 if pre:
                     yield f"{fam}[M={M}] OUT2", out2.double(), *rb["OUT2"]
     _catch(f"fp32 layer tail, proj={proj} pre={pre}", R.LN_FAULTS + R.EPI_FAULTS, attempts)
+
+
+MM64 = {"split": R.mm64, "bf16": R.mm64_bf}
+
+
+@pytest.mark.parametrize("mode", ["split", "bf16"])
+def test_every_planted_error_is_caught_mc_forms(mode):
+    """The faults of the ride, the gather and the pre-norm form, evaluated in float64 on the mode's operands (mode "bf16":
+    rounded once), so that the distance is the fault's alone: the same evaluation without a fault stays inside every bound.
+    The pre-norm faults exist in the single-piece mode only: the split has no such kernel (tail_ref_bound refuses it)."""
+    def attempts(fault):
+        pre = fault in R.PRE_FAULTS
+        for M, ff, nq in ((R.MC_MS[0], R.MC_WALK_FF[mode], 96), (R.MC_MS[1], R.MC_WALK_FF[mode], 96)):
+            for fam in R.mc_families(mode, M):
+                c = R.tail_mc_case(fam, M, ff, nq)
+                rb = R.tail_ref_bound(c, mode, True, pre, ride=not pre)
+                outs = R.eval_tail(c, MM64[mode], torch.float64, True, pre, fault, ride=not pre, gather=True)
+                for name, o in zip(("OUT", "OUT2", "QKV"), outs):
+                    if o is not None:
+                        yield f"{fam}[M={M}, ff={ff}] {name}", o, *rb[name]
+    faults = (None,) + R.RIDE_FAULTS + R.GATHER_FAULTS + (R.PRE_FAULTS if mode == "bf16" else ())
+    clean = max(R.worst_ratio(o, ref, bound) for _, o, ref, bound in attempts(None))
+    assert clean <= 1.0, ("the evaluation without a fault leaves its bound", mode, clean)
+    if mode == "bf16":
+        c = R.tail_mc_case("benign", R.MC_MS[0], R.MC_WALK_FF[mode], 96)
+        rb = R.tail_ref_bound(c, mode, True, True)
+        out, out2 = R.eval_tail(c, MM64[mode], torch.float64, True, True, gather=True)
+        assert max(R.worst_ratio(out, *rb["OUT"]), R.worst_ratio(out2, *rb["OUT2"])) <= 1.0
+    _catch(f"matrix-core tail forms, mode {mode} (ride, gather{', pre-norm' if mode == 'bf16' else '; no pre-norm kernel'})",
+           faults[1:], attempts)
 
 
 def test_every_planted_error_is_caught_split_class():

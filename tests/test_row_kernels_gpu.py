@@ -23,6 +23,13 @@ Which test enters which kernel or form:
                                         test_fp32_tail_families[ff-M] (SPREAD: ff = 1024; ROWS64: post-norm only)
   cone_test_ffn_split, cone_test_proj_ffn_split, CONE_TEST_PACK [| CONE_TEST_SINGLE_PIECE]
                                         test_matrix_core_tail_families[mode-ff-M]
+                                        (ffn_split_kernel<false, false> / <true, false>, ffn_bf16_kernel<false, false, false> /
+                                        <true, false, false>, one tile per workgroup, dense rows, no M_dev)
+  cone_test_tail_mc                     tests/test_tail_mc_forms_gpu.py: the same kernels and ffn_split_kernel<true, true>,
+                                        ffn_bf16_kernel<true, true, false> (the q | k | v ride) and <true, false, true> (pre-norm,
+                                        OUT2 set or NULL), with r_idx / R2, M_dev, padded strides, and walked (n_cu = 2, 1 at
+                                        677 rows) as well as un-walked; its docstring names the test per kernel
+  cone_test_rows_mc                     ... rows256_split_kernel / rows256_bf16_kernel walked and un-walked, ldx / ldc, M_dev
   cone_test_rows_split, both modes      test_matrix_core_row_gemm_families[mode-N] (pow2 at s = -40, 40, -80; tiny measured)
   cone_test_gemm_bf16                   test_gemm_bf16_families[N-K]
   cone_l2_normalize_rows                test_l2_normalize_families[dim]
